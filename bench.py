@@ -1,7 +1,19 @@
 #!/usr/bin/env python3
 """bench.py -- simulated WFC3-IR exposures/sec on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg4]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg4] [--dump-outputs DIR] [--full]
+
+A plain run does what the headline figure needs and nothing else: set up, W warm-up exposures, ONE timed pass of exactly
+K exposures (no HIP events in it), the outputs of the last timed exposure written if --dump-outputs is given, and the
+JSON line (metric, value, unit, ms_per_step, dtype, config, ...).  --full adds everything below: five repetitions of
+the timed region with k_ramp's HIP events (`value` = their median), the roofline, the per-kernel breakdown, the
+sustained pass, the like-for-like modes, the host pipeline and the CPU baseline.
+
+--dump-outputs DIR writes what the timed path computed in its last step -- the reads of that exposure, what
+ctx.download() hands a caller -- as DIR/reads.npy (float32, or float64 with --out-f64).  Reads larger than
+DUMP_BYTES are written as a fixed, seeded sample of pixels taken from every read (DIR/reads.npy, (reads, pixels)) with
+the flat pixel indices of the sample in DIR/reads_pixels.npy (float64).  The inputs are synthetic and seeded: the same
+arguments give the same exposures on every run.
 
 One "step" = one whole exposure (1014x1014 frame, NSAMP = 16, 128-sub-sample
 spatial scan, 1e9 electrons: BASELINE.json configs[3], the configuration the
@@ -20,11 +32,11 @@ JSON line; a line that does not report N ranks is an error.  The ranks meet
 over gloo for the barrier and the max-over-ranks of the elapsed time -- there
 is nothing for RCCL to do in this path.
 
-The timed region is repeated REPS times (each repetition = exactly K steps
-bracketed by a barrier + device synchronisation, max over ranks); `value` is
-the median repetition, the others are listed in `repetitions`.
+The timed region is exactly K steps bracketed by a barrier + device
+synchronisation, max over ranks.  With --full it is repeated REPS times;
+`value` is then the median repetition, the others are listed in `repetitions`.
 
-Prints ONE JSON line on rank 0 (the driver's contract) with extra objects:
+Prints ONE JSON line on rank 0 (the driver's contract); with --full it carries extra objects:
   roofline      the fused up-the-ramp kernel k_ramp against the HBM roof
   cpu_baseline  the reference's C thrower + the numpy restatement of the host
                 loop, timed on this box's host cores on a bounded sample
@@ -59,6 +71,24 @@ SUSTAIN_S = 6.5       # length of the sustained-rate pass (longer than the perio
 READS_LABEL = {False: "f32 reads (the default of ExposureGenerator, Observation, VisitRunner and the CLI)",
                True: "f64 reads (out_dtype=float64 / --float64-reads: the reference's dtype)"}
 RAMP_EVENTS_EVERY = 4   # k_ramp's HIP events in the timed region: on every 4th exposure (they cost the stream ~10 us a pair)
+DUMP_BYTES = 48 * 10**6  # --dump-outputs: reads larger than this are written as a seeded sample of pixels
+DUMP_SEED = 20261016     # ... the same sample on every run
+
+
+def dump_outputs(d, reads):
+    """`--dump-outputs DIR`: the reads of the last timed exposure as DIR/reads.npy; reads larger than DUMP_BYTES as the
+    same seeded sample of pixels of every read, (reads, pixels), with the sample's flat pixel indices (ascending) in
+    DIR/reads_pixels.npy as float64.  The sample of a float64 run is a subset of the float32 run's.  -> the names written"""
+    os.makedirs(d, exist_ok=True)
+    if reads.nbytes <= DUMP_BYTES:
+        np.save(os.path.join(d, "reads.npy"), reads)
+        return ["reads"]
+    flat = reads.reshape(reads.shape[0], -1)
+    n = DUMP_BYTES // (flat.shape[0] * flat.itemsize + 8)
+    idx = np.sort(np.random.default_rng(DUMP_SEED).permutation(flat.shape[1])[:n])
+    np.save(os.path.join(d, "reads.npy"), np.ascontiguousarray(flat[:, idx]))
+    np.save(os.path.join(d, "reads_pixels.npy"), idx.astype(np.float64))
+    return ["reads", "reads_pixels"]
 
 
 def ramp_bytes(N, S, R, out_bytes, acc_segments=None):
@@ -286,7 +316,12 @@ def main():
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--config", default="cfg4")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="every figure besides the headline: repetitions, roofline, per-kernel breakdown, sustained "
+                         "pass, like-for-like modes, host pipeline, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the reads of the last timed exposure to DIR/reads.npy (a seeded sample if large)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline")
     ap.add_argument("--out-f64", action="store_true", help="float64 reads (the reference's dtype) in the timed region")
     ap.add_argument("--thrower", default="split", choices=["split", "electron"],
                     help="split: narrow PSF component drawn as a multinomial (WAYNE_RNG_SPLIT, same distribution); "
@@ -296,8 +331,8 @@ def main():
                          "per-kernel event times are clean; the 2-stream rate is reported separately as two_streams)")
     ap.add_argument("--dry-run", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--no-extra-pass", action="store_true",
-                    help="skip the passes after the timed region (use under rocprofv3 so that the kernel statistics "
-                         "cover the timed region only)")
+                    help="with --full: skip the passes after the timed region (use under rocprofv3 so that the kernel "
+                         "statistics cover the timed region only)")
     args = ap.parse_args()
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -399,17 +434,21 @@ def main():
     def slot_of(j):
         return (j % n_res) * stride
 
-    # timed region: HIP events around the roofline kernel only (every event pair costs a few microseconds
-    # of stream time; the other kernels are timed in the breakdown pass below)
+    # timed region.  --full: REPS repetitions with HIP events around the roofline kernel only (every event pair costs a
+    # few microseconds of stream time; the other kernels are timed in the breakdown pass below).  A plain run: one pass,
+    # no events
     timed(slot_of, 0, args.warmup)
     reruns_before = ctx.reruns
-    ctx.profile_select(["k_ramp"])
-    ctx.profile_enable(True)
-    ctx.profile_reset()
+    if args.full:
+        ctx.profile_select(["k_ramp"])
+        ctx.profile_enable(True)
+    ctx.profile_reset()                               # (also zeroes the device's electron counter)
     del own_rates[:]
-    reps = [timed(slot_of, args.steps, 0, events_every=RAMP_EVENTS_EVERY) for _ in range(REPS)]
+    reps = [timed(slot_of, args.steps, 0, events_every=RAMP_EVENTS_EVERY if args.full else 0)
+            for _ in range(REPS if args.full else 1)]
     rank_rates = list(own_rates)                      # this rank's exposures/s in each repetition of the timed region
-    ctx.profile_enable(True)
+    if args.full:
+        ctx.profile_enable(True)
     prof_ramp = ctx.profile_get()
     elapsed = float(np.median(reps))
     # every exposure of the timed region must have been complete: a slot whose status word says otherwise would have
@@ -432,6 +471,54 @@ def main():
             raise SystemExit("ranks disagree: %s" % (got,))
         per_rank = {r: rates for r, _, rates in got}
 
+    # sanity: the last timed exposure really produced a frame; its reads are what --dump-outputs writes
+    reads = ctx.download(slot_of(args.steps - 1))
+    assert np.isfinite(reads).all() and reads[-1].max() > 100.0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, reads)
+    del reads
+
+    ramp_variant = ctx.ramp_variant(slot_of(0))          # the instantiation `value` (and `roofline`) were measured on
+
+    def headline(electrons):
+        """The keys of every line: what a plain run prints."""
+        line = {
+            "metric": "simulated WFC3-IR exposures/sec (1014x1014, NSAMP=16, spatial scan)",
+            "value": args.steps * n_gpus / elapsed, "unit": "exposures/s", "n_gpus": n_gpus, "steps": args.steps,
+            "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True,
+            "scaling": "weak", "vs_baseline": None,
+            "dtype": dtype_label(ramp_variant, args.out_f64),
+            "data": "synthetic",
+            "ranks_reported": ranks_reported,
+            "full": bool(args.full),
+            "config": {"workload": "%s: %s spatial scan %g px/s, SUBARRAY=%d (frame %dx%d), %s NSAMP=%d, "
+                                   "K=%d sub-samples, W=%d bins, %.3g electrons/exposure, all detector effects on "
+                                   "(flat, sky, cosmic rays, gain, dark, non-linearity, clip, read noise), "
+                                   "thrower=%s, %s, %s, device-complete reads in HBM" % (
+                                       args.config, gr.name, visit.scan_speed, visit.SUBARRAY, eng.N, eng.N,
+                                       visit.SAMPSEQ, visit.NSAMP, visit.K, W, electrons,
+                                       "split (wide component per electron, narrow component multinomial)"
+                                       if args.thrower == "split" else "per-electron",
+                                       READS_LABEL[bool(args.out_f64)],
+                                       "one HIP stream" if args.streams == 1 else "two HIP streams (what VisitRunner runs)"),
+                       "exposures_per_rank": args.steps, "sharding": "round-robin exposures, no collective"},
+        }
+        lib_path, lib_flags = _lib.library_info()
+        line["library"] = {"path": os.path.relpath(lib_path, ROOT), "build_flags": lib_flags, "abi": _lib.ABI_VERSION}
+        if lib_flags:
+            # a negative-control or timing build (its sources say "wrong frames"): not a measurement of the product
+            line["value"] = None
+            line["library"]["note"] = "value withheld: this library was built with %s" % lib_flags
+        return line
+
+    if not args.full:
+        if rank == 0:
+            emit_line(headline(prof_ramp["electrons"] / args.steps))      # (the timed pass's exposures)
+        if dist is not None:
+            dist.barrier(group=grp)
+            dist.destroy_process_group()
+        return
+
     # breakdown pass (not part of `value`): the same exposures again with every kernel timed
     ctx.profile_select(None)
     ctx.profile_reset()
@@ -453,10 +540,6 @@ def main():
                      "vs_value": (n_sus / e_sus) / (args.steps / elapsed),
                      "note": "%d exposures per rank back to back on one stream (the timed region's workload and slots), "
                              "barrier + synchronise either side, max over ranks" % n_sus}
-
-    # sanity: the last exposure really produced a frame
-    reads = ctx.download(slot_of(args.steps - 1))
-    assert np.isfinite(reads).all() and reads[-1].max() > 100.0
 
     extras = {}
     out_mb = (eng.R + 1) * eng.S * eng.S * 4 / 1e6
@@ -485,7 +568,6 @@ def main():
         ctx.profile_select(None)
         return steps * n_gpus / e, pr["ms"] / max(pr["launches"], 1), pr["launches"]
 
-    ramp_variant = ctx.ramp_variant(slot_of(0))          # the instantiation `value` and `roofline` were measured on
     use_box0, _, segs0 = ctx.debug_boxes(slot_of(0))
 
     if n_gpus == 1 and not args.no_extra_pass:
@@ -656,14 +738,8 @@ def main():
         thrower_ms = throw_ms if forked else throw_ms + narrow_ms
         electrons = prof["electrons"] / max(n_break, 1)
         rates = sorted(args.steps * n_gpus / e for e in reps)
-        line = {
-            "metric": "simulated WFC3-IR exposures/sec (1014x1014, NSAMP=16, spatial scan)",
-            "value": args.steps * n_gpus / elapsed, "unit": "exposures/s", "n_gpus": n_gpus, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True,
-            "scaling": "weak", "vs_baseline": None,
-            "dtype": dtype_label(ramp_variant, args.out_f64),
-            "data": "synthetic",
-            "ranks_reported": ranks_reported,
+        line = headline(electrons)
+        line.update({
             "repetitions": {"n": REPS, "steps_each": args.steps, "values": [args.steps * n_gpus / e for e in reps],
                             "median": rates[len(rates) // 2], "min": rates[0], "max": rates[-1],
                             "per_rank_exposures_s": {str(r): [round(x, 1) for x in per_rank[r]] for r in sorted(per_rank)},
@@ -671,17 +747,6 @@ def main():
                             "note": "value = the median repetition; each is exactly `steps` exposures per rank between "
                                     "barrier + synchronise, max over ranks; per_rank_exposures_s: every rank's own rate "
                                     "in each repetition by its own clock (an imbalance shows here, not in the max)"},
-            "config": {"workload": "%s: %s spatial scan %g px/s, SUBARRAY=%d (frame %dx%d), %s NSAMP=%d, "
-                                   "K=%d sub-samples, W=%d bins, %.3g electrons/exposure, all detector effects on "
-                                   "(flat, sky, cosmic rays, gain, dark, non-linearity, clip, read noise), "
-                                   "thrower=%s, %s, %s, device-complete reads in HBM" % (
-                                       args.config, gr.name, visit.scan_speed, visit.SUBARRAY, N, N, visit.SAMPSEQ,
-                                       visit.NSAMP, K, W, electrons,
-                                       "split (wide component per electron, narrow component multinomial)"
-                                       if args.thrower == "split" else "per-electron",
-                                       READS_LABEL[bool(args.out_f64)],
-                                       "one HIP stream" if args.streams == 1 else "two HIP streams (what VisitRunner runs)"),
-                       "exposures_per_rank": args.steps, "sharding": "round-robin exposures, no collective"},
             "roofline": {"bound": "hbm", "kernel": ramp_variant, "achieved": achieved, "peak": HBM_PEAK_GBS,
                          "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": None,
                          "bytes_per_launch": rb, "ms_per_launch": ramp_ms,
@@ -707,13 +772,7 @@ def main():
                         "note": "split mode: the k_throw interval spans k_throw (bins beyond a lane's cap: normally none) + "
                                 "k_lane on the slot's stream with k_narrow beside them on a side stream"
                         if forked else "k_throw + k_lane (one interval), then k_narrow, on one stream"},
-        }
-        lib_path, lib_flags = _lib.library_info()
-        line["library"] = {"path": os.path.relpath(lib_path, ROOT), "build_flags": lib_flags, "abi": _lib.ABI_VERSION}
-        if lib_flags:
-            # a negative-control or timing build (its sources say "wrong frames"): not a measurement of the product
-            line["value"] = None
-            line["library"]["note"] = "value withheld: this library was built with %s" % lib_flags
+        })
         line["sustained"] = sustained
         cold = extras.pop("ramp_cold", None)
         if cold and "ms_per_launch" in cold and cold["ms_per_launch"] > 0:

@@ -1,9 +1,11 @@
-"""GPU: bench.py prints exactly one JSON line carrying the contract's keys."""
+"""GPU: bench.py prints exactly one JSON line carrying the contract's keys (all of them with --full, the headline's in a
+plain run) and writes the outputs of its last timed step when asked."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -12,7 +14,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 @pytest.mark.gpu
 def test_bench_line_has_the_contract_keys():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "1",
-                          "--no-cpu-baseline"], capture_output=True, text=True, timeout=600)
+                          "--full", "--no-cpu-baseline"], capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
     assert len(lines) == 1
@@ -71,6 +73,69 @@ def test_bench_line_has_the_contract_keys():
     assert d["library"] == {"path": os.path.relpath(lib_path, ROOT), "build_flags": "", "abi": 7}
     assert rep["incomplete_exposures"] == 0 and rep["second_runs_in_timed_region"] == 0
 
+
+HEADLINE = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
+            "vs_baseline", "dtype", "data", "ranks_reported", "full", "config", "library")
+
+
+def _plain_run(out_dir):
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "6", "--warmup", "2",
+                          "--dump-outputs", str(out_dir)], capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1
+    return json.loads(lines[0])
+
+
+@pytest.mark.gpu
+def test_plain_run_prints_the_headline_and_dumps_its_last_step(tmp_path):
+    # a plain run: one timed pass of exactly `steps` exposures and the headline keys only -- nothing that --full measures
+    d = _plain_run(tmp_path / "a")
+    assert sorted(d) == sorted(HEADLINE)
+    assert d["metric"].startswith("simulated WFC3-IR exposures/sec") and d["unit"] == "exposures/s"
+    assert d["n_gpus"] == 1 and d["steps"] == 6 and d["warmup"] == 2 and d["higher_is_better"] is True
+    assert d["full"] is False and d["ranks_reported"] == 1 and d["data"] == "synthetic"
+    assert d["value"] > 100 and abs(d["ms_per_step"] * d["value"] - 1000.0) < 1.0      # one GPU: value = 1000 / ms_per_step
+    assert d["dtype"].startswith("k_ramp<float, true, 1, false, true>") and "all-f32 per-read chain" in d["dtype"]
+    import bench
+    assert bench.READS_LABEL[False] in d["config"]["workload"] and "one HIP stream" in d["config"]["workload"]
+    # the reads of the last timed exposure (16 reads of 1024 x 1024 float32: more than the budget, so a seeded sample)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["reads.npy", "reads_pixels.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= 64e6
+    reads, px = np.load(tmp_path / "a" / "reads.npy"), np.load(tmp_path / "a" / "reads_pixels.npy")
+    assert reads.dtype == np.float32 and px.dtype == np.float64 and reads.shape == (16, px.size)
+    assert np.isfinite(reads).all() and reads[-1].max() > 100.0
+    # the same arguments: the same inputs, the same outputs
+    e = _plain_run(tmp_path / "b")
+    assert e["config"] == d["config"] and e["dtype"] == d["dtype"]
+    np.testing.assert_array_equal(np.load(tmp_path / "b" / "reads_pixels.npy"), px)
+    np.testing.assert_array_equal(np.load(tmp_path / "b" / "reads.npy"), reads)
+
+
+def test_dump_outputs_writes_small_reads_whole_and_a_seeded_sample_of_large_ones(tmp_path):
+    # CPU: the writer of --dump-outputs
+    sys.path.insert(0, ROOT)
+    import bench
+    small = np.random.default_rng(1).random((5, 256, 256), dtype=np.float32)
+    assert bench.dump_outputs(str(tmp_path / "s"), small) == ["reads"]
+    np.testing.assert_array_equal(np.load(tmp_path / "s" / "reads.npy"), small)
+    big = np.arange(16 * 1024 * 1024, dtype=np.float32).reshape(16, 1024, 1024)
+    assert bench.dump_outputs(str(tmp_path / "b"), big) == ["reads", "reads_pixels"]
+    assert sum(os.path.getsize(tmp_path / "b" / f) for f in os.listdir(tmp_path / "b")) <= 64e6
+    reads, px = np.load(tmp_path / "b" / "reads.npy"), np.load(tmp_path / "b" / "reads_pixels.npy")
+    idx = px.astype(np.int64)
+    assert reads.dtype == np.float32 and px.dtype == np.float64 and np.array_equal(idx, px)
+    assert idx.size > 500000 and idx[0] >= 0 and idx[-1] < 1024 * 1024 and np.all(np.diff(idx) > 0)
+    np.testing.assert_array_equal(reads, big.reshape(16, -1)[:, idx])
+    # the same sample on every call; the sample of float64 reads is a subset of that of float32 reads
+    bench.dump_outputs(str(tmp_path / "b2"), big)
+    np.testing.assert_array_equal(np.load(tmp_path / "b2" / "reads_pixels.npy"), px)
+    bench.dump_outputs(str(tmp_path / "d"), big.astype(np.float64))
+    px64 = np.load(tmp_path / "d" / "reads_pixels.npy")
+    assert np.load(tmp_path / "d" / "reads.npy").dtype == np.float64 and 0 < px64.size < px.size
+    assert np.isin(px64, px).all()
+    assert sum(os.path.getsize(tmp_path / "d" / f) for f in os.listdir(tmp_path / "d")) <= 64e6
 
 def test_every_ramp_instantiation_gets_the_arithmetic_it_runs():
     # `dtype` names the arithmetic of the timed kernels from the instantiation the library reports

@@ -7,16 +7,33 @@ GPU:
       ~ oracle/split_oracle.c, the CPU statement of the device's default mode                  <- pins the split law
   (device == split_oracle.c on the same counters: tests/test_split_gpu.py)
 
-Ensembles are smaller than on the GPU box (the CPU suite has minutes, not seconds per frame to spend).
+Ensembles are smaller than on the GPU box (the CPU suite has minutes, not seconds per frame to spend).  The reference's
+ensembles are stored under tests/golden/ (ensemble_ref_<name>.npz, written by `python tests/test_ensemble_cpu.py` where
+oracle/_ref is built); where oracle/_ref is present the stored frames are held to the library's frames as well.
 """
+import os
+
 import numpy as np
 import pytest
 
 import ensemble_stats as es
-from conftest import load_golden_psf
+from conftest import GOLDEN, load_golden_psf
 from oracle import clib
 
-needs_ref = pytest.mark.skipif(not clib.have_ref(), reason="oracle/_ref not built")
+
+def _reference_frames(args, n, m_ref):
+    tests = np.random.RandomState(5).randint(0, 100000, m_ref)
+    return np.stack([clib.psf_reference(*args, n, n, int(tests[m]), 1 if m % 2 == 0 else 4).reshape(n, n)
+                     for m in range(m_ref)])
+
+
+def _reference_ensemble(name, args, n, m_ref):
+    """m_ref frames of the reference C thrower (different `test` seeds, 1 and 4 OpenMP threads) from tests/golden/."""
+    A = np.load(os.path.join(GOLDEN, "ensemble_ref_%s.npz" % name))["frames"].astype(np.int32)
+    assert A.shape == (m_ref, n, n)
+    if clib.have_ref():
+        np.testing.assert_array_equal(A, _reference_frames(args, n, m_ref))
+    return A
 
 
 def _inputs(name):
@@ -27,16 +44,13 @@ def _inputs(name):
     return k, (k["counts"].astype(np.int64) * 20).astype(np.int32), 64, 200
 
 
-@needs_ref
 @pytest.mark.parametrize("name", ["bright", "edge"])
 def test_reference_and_split_oracle_ensembles_follow_the_exact_moments(name):
     k, counts, m_ref, m_split = _inputs(name)
     n = k["nr"]
     args = (counts, k["x"], k["y"], k["ratio"], k["sl"], k["sh"])
     mean, var, var_other, _ = es.analytic_moments(*args, n)
-    tests = np.random.RandomState(5).randint(0, 100000, m_ref)
-    A = np.stack([clib.psf_reference(*args, n, n, int(tests[m]), 1 if m % 2 == 0 else 4).reshape(n, n)
-                  for m in range(m_ref)])
+    A = _reference_ensemble(name, args, n, m_ref)
     B = np.stack([clib.psf_split_oracle(*args, n, 1963, m, m % 7).reshape(n, n) for m in range(m_split)])
     bad = ["reference: " + b for b in es.check_moments(es.compare_with_moments(A, mean, var, var_other))]
     bad += ["reference: " + b for b in es.check_wings_against_moments(es.wings_against_moments(A, mean, var, k["x"], k["y"]))]
@@ -83,3 +97,13 @@ def test_the_statistics_see_a_wrong_law():
     assert s["n_split"] >= 50
     assert (s["split_ratio_exact"] - 1.0) > 4.0 * s["split_se"], s      # excess variance of the random split shows
     assert abs(s["split_ratio_other"] - 1.0) < 4.0 * s["split_se"] + 0.002, s
+
+
+if __name__ == "__main__":
+    # (re)write the reference's ensembles under tests/golden/ -- needs oracle/_ref
+    assert clib.have_ref(), "oracle/_ref not built"
+    for name in ("bright", "edge"):
+        k, counts, m_ref, _ = _inputs(name)
+        A = _reference_frames((counts, k["x"], k["y"], k["ratio"], k["sl"], k["sh"]), k["nr"], m_ref)
+        assert 0 <= A.min() and A.max() < 2 ** 16
+        np.savez_compressed(os.path.join(GOLDEN, "ensemble_ref_%s.npz" % name), frames=A.astype(np.uint16))

@@ -1,10 +1,13 @@
 """CPU: the oracle's C restatement of PSF() against the golden vectors that
-the reference's own compiled C produced (scripts/make_golden_psf.py), and --
-where oracle/_ref is present -- against that library directly."""
+the reference's own compiled C produced (scripts/make_golden_psf.py; the random
+cases: tests/golden/ref_psf_random.npz, written by `python tests/test_psf_oracle.py`),
+and -- where oracle/_ref is present -- against that library directly."""
+import os
+
 import numpy as np
 import pytest
 
-from conftest import golden_psf_cases, load_golden_psf
+from conftest import GOLDEN, golden_psf_cases, load_golden_psf
 from oracle import clib
 
 CASES = golden_psf_cases()
@@ -23,9 +26,7 @@ def test_oracle_matches_reference_golden(name):
     np.testing.assert_array_equal(got, k["frame"])  # bit-exact: integer counts
 
 
-@pytest.mark.skipif(not clib.have_ref(), reason="oracle/_ref not built (no /root/reference here)")
-@pytest.mark.parametrize("threads", [1, 2, 5, 8])
-def test_oracle_matches_compiled_reference_random(threads):
+def _random_cases(threads):
     rng = np.random.RandomState(100 + threads)
     for trial in range(4):
         W = int(rng.randint(1, 400))
@@ -37,9 +38,23 @@ def test_oracle_matches_compiled_reference_random(threads):
         sl = rng.uniform(0.3, 1.0, W)
         sh = rng.uniform(3, 8, W)
         test = int(rng.randint(0, 100000))
-        a = clib.psf_oracle(counts, x, y, ratio, sl, sh, N, N, test, threads)
-        b = clib.psf_reference(counts, x, y, ratio, sl, sh, N, N, test, threads)
+        yield trial, (counts, x, y, ratio, sl, sh, N, N, test, threads)
+
+
+RANDOM_REF = os.path.join(GOLDEN, "ref_psf_random.npz")
+
+
+@pytest.mark.parametrize("threads", [1, 2, 5, 8])
+def test_oracle_matches_compiled_reference_random(threads):
+    # the reference's frames of these inputs are stored (flat, int32); where oracle/_ref is present it is asked too
+    want = np.load(RANDOM_REF)
+    for trial, args in _random_cases(threads):
+        a = clib.psf_oracle(*args)
+        b = want["t%d_%d" % (threads, trial)]
+        assert b.size == args[6] * args[7]
         np.testing.assert_array_equal(a, b)
+        if clib.have_ref():
+            np.testing.assert_array_equal(clib.psf_reference(*args), b)
 
 
 def test_rand_r_restatement_matches_glibc():
@@ -70,3 +85,10 @@ def test_invalid_inputs_raise():
         clib.psf_oracle(np.array([1, -1, 2]), one, one, one, one, one, 8, 8, 0, 1)
     with pytest.raises(ValueError):  # ssum * threads overflows the reference's int
         clib.psf_oracle(np.array([2 ** 30, 2 ** 30 - 1, 0]), one, one, one, one, one, 8, 8, 0, 2)
+
+
+if __name__ == "__main__":
+    # (re)write tests/golden/ref_psf_random.npz from the reference's compiled C -- needs oracle/_ref
+    assert clib.have_ref(), "oracle/_ref not built"
+    np.savez_compressed(RANDOM_REF, **{"t%d_%d" % (t, trial): clib.psf_reference(*args).astype(np.int32)
+                                       for t in (1, 2, 5, 8) for trial, args in _random_cases(t)})

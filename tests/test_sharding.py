@@ -120,7 +120,7 @@ def test_bench_launches_its_own_ranks():
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
         env.pop(k, None)
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--steps", "3", "--warmup", "1",
-                          "--no-cpu-baseline"], capture_output=True, text=True, timeout=900, env=env)
+                          "--full", "--no-cpu-baseline"], capture_output=True, text=True, timeout=900, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
     assert len(lines) == 1
@@ -137,3 +137,22 @@ def test_bench_launches_its_own_ranks():
         assert all(len(v) == 3 and min(v) > 1 for v in leg["per_rank_exposures_s"].values())
         assert leg["value"] <= 1.001 * sum(max(v) for v in leg["per_rank_exposures_s"].values())
     assert "two_streams" not in d and "per_electron" not in d          # the like-for-like passes are N = 1 only
+
+
+@pytest.mark.gpu
+def test_plain_bench_launches_its_own_ranks():
+    # the same launch without --full: rank 0's line reports every rank and carries the headline keys only
+    import json
+    import subprocess
+    env = dict(os.environ, WAYNE_BENCH_SHARE_GPU="1")
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
+        env.pop(k, None)
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--steps", "3", "--warmup", "1"],
+                         capture_output=True, text=True, timeout=900, env=env)
+    assert out.returncode == 0, out.stderr[-3000:]
+    lines = [l for l in out.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["n_gpus"] == 4 and d["ranks_reported"] == 4 and d["full"] is False and d["steps"] == 3
+    assert d["value"] > 50 and abs(d["value"] - 4 * 1000.0 / d["ms_per_step"]) < 1e-6 * d["value"]
+    assert "delivered" not in d and "end_to_end" not in d and "repetitions" not in d

@@ -82,11 +82,14 @@ def test_exposure_file_layout_and_primary_header(tmp_path):
     assert p0["SMA"] == pytest.approx(0.047309 / (1.155 * 0.00465047), rel=1e-3) and p0["LD2"] == pytest.approx(-0.7)
 
 
-def test_fits_reads_reference_data_files():
-    # the reference's own small FITS data files, when its tree is present (not on the GPU box)
-    ref = "/root/reference/wayne/data"
-    if not os.path.exists(ref):
-        pytest.skip("reference tree not present")
+def test_fits_reads_reference_data_files(tmp_path):
+    # two of the reference's own small FITS data files (wayne/data), stored gzipped under tests/golden/
+    import gzip
+    import shutil
+    ref = str(tmp_path)
+    for name in ("wfc3_ir_initial_bias_256.fits", "wfc3_ir_g141_src_004_syn.fits"):
+        with gzip.open(os.path.join(HERE, "golden", name + ".gz"), "rb") as a, open(os.path.join(ref, name), "wb") as b:
+            shutil.copyfileobj(a, b)
     bias = fitsio.read(os.path.join(ref, "wfc3_ir_initial_bias_256.fits"))[1].data
     np.testing.assert_array_equal(bias, np.load(detector.WFC3_IR().initial_bias))
     tab = fitsio.read(os.path.join(ref, "wfc3_ir_g141_src_004_syn.fits"))[1].data
@@ -293,9 +296,8 @@ def test_generate_exposure_follows_the_references_bookkeeping():
 
 
 def test_example_yaml_of_the_reference_parses():
-    ex = "/root/reference/examples"
-    if not os.path.exists(ex):
-        pytest.skip("reference tree not present")
+    # the reference's example visit, byte for byte (tests/test_example_visit.py holds the copy to the reference's hashes)
+    ex = os.path.join(HERE, "fixtures", "example_visit")
     cfg = yaml.safe_load(open(os.path.join(ex, "hd209458b_12181_simulation_parameters.yml")))
     obs = run_visit.build_observation(cfg, ex)
     assert len(obs.exp_start_times) == 121 and obs.SUBARRAY == 256 and obs.sample_rate == 10
