@@ -298,6 +298,39 @@ int wayne_exposure_run_back(wayne_ctx *ctx, int slot);
  * No reference counterpart: the reference has one float64 numpy path (exposure_generator.py:407-515). */
 int wayne_exposure_ramp_variant(wayne_ctx *ctx, int slot, char *buf, int cap);
 
+/* ---- contaminating field stars (no reference counterpart) --------------- */
+
+/*
+ * A second (third, ...) star whose first-order spectrum lands on the same exposure.  Its part of the exposure is
+ * exactly the front half of the single-source exposure with x_ref + dx, y_ref + dy, its own wl_um / flux,
+ * depth = NULL (contaminants do not transit), cosmic_rate < 0 and seed = wayne_source_seed(seed, tag); everything
+ * else is the exposure's own.  Its electrons add into the same int64 accumulators as the target's; the stages that
+ * belong to the exposure as a whole (sky, reads, noise, cosmic rays) run once, with the visit seed.
+ * Not supported: zeroth / second orders, a contaminant in the direct image, a varying contaminant, per-sub-sample
+ * offsets, WAYNE_RNG_REPLAY.
+ */
+typedef struct wayne_source_desc {
+  uint32_t tag;          /* >= 1, unique within the exposure: selects the source's random streams */
+  int n_wl;              /* 2 .. 32768 */
+  const double *wl_um;   /* [W] */
+  const double *flux;    /* [W] same units and scaling as wayne_exposure_desc.flux */
+  double dx, dy;         /* detector-pixel offset from the target; added to x_ref[k] / y_ref[k] of every sub-sample */
+} wayne_source_desc;
+
+#define WAYNE_MAX_SOURCES 8 /* contaminants per exposure */
+
+/* After wayne_exposure_upload, before run: extra sources of the slot's exposure (n = 0 clears).
+ * wayne_exposure_upload clears the list, so callers that never call this get today's exposure.
+ * WAYNE_E_INVALID (the slot stays usable, without contaminants) in replay mode, on a zero or duplicate tag, a
+ * non-finite offset, n > WAYNE_MAX_SOURCES or a bad n_wl; WAYNE_E_STATE on a slot that is not uploaded. */
+int wayne_exposure_set_sources(wayne_ctx *ctx, int slot, const wayne_source_desc *src, int n);
+/* The visit seed a source's streams use: tag 0 -> seed; otherwise word 0 of
+ * philox4x32_10(ctr = (tag, 0, 0, 0), key = (seed, STAGE_SOURCE)).  Pure host arithmetic. */
+uint32_t wayne_source_seed(uint32_t seed, uint32_t tag);
+/* debug_fetch for source i (0 = target, 1.. = list order): counts / x_pos / y_pos [K*W_i]. */
+int wayne_exposure_debug_fetch_source(wayne_ctx *ctx, int slot, int source, int32_t *counts, double *x_pos,
+                                      double *y_pos);
+
 /* ---- measurement ------------------------------------------------------- */
 
 #define WAYNE_PROF_KERNELS 8

@@ -28,6 +28,7 @@ F_OUT_F64 = 1 << 16
 F_EXACT_SAMPLERS = 1 << 17
 PROF_KERNELS = 8
 ABI_VERSION = 7
+MAX_SOURCES = 8   # contaminants per exposure (WAYNE_MAX_SOURCES)
 
 
 class WayneError(RuntimeError):
@@ -72,6 +73,11 @@ class ExposureDesc(C.Structure):
                 ("lc_z", _dp), ("lc_hidden", _dp), ("lc_rp", _dp), ("lc_ld", C.c_double * 4)]
 
 
+class SourceDesc(C.Structure):
+    _fields_ = [("tag", C.c_uint32), ("n_wl", C.c_int), ("wl_um", _dp), ("flux", _dp),
+                ("dx", C.c_double), ("dy", C.c_double)]
+
+
 class Profile(C.Structure):
     _fields_ = [("name", C.c_char_p * PROF_KERNELS), ("launches", C.c_uint64 * PROF_KERNELS),
                 ("ms", C.c_double * PROF_KERNELS), ("electrons", C.c_uint64)]
@@ -114,6 +120,9 @@ SYMBOLS = {
     "wayne_exposure_run_front": (C.c_int, [_vp, C.c_int]),
     "wayne_exposure_run_back": (C.c_int, [_vp, C.c_int]),
     "wayne_exposure_ramp_variant": (C.c_int, [_vp, C.c_int, C.c_char_p, C.c_int]),
+    "wayne_exposure_set_sources": (C.c_int, [_vp, C.c_int, C.POINTER(SourceDesc), C.c_int]),
+    "wayne_source_seed": (C.c_uint32, [C.c_uint32, C.c_uint32]),
+    "wayne_exposure_debug_fetch_source": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp]),
     "wayne_profile_enable": (C.c_int, [_vp, C.c_int]),
     "wayne_profile_select": (C.c_int, [_vp, C.c_uint]),
     "wayne_profile_reset": (C.c_int, [_vp]),
@@ -343,9 +352,45 @@ class Context(object):
         return make_desc(*a, **k)
 
     def upload(self, slot, desc):
+        """Stage the descriptor in `slot`; contaminants it carries (make_desc(sources=...)) are set with it."""
         self.check(self._L.wayne_exposure_upload(self._h, int(slot), C.byref(desc)))
         self._slot_meta = getattr(self, "_slot_meta", {})
         self._slot_meta[slot] = (desc.n_samples, desc.n_wl, desc.n_reads, bool(desc.flags & F_OUT_F64))
+        self._slot_src = getattr(self, "_slot_src", {})
+        self._slot_src[slot] = ()
+        sources = getattr(desc, "_sources", None)
+        if sources:
+            self.set_sources(slot, sources)
+
+    def set_sources(self, slot, sources):
+        """Contaminating field stars of the slot's uploaded exposure: a sequence of objects with tag, wl, flux, dx, dy
+        (sources.Contaminant) -- [] clears.  See wayne_exposure_set_sources."""
+        sources = list(sources)
+        arr = (SourceDesc * max(len(sources), 1))()
+        keep = []
+        for i, s in enumerate(sources):
+            wl, fl = f64(s.wl), f64(s.flux)
+            if wl.size != fl.size:
+                raise ValueError("contaminant %d: wl and flux differ in length" % i)
+            keep += [wl, fl]
+            arr[i].tag, arr[i].n_wl = int(s.tag), wl.size
+            arr[i].wl_um, arr[i].flux = ptr(wl, C.c_double), ptr(fl, C.c_double)
+            arr[i].dx, arr[i].dy = float(s.dx), float(s.dy)
+        self._slot_src = getattr(self, "_slot_src", {})
+        self._slot_src[slot] = ()        # (a refused list leaves the slot with the target alone)
+        self.check(self._L.wayne_exposure_set_sources(self._h, int(slot), arr, len(sources)))
+        self._slot_src[slot] = tuple(int(k.size) for k in keep[0::2])
+
+    def debug_fetch_source(self, slot, source):
+        """(counts, x_pos, y_pos) [K, W_i] of source `source` of the slot's last run (0 = the target)."""
+        K, W, R, _ = self._slot_meta[slot]
+        if source > 0:
+            W = self._slot_src[slot][source - 1]
+        counts = np.empty((K, W), dtype=np.int32)
+        x = np.empty((K, W), dtype=np.float64)
+        y = np.empty((K, W), dtype=np.float64)
+        self.check(self._L.wayne_exposure_debug_fetch_source(self._h, int(slot), int(source), ptr(counts), ptr(x), ptr(y)))
+        return counts, x, y
 
     def run(self, slot):
         self.check(self._L.wayne_exposure_run(self._h, int(slot)))
@@ -457,7 +502,9 @@ class Context(object):
 def make_desc(seed, exposure_index, flags, sub_scale, wl_um, flux, depth, x_ref, y_ref, dur_ms,
               sample_read, read_dt_s, replay_seed=None, rng_mode=RNG_PHILOX, threads_compat=1,
               sky_ct_s=0.0, cosmic_rate=-1.0, scale_factor=1.0, noise_mean=0.0, noise_std=0.0,
-              thrower_margin=0, thrower_splits=0, lc_z=None, lc_hidden=None, lc_rp=None, lc_ld=None):
+              thrower_margin=0, thrower_splits=0, lc_z=None, lc_hidden=None, lc_rp=None, lc_ld=None, sources=None):
+    """The exposure descriptor.  `sources`: contaminating field stars (sources.Contaminant), carried beside the C struct
+    and set by Context.upload (wayne_exposure_set_sources); None or [] = the target alone."""
     d = ExposureDesc()
     keep = []
 
@@ -503,6 +550,7 @@ def make_desc(seed, exposure_index, flags, sub_scale, wl_um, flux, depth, x_ref,
             d.lc_hidden = ptr(lc_hidden, C.c_double)
         d.lc_ld[:] = [float(v) for v in lc_ld]
     d._keep = keep
+    d._sources = tuple(sources) if sources else ()
     return d
 
 
@@ -516,6 +564,11 @@ def philox4x32(ctr, key):
     out = np.empty(4, dtype=np.uint32)
     load().wayne_philox4x32(ptr(ctr), ptr(key), ptr(out))
     return out
+
+
+def source_seed(seed, tag):
+    """The visit seed of contaminant `tag` (tag 0: `seed` itself); see wayne_source_seed."""
+    return int(load().wayne_source_seed(int(seed) & 0xFFFFFFFF, int(tag) & 0xFFFFFFFF))
 
 
 def host_sample_draws(seed, exposure, n_samples):

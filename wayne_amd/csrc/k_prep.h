@@ -16,8 +16,9 @@ __global__ void k_prep_wl(GrismDev g, int W, const double* __restrict__ wl, WlAr
                           const double* __restrict__ x_ref, const double* __restrict__ y_ref, double* __restrict__ tr) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   // the exposure's status words (total electrons, overflow flag) start from zero: cleared here, by the
-  // first kernel of the exposure, instead of by a separate fill in front of it
-  if (i < 16) misc[i] = 0u;
+  // first kernel of the exposure, instead of by a separate fill in front of it (misc = NULL: a contaminant's
+  // k_prep_wl, which runs after the target's)
+  if (misc && i < 16) misc[i] = 0u;
   if (i < K) {
     double* t = tr + kTrStride * (size_t)i;
     trace_coeffs(g, x_ref[i], y_ref[i], t);

@@ -45,6 +45,8 @@ enum Stage : uint32_t {
                       //   first); an electron whose radius half-word is 0 refines it from a side LCG seeded by the same block (k_lane)
   STAGE_POOL = 11,    // seeded stream (bin group w >> 4, column j of the group's window, sub-sample k, exposure): the row chain
                       //   of the electrons the 16 bins of a group put into that column (k_narrow, pooled rows)
+  STAGE_SOURCE = 12,  // Philox block  (tag, 0, 0, 0)                            word 0: the visit seed of contaminant `tag`
+                      //   (wayne_source_seed); its thrower-side stages (COUNTS .. POOL) run under that seed
 };
 constexpr uint32_t kThrowBlock = 128;   // electrons per STAGE_THROW stream
 

@@ -57,26 +57,64 @@ struct DevBuf {
   template <class T> T* as() const { return (T*)p; }
 };
 
-struct Slot {
+// What one source (the target, or a contaminating field star: wayne_exposure_set_sources) of an exposure holds: its
+// inputs, its per-bin and per-sub-sample scratch and its launch plan.  Each source has buffers of its own: with
+// fork_narrow, k_narrow of one source still reads its counts / prefix on the side stream while the main stream moves on.
+struct SourceState {
+  bool fused_last = false;    // the last front half ran fused: positions / routing arrays were not written (debug_fetch)
+  PrepArgs last_prep{};       // ... and k_prep_sub's arguments of that run
+  int last_chunks = 0;
+  int W = 0;
+  uint32_t seed = 0;          // visit seed of the source's thrower-side streams (wayne_source_seed)
+  DevBuf wl, flux, xref, yref;   // target: views into the slot's in_dev; contaminant: views into src_dev
+  DevBuf ratio, sigl, sigh, sens, dlam;
+  DevBuf counts, nwide, nsplit, nlane, prefix, xpos, ypos, sub, chunk_total, chunk_box, tr;
+  int kb = 1;             // sub-samples a workgroup of k_lane takes (k_lane, "BATCHES")
+  bool thin = false;      // few electrons per (workgroup, sub-sample): k_lane flushes from its first-touch list
+  double max_narrow = 0.;   // host estimate: most narrow electrons expected in a bin of the longest sub-sample
+  double max_chunk_electrons = 0.;   // host estimate: electrons of the fullest k_lane chunk in the longest sub-sample
+  double est_thrown = 0.;   // host estimate of the electrons k_throw handles in the longest sub-sample
+  unsigned char chunk_order[kMaxChunks] = {0};   // chunks of kNarrowThreads bins, most electrons first (ThrowArgs::chunk_order)
+  unsigned char lane_order[kMaxChunks] = {0};    // chunks of kLaneThreads bins, most electrons first
+  // a contaminant's own inputs (wl, flux, offset positions): a pinned arena and its device mirror, one copy
+  DevBuf src_dev;
+  char* src_stage = nullptr;
+  size_t src_stage_cap = 0;
+  hipEvent_t src_stage_ev = nullptr;
+  bool src_stage_pending = false;
+  void release_source() {
+    for (DevBuf* b : {&wl, &flux, &xref, &yref, &ratio, &sigl, &sigh, &sens, &dlam, &counts, &nwide, &nsplit, &nlane, &prefix,
+                      &xpos, &ypos, &sub, &chunk_total, &chunk_box, &tr, &src_dev})
+      b->release();
+    if (src_stage) (void)hipHostFree(src_stage);
+    src_stage = nullptr;
+    src_stage_cap = 0;
+    if (src_stage_ev) (void)hipEventDestroy(src_stage_ev);
+    src_stage_ev = nullptr;
+    src_stage_pending = false;
+  }
+};
+
+constexpr int kMaxSources = WAYNE_MAX_SOURCES;   // contaminants per exposure
+
+// An exposure slot.  Its own SourceState is the target's (source 0); extra[0 .. n_extra) are the contaminants.
+struct Slot : SourceState {
   bool uploaded = false;
   bool front_done = false;
   bool acc_dirty = false;
   bool acc_init = false;
-  bool fused_last = false;    // the last front half ran fused: positions / routing arrays were not written (debug_fetch)
-  PrepArgs last_prep{};       // ... and k_prep_sub's arguments of that run
-  int last_chunks = 0;
   bool force_throw = false;   // the last run met a bin beyond a lane's reach: run with k_throw (set by check_status)
   bool ran = false;           // a whole run was enqueued whose status word nobody has looked at yet (settle)
   wayne_exposure_desc d{};  // host copy (pointers are NOT valid after upload)
-  int W = 0, K = 0, R = 0;
+  int K = 0, R = 0;
   bool has_depth = false, has_replay_seed = false, has_lc = false, has_lc_hidden = false;
-  DevBuf wl, flux, depth, xref, yref, dur, rseed, sread, read_dt, lc_z, lc_hidden, lc_rp;   // views into in_dev (depth: owned when computed by k_lightcurve)
-  DevBuf ratio, sigl, sigh, sens, dlam;
-  DevBuf counts, nwide, nsplit, nlane, prefix, xpos, ypos, sub, chunk_total, chunk_box, tr;
+  DevBuf depth, dur, rseed, sread, read_dt, lc_z, lc_hidden, lc_rp;   // views into in_dev (depth: owned when computed by k_lightcurve)
+  int n_extra = 0;                 // contaminants of this exposure (wayne_exposure_set_sources; cleared by upload)
+  SourceState extra[kMaxSources];
+  uint32_t extra_tag[kMaxSources] = {0};
+  SourceState& source(int i) { return i == 0 ? *this : extra[i - 1]; }
   DevBuf acc, out, misc;  // misc: [0] total electrons (u64), [1] status (int)
   DevBuf seg;             // cosmic-ray segments (CosmicArgs::seg): zeroed when allocated, k_ramp clears what it reads
-  int kb = 1;             // sub-samples a workgroup of k_lane takes (k_lane, "BATCHES")
-  bool thin = false;      // few electrons per (workgroup, sub-sample): k_lane flushes from its first-touch list
   bool use_box = false;   // acc_box is valid: k_ramp loads the accumulators of a read only inside it (and where `seg` says)
   int acc_box[16][4] = {{0}};
   DevBuf in_dev;          // device mirror of the staging arena: the descriptor's arrays arrive in ONE copy
@@ -97,11 +135,6 @@ struct Slot {
   unsigned char sky_tab0[16] = {0};
   std::vector<double> read_dt_host;
   double lc_p_lo = 0., lc_p_hi = 0.;   // range of lc_rp
-  double max_narrow = 0.;   // host estimate: most narrow electrons expected in a bin of the longest sub-sample
-  double max_chunk_electrons = 0.;   // host estimate: electrons of the fullest k_lane chunk in the longest sub-sample
-  double est_thrown = 0.;   // host estimate of the electrons k_throw handles in the longest sub-sample
-  unsigned char chunk_order[kMaxChunks] = {0};   // chunks of kNarrowThreads bins, most electrons first (ThrowArgs::chunk_order)
-  unsigned char lane_order[kMaxChunks] = {0};    // chunks of kLaneThreads bins, most electrons first
   // pinned staging arena of the descriptor's arrays: uploads are enqueued from here, so
   // wayne_exposure_upload returns without waiting for the slot's stream to drain
   char* stage = nullptr;
@@ -109,9 +142,10 @@ struct Slot {
   hipEvent_t stage_ev = nullptr;
   bool stage_pending = false;
   void release() {
-    for (DevBuf* b : {&wl, &flux, &depth, &xref, &yref, &dur, &rseed, &sread, &read_dt, &lc_z, &lc_hidden, &lc_rp, &ratio, &sigl,
-                      &sigh, &sens, &dlam, &counts, &nwide, &nsplit, &nlane, &prefix, &xpos, &ypos, &sub, &chunk_total, &chunk_box, &tr, &acc, &out,
-                      &misc, &seg, &sky_tab, &in_dev})
+    release_source();
+    for (SourceState& e : extra) e.release_source();
+    n_extra = 0;
+    for (DevBuf* b : {&depth, &dur, &rseed, &sread, &read_dt, &lc_z, &lc_hidden, &lc_rp, &acc, &out, &misc, &seg, &sky_tab, &in_dev})
       b->release();
     if (sky_tab_host) (void)hipHostFree(sky_tab_host);
     sky_tab_host = nullptr;
@@ -203,6 +237,7 @@ struct wayne_ctx {
   // what the upload keeps per spectrum (host_plan.h): per-bin count rates through this grism's sensitivity, the wide
   // fraction and sigma_l of a bin, the largest PSF sigma and the wavelength range -- cached on the spectrum's content
   plan::SpectrumEstimate est;
+  plan::SpectrumEstimate src_est[kMaxSources];   // the same for the contaminants, one cache per list position
   // calibration
   bool have_cal = false;
   int subarray = 0, N = 0, S = 0, cal_R = 0;
@@ -234,6 +269,18 @@ struct wayne_ctx {
 };
 
 namespace {
+
+// k_lane's batches and its first-touch flush list of one source (knobs `batch` / `thin` applied)
+void plan_lanes(const wayne_ctx* c, SourceState& ss, int K, int W) {
+  {
+    // k_lane's batches and its first-touch flush list (plan::lane_batches)
+    int kb = 1;
+    plan::lane_batches(K, W, ss.max_chunk_electrons, &kb, &ss.thin);
+    if (c->knobs.batch >= 0) kb = (int)std::min<long long>(std::max<long long>(c->knobs.batch, 1), kLaneBatchMax);
+    ss.kb = kb;
+    if (c->knobs.thin >= 0) ss.thin = c->knobs.thin != 0;
+  }
+}
 
 int fail(wayne_ctx* c, int code, const std::string& msg) {
   if (c) c->err = msg;
@@ -470,6 +517,15 @@ void (*select_ramp(const wayne_ctx* c, const Slot& s, std::string* name))(RampAr
   return kern;
 }
 
+}  // namespace
+
+namespace {
+// host copy of a descriptor array of the slot's last upload: the pinned staging arena still holds it (at the offset
+// of the array's view in the device mirror) until the slot is uploaded again
+template <class T> const T* staged_host(const Slot& s, const DevBuf& b) {
+  return (const T*)(s.stage + ((const char*)b.p - (const char*)s.in_dev.p));
+}
+bool box_empty(const int* b) { return b[0] >= b[1] || b[2] >= b[3]; }
 }  // namespace
 
 extern "C" {
@@ -852,6 +908,7 @@ int wayne_ctx_set_grism(wayne_ctx* c, const wayne_grism_desc* g) {
   c->have_grism = true;
   // (... which also forgets what the upload kept per spectrum: it was worked out with the previous grism)
   c->est.set_grism(d, g->sens_wl_um, g->sens_val, g->n_sens);
+  for (plan::SpectrumEstimate& e : c->src_est) e.set_grism(d, g->sens_wl_um, g->sens_val, g->n_sens);
   return WAYNE_OK;
 }
 
@@ -949,6 +1006,7 @@ int wayne_exposure_upload(wayne_ctx* c, int slot, const wayne_exposure_desc* d) 
   s.uploaded = false;
   s.front_done = false;
   s.fused_last = false;      // (last_prep points into buffers this call may re-allocate)
+  s.n_extra = 0;             // a new exposure has no contaminants until wayne_exposure_set_sources says so
   int rc;
   const size_t KW = (size_t)K * W;
   {
@@ -1033,6 +1091,7 @@ int wayne_exposure_upload(wayne_ctx* c, int slot, const wayne_exposure_desc* d) 
   s.d.replay_seed = s.d.sample_read = nullptr;
   s.d.lc_z = s.d.lc_hidden = s.d.lc_rp = nullptr;
   s.W = W; s.K = K; s.R = R;
+  s.seed = d->seed;
   s.read_dt_host.assign(d->read_dt_s, d->read_dt_s + R);
   lap(0, t_lap);     // staging, copies, reservations
   {
@@ -1043,14 +1102,7 @@ int wayne_exposure_upload(wayne_ctx* c, int slot, const wayne_exposure_desc* d) 
     std::memcpy(s.lane_order, tp.lane_order, sizeof s.lane_order);
   }
   lap(1, t_lap);
-  {
-    // k_lane's batches and its first-touch flush list (plan::lane_batches)
-    int kb = 1;
-    plan::lane_batches(K, W, s.max_chunk_electrons, &kb, &s.thin);
-    if (c->knobs.batch >= 0) kb = (int)std::min<long long>(std::max<long long>(c->knobs.batch, 1), kLaneBatchMax);
-    s.kb = kb;
-    if (c->knobs.thin >= 0) s.thin = c->knobs.thin != 0;
-  }
+  plan_lanes(c, s, K, W);
   s.use_box = plan::accumulator_boxes(c->est, W, d->wl_um, d->flux, K, R, c->S, d->sub_scale, d->x_ref, d->y_ref,
                                       d->sample_read, s.acc_box) && !(c->knobs.no_acc_box > 0);
   lap(2, t_lap);
@@ -1070,6 +1122,183 @@ int wayne_exposure_upload(wayne_ctx* c, int slot, const wayne_exposure_desc* d) 
   return WAYNE_OK;
 }
 
+// The front half of one source of slot `s` (src 0 = the target, 1.. = its contaminants): prep, thrower, and -- with the
+// target only -- the cosmic rays.  A contaminant is planned and launched exactly as the single-source exposure of its
+// inputs would be (its own estimates, batches, thin / fused choice, skip_narrow and splits).
+static int front_source(wayne_ctx* c, int slot, Slot& s, SourceState& ss, int src) {
+  const wayne_exposure_desc& d = s.d;
+  const int W = ss.W, K = s.K, R = s.R, N = c->N, S = c->S;
+  WlArrays wa{ss.ratio.as<double>(), ss.sigl.as<double>(), ss.sigh.as<double>(), ss.sens.as<double>(),
+              ss.dlam.as<double>()};
+  {
+    ProfScope ps(c, PK_PREP_WL);
+    hipLaunchKernelGGL(k_prep_wl, dim3((std::max(W, K) + 255) / 256), dim3(256), 0, c->stream, c->g, W,
+                       ss.wl.as<double>(), wa, src == 0 ? s.misc.as<uint32_t>() : nullptr, K, ss.xref.as<double>(), ss.yref.as<double>(),
+                       ss.tr.as<double>());
+    HIP_TRY(c, hipGetLastError());
+  }
+  // margin of a thrower workgroup's tile around its slice of the trace: 5 sigma_h, so that practically no electron
+  // takes the in-loop global-atomic path (see k_lane)
+  bool skip_narrow = false;
+  bool lane_unlimited = false;   // split mode without a k_throw launch: the lanes take every bin (up to kLaneReach)
+  bool fused = false;            // ... and no k_prep_sub either: k_lane<.., FUSED> plans its bins itself
+  const int margin = d.thrower_margin > 0 ? d.thrower_margin : 30;
+  PrepArgs prep_args{};
+  CosmicArgs cosmic_args{};
+  {
+    PrepArgs& a = prep_args;
+    a.g = c->g;
+    a.W = W; a.K = K; a.N = N;
+    a.sub_scale = d.sub_scale;
+    a.margin = margin;
+    a.max_tile = 0x7FFFFFFF;      // the sub-sample rectangle is only the clip region of the workgroup tiles
+    a.seed = ss.seed; a.exposure = d.exposure_index; a.flags = d.flags;
+    a.scale_factor = d.scale_factor;
+    a.wl = ss.wl.as<double>(); a.flux = ss.flux.as<double>();
+    a.depth = (src == 0 && s.has_depth) ? s.depth.as<double>() : nullptr;   // (contaminants do not transit)
+    a.x_ref = ss.xref.as<double>(); a.y_ref = ss.yref.as<double>(); a.dur_ms = s.dur.as<double>();
+    a.replay_seed = s.has_replay_seed ? s.rseed.as<int32_t>() : nullptr;
+    a.sample_read = s.sread.as<int32_t>();
+    a.tr = ss.tr.as<double>();
+    a.wa = wa;
+    a.counts = ss.counts.as<int32_t>(); a.nwide = ss.nwide.as<int32_t>();
+    a.nsplit = ss.nsplit.as<int32_t>();
+    a.nlane = ss.nlane.as<int32_t>();
+    a.split_min = (d.rng_mode == WAYNE_RNG_SPLIT) ? kSplitMin : 0;
+    // no bin expected beyond a lane's cap (the rule on every BASELINE configuration): k_throw is not launched at
+    // all -- an empty launch still costs ~8 us of the exposure's critical path -- and the lanes take what they
+    // find up to kLaneReach electrons; a bin beyond that (the estimate carries no Poisson noise) sets status bit 1
+    // and the exposure is run again with k_throw when its status is read (check_status)
+    // (knob `lane_reach`: a test knob that lowers the lanes' reach so that the re-run path can be exercised)
+    int reach = kLaneReach;
+    if (c->knobs.lane_reach >= 0) reach = (int)std::min<long long>(std::max<long long>(c->knobs.lane_reach, 1), kLaneReach);
+    lane_unlimited = d.rng_mode == WAYNE_RNG_SPLIT && ss.est_thrown <= 0. && d.thrower_splits <= 0 && !s.force_throw &&
+                     c->knobs.throw_wgs < 0;
+    a.lane_max = lane_unlimited ? reach : kLaneMax;
+    a.prefix = ss.prefix.as<uint32_t>(); a.xpos = ss.xpos.as<double>(); a.ypos = ss.ypos.as<double>();
+    a.sub = ss.sub.as<SubInfo>();
+    a.total_electrons = c->counters.as<unsigned long long>();
+    a.status = (int*)(s.misc.as<char>() + 8);
+    const int n_chunks = (W + kPrepThreads - 1) / kPrepThreads;
+    a.chunk_total = ss.chunk_total.as<uint32_t>();
+    a.chunk_box = ss.chunk_box.as<double>();
+    a.fix_inline = lane_unlimited ? 1 : 0;
+    // a finely sampled scan holds a few electrons per bin and sub-sample: no bin is expected to reach the
+    // multinomial's threshold (mean <= 6 against kSplitMin = 32: 1e-13 per draw), k_narrow's launch would only find
+    // that out workgroup by workgroup (0.04 ms at K = 2233) -- it is left out, and a bin that qualifies after all
+    // flags the run, which is then repeated with every kernel (check_status)
+    skip_narrow = lane_unlimited && ss.max_narrow <= 6. && !(c->knobs.keep_narrow > 0);
+    a.no_narrow = skip_narrow ? 1 : 0;
+    CosmicArgs& ca = cosmic_args;
+    ca.R = R; ca.N = N; ca.S = S; ca.seed = ss.seed; ca.exposure = d.exposure_index;
+    ca.rate = (src == 0 && d.cosmic_rate >= 0.) ? d.cosmic_rate : -1.;   // (cosmic rays: once, with the target)
+    ca.read_dt = s.read_dt.as<double>(); ca.acc = s.acc.as<long long>();
+    ca.seg = s.seg.as<uint32_t>();
+    // thin exposure, nothing for k_throw or k_narrow expected: the lanes plan their bins themselves (k_lane, FUSED)
+    fused = lane_unlimited && skip_narrow && ss.thin && !(c->knobs.no_fuse > 0);
+    ss.fused_last = fused;
+    ss.last_prep = a;
+    ss.last_chunks = n_chunks;
+    if (!fused) {
+      ProfScope ps(c, PK_PREP_SUB);
+      hipLaunchKernelGGL(k_prep_sub, dim3(K, n_chunks), dim3(kPrepThreads), 0, c->stream, a, ca);
+      HIP_TRY(c, hipGetLastError());
+      if (!a.fix_inline) {
+        hipLaunchKernelGGL(k_prep_fix, dim3(K), dim3(kPrepThreads), 0, c->stream, a, n_chunks);
+        HIP_TRY(c, hipGetLastError());
+      }
+    }
+  }
+  {
+    ThrowArgs a{};
+    a.W = W; a.K = K; a.N = N; a.S = S;
+    a.kb = ss.kb;
+    // grid: one unit (128 electrons; 1 in replay mode) per lane of the workgroups of a sub-sample, from
+    // the host's estimate of the electrons + 8 %, but at least ~4 workgroups per CU over the launch
+    // (knob `throw_wgs` / desc.thrower_splits override); k_throw shares out what it actually finds
+    const int min_wgs = 1024;
+    int splits = d.thrower_splits;
+    if (splits <= 0) {
+      if (c->knobs.throw_wgs >= 0) {
+        splits = (int)std::max<long long>(1, (std::max<long long>(c->knobs.throw_wgs, 1) + K - 1) / K);
+      } else {
+        const double unit = (d.rng_mode == WAYNE_RNG_REPLAY) ? 1. : (double)kThrowBlock;
+        const double lanes = 1.08 * ss.est_thrown / unit;
+        splits = (int)std::min(4096., std::ceil(lanes / kThrowThreads));
+        // split mode with no bin expected beyond a lane's cap: k_throw finds nothing to do (any stray bin is
+        // handled by the one workgroup per sub-sample launched here)
+        if (d.rng_mode == WAYNE_RNG_SPLIT && ss.est_thrown <= 0. && !s.force_throw) splits = -1;
+        // a lane takes several units when the launch would exceed ~24 workgroups per CU: then ~12 per CU
+        // (each lane a handful of units) is the measured optimum (scripts/sweep_throw.py)
+        const int cap = std::max(1, (3072 + K - 1) / K);
+        if (splits > 2 * cap) splits = cap;
+        splits = splits < 0 ? 1 : std::max(splits, (min_wgs + K - 1) / K);
+      }
+    }
+    a.min_wgs = min_wgs;
+    a.splits = std::min(splits, 4096);
+    a.margin = margin;
+    const int lds_ints = thrower_lds_ints(c, a.splits, margin);
+    a.lds_ints = lds_ints;
+    a.threads_compat = d.threads_compat;
+    a.seed = ss.seed; a.exposure = d.exposure_index; a.subsample0 = 0;
+    a.flags = d.flags;
+    // grism.py:363: indices + (1014 - size) / 2 -- the same number as the frame offset 507 - SUBARRAY / 2
+    // (exposure_generator.py:630) for every sub-array, so the descriptor's sub_scale serves both: 0 for the
+    // full array, or the reference's -5 there when the caller keeps its quirks (the host then uploads the
+    // flat planes rolled by +5 px, numpy's wrap-around for the negative indices)
+    a.flat_off = d.sub_scale;
+    a.flat_wmin = c->g.flat_wmin; a.flat_wmax = c->g.flat_wmax;
+    a.flat_inv_range = 1.0 / (c->g.flat_wmax - c->g.flat_wmin);
+    a.sub = ss.sub.as<SubInfo>(); a.prefix = ss.prefix.as<uint32_t>(); a.nwide = ss.nwide.as<int32_t>();
+    a.nsplit = ss.nsplit.as<int32_t>();
+    a.nlane = ss.nlane.as<int32_t>();
+    std::memcpy(a.chunk_order, ss.chunk_order, sizeof a.chunk_order);
+    std::memcpy(a.lane_order, ss.lane_order, sizeof a.lane_order);
+    a.xpos = ss.xpos.as<double>(); a.ypos = ss.ypos.as<double>();
+    a.sigl = ss.sigl.as<double>(); a.sigh = ss.sigh.as<double>();
+    for (int i = 0; i < 4; ++i) a.flat[i] = c->has_flat ? c->flat[i].as<float>() : nullptr;
+    a.acc = s.acc.as<long long>();
+    a.frame = nullptr;
+    if ((d.flags & WAYNE_F_ADD_FLAT) && !c->has_flat) return fail(c, WAYNE_E_STATE, "run: add_flat without a flat cube");
+    const int si_ = slot % c->n_streams;
+    const bool fork = d.rng_mode == WAYNE_RNG_SPLIT && c->fork_narrow && !skip_narrow;
+    hipStream_t main_stream = c->stream;
+    {
+      // (with the fork, the PK_THROW interval spans all thrower kernels; PK_NARROW / PK_LANE are those kernels' own)
+      ProfScope ps_throw(c, PK_THROW);
+      if (fork) {
+        HIP_TRY(c, hipEventRecord(c->ev_fork[si_], main_stream));
+        HIP_TRY(c, hipStreamWaitEvent(c->side[si_], c->ev_fork[si_], 0));
+        c->stream = c->side[si_];
+        int rc;
+        {
+          ProfScope ps(c, PK_NARROW);
+          rc = launch_narrow<1>(c, a, (d.flags & WAYNE_F_EXACT_SAMPLERS) != 0);
+        }
+        if (rc == WAYNE_OK && hipEventRecord(c->ev_join[si_], c->side[si_]) != hipSuccess)
+          rc = fail(c, WAYNE_E_HIP, "run: event record on the side stream");
+        c->stream = main_stream;
+        if (rc) return rc;
+      }
+      int rc = lane_unlimited ? (int)WAYNE_OK
+               : (d.rng_mode == WAYNE_RNG_REPLAY) ? launch_throw<0, 1>(c, a, lds_ints) : launch_throw<1, 1>(c, a, lds_ints);
+      if (rc) return rc;
+      if (d.rng_mode == WAYNE_RNG_SPLIT) {
+        ProfScope ps(c, PK_LANE);
+        if ((rc = fused ? launch_lane<1>(c, a, true, &prep_args, &cosmic_args) : launch_lane<1>(c, a, ss.thin))) return rc;
+      }
+      if (fork) HIP_TRY(c, hipStreamWaitEvent(main_stream, c->ev_join[si_], 0));
+    }
+    if (!fork && d.rng_mode == WAYNE_RNG_SPLIT && !skip_narrow) {
+      ProfScope ps(c, PK_NARROW);
+      int rc = launch_narrow<1>(c, a, (d.flags & WAYNE_F_EXACT_SAMPLERS) != 0);
+      if (rc) return rc;
+    }
+  }
+  return WAYNE_OK;
+}
+
 int wayne_exposure_run_front(wayne_ctx* c, int slot) {
   if (!c) return WAYNE_E_INVALID;
   if (slot < 0 || slot >= kSlots) return fail(c, WAYNE_E_INVALID, "run: slot");
@@ -1078,7 +1307,7 @@ int wayne_exposure_run_front(wayne_ctx* c, int slot) {
   (void)hipSetDevice(c->device);
   use_slot_stream(c, slot);
   const wayne_exposure_desc& d = s.d;
-  const int W = s.W, K = s.K, R = s.R, N = c->N, S = c->S;
+  const int W = s.W, K = s.K, R = s.R, S = c->S;
   const size_t SS = (size_t)S * S;
   if (c->n_streams == 2) {
     const int other = 1 - slot % 2;
@@ -1116,173 +1345,9 @@ int wayne_exposure_run_front(wayne_ctx* c, int slot) {
     HIP_TRY(c, hipGetLastError());
   }
 
-  WlArrays wa{s.ratio.as<double>(), s.sigl.as<double>(), s.sigh.as<double>(), s.sens.as<double>(),
-              s.dlam.as<double>()};
-  {
-    ProfScope ps(c, PK_PREP_WL);
-    hipLaunchKernelGGL(k_prep_wl, dim3((std::max(W, K) + 255) / 256), dim3(256), 0, c->stream, c->g, W,
-                       s.wl.as<double>(), wa, s.misc.as<uint32_t>(), K, s.xref.as<double>(), s.yref.as<double>(),
-                       s.tr.as<double>());
-    HIP_TRY(c, hipGetLastError());
-  }
-  // margin of a thrower workgroup's tile around its slice of the trace: 5 sigma_h, so that practically no electron
-  // takes the in-loop global-atomic path (see k_lane)
-  bool skip_narrow = false;
-  bool lane_unlimited = false;   // split mode without a k_throw launch: the lanes take every bin (up to kLaneReach)
-  bool fused = false;            // ... and no k_prep_sub either: k_lane<.., FUSED> plans its bins itself
-  const int margin = d.thrower_margin > 0 ? d.thrower_margin : 30;
-  PrepArgs prep_args{};
-  CosmicArgs cosmic_args{};
-  {
-    PrepArgs& a = prep_args;
-    a.g = c->g;
-    a.W = W; a.K = K; a.N = N;
-    a.sub_scale = d.sub_scale;
-    a.margin = margin;
-    a.max_tile = 0x7FFFFFFF;      // the sub-sample rectangle is only the clip region of the workgroup tiles
-    a.seed = d.seed; a.exposure = d.exposure_index; a.flags = d.flags;
-    a.scale_factor = d.scale_factor;
-    a.wl = s.wl.as<double>(); a.flux = s.flux.as<double>();
-    a.depth = s.has_depth ? s.depth.as<double>() : nullptr;
-    a.x_ref = s.xref.as<double>(); a.y_ref = s.yref.as<double>(); a.dur_ms = s.dur.as<double>();
-    a.replay_seed = s.has_replay_seed ? s.rseed.as<int32_t>() : nullptr;
-    a.sample_read = s.sread.as<int32_t>();
-    a.tr = s.tr.as<double>();
-    a.wa = wa;
-    a.counts = s.counts.as<int32_t>(); a.nwide = s.nwide.as<int32_t>();
-    a.nsplit = s.nsplit.as<int32_t>();
-    a.nlane = s.nlane.as<int32_t>();
-    a.split_min = (d.rng_mode == WAYNE_RNG_SPLIT) ? kSplitMin : 0;
-    // no bin expected beyond a lane's cap (the rule on every BASELINE configuration): k_throw is not launched at
-    // all -- an empty launch still costs ~8 us of the exposure's critical path -- and the lanes take what they
-    // find up to kLaneReach electrons; a bin beyond that (the estimate carries no Poisson noise) sets status bit 1
-    // and the exposure is run again with k_throw when its status is read (check_status)
-    // (knob `lane_reach`: a test knob that lowers the lanes' reach so that the re-run path can be exercised)
-    int reach = kLaneReach;
-    if (c->knobs.lane_reach >= 0) reach = (int)std::min<long long>(std::max<long long>(c->knobs.lane_reach, 1), kLaneReach);
-    lane_unlimited = d.rng_mode == WAYNE_RNG_SPLIT && s.est_thrown <= 0. && d.thrower_splits <= 0 && !s.force_throw &&
-                     c->knobs.throw_wgs < 0;
-    a.lane_max = lane_unlimited ? reach : kLaneMax;
-    a.prefix = s.prefix.as<uint32_t>(); a.xpos = s.xpos.as<double>(); a.ypos = s.ypos.as<double>();
-    a.sub = s.sub.as<SubInfo>();
-    a.total_electrons = c->counters.as<unsigned long long>();
-    a.status = (int*)(s.misc.as<char>() + 8);
-    const int n_chunks = (W + kPrepThreads - 1) / kPrepThreads;
-    a.chunk_total = s.chunk_total.as<uint32_t>();
-    a.chunk_box = s.chunk_box.as<double>();
-    a.fix_inline = lane_unlimited ? 1 : 0;
-    // a finely sampled scan holds a few electrons per bin and sub-sample: no bin is expected to reach the
-    // multinomial's threshold (mean <= 6 against kSplitMin = 32: 1e-13 per draw), k_narrow's launch would only find
-    // that out workgroup by workgroup (0.04 ms at K = 2233) -- it is left out, and a bin that qualifies after all
-    // flags the run, which is then repeated with every kernel (check_status)
-    skip_narrow = lane_unlimited && s.max_narrow <= 6. && !(c->knobs.keep_narrow > 0);
-    a.no_narrow = skip_narrow ? 1 : 0;
-    CosmicArgs& ca = cosmic_args;
-    ca.R = R; ca.N = N; ca.S = S; ca.seed = d.seed; ca.exposure = d.exposure_index;
-    ca.rate = (d.cosmic_rate >= 0.) ? d.cosmic_rate : -1.;
-    ca.read_dt = s.read_dt.as<double>(); ca.acc = s.acc.as<long long>();
-    ca.seg = s.seg.as<uint32_t>();
-    // thin exposure, nothing for k_throw or k_narrow expected: the lanes plan their bins themselves (k_lane, FUSED)
-    fused = lane_unlimited && skip_narrow && s.thin && !(c->knobs.no_fuse > 0);
-    s.fused_last = fused;
-    s.last_prep = a;
-    s.last_chunks = n_chunks;
-    if (!fused) {
-      ProfScope ps(c, PK_PREP_SUB);
-      hipLaunchKernelGGL(k_prep_sub, dim3(K, n_chunks), dim3(kPrepThreads), 0, c->stream, a, ca);
-      HIP_TRY(c, hipGetLastError());
-      if (!a.fix_inline) {
-        hipLaunchKernelGGL(k_prep_fix, dim3(K), dim3(kPrepThreads), 0, c->stream, a, n_chunks);
-        HIP_TRY(c, hipGetLastError());
-      }
-    }
-  }
-  {
-    ThrowArgs a{};
-    a.W = W; a.K = K; a.N = N; a.S = S;
-    a.kb = s.kb;
-    // grid: one unit (128 electrons; 1 in replay mode) per lane of the workgroups of a sub-sample, from
-    // the host's estimate of the electrons + 8 %, but at least ~4 workgroups per CU over the launch
-    // (knob `throw_wgs` / desc.thrower_splits override); k_throw shares out what it actually finds
-    const int min_wgs = 1024;
-    int splits = d.thrower_splits;
-    if (splits <= 0) {
-      if (c->knobs.throw_wgs >= 0) {
-        splits = (int)std::max<long long>(1, (std::max<long long>(c->knobs.throw_wgs, 1) + K - 1) / K);
-      } else {
-        const double unit = (d.rng_mode == WAYNE_RNG_REPLAY) ? 1. : (double)kThrowBlock;
-        const double lanes = 1.08 * s.est_thrown / unit;
-        splits = (int)std::min(4096., std::ceil(lanes / kThrowThreads));
-        // split mode with no bin expected beyond a lane's cap: k_throw finds nothing to do (any stray bin is
-        // handled by the one workgroup per sub-sample launched here)
-        if (d.rng_mode == WAYNE_RNG_SPLIT && s.est_thrown <= 0. && !s.force_throw) splits = -1;
-        // a lane takes several units when the launch would exceed ~24 workgroups per CU: then ~12 per CU
-        // (each lane a handful of units) is the measured optimum (scripts/sweep_throw.py)
-        const int cap = std::max(1, (3072 + K - 1) / K);
-        if (splits > 2 * cap) splits = cap;
-        splits = splits < 0 ? 1 : std::max(splits, (min_wgs + K - 1) / K);
-      }
-    }
-    a.min_wgs = min_wgs;
-    a.splits = std::min(splits, 4096);
-    a.margin = margin;
-    const int lds_ints = thrower_lds_ints(c, a.splits, margin);
-    a.lds_ints = lds_ints;
-    a.threads_compat = d.threads_compat;
-    a.seed = d.seed; a.exposure = d.exposure_index; a.subsample0 = 0;
-    a.flags = d.flags;
-    // grism.py:363: indices + (1014 - size) / 2 -- the same number as the frame offset 507 - SUBARRAY / 2
-    // (exposure_generator.py:630) for every sub-array, so the descriptor's sub_scale serves both: 0 for the
-    // full array, or the reference's -5 there when the caller keeps its quirks (the host then uploads the
-    // flat planes rolled by +5 px, numpy's wrap-around for the negative indices)
-    a.flat_off = d.sub_scale;
-    a.flat_wmin = c->g.flat_wmin; a.flat_wmax = c->g.flat_wmax;
-    a.flat_inv_range = 1.0 / (c->g.flat_wmax - c->g.flat_wmin);
-    a.sub = s.sub.as<SubInfo>(); a.prefix = s.prefix.as<uint32_t>(); a.nwide = s.nwide.as<int32_t>();
-    a.nsplit = s.nsplit.as<int32_t>();
-    a.nlane = s.nlane.as<int32_t>();
-    std::memcpy(a.chunk_order, s.chunk_order, sizeof a.chunk_order);
-    std::memcpy(a.lane_order, s.lane_order, sizeof a.lane_order);
-    a.xpos = s.xpos.as<double>(); a.ypos = s.ypos.as<double>();
-    a.sigl = s.sigl.as<double>(); a.sigh = s.sigh.as<double>();
-    for (int i = 0; i < 4; ++i) a.flat[i] = c->has_flat ? c->flat[i].as<float>() : nullptr;
-    a.acc = s.acc.as<long long>();
-    a.frame = nullptr;
-    if ((d.flags & WAYNE_F_ADD_FLAT) && !c->has_flat) return fail(c, WAYNE_E_STATE, "run: add_flat without a flat cube");
-    const int si_ = slot % c->n_streams;
-    const bool fork = d.rng_mode == WAYNE_RNG_SPLIT && c->fork_narrow && !skip_narrow;
-    hipStream_t main_stream = c->stream;
-    {
-      // (with the fork, the PK_THROW interval spans all thrower kernels; PK_NARROW / PK_LANE are those kernels' own)
-      ProfScope ps_throw(c, PK_THROW);
-      if (fork) {
-        HIP_TRY(c, hipEventRecord(c->ev_fork[si_], main_stream));
-        HIP_TRY(c, hipStreamWaitEvent(c->side[si_], c->ev_fork[si_], 0));
-        c->stream = c->side[si_];
-        int rc;
-        {
-          ProfScope ps(c, PK_NARROW);
-          rc = launch_narrow<1>(c, a, (d.flags & WAYNE_F_EXACT_SAMPLERS) != 0);
-        }
-        if (rc == WAYNE_OK && hipEventRecord(c->ev_join[si_], c->side[si_]) != hipSuccess)
-          rc = fail(c, WAYNE_E_HIP, "run: event record on the side stream");
-        c->stream = main_stream;
-        if (rc) return rc;
-      }
-      int rc = lane_unlimited ? (int)WAYNE_OK
-               : (d.rng_mode == WAYNE_RNG_REPLAY) ? launch_throw<0, 1>(c, a, lds_ints) : launch_throw<1, 1>(c, a, lds_ints);
-      if (rc) return rc;
-      if (d.rng_mode == WAYNE_RNG_SPLIT) {
-        ProfScope ps(c, PK_LANE);
-        if ((rc = fused ? launch_lane<1>(c, a, true, &prep_args, &cosmic_args) : launch_lane<1>(c, a, s.thin))) return rc;
-      }
-      if (fork) HIP_TRY(c, hipStreamWaitEvent(main_stream, c->ev_join[si_], 0));
-    }
-    if (!fork && d.rng_mode == WAYNE_RNG_SPLIT && !skip_narrow) {
-      ProfScope ps(c, PK_NARROW);
-      int rc = launch_narrow<1>(c, a, (d.flags & WAYNE_F_EXACT_SAMPLERS) != 0);
-      if (rc) return rc;
-    }
+  for (int i = 0; i <= s.n_extra; ++i) {
+    int rc = front_source(c, slot, s, s.source(i), i);
+    if (rc) return rc;
   }
   s.acc_dirty = true;
   s.front_done = true;
@@ -1494,28 +1559,30 @@ int wayne_exposure_synthesize(wayne_ctx* c, const wayne_exposure_desc* d, void* 
   return wayne_exposure_download(c, 0, out_reads);
 }
 
-int wayne_exposure_debug_fetch(wayne_ctx* c, int slot, int32_t* counts, double* x_pos, double* y_pos,
-                               double* acc_e) {
+// debug_fetch of source `src` of the slot (0 = the target; acc_e is the slot's, shared by all sources)
+static int fetch_source(wayne_ctx* c, int slot, int src, int32_t* counts, double* x_pos, double* y_pos, double* acc_e) {
   if (!c) return WAYNE_E_INVALID;
   if (slot < 0 || slot >= kSlots) return fail(c, WAYNE_E_INVALID, "debug_fetch: slot");
   Slot& s = c->slots[slot];
   if (!s.uploaded) return fail(c, WAYNE_E_STATE, "debug_fetch: slot not uploaded");
+  if (src < 0 || src > s.n_extra) return fail(c, WAYNE_E_INVALID, "debug_fetch: no such source in this slot");
+  SourceState& ss = s.source(src);
   (void)hipSetDevice(c->device);
   use_slot_stream(c, slot);
-  const size_t KW = (size_t)s.K * s.W;
-  if (counts) HIP_TRY(c, hipMemcpyAsync(counts, s.counts.p, KW * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-  if (s.fused_last && (x_pos || y_pos)) {
+  const size_t KW = (size_t)s.K * ss.W;
+  if (counts) HIP_TRY(c, hipMemcpyAsync(counts, ss.counts.p, KW * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+  if (ss.fused_last && (x_pos || y_pos)) {
     // a fused front half kept no positions: k_prep_sub works them out now (same code, same inputs; its cosmic-ray
     // stage off and its electron count into a spare counter)
-    PrepArgs a = s.last_prep;
+    PrepArgs a = ss.last_prep;
     a.total_electrons = c->counters.as<unsigned long long>() + 1;
     CosmicArgs off{};
     off.rate = -1.;
-    hipLaunchKernelGGL(k_prep_sub, dim3(s.K, s.last_chunks), dim3(kPrepThreads), 0, c->stream, a, off);
+    hipLaunchKernelGGL(k_prep_sub, dim3(s.K, ss.last_chunks), dim3(kPrepThreads), 0, c->stream, a, off);
     HIP_TRY(c, hipGetLastError());
   }
-  if (x_pos) HIP_TRY(c, hipMemcpyAsync(x_pos, s.xpos.p, KW * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  if (y_pos) HIP_TRY(c, hipMemcpyAsync(y_pos, s.ypos.p, KW * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  if (x_pos) HIP_TRY(c, hipMemcpyAsync(x_pos, ss.xpos.p, KW * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  if (y_pos) HIP_TRY(c, hipMemcpyAsync(y_pos, ss.ypos.p, KW * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   {
     // (between run_front and run_back: a run that met a bin beyond the lanes' reach is repeated with k_throw first)
     bool rerun = false;
@@ -1525,7 +1592,7 @@ int wayne_exposure_debug_fetch(wayne_ctx* c, int slot, int32_t* counts, double* 
       s.force_throw = true;
       c->reruns += 1;
       if ((rc = wayne_exposure_run_front(c, slot))) return rc;
-      return wayne_exposure_debug_fetch(c, slot, counts, x_pos, y_pos, acc_e);
+      return fetch_source(c, slot, src, counts, x_pos, y_pos, acc_e);
     }
   }
   if (acc_e) {
@@ -1536,6 +1603,15 @@ int wayne_exposure_debug_fetch(wayne_ctx* c, int slot, int32_t* counts, double* 
     for (size_t i = 0; i < n; ++i) acc_e[i] = (double)tmp[i] * kInvQ;
   }
   return check_status(c, s);
+}
+
+int wayne_exposure_debug_fetch(wayne_ctx* c, int slot, int32_t* counts, double* x_pos, double* y_pos,
+                               double* acc_e) {
+  return fetch_source(c, slot, 0, counts, x_pos, y_pos, acc_e);
+}
+
+int wayne_exposure_debug_fetch_source(wayne_ctx* c, int slot, int source, int32_t* counts, double* x_pos, double* y_pos) {
+  return fetch_source(c, slot, source, counts, x_pos, y_pos, nullptr);
 }
 
 int wayne_exposure_debug_boxes(wayne_ctx* c, int slot, int32_t* boxes, int32_t* segments, int* use_box) {
@@ -1573,6 +1649,133 @@ int wayne_exposure_debug_depth(wayne_ctx* c, int slot, double* depth) {
   HIP_TRY(c, hipMemcpyAsync(depth, s.depth.p, (size_t)s.K * s.W * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   return WAYNE_OK;
+}
+
+// ---------------------------------------------------------------------------
+// contaminating field stars
+// ---------------------------------------------------------------------------
+
+int wayne_exposure_set_sources(wayne_ctx* c, int slot, const wayne_source_desc* src, int n) {
+  if (!c) return WAYNE_E_INVALID;
+  if (slot < 0 || slot >= kSlots) return fail(c, WAYNE_E_INVALID, "set_sources: slot");
+  Slot& s = c->slots[slot];
+  if (!s.uploaded) return fail(c, WAYNE_E_STATE, "set_sources: slot not uploaded");
+  if (n < 0 || n > kMaxSources) return fail(c, WAYNE_E_INVALID, "set_sources: n must be 0 .. WAYNE_MAX_SOURCES");
+  if (n > 0 && !src) return fail(c, WAYNE_E_INVALID, "set_sources: null list");
+  if (n > 0 && s.d.rng_mode == WAYNE_RNG_REPLAY)
+    return fail(c, WAYNE_E_INVALID, "set_sources: replay mode reproduces the reference, which has no second star");
+  const int K = s.K, R = s.R;
+  for (int i = 0; i < n; ++i) {
+    const wayne_source_desc& q = src[i];
+    if (q.tag == 0) return fail(c, WAYNE_E_INVALID, "set_sources: tag 0 is the target's");
+    for (int j = 0; j < i; ++j)
+      if (src[j].tag == q.tag) return fail(c, WAYNE_E_INVALID, "set_sources: duplicate tag");
+    if (q.n_wl < 2 || q.n_wl > 32768) return fail(c, WAYNE_E_INVALID, "set_sources: n_wl must be 2 .. 32768");
+    if ((long long)K * q.n_wl > 0x7FFFFFFFLL) return fail(c, WAYNE_E_INVALID, "set_sources: K*W too large");
+    if (!q.wl_um || !q.flux) return fail(c, WAYNE_E_INVALID, "set_sources: null array");
+    if (!std::isfinite(q.dx) || !std::isfinite(q.dy)) return fail(c, WAYNE_E_INVALID, "set_sources: offset not finite");
+  }
+  (void)hipSetDevice(c->device);
+  use_slot_stream(c, slot);
+  // from here on a failure leaves the slot as uploaded: the target alone, with the target's boxes
+  s.n_extra = 0;
+  s.front_done = false;
+  const double* x0 = staged_host<double>(s, s.xref);
+  const double* y0 = staged_host<double>(s, s.yref);
+  const double* dur = staged_host<double>(s, s.dur);
+  const int32_t* sread = staged_host<int32_t>(s, s.sread);
+  const bool no_box = c->knobs.no_acc_box > 0;
+  s.use_box = plan::accumulator_boxes(c->est, s.W, staged_host<double>(s, s.wl), staged_host<double>(s, s.flux), K, R, c->S,
+                                      s.d.sub_scale, x0, y0, sread, s.acc_box) && !no_box;
+  if (n == 0) return WAYNE_OK;
+  bool use_box = s.use_box;
+  int box[16][4];
+  std::memcpy(box, s.acc_box, sizeof box);
+  for (int i = 0; i < n; ++i) {
+    const wayne_source_desc& q = src[i];
+    SourceState& e = s.extra[i];
+    const int W = q.n_wl;
+    const size_t KW = (size_t)K * W;
+    const size_t need = 2 * align64((size_t)W * 8) + 2 * align64((size_t)K * 8) + 256;
+    if (e.src_stage_pending) {       // the previous copy from this arena may still be running
+      HIP_TRY(c, hipEventSynchronize(e.src_stage_ev));
+      e.src_stage_pending = false;
+    }
+    if (e.src_stage_cap < need) {
+      if (e.src_stage) (void)hipHostFree(e.src_stage);
+      e.src_stage = nullptr;
+      e.src_stage_cap = 0;
+      if (hipHostMalloc((void**)&e.src_stage, need, hipHostMallocDefault) != hipSuccess)
+        return fail(c, WAYNE_E_NOMEM, "set_sources: pinned staging allocation failed");
+      e.src_stage_cap = need;
+    }
+    if (!e.src_stage_ev) HIP_TRY(c, hipEventCreateWithFlags(&e.src_stage_ev, hipEventDisableTiming));
+    HIP_TRY(c, e.src_dev.reserve(e.src_stage_cap));
+    size_t used = 0;
+    auto place = [&](DevBuf& b, size_t bytes) -> char* {
+      char* h = e.src_stage + used;
+      b.view((char*)e.src_dev.p + used);
+      used += align64(bytes);
+      return h;
+    };
+    std::memcpy(place(e.wl, (size_t)W * 8), q.wl_um, (size_t)W * 8);
+    std::memcpy(place(e.flux, (size_t)W * 8), q.flux, (size_t)W * 8);
+    double* xs = (double*)place(e.xref, (size_t)K * 8);
+    double* ys = (double*)place(e.yref, (size_t)K * 8);
+    for (int k = 0; k < K; ++k) { xs[k] = x0[k] + q.dx; ys[k] = y0[k] + q.dy; }
+    HIP_TRY(c, hipMemcpyAsync(e.src_dev.p, e.src_stage, used, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipEventRecord(e.src_stage_ev, c->stream));
+    e.src_stage_pending = true;
+    for (DevBuf* b : {&e.ratio, &e.sigl, &e.sigh, &e.sens, &e.dlam}) HIP_TRY(c, b->reserve((size_t)W * sizeof(double)));
+    HIP_TRY(c, e.counts.reserve(KW * sizeof(int32_t)));
+    HIP_TRY(c, e.nwide.reserve(KW * sizeof(int32_t)));
+    HIP_TRY(c, e.nsplit.reserve(KW * sizeof(int32_t)));
+    HIP_TRY(c, e.nlane.reserve(KW * sizeof(int32_t)));
+    HIP_TRY(c, e.prefix.reserve((size_t)K * (W + 1) * sizeof(uint32_t)));
+    HIP_TRY(c, e.xpos.reserve(KW * sizeof(double)));
+    HIP_TRY(c, e.ypos.reserve(KW * sizeof(double)));
+    HIP_TRY(c, e.sub.reserve((size_t)K * sizeof(SubInfo)));
+    HIP_TRY(c, e.tr.reserve((size_t)K * kTrStride * sizeof(double)));
+    {
+      const size_t n_chunks = (size_t)(W + kPrepThreads - 1) / kPrepThreads;
+      HIP_TRY(c, e.chunk_total.reserve((size_t)K * n_chunks * sizeof(uint32_t)));
+      HIP_TRY(c, e.chunk_box.reserve((size_t)K * n_chunks * 4 * sizeof(double)));
+    }
+    e.W = W;
+    e.seed = wayne_source_seed(s.d.seed, q.tag);
+    e.fused_last = false;
+    // the plan of the single-source exposure with these inputs (wayne_exposure_upload)
+    plan::ThrowPlan tp;
+    plan::estimate_thrown(c->src_est[i], W, q.wl_um, q.flux, K, dur, s.d.scale_factor, s.d.rng_mode, &tp);
+    e.est_thrown = tp.est_thrown; e.max_chunk_electrons = tp.max_chunk_electrons; e.max_narrow = tp.max_narrow;
+    std::memcpy(e.chunk_order, tp.chunk_order, sizeof e.chunk_order);
+    std::memcpy(e.lane_order, tp.lane_order, sizeof e.lane_order);
+    plan_lanes(c, e, K, W);
+    // k_ramp loads (and clears) an accumulator only inside its read's box: the box is the union over the sources, each
+    // at its own positions -- a contaminant's electrons outside it would vanish from this exposure and reappear in the
+    // next one of the slot
+    int b[16][4];
+    if (!plan::accumulator_boxes(c->src_est[i], W, q.wl_um, q.flux, K, R, c->S, s.d.sub_scale, xs, ys, sread, b)) {
+      use_box = false;
+    } else {
+      for (int r = 0; r < 16; ++r) {
+        if (box_empty(b[r])) continue;
+        if (box_empty(box[r])) { std::memcpy(box[r], b[r], sizeof b[r]); continue; }
+        box[r][0] = std::min(box[r][0], b[r][0]); box[r][1] = std::max(box[r][1], b[r][1]);
+        box[r][2] = std::min(box[r][2], b[r][2]); box[r][3] = std::max(box[r][3], b[r][3]);
+      }
+    }
+    s.extra_tag[i] = q.tag;
+  }
+  std::memcpy(s.acc_box, box, sizeof box);
+  s.use_box = use_box && !no_box;
+  s.n_extra = n;
+  return WAYNE_OK;
+}
+
+uint32_t wayne_source_seed(uint32_t seed, uint32_t tag) {
+  if (tag == 0) return seed;
+  return philox4x32_10(tag, 0u, 0u, 0u, seed, STAGE_SOURCE).v[0];
 }
 
 // ---------------------------------------------------------------------------

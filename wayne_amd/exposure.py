@@ -137,6 +137,11 @@ class Exposure(object):
                 for n_, v_ in enumerate(ld, 1):
                     cards.append(("LD%d" % n_, float(v_), "Non-linear limb darkening coeff %d" % n_))
         cards.append(("STARX", float(e.get("x_ref", 0.0)), "x position of star on frame (full frame))"))
+        contaminants = e.get("contaminants") or ()
+        if contaminants:
+            # field stars on the exposure (sources.Contaminant): only then, so that the files of other visits keep
+            # their bytes; exposure_file_is_whole compares these cards on --resume
+            cards += contaminant_cards(contaminants)
         return fitsio.Header(cards)
 
     def generate_fits(self, out_dir="", filename=None, ldcoeffs=None):
@@ -228,3 +233,15 @@ class FitsWriterPool(object):
         sys.setswitchinterval(self._switch_interval)
         if self._errors:
             raise self._errors[0]
+
+
+def contaminant_cards(contaminants):
+    """NCONTAM and, per contaminant n (1-based list position), CONTDXn / CONTDYn / CONTFRn: the primary header's record
+    of the field stars of an exposure (flux_ratio 0 when the Contaminant was built without one)."""
+    cards = [("NCONTAM", len(contaminants), "number of contaminating field stars")]
+    for n, c in enumerate(contaminants, 1):
+        fr = float(c.flux_ratio) if getattr(c, "flux_ratio", None) is not None else 0.0
+        cards += [("CONTDX%d" % n, float(c.dx), "contaminant %d: x offset from the target (px)" % n),
+                  ("CONTDY%d" % n, float(c.dy), "contaminant %d: y offset from the target (px)" % n),
+                  ("CONTFR%d" % n, fr, "contaminant %d: detected electrons / target's" % n)]
+    return cards

@@ -59,11 +59,21 @@ class Observation(object):
         # (BITPIX -64) either way, and a full-array exposure is 67 MB instead of 134 MB to bring over PCIe;
         # frame_options["out_dtype"] = np.float64 (CLI: --float64-reads) keeps the float64 arithmetic to the file.
         self.frame_options = {"out_dtype": np.float32}
+        self.contaminants = []       # field stars on every exposure (setup_contaminants)
 
     # -- setup_* (observation.py:46-291) ----------------------------------------
     def setup_observation(self, x_ref, y_ref, spatial_scan=False, scan_speed=False):
         self.x_ref, self.y_ref = x_ref, y_ref
         self.spatial_scan, self.scan_speed = spatial_scan, scan_speed
+
+    def setup_contaminants(self, contaminants):
+        """Field stars whose first-order spectra land on every exposure of the visit: a list of sources.Contaminant
+        (sources.from_config builds them from the YAML's `contaminants:` section); [] or None: the target alone."""
+        from .sources import MAX_CONTAMINANTS
+        contaminants = list(contaminants or [])
+        if len(contaminants) > MAX_CONTAMINANTS:
+            raise ValueError("at most %d contaminants" % MAX_CONTAMINANTS)
+        self.contaminants = contaminants
 
     def setup_simulator(self, sample_rate=False, clip_values_det_limits=True, threads=2):
         self.sample_rate = sample_rate
@@ -213,7 +223,23 @@ class Observation(object):
                     abs(float(p0["EXPSTART"]) - (float(self.exp_start_times[number - 1]) - 2400000.5)) < 1e-7)
         except (KeyError, TypeError, ValueError):
             return False
-        return bool(same) and all(size == S * S * 8 for (h, size) in hdus[1::5])
+        if not (same and self._contaminant_cards_match(p0)):
+            return False
+        return all(size == S * S * 8 for (h, size) in hdus[1::5])
+
+    def _contaminant_cards_match(self, p0):
+        """The file's NCONTAM / CONTDXn / CONTDYn / CONTFRn cards are this visit's contaminants (absent: none), so that
+        --resume after a contaminant was added or changed regenerates the files instead of mixing two fields."""
+        from .exposure import contaminant_cards
+        want = {k: v for (k, v, _) in contaminant_cards(self.contaminants)} if self.contaminants else {}
+        try:
+            if "NCONTAM" not in p0:
+                return not want
+            if not want or int(p0["NCONTAM"]) != want["NCONTAM"]:
+                return False
+            return all(abs(float(p0[k]) - float(v)) <= 1e-9 * max(1.0, abs(float(v))) for k, v in want.items())
+        except (KeyError, TypeError, ValueError):
+            return False
 
     def run_observation(self, rank=0, world=1, write_fits=True, resume=False):
         """Generate the direct image and every exposure (observation.py:388-413); with
@@ -358,6 +384,8 @@ class Observation(object):
                       add_read_noise=self.add_read_noise, add_stellar_noise=self.add_stellar_noise,
                       add_initial_bias=self.add_initial_bias, threads=self.threads)
         common.update(self.frame_options)
+        if self.contaminants:
+            common["contaminants"] = self.contaminants
         if self.spatial_scan:
             args = (x_ref, y_ref, self.x_jitter, self.y_jitter, self.wl, self.stellar_flux, planet_depths,
                     self.scan_speed, sample_rate, sample_mid_points, sample_durations, read_index)

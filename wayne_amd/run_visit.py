@@ -16,6 +16,9 @@ examples/hd209458b_12181_simulation_parameters.yml): sections `general`
   * `--resume`: exposures whose files are already in the output directory (whole, and this visit's: same start time and
     mode) are skipped; files are written under a temporary name and renamed, so an interrupted run leaves no partial
     file under a final name.  A resumed visit's files are those of an uninterrupted one (per-exposure Philox keys);
+  * an optional top-level `contaminants:` list puts field stars on every exposure (wayne_amd/sources.py): per entry
+    `dx`, `dy` (px from the target), `flux_ratio` (detected electrons relative to the target's) and a black-body
+    `temperature` or a PHOENIX `spectrum_file`; at most 8.  First order only, not in the direct image, constant;
   * `--gpus G`: the process starts G rank processes itself (one per GPU of this node, before anything touches a
     GPU) and waits for them; under an external launcher (WORLD_SIZE / RANK set, one process per GPU) it is one
     rank.  Each rank generates its round-robin share of the exposures (observation.py:403-405 is the axis) on the
@@ -31,7 +34,7 @@ import numpy as np
 import yaml
 
 from . import calibration as _cal
-from . import detector, grism, launch, observation, tools
+from . import detector, grism, launch, observation, sources, tools
 from .trend_generators import scan_speed_varations
 
 
@@ -131,6 +134,14 @@ def build_observation(cfg, base_dir=".", calibration=None, device=0):
     coeffs = _get(_get(cfg, "trends", {}), "visit_trend_coeffs")
     if coeffs:
         obs.setup_visit_trend(coeffs)
+    # optional `contaminants:` section (no reference counterpart): field stars on every exposure; every rank of a
+    # --gpus run builds its Observation here, from the same YAML, so each gets the same list
+    try:
+        contaminants = sources.from_config(_get(cfg, "contaminants"), chosen_grism, wl, stellar_flux_scaled, base_dir)
+    except sources.ContaminantConfigError as e:
+        raise WFC3SimConfigError(str(e))
+    if contaminants:
+        obs.setup_contaminants(contaminants)
     return obs
 
 

@@ -36,6 +36,8 @@ def descriptor_digest(desc):
             h.update(repr((name, v)).encode())
     for a in desc._keep:
         h.update(np.ascontiguousarray(a).tobytes())
+    for src in getattr(desc, "_sources", ()):      # contaminants (none: the digest of a descriptor without them)
+        h.update(src.digest_bytes())
     return h.hexdigest()
 
 
