@@ -331,6 +331,38 @@ uint32_t wayne_source_seed(uint32_t seed, uint32_t tag);
 int wayne_exposure_debug_fetch_source(wayne_ctx *ctx, int slot, int source, int32_t *counts, double *x_pos,
                                       double *y_pos);
 
+/* ---- charge trapping: the ramp effect per pixel (no reference counterpart) ---- */
+
+/*
+ * Two trap populations per pixel, p = 0 slow and 1 fast (the model of Zhou et al. 2017, AJ 153, 243): occupancy E_p
+ * (e-) obeys dE/dt = eta f (1 - E/N) - E/tau for the pixel's collected-charge rate f (e-/s), stepped exactly read
+ * interval by read interval on the device.  Read r shows what the pixel collected (its accumulators: thrower electrons
+ * of every source and cosmic-ray hits, plus its sky draws; not the gaussian-noise stage) minus
+ * (E_s + E_f)(r) - (E_s + E_f)(zero read).  Reference pixels are not trapped; nothing is drawn.
+ * E_p at the zero read comes from start[p]: a table over the pixel's mean rate f_bar = (sum of its accumulators +
+ * master sky x sum_r sky_ct_s read_dt[r]) / sum_r read_dt[r].  Point 0 is f = 0, points 1 .. n_rate-1 are log-spaced
+ * from rate_lo to rate_hi; the device interpolates linearly in f below rate_lo, linearly in ln f above it, and clamps at
+ * rate_hi.  The caller plans the table (wayne_amd/traps.py: the visit's history at f_bar), so exposures stay
+ * independent of each other.
+ */
+typedef struct wayne_trap_desc {
+  double n_traps[2];       /* capacity N_p (e-), > 0 */
+  double efficiency[2];    /* trapping efficiency eta_p in [0, 1] */
+  double lifetime_s[2];    /* lifetime tau_p (s), > 0 */
+  int n_rate;              /* G: points of each start table, 2 .. WAYNE_MAX_TRAP_RATES */
+  double rate_lo, rate_hi; /* e-/s, 0 < rate_lo < rate_hi (rate_lo <= rate_hi when G = 2) */
+  const double *start[2];  /* [G] each: E_p at the zero read, every entry in [0, n_traps[p]] */
+} wayne_trap_desc;
+
+#define WAYNE_MAX_TRAP_RATES 4096
+
+/* After wayne_exposure_upload, before run: trap the slot's exposure (t = NULL clears; upload clears too, so callers
+ * that never call this get today's exposure).  The table is staged in the slot.  WAYNE_E_INVALID (the slot stays usable,
+ * without traps) in replay mode, on non-finite values, n_traps <= 0, efficiency outside [0, 1], lifetime <= 0, n_rate
+ * outside 2 .. WAYNE_MAX_TRAP_RATES, bad rates or a table entry outside [0, n_traps]; WAYNE_E_STATE on a slot that is
+ * not uploaded.  The back half then launches k_ramp_trap<...> (wayne_exposure_ramp_variant names it). */
+int wayne_exposure_set_traps(wayne_ctx *ctx, int slot, const wayne_trap_desc *t);
+
 /* ---- measurement ------------------------------------------------------- */
 
 #define WAYNE_PROF_KERNELS 8

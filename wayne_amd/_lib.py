@@ -29,6 +29,7 @@ F_EXACT_SAMPLERS = 1 << 17
 PROF_KERNELS = 8
 ABI_VERSION = 7
 MAX_SOURCES = 8   # contaminants per exposure (WAYNE_MAX_SOURCES)
+MAX_TRAP_RATES = 4096   # points of a charge-trap start table (WAYNE_MAX_TRAP_RATES)
 
 
 class WayneError(RuntimeError):
@@ -78,6 +79,11 @@ class SourceDesc(C.Structure):
                 ("dx", C.c_double), ("dy", C.c_double)]
 
 
+class TrapDesc(C.Structure):
+    _fields_ = [("n_traps", C.c_double * 2), ("efficiency", C.c_double * 2), ("lifetime_s", C.c_double * 2),
+                ("n_rate", C.c_int), ("rate_lo", C.c_double), ("rate_hi", C.c_double), ("start", _dp * 2)]
+
+
 class Profile(C.Structure):
     _fields_ = [("name", C.c_char_p * PROF_KERNELS), ("launches", C.c_uint64 * PROF_KERNELS),
                 ("ms", C.c_double * PROF_KERNELS), ("electrons", C.c_uint64)]
@@ -122,6 +128,7 @@ SYMBOLS = {
     "wayne_exposure_ramp_variant": (C.c_int, [_vp, C.c_int, C.c_char_p, C.c_int]),
     "wayne_exposure_set_sources": (C.c_int, [_vp, C.c_int, C.POINTER(SourceDesc), C.c_int]),
     "wayne_source_seed": (C.c_uint32, [C.c_uint32, C.c_uint32]),
+    "wayne_exposure_set_traps": (C.c_int, [_vp, C.c_int, C.POINTER(TrapDesc)]),
     "wayne_exposure_debug_fetch_source": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp]),
     "wayne_profile_enable": (C.c_int, [_vp, C.c_int]),
     "wayne_profile_select": (C.c_int, [_vp, C.c_uint]),
@@ -352,7 +359,8 @@ class Context(object):
         return make_desc(*a, **k)
 
     def upload(self, slot, desc):
-        """Stage the descriptor in `slot`; contaminants it carries (make_desc(sources=...)) are set with it."""
+        """Stage the descriptor in `slot`; contaminants and charge traps it carries (make_desc(sources=..., traps=...))
+        are set with it."""
         self.check(self._L.wayne_exposure_upload(self._h, int(slot), C.byref(desc)))
         self._slot_meta = getattr(self, "_slot_meta", {})
         self._slot_meta[slot] = (desc.n_samples, desc.n_wl, desc.n_reads, bool(desc.flags & F_OUT_F64))
@@ -361,6 +369,27 @@ class Context(object):
         sources = getattr(desc, "_sources", None)
         if sources:
             self.set_sources(slot, sources)
+        traps = getattr(desc, "_traps", None)
+        if traps is not None:
+            self.set_traps(slot, traps)
+
+    def set_traps(self, slot, traps):
+        """Charge traps of the slot's uploaded exposure: a traps.ExposureTraps (the model and this exposure's start tables
+        [2, G]) -- None clears.  See wayne_exposure_set_traps."""
+        if traps is None:
+            self.check(self._L.wayne_exposure_set_traps(self._h, int(slot), None))
+            return
+        m, table = traps.traps, np.ascontiguousarray(traps.table, dtype=np.float64)
+        if table.ndim != 2 or table.shape[0] != 2:
+            raise ValueError("charge traps: the start tables have shape (2, G)")
+        t = TrapDesc()
+        t.n_traps[:] = [float(v) for v in m.array("n_traps")]
+        t.efficiency[:] = [float(v) for v in m.array("efficiency")]
+        t.lifetime_s[:] = [float(v) for v in m.array("lifetime_s")]
+        t.n_rate, t.rate_lo, t.rate_hi = int(table.shape[1]), float(m.rate_lo), float(m.rate_hi)
+        rows = [np.ascontiguousarray(table[0]), np.ascontiguousarray(table[1])]
+        t.start[0], t.start[1] = ptr(rows[0], C.c_double), ptr(rows[1], C.c_double)
+        self.check(self._L.wayne_exposure_set_traps(self._h, int(slot), C.byref(t)))
 
     def set_sources(self, slot, sources):
         """Contaminating field stars of the slot's uploaded exposure: a sequence of objects with tag, wl, flux, dx, dy
@@ -502,9 +531,12 @@ class Context(object):
 def make_desc(seed, exposure_index, flags, sub_scale, wl_um, flux, depth, x_ref, y_ref, dur_ms,
               sample_read, read_dt_s, replay_seed=None, rng_mode=RNG_PHILOX, threads_compat=1,
               sky_ct_s=0.0, cosmic_rate=-1.0, scale_factor=1.0, noise_mean=0.0, noise_std=0.0,
-              thrower_margin=0, thrower_splits=0, lc_z=None, lc_hidden=None, lc_rp=None, lc_ld=None, sources=None):
+              thrower_margin=0, thrower_splits=0, lc_z=None, lc_hidden=None, lc_rp=None, lc_ld=None, sources=None,
+              traps=None):
     """The exposure descriptor.  `sources`: contaminating field stars (sources.Contaminant), carried beside the C struct
-    and set by Context.upload (wayne_exposure_set_sources); None or [] = the target alone."""
+    and set by Context.upload (wayne_exposure_set_sources); None or [] = the target alone.  `traps`: charge traps
+    (traps.ExposureTraps, or a traps.ChargeTraps whose table is flat at `initial`), set by Context.upload
+    (wayne_exposure_set_traps); None = no trapping."""
     d = ExposureDesc()
     keep = []
 
@@ -551,6 +583,10 @@ def make_desc(seed, exposure_index, flags, sub_scale, wl_um, flux, depth, x_ref,
         d.lc_ld[:] = [float(v) for v in lc_ld]
     d._keep = keep
     d._sources = tuple(sources) if sources else ()
+    if traps is not None:
+        from . import traps as _traps
+        traps = _traps.for_exposure(traps)
+    d._traps = traps
     return d
 
 

@@ -40,6 +40,62 @@ struct RampArgs {
   uint32_t* seg;             // [ceil(S*S / 64)] read and cleared
 };
 
+// Charge trapping (wayne_exposure_set_traps; no reference counterpart): a pixel's two trap populations p (0 slow,
+// 1 fast) hold E_p electrons, dE/dt = eta f (1 - E/N) - E/tau for the pixel's collected-charge rate f.  Over a read
+// interval of constant f the exact step is E += (E_inf - E)(1 - e^{-c dt}), c = eta f / N + 1/tau, E_inf = eta f / c;
+// what the traps hold is missing from the read: observed(r) = collected(r) - (E(r) - E(0)).  E_p at the zero read is
+// the host's table `start` (grid point 0 = f 0, points 1 .. G-1 log-spaced from rate_lo to rate_hi) interpolated at
+// the pixel's mean rate f_bar over the exposure: linear in f below rate_lo, linear in ln f above it, clamped at rate_hi.
+struct TrapArgs {
+  const double* start_d;     // [2][G] float64 (the generic loop)
+  const float* start_f;      // [2][G] float32 (the production chain)
+  int G;
+  double rate_lo, ln_lo, u_scale;          // u_scale = (G - 2) / ln(rate_hi / rate_lo) (0 when G = 2)
+  double eta[2], eta_n[2], inv_tau[2];     // eta, eta / N, 1 / tau per population
+  double sum_dt;             // sum_r read_dt[r]
+  double sum_bg;             // sum_r (double)RampArgs::bg[r]: expected sky electrons of the exposure per unit master sky
+  // the per-read numbers in float32 for the production chain (scalar registers, no conversion in its read loop; the
+  // once-per-pixel table lookup, trap_start<float>, converts rate_lo / ln_lo / u_scale itself)
+  float eta_f[2], eta_n_f[2], inv_tau_f[2], inv_sum_dt_f, sum_bg_f;
+  float dt[16], inv_dt[16];  // read_dt[r] and 1 / read_dt[r]
+};
+
+// 1 - e^{-x} for x >= 0 without the cancellation of 1 - exp(-x) at small x (slow traps at sky rates: x ~ 2e-4 a read).
+// float32: a fifth-order Taylor polynomial below 1/8 (relative error < x^5 / 720 <= 5e-8), the hardware exp above
+// (absolute error ~6e-8, relative <= 5e-7 there).  float64: expm1.
+__device__ __forceinline__ float one_minus_exp_neg(float x) {
+  const float p = x * fmaf(x, fmaf(x, fmaf(x, fmaf(x, 1.f / 120.f, -1.f / 24.f), 1.f / 6.f), -0.5f), 1.f);
+  return x < 0.125f ? p : 1.0f - __builtin_amdgcn_exp2f(-1.4426950408889634f * x);
+}
+__device__ __forceinline__ double one_minus_exp_neg(double x) { return -expm1(-x); }
+
+// One read interval of one population at constant rate f: the exact step (above)
+template <class T>
+__device__ __forceinline__ T trap_step(T E, T f, T dt, T eta, T eta_n, T inv_tau) {
+  const T c = eta_n * f + inv_tau;
+  T einf;
+  if constexpr (std::is_same<T, float>::value) einf = (eta * f) * __builtin_amdgcn_rcpf(c);
+  else einf = (eta * f) / c;
+  return E + (einf - E) * one_minus_exp_neg(c * dt);
+}
+
+// E_p at the zero read: population `pop`'s start table at the pixel's mean rate f
+template <class T>
+__device__ __forceinline__ T trap_start(const T* tab, const TrapArgs& t, int pop, T f) {
+  const T* e = tab + pop * t.G;
+  const T lo = (T)t.rate_lo;
+  if (!(f > (T)0)) return e[0];
+  if (f < lo) return e[0] + (e[1] - e[0]) * (f / lo);
+  T ln_f;
+  if constexpr (std::is_same<T, float>::value) ln_f = __logf(f);
+  else ln_f = log(f);
+  const T u = (ln_f - (T)t.ln_lo) * (T)t.u_scale;
+  if (!(u < (T)(t.G - 2))) return e[t.G - 1];
+  const int i = (int)u;
+  const T w = u - (T)i;
+  return e[1 + i] + (e[2 + i] - e[1 + i]) * w;
+}
+
 // (kSkyAlias, kSkyPiece, kMaxReads: plan_consts.h)
 
 #ifndef WAYNE_RAMP_THREADS
@@ -303,8 +359,10 @@ __device__ __forceinline__ void sky_counts(const RampArgs& a, uint32_t p, int ti
 // remainder in pieces (a master sky with hot pixels)
 // NOISE: the optional gaussian noise stage (noise_mean / noise_std; off in every shipped configuration) is
 // compiled in or out: its stream would otherwise hold four registers of a kernel that lives at the 64-VGPR limit
-template <class OutT, bool FAST, int SKY, bool NOISE, bool ALLON>
-__device__ __forceinline__ void ramp_body(const RampArgs& a) {
+// TRAP: charge trapping (TrapArgs; k_ramp_trap only): the pixel's mean rate in a pre-pass over its live accumulators,
+// one interpolation of the start table, then per read and population the exact step of the trap occupancy
+template <class OutT, bool FAST, int SKY, bool NOISE, bool ALLON, bool TRAP = false>
+__device__ __forceinline__ void ramp_body(const RampArgs& a, const TrapArgs& tr = TrapArgs{}) {
   constexpr bool ALIAS = SKY != 0;
   typedef typename std::conditional<FAST, FastMath, ExactMath<float> >::type M;
   static_assert(kSkyAlias <= kRampThreads, "the sky tables and the per-thread sky counts share one LDS array");
@@ -494,6 +552,31 @@ __device__ __forceinline__ void ramp_body(const RampArgs& a) {
   double inv_g = 1.0 / kGain;
   if (interior && gainvar && !(std::is_same<OutT, float>::value && FAST && SKY == 1 && !NOISE)) inv_g = 1.0 / (double)g32;
 
+  // charge traps: the pixel's mean collected-charge rate over the exposure -- its accumulators (only the reads whose
+  // wave is live load anything) plus its EXPECTED sky -- and from it what its traps hold at the zero read.  Reference
+  // pixels are not trapped (their reads are set to zero below).
+  float te_s = 0.f, te_f = 0.f, te_0 = 0.f;              // production chain: slow, fast, their sum at the zero read
+  double td_s = 0., td_f = 0.;                           // generic loop
+  if constexpr (TRAP) {
+    if (interior) {
+      long long qs = 0;
+      for (int r = 0; r < a.R; ++r)
+        if (acc_live(r)) qs += ld_acc(r);
+      const float sky_px = skyv > 0.f ? skyv : 0.f;
+      if constexpr (std::is_same<OutT, float>::value && FAST && SKY == 1 && !NOISE) {
+        const float e_acc = fmaf((float)(int)(qs >> 32), 16.0f, (float)(uint32_t)qs * 3.725290298461914e-09f);
+        const float fbar = fmaf(sky_px, tr.sum_bg_f, e_acc) * tr.inv_sum_dt_f;
+        te_s = trap_start<float>(tr.start_f, tr, 0, fbar);
+        te_f = trap_start<float>(tr.start_f, tr, 1, fbar);
+        te_0 = te_s + te_f;
+      } else {
+        const double fbar = ((double)qs * kInvQ + (double)sky_px * tr.sum_bg) / tr.sum_dt;
+        td_s = trap_start<double>(tr.start_d, tr, 0, fbar);
+        td_f = trap_start<double>(tr.start_d, tr, 1, fbar);
+      }
+    }
+  }
+
   // software-pipelined ramp: the planes of read r+1 are requested before the
   // (VALU-heavy) work on read r so that HBM latency hides behind it.  The dark planes and the reads are
   // streamed once: non-temporal loads / stores (kNT; measured: 0.076 -> 0.070 ms)
@@ -561,12 +644,22 @@ __device__ __forceinline__ void ramp_body(const RampArgs& a) {
           bg_prev = bg_bits;                               // remainder mean and the thresholds of its search
           sr.set(fmaxf(skyv * bg - sky_base * bg, 0.f));
         }
+        float dn = 0.f;                                    // (TRAP) the electrons this read interval collected
         if (live) {                                        // (scalar branch)
           if (q != 0) __builtin_amdgcn_raw_buffer_store_b64(v2u{0u, 0u}, rs_acc, off8, (uint32_t)r * acc_plane, 0);
           Q += (unsigned long long)q;
           q_any = true;
+          if constexpr (TRAP) dn = fmaf((float)(int)(q >> 32), 16.0f, (float)(uint32_t)q * 3.725290298461914e-09f);
         }
-        if (has_sky_px && bg > 0.f) ksum += sky_draw_count_int(s_tab[tab + sky_lvl], sr, rn);   // (skyv = 0 off the sky; bg is the wave's)
+        if constexpr (TRAP) {
+          if (has_sky_px && bg > 0.f) {
+            const int k_sky = sky_draw_count_int(s_tab[tab + sky_lvl], sr, rn);
+            ksum += k_sky;
+            dn += (float)k_sky;
+          }
+        } else {
+          if (has_sky_px && bg > 0.f) ksum += sky_draw_count_int(s_tab[tab + sky_lvl], sr, rn);   // (skyv = 0 off the sky; bg is the wave's)
+        }
         float zd = 0.f, zr = 0.f;
         uint32_t w0, w1;
         rn.next2(w0, w1);
@@ -575,6 +668,12 @@ __device__ __forceinline__ void ramp_body(const RampArgs& a) {
         if (q_any) {                                       // (scalar branch; the asm keeps it one: 95 % of the waves skip it)
           asm volatile("" ::: "memory");
           e = fmaf((float)(int)(Q >> 32), 16.0f, fmaf((float)(uint32_t)Q, 3.725290298461914e-09f, e));
+        }
+        if constexpr (TRAP) {                              // the interval's rate -> each population's step; what the
+          const float f = dn * tr.inv_dt[r], dt = tr.dt[r];   // traps hold beyond the zero read's is not in the read
+          te_s = trap_step<float>(te_s, f, dt, tr.eta_f[0], tr.eta_n_f[0], tr.inv_tau_f[0]);
+          te_f = trap_step<float>(te_f, f, dt, tr.eta_f[1], tr.eta_n_f[1], tr.inv_tau_f[1]);
+          e = e - ((te_s + te_f) - te_0);
         }
         float v = e * inv_gf;
         if (f_dark) v = v + fmaf(de, zd, ds);              // (de: already max(err, 1e-5), see wayne_ctx_set_calibration)
@@ -619,6 +718,8 @@ __device__ __forceinline__ void ramp_body(const RampArgs& a) {
       // those saves a quarter of the kernel's HBM traffic
       if (q != 0) __builtin_amdgcn_raw_buffer_store_b64(v2u{0u, 0u}, rs_acc, off8, (uint32_t)r * acc_plane, 0);
       px = (double)q * kInvQ;
+      double chg;                    // (TRAP) collected charge of the interval: the gaussian-noise stage is not charge
+      if constexpr (TRAP) chg = px;
       if (do_noise) {                // _gen_noise (:477-484, :712-727)
         const double dt = a.read_dt[r];
         float z0, z1;
@@ -633,12 +734,34 @@ __device__ __forceinline__ void ramp_body(const RampArgs& a) {
             sky_c = s_c[r];
             srem.set(fmaxf(lam - sky_base * sky_c, 0.f));
           }
-          if (lam > 0.f) px = px + (double)sky_draw_count_int(s_tab[s_tab0[r] + sky_lvl], srem, rs);
+          if constexpr (TRAP) {
+            if (lam > 0.f) {
+              const double k = (double)sky_draw_count_int(s_tab[s_tab0[r] + sky_lvl], srem, rs);
+              px = px + k;
+              chg = chg + k;
+            }
+          } else {
+            if (lam > 0.f) px = px + (double)sky_draw_count_int(s_tab[s_tab0[r] + sky_lvl], srem, rs);
+          }
         } else if (ALIAS) {
-          if (lam > 0.f) px = px + (double)sky_draw<M, SKY == 2>(s_tab[s_tab0[r] + sky_lvl], sky_base * s_c[r], lam, rs);
+          if (lam > 0.f) {
+            const double k = (double)sky_draw<M, SKY == 2>(s_tab[s_tab0[r] + sky_lvl], sky_base * s_c[r], lam, rs);
+            px = px + k;
+            if constexpr (TRAP) chg = chg + k;
+          }
         } else {
-          px = px + (double)s_tab[r][tid];
+          const double k = (double)s_tab[r][tid];
+          px = px + k;
+          if constexpr (TRAP) chg = chg + k;
         }
+      }
+      if constexpr (TRAP) {          // charge traps (see the production chain), in fp64
+        const double dt = a.read_dt[r];
+        const double es = trap_step<double>(td_s, chg / dt, dt, tr.eta[0], tr.eta_n[0], tr.inv_tau[0]);
+        const double ef = trap_step<double>(td_f, chg / dt, dt, tr.eta[1], tr.eta_n[1], tr.inv_tau[1]);
+        px = px - ((es + ef) - (td_s + td_f));
+        td_s = es;
+        td_f = ef;
       }
       px = px * inv_g;               // electrons -> DN (:507-511)
     }
@@ -675,6 +798,13 @@ __global__ __launch_bounds__(kRampThreads) __attribute__((amdgpu_waves_per_eu(8,
 template <class OutT, bool FAST, int SKY, bool NOISE>
 __global__ __launch_bounds__(kRampThreads) void k_ramp_wide(RampArgs a) {
   ramp_body<OutT, FAST, SKY, NOISE, false>(a);
+}
+// With charge traps (wayne_exposure_set_traps): the same template list as k_ramp, so that a trace names the variant.
+// Not pinned: the production variants take 70-72 registers, and under the 64-register pin they spill 22-26 VGPRs.
+// At 72 registers one 1024-thread workgroup fits a CU (4 waves per SIMD), where k_ramp fits two (8 waves per SIMD).
+template <class OutT, bool FAST, int SKY, bool NOISE, bool ALLON>
+__global__ __launch_bounds__(kRampThreads) void k_ramp_trap(RampArgs a, TrapArgs t) {
+  ramp_body<OutT, FAST, SKY, NOISE, ALLON, true>(a, t);
 }
 
 }  // namespace wayne

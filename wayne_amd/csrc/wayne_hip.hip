@@ -135,6 +135,17 @@ struct Slot : SourceState {
   unsigned char sky_tab0[16] = {0};
   std::vector<double> read_dt_host;
   double lc_p_lo = 0., lc_p_hi = 0.;   // range of lc_rp
+  // charge traps of this exposure (wayne_exposure_set_traps; cleared by upload): the parameters, and the start tables
+  // in one device buffer -- [2][G] float64 (generic loop), then [2][G] float32 (production chain) -- from a pinned copy
+  bool traps_on = false;
+  double trap_n[2] = {1., 1.}, trap_eta[2] = {0., 0.}, trap_tau[2] = {1., 1.}, trap_lo = 0., trap_hi = 0.;
+  int trap_G = 0;
+  size_t trap_f_off = 0;             // byte offset of the float32 tables
+  DevBuf trap_tab;
+  char* trap_stage = nullptr;
+  size_t trap_stage_cap = 0;
+  hipEvent_t trap_ev = nullptr;
+  bool trap_pending = false;
   // pinned staging arena of the descriptor's arrays: uploads are enqueued from here, so
   // wayne_exposure_upload returns without waiting for the slot's stream to drain
   char* stage = nullptr;
@@ -145,8 +156,16 @@ struct Slot : SourceState {
     release_source();
     for (SourceState& e : extra) e.release_source();
     n_extra = 0;
-    for (DevBuf* b : {&depth, &dur, &rseed, &sread, &read_dt, &lc_z, &lc_hidden, &lc_rp, &acc, &out, &misc, &seg, &sky_tab, &in_dev})
+    for (DevBuf* b : {&depth, &dur, &rseed, &sread, &read_dt, &lc_z, &lc_hidden, &lc_rp, &acc, &out, &misc, &seg, &sky_tab, &in_dev,
+                      &trap_tab})
       b->release();
+    traps_on = false;
+    if (trap_stage) (void)hipHostFree(trap_stage);
+    trap_stage = nullptr;
+    trap_stage_cap = 0;
+    if (trap_ev) (void)hipEventDestroy(trap_ev);
+    trap_ev = nullptr;
+    trap_pending = false;
     if (sky_tab_host) (void)hipHostFree(sky_tab_host);
     sky_tab_host = nullptr;
     if (sky_tab_ev) (void)hipEventDestroy(sky_tab_ev);
@@ -496,8 +515,23 @@ int launch_lane(wayne_ctx* c, const ThrowArgs& a, bool thin, const PrepArgs* fus
 }
 
 
+// k_ramp_trap<reads' type, production / exact math, sky sampler, gaussian-noise stage, every switch on>
+typedef void (*RampTrapKernel)(RampArgs, TrapArgs);
+template <class OutT, bool FAST, int SKY>
+RampTrapKernel trap_noise(bool noise) { return noise ? k_ramp_trap<OutT, FAST, SKY, true, false> : k_ramp_trap<OutT, FAST, SKY, false, false>; }
+template <class OutT, bool FAST>
+RampTrapKernel trap_sky(int sky, bool noise) {
+  return sky == 1 ? trap_noise<OutT, FAST, 1>(noise) : sky == 2 ? trap_noise<OutT, FAST, 2>(noise) : trap_noise<OutT, FAST, 0>(noise);
+}
+RampTrapKernel pick_ramp_trap(bool f64, bool exact, int sky, bool noise, bool allon) {
+  if (allon) return k_ramp_trap<float, true, 1, false, true>;
+  return f64 ? (exact ? trap_sky<double, false>(sky, noise) : trap_sky<double, true>(sky, noise))
+             : (exact ? trap_sky<float, false>(sky, noise) : trap_sky<float, true>(sky, noise));
+}
+
 // The k_ramp instantiation the back half of slot `s` launches, and (if asked) its name as the kernel trace prints it.
-void (*select_ramp(const wayne_ctx* c, const Slot& s, std::string* name))(RampArgs) {
+// A slot with charge traps launches k_ramp_trap instead: *trap (when given) is then set, else left null.
+void (*select_ramp(const wayne_ctx* c, const Slot& s, std::string* name, RampTrapKernel* trap = nullptr))(RampArgs) {
   const wayne_exposure_desc& d = s.d;
   const bool f64 = (d.flags & WAYNE_F_OUT_F64) != 0, exact = (d.flags & WAYNE_F_EXACT_SAMPLERS) != 0;
   const int sky_mode = !s.sky_alias_on ? 0 : (s.sky_pieces ? 2 : 1);
@@ -507,11 +541,16 @@ void (*select_ramp(const wayne_ctx* c, const Slot& s, std::string* name))(RampAr
   const uint32_t all_on = WAYNE_F_ADD_DARK | WAYNE_F_ADD_NON_LINEAR | WAYNE_F_CLIP_DET_LIMITS | WAYNE_F_ADD_READ_NOISE;
   const bool allon = !f64 && !exact && sky_mode == 1 && !noise && (d.flags & all_on) == all_on && c->has_dark && c->has_lin;
   if (allon) kern = k_ramp<float, true, 1, false, true>;
+  if (trap) *trap = s.traps_on ? pick_ramp_trap(f64, exact, sky_mode, noise, allon) : nullptr;
   if (name) {
     const bool pinned = !exact && sky_mode != 0 && !noise;      // ramp_kernel(): k_ramp where it fits 64 registers, else k_ramp_wide
     char buf[96];
-    std::snprintf(buf, sizeof buf, "%s<%s, %s, %d, %s%s>", pinned ? "k_ramp" : "k_ramp_wide", f64 ? "double" : "float",
-                  exact ? "false" : "true", sky_mode, noise ? "true" : "false", pinned ? (allon ? ", true" : ", false") : "");
+    if (s.traps_on)
+      std::snprintf(buf, sizeof buf, "k_ramp_trap<%s, %s, %d, %s, %s>", f64 ? "double" : "float", exact ? "false" : "true",
+                    sky_mode, noise ? "true" : "false", allon ? "true" : "false");
+    else
+      std::snprintf(buf, sizeof buf, "%s<%s, %s, %d, %s%s>", pinned ? "k_ramp" : "k_ramp_wide", f64 ? "double" : "float",
+                    exact ? "false" : "true", sky_mode, noise ? "true" : "false", pinned ? (allon ? ", true" : ", false") : "");
     *name = buf;
   }
   return kern;
@@ -1007,6 +1046,7 @@ int wayne_exposure_upload(wayne_ctx* c, int slot, const wayne_exposure_desc* d) 
   s.front_done = false;
   s.fused_last = false;      // (last_prep points into buffers this call may re-allocate)
   s.n_extra = 0;             // a new exposure has no contaminants until wayne_exposure_set_sources says so
+  s.traps_on = false;        // ... and no charge traps until wayne_exposure_set_traps says so
   int rc;
   const size_t KW = (size_t)K * W;
   {
@@ -1399,9 +1439,37 @@ int wayne_exposure_run_back(wayne_ctx* c, int slot) {
   const unsigned blocks = (unsigned)(((size_t)S * S + threads - 1) / threads);
   {
     ProfScope ps(c, PK_RAMP, true);
-    void (*kern)(RampArgs) = select_ramp(c, s, nullptr);
-    if (ps.on) hipExtLaunchKernelGGL(kern, dim3(blocks), dim3(threads), 0, c->stream, ps.rec.a, ps.rec.b, 0, a);
-    else hipLaunchKernelGGL(kern, dim3(blocks), dim3(threads), 0, c->stream, a);
+    RampTrapKernel trap = nullptr;
+    void (*kern)(RampArgs) = select_ramp(c, s, nullptr, &trap);
+    if (trap) {
+      // charge traps (wayne_exposure_set_traps): the model, the per-read intervals and the staged start tables
+      TrapArgs t{};
+      t.G = s.trap_G;
+      t.start_d = s.trap_tab.as<double>();
+      t.start_f = (const float*)((const char*)s.trap_tab.p + s.trap_f_off);
+      t.rate_lo = s.trap_lo;
+      t.ln_lo = std::log(s.trap_lo);
+      t.u_scale = s.trap_G > 2 ? (double)(s.trap_G - 2) / std::log(s.trap_hi / s.trap_lo) : 0.;
+      for (int p = 0; p < 2; ++p) {
+        t.eta[p] = s.trap_eta[p];
+        t.eta_n[p] = s.trap_eta[p] / s.trap_n[p];
+        t.inv_tau[p] = 1.0 / s.trap_tau[p];
+        t.eta_f[p] = (float)t.eta[p]; t.eta_n_f[p] = (float)t.eta_n[p]; t.inv_tau_f[p] = (float)t.inv_tau[p];
+      }
+      for (int r = 0; r < s.R && r < 16; ++r) {
+        t.sum_dt += s.read_dt_host[r];
+        t.sum_bg += (double)a.bg[r];
+        t.dt[r] = (float)s.read_dt_host[r];
+        t.inv_dt[r] = (float)(1.0 / s.read_dt_host[r]);
+      }
+      t.inv_sum_dt_f = (float)(1.0 / t.sum_dt);
+      t.sum_bg_f = (float)t.sum_bg;
+      if (ps.on) hipExtLaunchKernelGGL(trap, dim3(blocks), dim3(threads), 0, c->stream, ps.rec.a, ps.rec.b, 0, a, t);
+      else hipLaunchKernelGGL(trap, dim3(blocks), dim3(threads), 0, c->stream, a, t);
+    } else {
+      if (ps.on) hipExtLaunchKernelGGL(kern, dim3(blocks), dim3(threads), 0, c->stream, ps.rec.a, ps.rec.b, 0, a);
+      else hipLaunchKernelGGL(kern, dim3(blocks), dim3(threads), 0, c->stream, a);
+    }
     HIP_TRY(c, hipGetLastError());
   }
   s.acc_dirty = false;
@@ -1770,6 +1838,78 @@ int wayne_exposure_set_sources(wayne_ctx* c, int slot, const wayne_source_desc* 
   std::memcpy(s.acc_box, box, sizeof box);
   s.use_box = use_box && !no_box;
   s.n_extra = n;
+  return WAYNE_OK;
+}
+
+// ---------------------------------------------------------------------------
+// charge trapping
+// ---------------------------------------------------------------------------
+
+int wayne_exposure_set_traps(wayne_ctx* c, int slot, const wayne_trap_desc* t) {
+  if (!c) return WAYNE_E_INVALID;
+  if (slot < 0 || slot >= kSlots) return fail(c, WAYNE_E_INVALID, "set_traps: slot");
+  Slot& s = c->slots[slot];
+  if (!s.uploaded) return fail(c, WAYNE_E_STATE, "set_traps: slot not uploaded");
+  s.traps_on = false;             // from here on a refusal leaves the slot usable, without traps
+  if (!t) return WAYNE_OK;
+  if (s.d.rng_mode == WAYNE_RNG_REPLAY)
+    return fail(c, WAYNE_E_INVALID, "set_traps: replay mode reproduces the reference, which has no charge traps");
+  const int G = t->n_rate;
+  if (G < 2 || G > WAYNE_MAX_TRAP_RATES) return fail(c, WAYNE_E_INVALID, "set_traps: n_rate must be 2 .. WAYNE_MAX_TRAP_RATES");
+  if (!std::isfinite(t->rate_lo) || !std::isfinite(t->rate_hi) || !(t->rate_lo > 0.) ||
+      !(G > 2 ? t->rate_hi > t->rate_lo : t->rate_hi >= t->rate_lo))
+    return fail(c, WAYNE_E_INVALID, "set_traps: need finite 0 < rate_lo < rate_hi");
+  for (int p = 0; p < 2; ++p) {
+    const double n = t->n_traps[p], eta = t->efficiency[p], tau = t->lifetime_s[p];
+    if (!std::isfinite(n) || !(n > 0.)) return fail(c, WAYNE_E_INVALID, "set_traps: n_traps must be finite and > 0");
+    if (!std::isfinite(eta) || !(eta >= 0. && eta <= 1.)) return fail(c, WAYNE_E_INVALID, "set_traps: efficiency must lie in [0, 1]");
+    if (!std::isfinite(tau) || !(tau > 0.)) return fail(c, WAYNE_E_INVALID, "set_traps: lifetime_s must be finite and > 0");
+    if (!t->start[p]) return fail(c, WAYNE_E_INVALID, "set_traps: null start table");
+    for (int j = 0; j < G; ++j) {
+      const double e = t->start[p][j];
+      if (!std::isfinite(e) || !(e >= 0. && e <= n))
+        return fail(c, WAYNE_E_INVALID, "set_traps: start table entries must lie in [0, n_traps]");
+    }
+  }
+  for (int r = 0; r < s.R; ++r)
+    if (!(s.read_dt_host[r] > 0.)) return fail(c, WAYNE_E_INVALID, "set_traps: every read interval must be > 0");
+  (void)hipSetDevice(c->device);
+  use_slot_stream(c, slot);
+  const size_t off_f = align64((size_t)2 * G * sizeof(double)), need = off_f + (size_t)2 * G * sizeof(float);
+  if (s.trap_pending) {              // the previous copy from the pinned tables may still be running
+    HIP_TRY(c, hipEventSynchronize(s.trap_ev));
+    s.trap_pending = false;
+  }
+  if (s.trap_stage_cap < need) {
+    if (s.trap_stage) (void)hipHostFree(s.trap_stage);
+    s.trap_stage = nullptr;
+    s.trap_stage_cap = 0;
+    if (hipHostMalloc((void**)&s.trap_stage, need, hipHostMallocDefault) != hipSuccess)
+      return fail(c, WAYNE_E_NOMEM, "set_traps: pinned staging allocation failed");
+    s.trap_stage_cap = need;
+  }
+  if (!s.trap_ev) HIP_TRY(c, hipEventCreateWithFlags(&s.trap_ev, hipEventDisableTiming));
+  double* hd = (double*)s.trap_stage;
+  float* hf = (float*)(s.trap_stage + off_f);
+  for (int p = 0; p < 2; ++p)
+    for (int j = 0; j < G; ++j) {
+      hd[p * G + j] = t->start[p][j];
+      hf[p * G + j] = (float)t->start[p][j];
+    }
+  HIP_TRY(c, s.trap_tab.reserve(s.trap_stage_cap));
+  HIP_TRY(c, hipMemcpyAsync(s.trap_tab.p, s.trap_stage, need, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipEventRecord(s.trap_ev, c->stream));
+  s.trap_pending = true;
+  for (int p = 0; p < 2; ++p) {
+    s.trap_n[p] = t->n_traps[p];
+    s.trap_eta[p] = t->efficiency[p];
+    s.trap_tau[p] = t->lifetime_s[p];
+  }
+  s.trap_lo = t->rate_lo;
+  s.trap_hi = t->rate_hi;
+  s.trap_G = G;
+  s.trap_f_off = off_f;
+  s.traps_on = true;
   return WAYNE_OK;
 }
 

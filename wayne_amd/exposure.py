@@ -142,6 +142,10 @@ class Exposure(object):
             # field stars on the exposure (sources.Contaminant): only then, so that the files of other visits keep
             # their bytes; exposure_file_is_whole compares these cards on --resume
             cards += contaminant_cards(contaminants)
+        traps = e.get("charge_traps")
+        if traps is not None:
+            # charge trapping (traps.ChargeTraps): only then, likewise; exposure_file_is_whole compares these cards too
+            cards += traps.cards()
         return fitsio.Header(cards)
 
     def generate_fits(self, out_dir="", filename=None, ldcoeffs=None):

@@ -27,6 +27,7 @@ import warnings
 import numpy as np
 
 from . import _lib, engine as _engine, exposure, lightcurve, tools
+from . import traps as _traps
 from .trend_generators import scan_speed_varations
 
 MS_PER_YEAR = 365.25 * 86400. * 1000.
@@ -118,7 +119,7 @@ class ExposureGenerator(object):
                        clip_values_det_limits=True, add_read_noise=True, add_stellar_noise=True,
                        add_initial_bias=True, progress_bar=None, threads=2,
                        rng_mode=_lib.RNG_SPLIT, out_dtype=np.float32, reference_quirks=False,
-                       record=None, exact_samplers=False, contaminants=None):
+                       record=None, exact_samplers=False, contaminants=None, charge_traps=None):
         """Generate a spatially scanned exposure (exposure_generator.py:178-405).
 
         Extra keywords (not in the reference): `rng_mode` -- RNG_SPLIT (default:
@@ -140,7 +141,10 @@ class ExposureGenerator(object):
         `exact_samplers` evaluates the per-pixel Poisson / normal draws with IEEE
         divide / sqrt and accurate log / exp / sin / cos instead of the hardware
         approximations (same algorithm and streams; for parity runs); `contaminants` -- field stars whose first-order
-        spectra land on the same exposure (a list of sources.Contaminant; staring_frame passes it on too).
+        spectra land on the same exposure (a list of sources.Contaminant; staring_frame passes it on too);
+        `charge_traps` -- per-pixel charge trapping, the ramp effect (traps.ExposureTraps: the model with this exposure's
+        start tables from its visit, as Observation.setup_charge_traps passes them; or a traps.ChargeTraps alone, whose
+        traps then start every pixel at `initial`).
         """
         start_time = time.time()
         slot = self._submit_slot
@@ -151,7 +155,7 @@ class ExposureGenerator(object):
             sample_mid_points, sample_durations, read_index, ssv_generator, noise_mean, noise_std, add_dark,
             add_flat, cosmic_rate, sky_background, scale_factor, add_gain_variations, add_non_linear,
             clip_values_det_limits, add_read_noise, add_stellar_noise, add_initial_bias, progress_bar, threads,
-            rng_mode, out_dtype, reference_quirks, exact_samplers, contaminants)
+            rng_mode, out_dtype, reference_quirks, exact_samplers, contaminants, charge_traps)
         if self._prepare_only:
             self._prepared = (eng, desc, start_time)        # host half done; launch(slot) does the rest
             return None
@@ -232,7 +236,7 @@ class ExposureGenerator(object):
                          clip_values_det_limits=True, add_read_noise=True, add_stellar_noise=True,
                          add_initial_bias=True, progress_bar=None, threads=2,
                          rng_mode=_lib.RNG_SPLIT, out_dtype=np.float32, reference_quirks=False,
-                         exact_samplers=False, contaminants=None):
+                         exact_samplers=False, contaminants=None, charge_traps=None):
         """The host half of scanning_frame: sample timing, scan positions, SSV,
         jitter / seed draws, spectrum crop (exposure_generator.py:247-334) ->
         one wayne_exposure_desc for the device.  Pure host code (`eng` may be
@@ -273,6 +277,11 @@ class ExposureGenerator(object):
             self.exp_info["contaminants"] = list(contaminants)     # (the FITS header names them: exposure.py)
         else:
             self.exp_info.pop("contaminants", None)
+        charge_traps = _traps.for_exposure(charge_traps)
+        if charge_traps is not None:
+            self.exp_info["charge_traps"] = charge_traps.traps     # (the FITS header records the model: exposure.py)
+        else:
+            self.exp_info.pop("charge_traps", None)
         self.exposure = exposure.Exposure(self.detector, self.grism, self.planet, self.exp_info)
 
         if add_dark and eng is not None and not eng.has_dark:
@@ -348,7 +357,7 @@ class ExposureGenerator(object):
             cosmic_rate=-1.0 if cosmic_rate is None else float(cosmic_rate),
             scale_factor=1.0 if scale_factor is None else float(scale_factor),
             noise_mean=float(noise_mean) if noise_mean else 0.0,
-            noise_std=float(noise_std) if noise_std else 0.0, sources=contaminants, **lc)
+            noise_std=float(noise_std) if noise_std else 0.0, sources=contaminants, traps=charge_traps, **lc)
 
     def direct_image(self, x_ref, y_ref):
         """The unscaled 2-D gaussian direct image used to calibrate x_ref / y_ref

@@ -60,6 +60,8 @@ class Observation(object):
         # frame_options["out_dtype"] = np.float64 (CLI: --float64-reads) keeps the float64 arithmetic to the file.
         self.frame_options = {"out_dtype": np.float32}
         self.contaminants = []       # field stars on every exposure (setup_contaminants)
+        self.charge_traps = None     # per-pixel charge trapping (setup_charge_traps)
+        self._trap_tables = None
 
     # -- setup_* (observation.py:46-291) ----------------------------------------
     def setup_observation(self, x_ref, y_ref, spatial_scan=False, scan_speed=False):
@@ -74,6 +76,26 @@ class Observation(object):
         if len(contaminants) > MAX_CONTAMINANTS:
             raise ValueError("at most %d contaminants" % MAX_CONTAMINANTS)
         self.contaminants = contaminants
+
+    def setup_charge_traps(self, traps):
+        """Per-pixel charge trapping, the ramp effect (traps.ChargeTraps; traps.ChargeTraps.from_config builds it from the
+        YAML's `charge_traps:` section); None: none.  Exposure i gets its start tables from the visit plan
+        (ChargeTraps.start_tables: the visit's history at each pixel's own mean rate), so exposures stay independent."""
+        from .traps import ChargeTraps
+        if traps is not None and not isinstance(traps, ChargeTraps):
+            raise TypeError("setup_charge_traps: expected traps.ChargeTraps or None")
+        self.charge_traps = traps
+        self._trap_tables = None
+
+    def exposure_traps(self, index):
+        """Exposure `index`'s charge traps (traps.ExposureTraps), or None without them."""
+        if self.charge_traps is None:
+            return None
+        from .traps import ExposureTraps
+        if self._trap_tables is None:
+            exptime = self.detector.exptime(self.NSAMP, self.SUBARRAY, self.SAMPSEQ)
+            self._trap_tables = self.charge_traps.start_tables(self.visit_plan, exptime, staring=not self.spatial_scan)
+        return ExposureTraps(self.charge_traps, self._trap_tables[index])
 
     def setup_simulator(self, sample_rate=False, clip_values_det_limits=True, threads=2):
         self.sample_rate = sample_rate
@@ -130,6 +152,7 @@ class Observation(object):
                                            exp_overhead=3.0)            # observation.py:229-233
             self.exp_start_times = self.visit_plan["exp_times"] / (24. * 60.) + self.start_JD
             self.visit_plan["exp_start_times"] = self.exp_start_times
+        self._trap_tables = None
 
     def setup_reductions(self, add_dark=True, add_flat=True, add_gain_variations=True, add_non_linear=True,
                          add_initial_bias=True):
@@ -223,7 +246,7 @@ class Observation(object):
                     abs(float(p0["EXPSTART"]) - (float(self.exp_start_times[number - 1]) - 2400000.5)) < 1e-7)
         except (KeyError, TypeError, ValueError):
             return False
-        if not (same and self._contaminant_cards_match(p0)):
+        if not (same and self._contaminant_cards_match(p0) and self._trap_cards_match(p0)):
             return False
         return all(size == S * S * 8 for (h, size) in hdus[1::5])
 
@@ -238,6 +261,20 @@ class Observation(object):
             if not want or int(p0["NCONTAM"]) != want["NCONTAM"]:
                 return False
             return all(abs(float(p0[k]) - float(v)) <= 1e-9 * max(1.0, abs(float(v))) for k, v in want.items())
+        except (KeyError, TypeError, ValueError):
+            return False
+
+    def _trap_cards_match(self, p0):
+        """The file's CTRAPS and CT* cards are this visit's charge traps (absent: none), so that --resume after the model
+        or its start tables' grid was switched on, off or changed regenerates the files."""
+        want = {k: v for (k, v, _) in self.charge_traps.cards()} if self.charge_traps is not None else {}
+        try:
+            if "CTRAPS" not in p0:
+                return not want
+            if not want or p0["CTRAPS"] is not True:
+                return False
+            return all(abs(float(p0[k]) - float(v)) <= 1e-9 * max(1.0, abs(float(v)))
+                       for k, v in want.items() if k != "CTRAPS")
         except (KeyError, TypeError, ValueError):
             return False
 
@@ -386,6 +423,8 @@ class Observation(object):
         common.update(self.frame_options)
         if self.contaminants:
             common["contaminants"] = self.contaminants
+        if self.charge_traps is not None:
+            common["charge_traps"] = self.exposure_traps(index_number)
         if self.spatial_scan:
             args = (x_ref, y_ref, self.x_jitter, self.y_jitter, self.wl, self.stellar_flux, planet_depths,
                     self.scan_speed, sample_rate, sample_mid_points, sample_durations, read_index)

@@ -19,6 +19,9 @@ examples/hd209458b_12181_simulation_parameters.yml): sections `general`
   * an optional top-level `contaminants:` list puts field stars on every exposure (wayne_amd/sources.py): per entry
     `dx`, `dy` (px from the target), `flux_ratio` (detected electrons relative to the target's) and a black-body
     `temperature` or a PHOENIX `spectrum_file`; at most 8.  First order only, not in the direct image, constant;
+  * an optional top-level `charge_traps:` section turns on per-pixel charge trapping, the ramp effect
+    (wayne_amd/traps.py): `slow` / `fast` mappings of n_traps, efficiency, lifetime_s, initial, orbit_fill; `{}` = the
+    defaults, an omitted key its default;
   * `--gpus G`: the process starts G rank processes itself (one per GPU of this node, before anything touches a
     GPU) and waits for them; under an external launcher (WORLD_SIZE / RANK set, one process per GPU) it is one
     rank.  Each rank generates its round-robin share of the exposures (observation.py:403-405 is the axis) on the
@@ -34,7 +37,7 @@ import numpy as np
 import yaml
 
 from . import calibration as _cal
-from . import detector, grism, launch, observation, sources, tools
+from . import detector, grism, launch, observation, sources, tools, traps
 from .trend_generators import scan_speed_varations
 
 
@@ -142,6 +145,13 @@ def build_observation(cfg, base_dir=".", calibration=None, device=0):
         raise WFC3SimConfigError(str(e))
     if contaminants:
         obs.setup_contaminants(contaminants)
+    # optional `charge_traps:` section (no reference counterpart): per-pixel charge trapping, the ramp effect; absent =
+    # none, `{}` = every default
+    if isinstance(cfg, dict) and "charge_traps" in cfg:
+        try:
+            obs.setup_charge_traps(traps.ChargeTraps.from_config(cfg["charge_traps"]))
+        except traps.ChargeTrapConfigError as e:
+            raise WFC3SimConfigError(str(e))
     return obs
 
 

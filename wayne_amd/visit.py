@@ -38,6 +38,9 @@ def descriptor_digest(desc):
         h.update(np.ascontiguousarray(a).tobytes())
     for src in getattr(desc, "_sources", ()):      # contaminants (none: the digest of a descriptor without them)
         h.update(src.digest_bytes())
+    traps = getattr(desc, "_traps", None)          # charge traps (none: likewise)
+    if traps is not None:
+        h.update(traps.digest_bytes())
     return h.hexdigest()
 
 
