@@ -115,7 +115,7 @@ MUTANTS = [
                  'asm("v_cvt_i32_f32 %0, %2\\n\\tv_cvt_i32_f32 %1, %3\\n\\tv_lshl_add_u32')]),
     dict(name="settle_never_reruns", stage="host: wayne_ctx_synchronize settles incomplete exposures (include/wayne_hip.h)",
          what="wayne_ctx_synchronize reads the status words and never runs a flagged exposure again",
-         edits=[("wayne_hip.hip", "} else if ((status & 2) && pass == 0) {", "} else if (false && (status & 2) && pass == 0) {")]),
+         edits=[("wayne_hip.hip", "const bool may_rerun = pass == 0;", "const bool may_rerun = false && pass == 0;")]),
     dict(name="wide_count_rounded", stage="A4 N = (int)(counts ratio) (pyparallel_menu.c:89)",
          what="the wide count rounded to nearest instead of truncated (thrower call and exposure path)",
          edits=[("host_plan.h", "                                                   : (int32_t)nw;",

@@ -10,6 +10,7 @@ import pstats
 import sys
 import time
 
+os.environ["WAYNE_UPLOAD_TIMING"] = "1"     # (knobs are frozen when a context is created: set before the first one)
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -32,5 +33,4 @@ pr.disable()
 st = pstats.Stats(pr)
 st.sort_stats("tottime").print_stats(22)
 from wayne_amd import engine  # noqa: E402
-os.environ["WAYNE_UPLOAD_TIMING"] = "1"
 engine.close_all()

@@ -21,16 +21,35 @@
 
 using namespace wayne;
 
+struct wayne_ctx;
+
 namespace {
+
+int fail(wayne_ctx* c, int code, const std::string& msg);   // (keeps `msg` as the context's last error: below, with the context)
+
+#define HIP_TRY(ctx, expr)                                                                     \
+  do {                                                                                         \
+    hipError_t e__ = (expr);                                                                   \
+    if (e__ != hipSuccess)                                                                     \
+      return fail((ctx), WAYNE_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e__));     \
+  } while (0)
+
+inline size_t align64(size_t n) { return (n + 63) & ~(size_t)63; }
 
 enum ProfKernel { PK_PREP_WL = 0, PK_PREP_SUB, PK_THROW, PK_COSMIC, PK_RAMP, PK_LIGHTCURVE, PK_NARROW, PK_LANE };
 const char* const kProfNames[WAYNE_PROF_KERNELS] = {"k_prep_wl", "k_prep_sub",   "k_throw",  "k_cosmic",   /* (cosmic rays ride in k_prep_sub: slot kept for the ABI) */
                                                     "k_ramp",    "k_lightcurve", "k_narrow", "k_lane"};
 
+// A device buffer: an allocation of its own (freed with it), or a view into another one.  Not copied: slots and sources
+// live in fixed arrays inside the context.
 struct DevBuf {
   void* p = nullptr;
   size_t cap = 0;
-  bool owns = true;        // false: a view into another allocation (the slot's input arena)
+  bool owns = true;        // false: a view into another allocation (a staging arena's device mirror)
+  DevBuf() = default;
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  ~DevBuf() { if (p && owns) (void)hipFree(p); }
   hipError_t reserve(size_t bytes) {
     if (!owns) { p = nullptr; cap = 0; owns = true; }
     if (bytes <= cap) return hipSuccess;
@@ -48,13 +67,70 @@ struct DevBuf {
     cap = 0;
     owns = false;
   }
-  void release() {
-    if (p && owns) (void)hipFree(p);
+  template <class T> T* as() const { return (T*)p; }
+};
+
+// A grow-only block of pinned host memory.
+struct PinnedBuf {
+  char* p = nullptr;
+  size_t cap = 0;
+  PinnedBuf() = default;
+  PinnedBuf(const PinnedBuf&) = delete;
+  PinnedBuf& operator=(const PinnedBuf&) = delete;
+  ~PinnedBuf() { if (p) (void)hipHostFree(p); }
+  bool reserve(size_t bytes) {      // false: no pinned memory (the block is then empty)
+    if (bytes <= cap) return true;
+    if (p) (void)hipHostFree(p);
     p = nullptr;
     cap = 0;
-    owns = true;
+    if (hipHostMalloc((void**)&p, bytes, hipHostMallocDefault) != hipSuccess) { p = nullptr; return false; }
+    cap = bytes;
+    return true;
   }
-  template <class T> T* as() const { return (T*)p; }
+};
+
+// A staging arena: a pinned block, its device mirror, and the event that tells when the last copy from the block into
+// the mirror is done.  The arrays of a call are placed at 64-byte-aligned offsets of the block and DevBuf views pointed at
+// the same offsets of the mirror: all of them reach the device in ONE copy, enqueued from pinned memory, so the call
+// returns without waiting for the stream -- the next begin() waits instead, before the block is overwritten.
+struct StageArena {
+  PinnedBuf host;
+  DevBuf dev;
+  hipEvent_t ev = nullptr;
+  bool pending = false;    // a copy out of `host` was enqueued that nobody has waited for yet
+  size_t used = 0;
+  ~StageArena() { if (ev) (void)hipEventDestroy(ev); }
+  // Room for `bytes`, empty.  (with_event = false: for a caller that synchronises its stream before it returns.)
+  int begin(wayne_ctx* c, size_t bytes, const char* nomem_msg, bool with_event = true) {
+    if (pending) { HIP_TRY(c, hipEventSynchronize(ev)); pending = false; }
+    if (!host.reserve(align64(bytes))) return fail(c, WAYNE_E_NOMEM, nomem_msg);
+    if (with_event && !ev) HIP_TRY(c, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    HIP_TRY(c, dev.reserve(host.cap));
+    used = 0;
+    return WAYNE_OK;
+  }
+  // The next `bytes` of the block (null: they do not fit); `view` is pointed at the same offset of the mirror.
+  char* place(DevBuf& view, size_t bytes) {
+    bytes = std::max<size_t>(bytes, 1);
+    if (used + bytes > host.cap) return nullptr;
+    char* h = host.p + used;
+    view.view((char*)dev.p + used);
+    used += align64(bytes);
+    return h;
+  }
+  bool put(DevBuf& view, const void* src, size_t bytes) {
+    char* h = place(view, bytes);
+    if (h && bytes) std::memcpy(h, src, bytes);
+    return h != nullptr;
+  }
+  int commit(wayne_ctx* c, hipStream_t stream) {
+    HIP_TRY(c, hipMemcpyAsync(dev.p, host.p, used, hipMemcpyHostToDevice, stream));   // one copy for all arrays
+    if (ev) { HIP_TRY(c, hipEventRecord(ev, stream)); pending = true; }
+    return WAYNE_OK;
+  }
+  // host copy of a placed array: the block still holds it (at the offset of the array's view in the mirror) until the
+  // next begin()
+  template <class T> const T* host_of(const DevBuf& view) const { return (const T*)(host.p + ((const char*)view.p - (const char*)dev.p)); }
 };
 
 // What one source (the target, or a contaminating field star: wayne_exposure_set_sources) of an exposure holds: its
@@ -66,7 +142,7 @@ struct SourceState {
   int last_chunks = 0;
   int W = 0;
   uint32_t seed = 0;          // visit seed of the source's thrower-side streams (wayne_source_seed)
-  DevBuf wl, flux, xref, yref;   // target: views into the slot's in_dev; contaminant: views into src_dev
+  DevBuf wl, flux, xref, yref;   // target: views into the slot's `stage`; contaminant: views into src_stage
   DevBuf ratio, sigl, sigh, sens, dlam;
   DevBuf counts, nwide, nsplit, nlane, prefix, xpos, ypos, sub, chunk_total, chunk_box, tr;
   int kb = 1;             // sub-samples a workgroup of k_lane takes (k_lane, "BATCHES")
@@ -76,23 +152,7 @@ struct SourceState {
   double est_thrown = 0.;   // host estimate of the electrons k_throw handles in the longest sub-sample
   unsigned char chunk_order[kMaxChunks] = {0};   // chunks of kNarrowThreads bins, most electrons first (ThrowArgs::chunk_order)
   unsigned char lane_order[kMaxChunks] = {0};    // chunks of kLaneThreads bins, most electrons first
-  // a contaminant's own inputs (wl, flux, offset positions): a pinned arena and its device mirror, one copy
-  DevBuf src_dev;
-  char* src_stage = nullptr;
-  size_t src_stage_cap = 0;
-  hipEvent_t src_stage_ev = nullptr;
-  bool src_stage_pending = false;
-  void release_source() {
-    for (DevBuf* b : {&wl, &flux, &xref, &yref, &ratio, &sigl, &sigh, &sens, &dlam, &counts, &nwide, &nsplit, &nlane, &prefix,
-                      &xpos, &ypos, &sub, &chunk_total, &chunk_box, &tr, &src_dev})
-      b->release();
-    if (src_stage) (void)hipHostFree(src_stage);
-    src_stage = nullptr;
-    src_stage_cap = 0;
-    if (src_stage_ev) (void)hipEventDestroy(src_stage_ev);
-    src_stage_ev = nullptr;
-    src_stage_pending = false;
-  }
+  StageArena src_stage;   // a contaminant's own inputs (wl, flux, offset positions)
 };
 
 constexpr int kMaxSources = WAYNE_MAX_SOURCES;   // contaminants per exposure
@@ -103,12 +163,12 @@ struct Slot : SourceState {
   bool front_done = false;
   bool acc_dirty = false;
   bool acc_init = false;
-  bool force_throw = false;   // the last run met a bin beyond a lane's reach: run with k_throw (set by check_status)
+  bool force_throw = false;   // the last run met a bin beyond a lane's reach: run with k_throw (set by look_at_status)
   bool ran = false;           // a whole run was enqueued whose status word nobody has looked at yet (settle)
   wayne_exposure_desc d{};  // host copy (pointers are NOT valid after upload)
   int K = 0, R = 0;
   bool has_depth = false, has_replay_seed = false, has_lc = false, has_lc_hidden = false;
-  DevBuf depth, dur, rseed, sread, read_dt, lc_z, lc_hidden, lc_rp;   // views into in_dev (depth: owned when computed by k_lightcurve)
+  DevBuf depth, dur, rseed, sread, read_dt, lc_z, lc_hidden, lc_rp;   // views into `stage` (depth: owned when computed by k_lightcurve)
   int n_extra = 0;                 // contaminants of this exposure (wayne_exposure_set_sources; cleared by upload)
   SourceState extra[kMaxSources];
   uint32_t extra_tag[kMaxSources] = {0};
@@ -117,16 +177,12 @@ struct Slot : SourceState {
   DevBuf seg;             // cosmic-ray segments (CosmicArgs::seg): zeroed when allocated, k_ramp clears what it reads
   bool use_box = false;   // acc_box is valid: k_ramp loads the accumulators of a read only inside it (and where `seg` says)
   int acc_box[16][4] = {{0}};
-  DevBuf in_dev;          // device mirror of the staging arena: the descriptor's arrays arrive in ONE copy
-  void* pinned = nullptr;  // pinned host copy of `out` (fetch_async / wait), followed by a copy of `misc`
-  size_t pinned_cap = 0;
-  struct Misc { unsigned long long electrons; int status; int pad; };
+  PinnedBuf pinned;       // pinned host copy of `out` (fetch_async / wait), followed by a copy of `misc`
+  struct Misc { unsigned long long electrons; int status; int pad; };   // the layout of `misc`, declared here only
   Misc* pinned_misc = nullptr;   // inside `pinned`: a copy into pageable memory would block the caller
-  // sky alias tables of this exposure (k_ramp): device copy, pinned host copy, the lam_max they were built for
+  // sky alias tables of this exposure (k_ramp): their arena, the view of the device copy, the lam_max they were built for
+  StageArena sky_stage;
   DevBuf sky_tab;
-  uint32_t* sky_tab_host = nullptr;
-  hipEvent_t sky_tab_ev = nullptr;
-  bool sky_tab_pending = false;
   std::vector<uint32_t> sky_tab_keys;
   bool sky_alias_on = false, sky_pieces = false;
   uint32_t sky_mask = 0;
@@ -136,53 +192,15 @@ struct Slot : SourceState {
   std::vector<double> read_dt_host;
   double lc_p_lo = 0., lc_p_hi = 0.;   // range of lc_rp
   // charge traps of this exposure (wayne_exposure_set_traps; cleared by upload): the parameters, and the start tables
-  // in one device buffer -- [2][G] float64 (generic loop), then [2][G] float32 (production chain) -- from a pinned copy
+  // in one arena -- [2][G] float64 (generic loop), then [2][G] float32 (production chain)
   bool traps_on = false;
   double trap_n[2] = {1., 1.}, trap_eta[2] = {0., 0.}, trap_tau[2] = {1., 1.}, trap_lo = 0., trap_hi = 0.;
   int trap_G = 0;
-  size_t trap_f_off = 0;             // byte offset of the float32 tables
-  DevBuf trap_tab;
-  char* trap_stage = nullptr;
-  size_t trap_stage_cap = 0;
-  hipEvent_t trap_ev = nullptr;
-  bool trap_pending = false;
-  // pinned staging arena of the descriptor's arrays: uploads are enqueued from here, so
+  StageArena trap_stage;
+  DevBuf trap_d, trap_f;             // views of the float64 / float32 tables
+  // staging arena of the descriptor's arrays: uploads are enqueued from here, so
   // wayne_exposure_upload returns without waiting for the slot's stream to drain
-  char* stage = nullptr;
-  size_t stage_cap = 0, stage_used = 0;
-  hipEvent_t stage_ev = nullptr;
-  bool stage_pending = false;
-  void release() {
-    release_source();
-    for (SourceState& e : extra) e.release_source();
-    n_extra = 0;
-    for (DevBuf* b : {&depth, &dur, &rseed, &sread, &read_dt, &lc_z, &lc_hidden, &lc_rp, &acc, &out, &misc, &seg, &sky_tab, &in_dev,
-                      &trap_tab})
-      b->release();
-    traps_on = false;
-    if (trap_stage) (void)hipHostFree(trap_stage);
-    trap_stage = nullptr;
-    trap_stage_cap = 0;
-    if (trap_ev) (void)hipEventDestroy(trap_ev);
-    trap_ev = nullptr;
-    trap_pending = false;
-    if (sky_tab_host) (void)hipHostFree(sky_tab_host);
-    sky_tab_host = nullptr;
-    if (sky_tab_ev) (void)hipEventDestroy(sky_tab_ev);
-    sky_tab_ev = nullptr;
-    sky_tab_pending = false;
-    sky_tab_keys.clear();
-    if (pinned) (void)hipHostFree(pinned);
-    pinned = nullptr;
-    pinned_misc = nullptr;
-    pinned_cap = 0;
-    if (stage) (void)hipHostFree(stage);
-    stage = nullptr;
-    stage_cap = stage_used = 0;
-    if (stage_ev) (void)hipEventDestroy(stage_ev);
-    stage_ev = nullptr;
-    stage_pending = false;
-  }
+  StageArena stage;
 };
 
 struct ProfRec {
@@ -230,8 +248,9 @@ constexpr size_t kMiscBytes = 64;   // status block of a slot: [0] electrons (u6
 
 constexpr size_t kCounterBytes = (size_t)kCounterStripes * kCounterStride * sizeof(unsigned long long);
 
-struct wayne_ctx {
-  int device = 0;
+// The streams and stream events of a context: a base of it, so that they are destroyed LAST -- a base goes after the
+// members of the struct derived from it, i.e. after every buffer, arena and pinned block of the context has been freed.
+struct CtxStreams {
   hipStream_t stream = nullptr;          // stream of the call in progress (one of streams[])
   hipStream_t streams[kStreams] = {nullptr, nullptr};
   // k_narrow of an exposure runs beside its k_throw (both only add into the accumulators): a side
@@ -244,10 +263,23 @@ struct wayne_ctx {
   // then both copy and share the PCIe link: 640 exposures/s -- instead of one copying while the other computes (810).
   hipEvent_t ev_kdone[kStreams] = {nullptr, nullptr};
   bool kdone_valid[kStreams] = {false, false};
+  ~CtxStreams() {
+    for (int i = 0; i < kStreams; ++i) {
+      if (streams[i]) (void)hipStreamDestroy(streams[i]);
+      if (side[i]) (void)hipStreamDestroy(side[i]);
+      if (ev_fork[i]) (void)hipEventDestroy(ev_fork[i]);
+      if (ev_join[i]) (void)hipEventDestroy(ev_join[i]);
+      if (ev_kdone[i]) (void)hipEventDestroy(ev_kdone[i]);
+    }
+  }
+};
+
+struct wayne_ctx : CtxStreams {
+  int device = 0;
   int n_streams = kStreams;              // knob `streams` = 1 serialises all exposures on one stream
   Knobs knobs;                           // frozen at creation (see Knobs)
   DevBuf status_all;                     // kSlots status blocks of kMiscBytes (Slot::misc views into it): ONE copy brings all of them back
-  char* status_host = nullptr;           // its pinned host mirror (settle)
+  PinnedBuf status_host;                 // its pinned host mirror (settle)
   std::string err;
   // grism
   bool have_grism = false;
@@ -271,9 +303,7 @@ struct wayne_ctx {
   Slot slots[kSlots];
   // psf_apply scratch
   DevBuf pa_prefix, pa_nwide, pa_nsplit, pa_nlane, pa_x, pa_y, pa_sl, pa_sh, pa_sub, pa_frame;
-  DevBuf pa_in;                 // device mirror of the staging arena (the arrays above are views into it)
-  char* pa_stage = nullptr;     // pinned: every input array of a call, copied to the device in one piece
-  size_t pa_stage_cap = 0;
+  StageArena pa_stage;          // every input array of a call, copied to the device in one piece (the arrays above but pa_frame are views into it)
   // profiling
   bool prof_on = false;
   unsigned prof_mask = ~0u;   // kernels timed while prof_on (wayne_profile_select)
@@ -291,27 +321,42 @@ namespace {
 
 // k_lane's batches and its first-touch flush list of one source (knobs `batch` / `thin` applied)
 void plan_lanes(const wayne_ctx* c, SourceState& ss, int K, int W) {
-  {
-    // k_lane's batches and its first-touch flush list (plan::lane_batches)
-    int kb = 1;
-    plan::lane_batches(K, W, ss.max_chunk_electrons, &kb, &ss.thin);
+  int kb = 1;
+  plan::lane_batches(K, W, ss.max_chunk_electrons, &kb, &ss.thin);
+  {   // a knob that is set overrules the planner
     if (c->knobs.batch >= 0) kb = (int)std::min<long long>(std::max<long long>(c->knobs.batch, 1), kLaneBatchMax);
-    ss.kb = kb;
     if (c->knobs.thin >= 0) ss.thin = c->knobs.thin != 0;
   }
+  ss.kb = kb;
+}
+
+// Scratch of one source for K sub-samples of W bins: per bin, per (sub-sample, bin), per sub-sample, per k_prep_sub chunk.
+int reserve_source(wayne_ctx* c, SourceState& ss, int K, int W) {
+  const size_t KW = (size_t)K * W, n_chunks = (size_t)(W + kPrepThreads - 1) / kPrepThreads;
+  for (DevBuf* b : {&ss.ratio, &ss.sigl, &ss.sigh, &ss.sens, &ss.dlam}) HIP_TRY(c, b->reserve((size_t)W * sizeof(double)));
+  for (DevBuf* b : {&ss.counts, &ss.nwide, &ss.nsplit, &ss.nlane}) HIP_TRY(c, b->reserve(KW * sizeof(int32_t)));
+  HIP_TRY(c, ss.prefix.reserve((size_t)K * (W + 1) * sizeof(uint32_t)));
+  HIP_TRY(c, ss.xpos.reserve(KW * sizeof(double)));
+  HIP_TRY(c, ss.ypos.reserve(KW * sizeof(double)));
+  HIP_TRY(c, ss.sub.reserve((size_t)K * sizeof(SubInfo)));
+  HIP_TRY(c, ss.tr.reserve((size_t)K * kTrStride * sizeof(double)));
+  HIP_TRY(c, ss.chunk_total.reserve(K * n_chunks * sizeof(uint32_t)));
+  HIP_TRY(c, ss.chunk_box.reserve(K * n_chunks * 4 * sizeof(double)));
+  return WAYNE_OK;
+}
+
+// ... and its launch plan: what plan::estimate_thrown worked out for its inputs, and k_lane's batches
+void adopt_plan(const wayne_ctx* c, SourceState& ss, int K, int W, const plan::ThrowPlan& tp) {
+  ss.est_thrown = tp.est_thrown; ss.max_chunk_electrons = tp.max_chunk_electrons; ss.max_narrow = tp.max_narrow;
+  std::memcpy(ss.chunk_order, tp.chunk_order, sizeof ss.chunk_order);
+  std::memcpy(ss.lane_order, tp.lane_order, sizeof ss.lane_order);
+  plan_lanes(c, ss, K, W);
 }
 
 int fail(wayne_ctx* c, int code, const std::string& msg) {
   if (c) c->err = msg;
   return code;
 }
-
-#define HIP_TRY(ctx, expr)                                                                     \
-  do {                                                                                         \
-    hipError_t e__ = (expr);                                                                   \
-    if (e__ != hipSuccess)                                                                     \
-      return fail((ctx), WAYNE_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e__));     \
-  } while (0)
 
 hipEvent_t get_event(wayne_ctx* c) {
   if (!c->ev_pool.empty()) {
@@ -328,17 +373,10 @@ struct ProfScope {
   wayne_ctx* c;
   ProfRec rec{};
   bool on;
-  ProfScope(wayne_ctx* c_, int kernel) : c(c_), on(c_->prof_on && ((c_->prof_mask >> kernel) & 1u)) {
-    if (!on) return;
-    rec.kernel = kernel;
-    rec.a = get_event(c);
-    rec.b = get_event(c);
-    if (!rec.a || !rec.b) { on = false; return; }
-    (void)hipEventRecord(rec.a, c->stream);
-  }
-  // For a single launch through hipExtLaunchKernel: the events then carry the kernel's own start and stop
+  bool ext = false;
+  // ext_launch: for a single launch through hipExtLaunchKernel: the events then carry the kernel's own start and stop
   // times (no marker packets before and after it in the stream).
-  ProfScope(wayne_ctx* c_, int kernel, bool ext_launch) : c(c_), on(c_->prof_on && ((c_->prof_mask >> kernel) & 1u)) {
+  ProfScope(wayne_ctx* c_, int kernel, bool ext_launch = false) : c(c_), on(c_->prof_on && ((c_->prof_mask >> kernel) & 1u)) {
     if (!on) return;
     rec.kernel = kernel;
     rec.a = get_event(c);
@@ -347,7 +385,6 @@ struct ProfScope {
     ext = ext_launch;
     if (!ext) (void)hipEventRecord(rec.a, c->stream);
   }
-  bool ext = false;
   ~ProfScope() {
     if (!on) return;
     if (!ext) (void)hipEventRecord(rec.b, c->stream);
@@ -389,20 +426,14 @@ int upload(wayne_ctx* c, DevBuf& b, const T* src, size_t n) {
   return WAYNE_OK;
 }
 
-inline size_t align64(size_t n) { return (n + 63) & ~(size_t)63; }
-
 // (the launch planner -- spectrum estimates, accumulator boxes, sky levels and alias tables -- is host_plan.h: host-only
 // code that the CPU harness under tests/native builds with sanitizers)
 using plan::build_sky_alias;
 
-// Copy `n` elements into the slot's pinned arena and enqueue the host-to-device copy from there.
+// Copy `n` elements of the descriptor into the slot's staging arena.
 template <class T>
 int upload_staged(wayne_ctx* c, Slot& s, DevBuf& b, const T* src, size_t n) {
-  const size_t bytes = std::max<size_t>(n, 1) * sizeof(T);
-  if (s.stage_used + bytes > s.stage_cap) return fail(c, WAYNE_E_NOMEM, "upload: staging arena too small");
-  if (n) std::memcpy(s.stage + s.stage_used, src, n * sizeof(T));
-  b.view((char*)s.in_dev.p + s.stage_used);      // same offset in the device mirror (copied in one piece)
-  s.stage_used += align64(bytes);
+  if (!s.stage.put(b, src, n * sizeof(T))) return fail(c, WAYNE_E_NOMEM, "upload: staging arena too small");
   return WAYNE_OK;
 }
 
@@ -417,21 +448,17 @@ int prepare_sky_tables(wayne_ctx* c, Slot& s) {
   if (!sp.alias_on) { s.sky_pieces = false; return WAYNE_OK; }    // (no sky, or a read whose rates fit no table: the direct sampler)
   if (sp.keys != s.sky_tab_keys || !s.sky_tab.p) {
     const size_t bytes = (size_t)kMaxReads * kSkyAlias * sizeof(uint32_t);
-    HIP_TRY(c, s.sky_tab.reserve(bytes));
-    if (!s.sky_tab_host && hipHostMalloc((void**)&s.sky_tab_host, bytes, hipHostMallocDefault) != hipSuccess)
-      return fail(c, WAYNE_E_NOMEM, "upload: pinned allocation for the sky tables failed");
-    if (!s.sky_tab_ev) HIP_TRY(c, hipEventCreateWithFlags(&s.sky_tab_ev, hipEventDisableTiming));
-    if (s.sky_tab_pending) { HIP_TRY(c, hipEventSynchronize(s.sky_tab_ev)); s.sky_tab_pending = false; }
-    std::memset(s.sky_tab_host, 0, bytes);
+    int rc = s.sky_stage.begin(c, bytes, "upload: pinned allocation for the sky tables failed");
+    if (rc) return rc;
+    uint32_t* tab = (uint32_t*)s.sky_stage.place(s.sky_tab, bytes);
+    std::memset(tab, 0, bytes);
     for (size_t t = 0; t < sp.keys.size() && t < (size_t)kMaxReads; ++t) {
       // (a table is ~1 us to build -- no cache: the sky level, and with it every rate, changes with the exposure)
       float lam;
       std::memcpy(&lam, &sp.keys[t], 4);
-      build_sky_alias((double)lam, s.sky_tab_host + t * kSkyAlias);
+      build_sky_alias((double)lam, tab + t * kSkyAlias);
     }
-    HIP_TRY(c, hipMemcpyAsync(s.sky_tab.p, s.sky_tab_host, bytes, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipEventRecord(s.sky_tab_ev, c->stream));
-    s.sky_tab_pending = true;
+    if ((rc = s.sky_stage.commit(c, c->stream))) return rc;
     s.sky_tab_keys = sp.keys;
   }
   s.sky_alias_on = true;
@@ -559,11 +586,6 @@ void (*select_ramp(const wayne_ctx* c, const Slot& s, std::string* name, RampTra
 }  // namespace
 
 namespace {
-// host copy of a descriptor array of the slot's last upload: the pinned staging arena still holds it (at the offset
-// of the array's view in the device mirror) until the slot is uploaded again
-template <class T> const T* staged_host(const Slot& s, const DevBuf& b) {
-  return (const T*)(s.stage + ((const char*)b.p - (const char*)s.in_dev.p));
-}
 bool box_empty(const int* b) { return b[0] >= b[1] || b[2] >= b[3]; }
 }  // namespace
 
@@ -611,7 +633,7 @@ wayne_ctx* wayne_ctx_create(int device, int* status) {
   c->device = device;
   for (int i = 0; i < kStreams; ++i)
     if (hipStreamCreateWithFlags(&c->streams[i], hipStreamNonBlocking) != hipSuccess) {
-      for (int j = 0; j < i; ++j) (void)hipStreamDestroy(c->streams[j]);
+      c->streams[i] = nullptr;
       delete c;
       set(WAYNE_E_HIP);
       return nullptr;
@@ -634,11 +656,7 @@ wayne_ctx* wayne_ctx_create(int device, int* status) {
   if (c->knobs.streams >= 0) c->n_streams = (int)std::min<long long>(std::max<long long>(c->knobs.streams, 1), kStreams);
   if (c->counters.reserve(kCounterBytes) != hipSuccess || hipMemset(c->counters.p, 0, kCounterBytes) != hipSuccess ||
       c->status_all.reserve(kSlots * kMiscBytes) != hipSuccess || hipMemset(c->status_all.p, 0, kSlots * kMiscBytes) != hipSuccess ||
-      hipHostMalloc((void**)&c->status_host, kSlots * kMiscBytes, hipHostMallocDefault) != hipSuccess) {
-    c->counters.release();
-    c->status_all.release();
-    if (c->status_host) (void)hipHostFree(c->status_host);
-    for (int i = 0; i < kStreams; ++i) (void)hipStreamDestroy(c->streams[i]);
+      !c->status_host.reserve(kSlots * kMiscBytes)) {
     delete c;
     set(WAYNE_E_NOMEM);
     return nullptr;
@@ -657,25 +675,37 @@ void wayne_ctx_destroy(wayne_ctx* c) {
   (void)sync_all(c);
   for (ProfRec& r : c->prof) { (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b); }
   for (hipEvent_t e : c->ev_pool) (void)hipEventDestroy(e);
-  for (Slot& s : c->slots) s.release();
-  if (c->status_host) (void)hipHostFree(c->status_host);
-  for (DevBuf* b : {&c->counters, &c->status_all, &c->sens_wl, &c->sens_val, &c->pfl, &c->sky, &c->dark_sci, &c->dark_err, &c->zero_read,
-                    &c->pa_prefix, &c->pa_nwide, &c->pa_nsplit, &c->pa_nlane, &c->pa_x, &c->pa_y, &c->pa_sl, &c->pa_sh, &c->pa_sub,
-                    &c->pa_frame, &c->pa_in})
-    b->release();
-  if (c->pa_stage) (void)hipHostFree(c->pa_stage);
-  for (int i = 0; i < 4; ++i) { c->flat[i].release(); c->lin[i].release(); }
-  for (int i = 0; i < kStreams; ++i) {
-    (void)hipStreamDestroy(c->streams[i]);
-    if (c->side[i]) (void)hipStreamDestroy(c->side[i]);
-    if (c->ev_fork[i]) (void)hipEventDestroy(c->ev_fork[i]);
-    if (c->ev_join[i]) (void)hipEventDestroy(c->ev_join[i]);
-    if (c->ev_kdone[i]) (void)hipEventDestroy(c->ev_kdone[i]);
-  }
-  delete c;
+  delete c;     // the members free what they own; then ~CtxStreams: the streams and their events go last
 }
 
 const char* wayne_last_error(const wayne_ctx* c) { return c ? c->err.c_str() : "null context"; }
+
+// The status block of a slot, from the device (the call waits for the slot's stream, c->stream)
+static int read_status(wayne_ctx* c, const Slot& s, Slot::Misc* m) {
+  HIP_TRY(c, hipMemcpyAsync(m, s.misc.p, sizeof *m, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return WAYNE_OK;
+}
+
+// Look at the status word of the slot's last run -- in `host_copy` of its status block if the caller has brought one
+// back already, else read from the device (read_status).  Bit 0 = overflow: WAYNE_E_OVERFLOW.  Bit 1 = a bin beyond the
+// lanes' reach in an exposure launched without k_throw: if the caller names what to run `again` (wayne_exposure_run,
+// or wayne_exposure_run_front between the two halves), that is enqueued, now with k_throw, and *reran set -- the caller
+// then fetches what it needs a second time and looks again, without `again`.  The one place that re-runs an exposure.
+static int look_at_status(wayne_ctx* c, int slot, const Slot::Misc* host_copy, int (*again)(wayne_ctx*, int) = nullptr,
+                          bool* reran = nullptr) {
+  Slot& s = c->slots[slot];
+  Slot::Misc m{};
+  if (host_copy) m = *host_copy;
+  else if (int rc = read_status(c, s, &m)) return rc;
+  s.ran = false;                           // looked at
+  if (m.status & 1) return fail(c, WAYNE_E_OVERFLOW, "exposure: a sub-sample holds >= 2^32 electrons (or a bin >= 2^31)");
+  if (!(m.status & 2) || !again) return WAYNE_OK;
+  s.force_throw = true;
+  c->reruns += 1;
+  *reran = true;
+  return again(c, slot);
+}
 
 // Every slot whose last whole run nobody has looked at yet: read its status word (all of them in ONE copy) and run a
 // slot that met a bin beyond its launch sequence's reach a second time, with the general sequence.  Called with all
@@ -687,22 +717,16 @@ static int settle(wayne_ctx* c) {
     for (int i = 0; i < kSlots; ++i)
       if (c->slots[i].ran && c->slots[i].uploaded) hi = i;
     if (hi < 0) break;
-    HIP_TRY(c, hipMemcpy(c->status_host, c->status_all.p, (size_t)(hi + 1) * kMiscBytes, hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(c->status_host.p, c->status_all.p, (size_t)(hi + 1) * kMiscBytes, hipMemcpyDeviceToHost));
+    const bool may_rerun = pass == 0;     // (the second pass takes a run as it is)
     bool again = false;
     for (int i = 0; i <= hi; ++i) {
-      Slot& s = c->slots[i];
+      const Slot& s = c->slots[i];
       if (!s.ran || !s.uploaded) continue;
-      s.ran = false;
-      const int status = ((const Slot::Misc*)(c->status_host + (size_t)i * kMiscBytes))->status;
-      if (status & 1) {
-        err = fail(c, WAYNE_E_OVERFLOW, "exposure: a sub-sample holds >= 2^32 electrons (or a bin >= 2^31)");
-      } else if ((status & 2) && pass == 0) {
-        s.force_throw = true;
-        c->reruns += 1;
-        int rc = wayne_exposure_run(c, i);
-        if (rc) return rc;
-        again = true;
-      }
+      const int rc = look_at_status(c, i, (const Slot::Misc*)(c->status_host.p + (size_t)i * kMiscBytes),
+                                    may_rerun ? wayne_exposure_run : nullptr, &again);
+      if (rc == WAYNE_E_OVERFLOW) err = rc;
+      else if (rc) return rc;
     }
     if (!again) break;
     int rc = sync_all(c);
@@ -844,31 +868,14 @@ int wayne_psf_apply_ex(wayne_ctx* c, const int32_t* counts, int size, const doub
       // one pinned arena, one host-to-device copy (nine pageable copies cost ~0.1 ms of a 0.35 ms call)
       const size_t n = (size_t)size;
       const size_t need = align64((n + 1) * 4) + 3 * align64(n * 4) + 4 * align64(n * 8) + align64(sizeof(SubInfo)) + 64;
-      if (c->pa_stage_cap < need) {
-        if (c->pa_stage) (void)hipHostFree(c->pa_stage);
-        c->pa_stage = nullptr;
-        c->pa_stage_cap = 0;
-        if (hipHostMalloc((void**)&c->pa_stage, need, hipHostMallocDefault) != hipSuccess)
-          return fail(c, WAYNE_E_NOMEM, "psf_apply: pinned staging allocation failed");
-        c->pa_stage_cap = need;
-      }
-      HIP_TRY(c, c->pa_in.reserve(c->pa_stage_cap));
-      size_t used = 0;
-      auto stage = [&](DevBuf& b, const void* src, size_t bytes) {
-        if (bytes) std::memcpy(c->pa_stage + used, src, bytes);
-        b.view((char*)c->pa_in.p + used);
-        used += align64(std::max<size_t>(bytes, 1));
-      };
-      stage(c->pa_prefix, prefix.data(), (n + 1) * 4);
-      stage(c->pa_nwide, nwide.data(), n * 4);
-      stage(c->pa_nsplit, nsplit.data(), n * 4);
-      stage(c->pa_nlane, nlane.data(), n * 4);
-      stage(c->pa_x, x_pos, n * 8);
-      stage(c->pa_y, y_pos, n * 8);
-      stage(c->pa_sl, psf_sigmal, n * 8);
-      stage(c->pa_sh, psf_sigmah, n * 8);
-      stage(c->pa_sub, &si, sizeof si);
-      HIP_TRY(c, hipMemcpyAsync(c->pa_in.p, c->pa_stage, used, hipMemcpyHostToDevice, c->stream));
+      StageArena& st = c->pa_stage;       // (no event: this call synchronises the stream before it returns)
+      if ((rc = st.begin(c, need, "psf_apply: pinned staging allocation failed", false))) return rc;
+      const bool fits = st.put(c->pa_prefix, prefix.data(), (n + 1) * 4) && st.put(c->pa_nwide, nwide.data(), n * 4) &&
+                        st.put(c->pa_nsplit, nsplit.data(), n * 4) && st.put(c->pa_nlane, nlane.data(), n * 4) &&
+                        st.put(c->pa_x, x_pos, n * 8) && st.put(c->pa_y, y_pos, n * 8) && st.put(c->pa_sl, psf_sigmal, n * 8) &&
+                        st.put(c->pa_sh, psf_sigmah, n * 8) && st.put(c->pa_sub, &si, sizeof si);
+      if (!fits) return fail(c, WAYNE_E_NOMEM, "psf_apply: staging arena too small");
+      if ((rc = st.commit(c, c->stream))) return rc;
     }
 
     ThrowArgs a{};
@@ -1054,21 +1061,8 @@ int wayne_exposure_upload(wayne_ctx* c, int slot, const wayne_exposure_desc* d) 
     size_t need = 2 * align64((size_t)W * 8) + 3 * align64((size_t)K * 8) + 2 * align64((size_t)K * 4) + align64((size_t)R * 8) + 1024;
     if (d->lc_z) need += 2 * align64((size_t)K * 8) + align64((size_t)W * 8);
     if (d->depth) need += align64(KW * 8);
-    if (s.stage_pending) {           // the previous upload of this slot may still be reading the arena
-      HIP_TRY(c, hipEventSynchronize(s.stage_ev));
-      s.stage_pending = false;
-    }
-    if (s.stage_cap < need) {
-      if (s.stage) (void)hipHostFree(s.stage);
-      s.stage = nullptr;
-      s.stage_cap = 0;
-      if (hipHostMalloc((void**)&s.stage, need, hipHostMallocDefault) != hipSuccess)
-        return fail(c, WAYNE_E_NOMEM, "upload: pinned staging allocation failed");
-      s.stage_cap = need;
-    }
-    if (!s.stage_ev) HIP_TRY(c, hipEventCreateWithFlags(&s.stage_ev, hipEventDisableTiming));
-    s.stage_used = 0;
-    HIP_TRY(c, s.in_dev.reserve(s.stage_cap));
+    // (waits if the previous upload of this slot is still reading the arena)
+    if ((rc = s.stage.begin(c, need, "upload: pinned staging allocation failed"))) return rc;
   }
   if ((rc = upload_staged(c, s, s.wl, d->wl_um, (size_t)W))) return rc;
   if ((rc = upload_staged(c, s, s.flux, d->flux, (size_t)W))) return rc;
@@ -1093,25 +1087,10 @@ int wayne_exposure_upload(wayne_ctx* c, int slot, const wayne_exposure_desc* d) 
   if (s.has_replay_seed && (rc = upload_staged(c, s, s.rseed, d->replay_seed, (size_t)K))) return rc;
   if ((rc = upload_staged(c, s, s.sread, d->sample_read, (size_t)K))) return rc;
   if ((rc = upload_staged(c, s, s.read_dt, d->read_dt_s, (size_t)R))) return rc;
-  HIP_TRY(c, hipMemcpyAsync(s.in_dev.p, s.stage, s.stage_used, hipMemcpyHostToDevice, c->stream));   // one copy for all arrays
-  HIP_TRY(c, hipEventRecord(s.stage_ev, c->stream));
-  s.stage_pending = true;
-  for (DevBuf* b : {&s.ratio, &s.sigl, &s.sigh, &s.sens, &s.dlam}) HIP_TRY(c, b->reserve((size_t)W * sizeof(double)));
-  HIP_TRY(c, s.counts.reserve(KW * sizeof(int32_t)));
-  HIP_TRY(c, s.nwide.reserve(KW * sizeof(int32_t)));
-  HIP_TRY(c, s.nsplit.reserve(KW * sizeof(int32_t)));
-  HIP_TRY(c, s.nlane.reserve(KW * sizeof(int32_t)));
-  HIP_TRY(c, s.prefix.reserve((size_t)K * (W + 1) * sizeof(uint32_t)));
-  HIP_TRY(c, s.xpos.reserve(KW * sizeof(double)));
-  HIP_TRY(c, s.ypos.reserve(KW * sizeof(double)));
-  HIP_TRY(c, s.sub.reserve((size_t)K * sizeof(SubInfo)));
-  HIP_TRY(c, s.tr.reserve((size_t)K * kTrStride * sizeof(double)));
-  {
-    const size_t n_chunks = (size_t)(W + kPrepThreads - 1) / kPrepThreads;
-    if (n_chunks > (size_t)kMaxPrepChunks || W > 32768) return fail(c, WAYNE_E_INVALID, "upload: more than 32768 wavelength bins");
-    HIP_TRY(c, s.chunk_total.reserve((size_t)K * n_chunks * sizeof(uint32_t)));
-    HIP_TRY(c, s.chunk_box.reserve((size_t)K * n_chunks * 4 * sizeof(double)));
-  }
+  if ((rc = s.stage.commit(c, c->stream))) return rc;
+  if ((size_t)(W + kPrepThreads - 1) / kPrepThreads > (size_t)kMaxPrepChunks || W > 32768)
+    return fail(c, WAYNE_E_INVALID, "upload: more than 32768 wavelength bins");
+  if ((rc = reserve_source(c, s, K, W))) return rc;
   s.misc.view((char*)c->status_all.p + (size_t)slot * kMiscBytes);
   s.ran = false;
   const size_t SS = (size_t)c->S * c->S;
@@ -1137,12 +1116,9 @@ int wayne_exposure_upload(wayne_ctx* c, int slot, const wayne_exposure_desc* d) 
   {
     plan::ThrowPlan tp;
     plan::estimate_thrown(c->est, W, d->wl_um, d->flux, K, d->dur_ms, d->scale_factor, d->rng_mode, &tp);
-    s.est_thrown = tp.est_thrown; s.max_chunk_electrons = tp.max_chunk_electrons; s.max_narrow = tp.max_narrow;
-    std::memcpy(s.chunk_order, tp.chunk_order, sizeof s.chunk_order);
-    std::memcpy(s.lane_order, tp.lane_order, sizeof s.lane_order);
+    adopt_plan(c, s, K, W, tp);
   }
   lap(1, t_lap);
-  plan_lanes(c, s, K, W);
   s.use_box = plan::accumulator_boxes(c->est, W, d->wl_um, d->flux, K, R, c->S, d->sub_scale, d->x_ref, d->y_ref,
                                       d->sample_read, s.acc_box) && !(c->knobs.no_acc_box > 0);
   lap(2, t_lap);
@@ -1208,7 +1184,7 @@ static int front_source(wayne_ctx* c, int slot, Slot& s, SourceState& ss, int sr
     // no bin expected beyond a lane's cap (the rule on every BASELINE configuration): k_throw is not launched at
     // all -- an empty launch still costs ~8 us of the exposure's critical path -- and the lanes take what they
     // find up to kLaneReach electrons; a bin beyond that (the estimate carries no Poisson noise) sets status bit 1
-    // and the exposure is run again with k_throw when its status is read (check_status)
+    // and the exposure is run again with k_throw when its status is read (look_at_status; settle for a whole batch)
     // (knob `lane_reach`: a test knob that lowers the lanes' reach so that the re-run path can be exercised)
     int reach = kLaneReach;
     if (c->knobs.lane_reach >= 0) reach = (int)std::min<long long>(std::max<long long>(c->knobs.lane_reach, 1), kLaneReach);
@@ -1226,7 +1202,7 @@ static int front_source(wayne_ctx* c, int slot, Slot& s, SourceState& ss, int sr
     // a finely sampled scan holds a few electrons per bin and sub-sample: no bin is expected to reach the
     // multinomial's threshold (mean <= 6 against kSplitMin = 32: 1e-13 per draw), k_narrow's launch would only find
     // that out workgroup by workgroup (0.04 ms at K = 2233) -- it is left out, and a bin that qualifies after all
-    // flags the run, which is then repeated with every kernel (check_status)
+    // flags the run, which is then repeated with every kernel (look_at_status)
     skip_narrow = lane_unlimited && ss.max_narrow <= 6. && !(c->knobs.keep_narrow > 0);
     a.no_narrow = skip_narrow ? 1 : 0;
     CosmicArgs& ca = cosmic_args;
@@ -1445,8 +1421,8 @@ int wayne_exposure_run_back(wayne_ctx* c, int slot) {
       // charge traps (wayne_exposure_set_traps): the model, the per-read intervals and the staged start tables
       TrapArgs t{};
       t.G = s.trap_G;
-      t.start_d = s.trap_tab.as<double>();
-      t.start_f = (const float*)((const char*)s.trap_tab.p + s.trap_f_off);
+      t.start_d = s.trap_d.as<double>();
+      t.start_f = s.trap_f.as<float>();
       t.rate_lo = s.trap_lo;
       t.ln_lo = std::log(s.trap_lo);
       t.u_scale = s.trap_G > 2 ? (double)(s.trap_G - 2) / std::log(s.trap_hi / s.trap_lo) : 0.;
@@ -1506,36 +1482,20 @@ int wayne_exposure_status(wayne_ctx* c, int slot, int* status) {
   (void)hipSetDevice(c->device);
   use_slot_stream(c, slot);
   Slot::Misc m{};
-  HIP_TRY(c, hipMemcpyAsync(&m, s.misc.p, sizeof m, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  int rc = read_status(c, s, &m);
+  if (rc) return rc;
   *status = m.status;
   return WAYNE_OK;
 }
 
 unsigned long long wayne_ctx_reruns(const wayne_ctx* c) { return c ? (unsigned long long)c->reruns : 0ull; }
 
-// Status word of the slot's last run: bit 0 = overflow (an error), bit 1 = a bin beyond the lanes' reach in an
-// exposure launched without k_throw (*rerun is set: the caller runs the exposure again, now with k_throw).
-static int check_status(wayne_ctx* c, Slot& s, bool* rerun = nullptr) {
-  struct { unsigned long long electrons; int status; int pad; } m{};
-  HIP_TRY(c, hipMemcpyAsync(&m, s.misc.p, sizeof m, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  s.ran = false;                           // looked at
-  if (m.status & 1) return fail(c, WAYNE_E_OVERFLOW, "exposure: a sub-sample holds >= 2^32 electrons (or a bin >= 2^31)");
-  if (rerun) *rerun = (m.status & 2) != 0;
-  return WAYNE_OK;
-}
-
 int wayne_exposure_run_checked(wayne_ctx* c, int slot) {
   int rc = wayne_exposure_run(c, slot);
   if (rc) return rc;
-  Slot& s = c->slots[slot];
-  bool rerun = false;
-  if ((rc = check_status(c, s, &rerun)) || !rerun) return rc;
-  s.force_throw = true;
-  c->reruns += 1;
-  if ((rc = wayne_exposure_run(c, slot))) return rc;
-  return check_status(c, s);
+  bool reran = false;
+  if ((rc = look_at_status(c, slot, nullptr, wayne_exposure_run, &reran)) || !reran) return rc;
+  return look_at_status(c, slot, nullptr);
 }
 
 int wayne_exposure_download(wayne_ctx* c, int slot, void* out_reads) {
@@ -1548,14 +1508,11 @@ int wayne_exposure_download(wayne_ctx* c, int slot, void* out_reads) {
   const size_t SS = (size_t)c->S * c->S;
   const size_t out_elem = (s.d.flags & WAYNE_F_OUT_F64) ? sizeof(double) : sizeof(float);
   HIP_TRY(c, hipMemcpyAsync(out_reads, s.out.p, (size_t)(s.R + 1) * SS * out_elem, hipMemcpyDeviceToHost, c->stream));
-  bool rerun = false;
-  int rc = check_status(c, s, &rerun);
-  if (rc || !rerun) return rc;
-  s.force_throw = true;
-  c->reruns += 1;
-  if ((rc = wayne_exposure_run(c, slot))) return rc;
+  bool reran = false;
+  int rc = look_at_status(c, slot, nullptr, wayne_exposure_run, &reran);
+  if (rc || !reran) return rc;
   HIP_TRY(c, hipMemcpyAsync(out_reads, s.out.p, (size_t)(s.R + 1) * SS * out_elem, hipMemcpyDeviceToHost, c->stream));
-  return check_status(c, s);
+  return look_at_status(c, slot, nullptr);
 }
 
 int wayne_exposure_fetch_async(wayne_ctx* c, int slot) {
@@ -1567,16 +1524,10 @@ int wayne_exposure_fetch_async(wayne_ctx* c, int slot) {
   use_slot_stream(c, slot);
   const size_t SS = (size_t)c->S * c->S;
   const size_t bytes = (size_t)(s.R + 1) * SS * ((s.d.flags & WAYNE_F_OUT_F64) ? sizeof(double) : sizeof(float));
-  const size_t tail = (bytes + 63) & ~(size_t)63;
-  if (s.pinned_cap < tail + 64) {
-    if (s.pinned) (void)hipHostFree(s.pinned);
-    s.pinned = nullptr;
-    s.pinned_cap = 0;
-    if (hipHostMalloc(&s.pinned, tail + 64, hipHostMallocDefault) != hipSuccess)
-      return fail(c, WAYNE_E_NOMEM, "fetch_async: pinned host allocation failed");
-    s.pinned_cap = tail + 64;
-  }
-  s.pinned_misc = (Slot::Misc*)((char*)s.pinned + tail);
+  const size_t tail = align64(bytes);
+  s.pinned_misc = nullptr;
+  if (!s.pinned.reserve(tail + 64)) return fail(c, WAYNE_E_NOMEM, "fetch_async: pinned host allocation failed");
+  s.pinned_misc = (Slot::Misc*)(s.pinned.p + tail);
   // The copy follows the slot's kernels on the slot's own stream: while it runs (1.2 ms at 55 GB/s for a full
   // frame) the kernels of the exposure in the next slot run on the other stream.  (A separate copy stream fed by
   // events was measured: 660-700 exposures/s instead of 810-826 -- scripts/probe_pipeline.py.)
@@ -1584,7 +1535,7 @@ int wayne_exposure_fetch_async(wayne_ctx* c, int slot) {
     HIP_TRY(c, hipEventRecord(c->ev_kdone[slot % 2], c->stream));
     c->kdone_valid[slot % 2] = true;
   }
-  HIP_TRY(c, hipMemcpyAsync(s.pinned, s.out.p, bytes, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(s.pinned.p, s.out.p, bytes, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipMemcpyAsync(s.pinned_misc, s.misc.p, sizeof(Slot::Misc), hipMemcpyDeviceToHost, c->stream));
   return WAYNE_OK;
 }
@@ -1593,26 +1544,17 @@ int wayne_exposure_wait(wayne_ctx* c, int slot, void** host_reads) {
   if (!c || !host_reads) return WAYNE_E_INVALID;
   if (slot < 0 || slot >= kSlots) return fail(c, WAYNE_E_INVALID, "wait: slot");
   Slot& s = c->slots[slot];
-  if (!s.uploaded || !s.pinned || !s.pinned_misc) return fail(c, WAYNE_E_STATE, "wait: fetch_async first");
+  if (!s.uploaded || !s.pinned.p || !s.pinned_misc) return fail(c, WAYNE_E_STATE, "wait: fetch_async first");
   (void)hipSetDevice(c->device);
   use_slot_stream(c, slot);
   HIP_TRY(c, hipStreamSynchronize(c->stream));
-  *host_reads = s.pinned;
-  s.ran = false;                             // looked at (the status word came with the reads)
-  if (s.pinned_misc->status & 1)
-    return fail(c, WAYNE_E_OVERFLOW, "exposure: a sub-sample holds >= 2^32 electrons (or a bin >= 2^31)");
-  if (s.pinned_misc->status & 2) {           // a bin beyond the lanes' reach: once more, with k_throw
-    s.force_throw = true;
-    c->reruns += 1;
-    int rc = wayne_exposure_run(c, slot);
-    if (rc == WAYNE_OK) rc = wayne_exposure_fetch_async(c, slot);
-    if (rc) return rc;
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    s.ran = false;
-    if (s.pinned_misc->status & 1)
-      return fail(c, WAYNE_E_OVERFLOW, "exposure: a sub-sample holds >= 2^32 electrons (or a bin >= 2^31)");
-  }
-  return WAYNE_OK;
+  *host_reads = s.pinned.p;
+  bool reran = false;                        // (the status word came with the reads)
+  int rc = look_at_status(c, slot, s.pinned_misc, wayne_exposure_run, &reran);
+  if (rc || !reran) return rc;
+  if ((rc = wayne_exposure_fetch_async(c, slot))) return rc;     // a bin beyond the lanes' reach: once more, with k_throw
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return look_at_status(c, slot, s.pinned_misc);
 }
 
 void* wayne_exposure_device_reads(wayne_ctx* c, int slot) {
@@ -1653,15 +1595,10 @@ static int fetch_source(wayne_ctx* c, int slot, int src, int32_t* counts, double
   if (y_pos) HIP_TRY(c, hipMemcpyAsync(y_pos, ss.ypos.p, KW * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   {
     // (between run_front and run_back: a run that met a bin beyond the lanes' reach is repeated with k_throw first)
-    bool rerun = false;
-    int rc = check_status(c, s, &rerun);
+    bool reran = false;
+    int rc = look_at_status(c, slot, nullptr, s.front_done ? wayne_exposure_run_front : nullptr, &reran);
     if (rc) return rc;
-    if (rerun && s.front_done) {
-      s.force_throw = true;
-      c->reruns += 1;
-      if ((rc = wayne_exposure_run_front(c, slot))) return rc;
-      return fetch_source(c, slot, src, counts, x_pos, y_pos, acc_e);
-    }
+    if (reran) return fetch_source(c, slot, src, counts, x_pos, y_pos, acc_e);
   }
   if (acc_e) {
     const size_t n = (size_t)s.R * c->S * c->S;
@@ -1670,7 +1607,7 @@ static int fetch_source(wayne_ctx* c, int slot, int src, int32_t* counts, double
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     for (size_t i = 0; i < n; ++i) acc_e[i] = (double)tmp[i] * kInvQ;
   }
-  return check_status(c, s);
+  return look_at_status(c, slot, nullptr);
 }
 
 int wayne_exposure_debug_fetch(wayne_ctx* c, int slot, int32_t* counts, double* x_pos, double* y_pos,
@@ -1748,12 +1685,13 @@ int wayne_exposure_set_sources(wayne_ctx* c, int slot, const wayne_source_desc* 
   // from here on a failure leaves the slot as uploaded: the target alone, with the target's boxes
   s.n_extra = 0;
   s.front_done = false;
-  const double* x0 = staged_host<double>(s, s.xref);
-  const double* y0 = staged_host<double>(s, s.yref);
-  const double* dur = staged_host<double>(s, s.dur);
-  const int32_t* sread = staged_host<int32_t>(s, s.sread);
+  // (the target's arrays, as the slot's arena still holds them)
+  const double* x0 = s.stage.host_of<double>(s.xref);
+  const double* y0 = s.stage.host_of<double>(s.yref);
+  const double* dur = s.stage.host_of<double>(s.dur);
+  const int32_t* sread = s.stage.host_of<int32_t>(s.sread);
   const bool no_box = c->knobs.no_acc_box > 0;
-  s.use_box = plan::accumulator_boxes(c->est, s.W, staged_host<double>(s, s.wl), staged_host<double>(s, s.flux), K, R, c->S,
+  s.use_box = plan::accumulator_boxes(c->est, s.W, s.stage.host_of<double>(s.wl), s.stage.host_of<double>(s.flux), K, R, c->S,
                                       s.d.sub_scale, x0, y0, sread, s.acc_box) && !no_box;
   if (n == 0) return WAYNE_OK;
   bool use_box = s.use_box;
@@ -1763,62 +1701,23 @@ int wayne_exposure_set_sources(wayne_ctx* c, int slot, const wayne_source_desc* 
     const wayne_source_desc& q = src[i];
     SourceState& e = s.extra[i];
     const int W = q.n_wl;
-    const size_t KW = (size_t)K * W;
-    const size_t need = 2 * align64((size_t)W * 8) + 2 * align64((size_t)K * 8) + 256;
-    if (e.src_stage_pending) {       // the previous copy from this arena may still be running
-      HIP_TRY(c, hipEventSynchronize(e.src_stage_ev));
-      e.src_stage_pending = false;
-    }
-    if (e.src_stage_cap < need) {
-      if (e.src_stage) (void)hipHostFree(e.src_stage);
-      e.src_stage = nullptr;
-      e.src_stage_cap = 0;
-      if (hipHostMalloc((void**)&e.src_stage, need, hipHostMallocDefault) != hipSuccess)
-        return fail(c, WAYNE_E_NOMEM, "set_sources: pinned staging allocation failed");
-      e.src_stage_cap = need;
-    }
-    if (!e.src_stage_ev) HIP_TRY(c, hipEventCreateWithFlags(&e.src_stage_ev, hipEventDisableTiming));
-    HIP_TRY(c, e.src_dev.reserve(e.src_stage_cap));
-    size_t used = 0;
-    auto place = [&](DevBuf& b, size_t bytes) -> char* {
-      char* h = e.src_stage + used;
-      b.view((char*)e.src_dev.p + used);
-      used += align64(bytes);
-      return h;
-    };
-    std::memcpy(place(e.wl, (size_t)W * 8), q.wl_um, (size_t)W * 8);
-    std::memcpy(place(e.flux, (size_t)W * 8), q.flux, (size_t)W * 8);
-    double* xs = (double*)place(e.xref, (size_t)K * 8);
-    double* ys = (double*)place(e.yref, (size_t)K * 8);
+    StageArena& st = e.src_stage;
+    int rc = st.begin(c, 2 * align64((size_t)W * 8) + 2 * align64((size_t)K * 8) + 256, "set_sources: pinned staging allocation failed");
+    if (rc) return rc;
+    const bool fits = st.put(e.wl, q.wl_um, (size_t)W * 8) && st.put(e.flux, q.flux, (size_t)W * 8);
+    double* xs = (double*)st.place(e.xref, (size_t)K * 8);
+    double* ys = (double*)st.place(e.yref, (size_t)K * 8);
+    if (!fits || !xs || !ys) return fail(c, WAYNE_E_NOMEM, "set_sources: staging arena too small");
     for (int k = 0; k < K; ++k) { xs[k] = x0[k] + q.dx; ys[k] = y0[k] + q.dy; }
-    HIP_TRY(c, hipMemcpyAsync(e.src_dev.p, e.src_stage, used, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipEventRecord(e.src_stage_ev, c->stream));
-    e.src_stage_pending = true;
-    for (DevBuf* b : {&e.ratio, &e.sigl, &e.sigh, &e.sens, &e.dlam}) HIP_TRY(c, b->reserve((size_t)W * sizeof(double)));
-    HIP_TRY(c, e.counts.reserve(KW * sizeof(int32_t)));
-    HIP_TRY(c, e.nwide.reserve(KW * sizeof(int32_t)));
-    HIP_TRY(c, e.nsplit.reserve(KW * sizeof(int32_t)));
-    HIP_TRY(c, e.nlane.reserve(KW * sizeof(int32_t)));
-    HIP_TRY(c, e.prefix.reserve((size_t)K * (W + 1) * sizeof(uint32_t)));
-    HIP_TRY(c, e.xpos.reserve(KW * sizeof(double)));
-    HIP_TRY(c, e.ypos.reserve(KW * sizeof(double)));
-    HIP_TRY(c, e.sub.reserve((size_t)K * sizeof(SubInfo)));
-    HIP_TRY(c, e.tr.reserve((size_t)K * kTrStride * sizeof(double)));
-    {
-      const size_t n_chunks = (size_t)(W + kPrepThreads - 1) / kPrepThreads;
-      HIP_TRY(c, e.chunk_total.reserve((size_t)K * n_chunks * sizeof(uint32_t)));
-      HIP_TRY(c, e.chunk_box.reserve((size_t)K * n_chunks * 4 * sizeof(double)));
-    }
+    if ((rc = st.commit(c, c->stream))) return rc;
+    if ((rc = reserve_source(c, e, K, W))) return rc;
     e.W = W;
     e.seed = wayne_source_seed(s.d.seed, q.tag);
     e.fused_last = false;
     // the plan of the single-source exposure with these inputs (wayne_exposure_upload)
     plan::ThrowPlan tp;
     plan::estimate_thrown(c->src_est[i], W, q.wl_um, q.flux, K, dur, s.d.scale_factor, s.d.rng_mode, &tp);
-    e.est_thrown = tp.est_thrown; e.max_chunk_electrons = tp.max_chunk_electrons; e.max_narrow = tp.max_narrow;
-    std::memcpy(e.chunk_order, tp.chunk_order, sizeof e.chunk_order);
-    std::memcpy(e.lane_order, tp.lane_order, sizeof e.lane_order);
-    plan_lanes(c, e, K, W);
+    adopt_plan(c, e, K, W, tp);
     // k_ramp loads (and clears) an accumulator only inside its read's box: the box is the union over the sources, each
     // at its own positions -- a contaminant's electrons outside it would vanish from this exposure and reappear in the
     // next one of the slot
@@ -1875,31 +1774,18 @@ int wayne_exposure_set_traps(wayne_ctx* c, int slot, const wayne_trap_desc* t) {
     if (!(s.read_dt_host[r] > 0.)) return fail(c, WAYNE_E_INVALID, "set_traps: every read interval must be > 0");
   (void)hipSetDevice(c->device);
   use_slot_stream(c, slot);
-  const size_t off_f = align64((size_t)2 * G * sizeof(double)), need = off_f + (size_t)2 * G * sizeof(float);
-  if (s.trap_pending) {              // the previous copy from the pinned tables may still be running
-    HIP_TRY(c, hipEventSynchronize(s.trap_ev));
-    s.trap_pending = false;
-  }
-  if (s.trap_stage_cap < need) {
-    if (s.trap_stage) (void)hipHostFree(s.trap_stage);
-    s.trap_stage = nullptr;
-    s.trap_stage_cap = 0;
-    if (hipHostMalloc((void**)&s.trap_stage, need, hipHostMallocDefault) != hipSuccess)
-      return fail(c, WAYNE_E_NOMEM, "set_traps: pinned staging allocation failed");
-    s.trap_stage_cap = need;
-  }
-  if (!s.trap_ev) HIP_TRY(c, hipEventCreateWithFlags(&s.trap_ev, hipEventDisableTiming));
-  double* hd = (double*)s.trap_stage;
-  float* hf = (float*)(s.trap_stage + off_f);
+  const size_t bytes_d = (size_t)2 * G * sizeof(double), bytes_f = (size_t)2 * G * sizeof(float);
+  int rc = s.trap_stage.begin(c, align64(bytes_d) + bytes_f, "set_traps: pinned staging allocation failed");
+  if (rc) return rc;
+  double* hd = (double*)s.trap_stage.place(s.trap_d, bytes_d);
+  float* hf = (float*)s.trap_stage.place(s.trap_f, bytes_f);
+  if (!hd || !hf) return fail(c, WAYNE_E_NOMEM, "set_traps: staging arena too small");
   for (int p = 0; p < 2; ++p)
     for (int j = 0; j < G; ++j) {
       hd[p * G + j] = t->start[p][j];
       hf[p * G + j] = (float)t->start[p][j];
     }
-  HIP_TRY(c, s.trap_tab.reserve(s.trap_stage_cap));
-  HIP_TRY(c, hipMemcpyAsync(s.trap_tab.p, s.trap_stage, need, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(c, hipEventRecord(s.trap_ev, c->stream));
-  s.trap_pending = true;
+  if ((rc = s.trap_stage.commit(c, c->stream))) return rc;
   for (int p = 0; p < 2; ++p) {
     s.trap_n[p] = t->n_traps[p];
     s.trap_eta[p] = t->efficiency[p];
@@ -1908,7 +1794,6 @@ int wayne_exposure_set_traps(wayne_ctx* c, int slot, const wayne_trap_desc* t) {
   s.trap_lo = t->rate_lo;
   s.trap_hi = t->rate_hi;
   s.trap_G = G;
-  s.trap_f_off = off_f;
   s.traps_on = true;
   return WAYNE_OK;
 }
