@@ -243,7 +243,8 @@ class Context(object):
             raise cls(st.value, "wayne_ctx_create(device=%d): %s -- the HIP path is the only path, "
                                 "there is no CPU fallback" % (device, msg))
         self.device = device
-        self._keep = []  # arrays referenced by descriptors during a call
+        self._slot_meta = {}     # slot -> (K, W, R, float64 reads) of the descriptor uploaded last
+        self._slot_src = {}      # slot -> bins of each of its contaminants
         _live_contexts.add(self)
         for name, value in _knob_defaults.items():
             self.set_knob(name, value)
@@ -362,9 +363,7 @@ class Context(object):
         """Stage the descriptor in `slot`; contaminants and charge traps it carries (make_desc(sources=..., traps=...))
         are set with it."""
         self.check(self._L.wayne_exposure_upload(self._h, int(slot), C.byref(desc)))
-        self._slot_meta = getattr(self, "_slot_meta", {})
         self._slot_meta[slot] = (desc.n_samples, desc.n_wl, desc.n_reads, bool(desc.flags & F_OUT_F64))
-        self._slot_src = getattr(self, "_slot_src", {})
         self._slot_src[slot] = ()
         sources = getattr(desc, "_sources", None)
         if sources:
@@ -405,7 +404,6 @@ class Context(object):
             arr[i].tag, arr[i].n_wl = int(s.tag), wl.size
             arr[i].wl_um, arr[i].flux = ptr(wl, C.c_double), ptr(fl, C.c_double)
             arr[i].dx, arr[i].dy = float(s.dx), float(s.dy)
-        self._slot_src = getattr(self, "_slot_src", {})
         self._slot_src[slot] = ()        # (a refused list leaves the slot with the target alone)
         self.check(self._L.wayne_exposure_set_sources(self._h, int(slot), arr, len(sources)))
         self._slot_src[slot] = tuple(int(k.size) for k in keep[0::2])

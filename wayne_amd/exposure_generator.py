@@ -50,8 +50,7 @@ class ExposureGenerator(object):
         self.NSAMP, self.SAMPSEQ, self.SUBARRAY = NSAMP, SAMPSEQ, SUBARRAY
         self.calibration = calibration if calibration is not None else grism.calibration
         self.device, self.seed, self.exposure_index = device, seed, exposure_index
-        self._submit_slot, self._pending = None, None      # pipelined use: submit() / collect()
-        self._prepare_only, self._prepared = False, None   # ... or prepare() on one thread, launch() / collect() on another
+        self._prepared = None      # (engine, descriptor, start time) of prepare()
 
         self.exptime = self.detector.exptime(NSAMP, SUBARRAY, SAMPSEQ)             # s
         self.read_times = self.detector.get_read_times(NSAMP, SUBARRAY, SAMPSEQ)   # s
@@ -97,19 +96,23 @@ class ExposureGenerator(object):
         return y_ref + (np.asarray(mid_points, dtype=float) * scan_speed)
 
     # -- exposures ---------------------------------------------------------------
-    def staring_frame(self, x_ref, y_ref, x_jitter, y_jitter, wl, stellar_flux, planet_signal,
-                      sample_mid_points, sample_durations, read_index, noise_mean, noise_std, add_dark,
-                      add_flat, cosmic_rate, sky_background, scale_factor, add_gain_variations,
-                      add_non_linear, clip_values_det_limits, add_read_noise, add_stellar_noise,
-                      add_initial_bias, progress_bar=None, threads=2, **kw):
-        """A staring exposure is a scan at speed 0 sampled once per read (:146-176)."""
-        self.scanning_frame(
-            x_ref, y_ref, x_jitter, y_jitter, wl, stellar_flux, planet_signal, 0.0, MS_PER_YEAR,
-            sample_mid_points, sample_durations, read_index, None, noise_mean, noise_std, add_dark, add_flat,
-            cosmic_rate, sky_background, scale_factor, add_gain_variations, add_non_linear,
-            clip_values_det_limits, add_read_noise, add_stellar_noise, add_initial_bias, progress_bar, threads,
-            **kw)
-        return self.exposure
+    @staticmethod
+    def _staring_as_scan(x_ref, y_ref, x_jitter, y_jitter, wl, stellar_flux, planet_signal,
+                         sample_mid_points, sample_durations, read_index, noise_mean, noise_std, add_dark,
+                         add_flat, cosmic_rate, sky_background, scale_factor, add_gain_variations,
+                         add_non_linear, clip_values_det_limits, add_read_noise, add_stellar_noise,
+                         add_initial_bias, progress_bar=None, threads=2, **kw):
+        """staring_frame's argument list (the reference's, :146-176) as scanning_frame's -> (args, keywords)."""
+        return (x_ref, y_ref, x_jitter, y_jitter, wl, stellar_flux, planet_signal, 0.0, MS_PER_YEAR,
+                sample_mid_points, sample_durations, read_index, None, noise_mean, noise_std, add_dark, add_flat,
+                cosmic_rate, sky_background, scale_factor, add_gain_variations, add_non_linear,
+                clip_values_det_limits, add_read_noise, add_stellar_noise, add_initial_bias, progress_bar,
+                threads), kw
+
+    def staring_frame(self, *args, **kw):
+        """A staring exposure is a scan at speed 0 sampled once per read (:146-176); arguments: _staring_as_scan."""
+        args, kw = self._staring_as_scan(*args, **kw)
+        return self.scanning_frame(*args, **kw)
 
     def scanning_frame(self, x_ref, y_ref, x_jitter, y_jitter, wl, stellar_flux, planet_signal,
                        scan_speed, sample_rate, sample_mid_points=None, sample_durations=None,
@@ -146,26 +149,12 @@ class ExposureGenerator(object):
         start tables from its visit, as Observation.setup_charge_traps passes them; or a traps.ChargeTraps alone, whose
         traps then start every pixel at `initial`).
         """
-        start_time = time.time()
-        slot = self._submit_slot
-        eng = _engine.get_engine(self.device, self.grism, self.detector, self.calibration, self.NSAMP,
-                                 self.SAMPSEQ, self.SUBARRAY, add_initial_bias, g102_flat_quirk=reference_quirks)
-        desc = self.build_descriptor(
-            eng, x_ref, y_ref, x_jitter, y_jitter, wl, stellar_flux, planet_signal, scan_speed, sample_rate,
+        eng, desc, start_time = self._host_half(
+            x_ref, y_ref, x_jitter, y_jitter, wl, stellar_flux, planet_signal, scan_speed, sample_rate,
             sample_mid_points, sample_durations, read_index, ssv_generator, noise_mean, noise_std, add_dark,
             add_flat, cosmic_rate, sky_background, scale_factor, add_gain_variations, add_non_linear,
             clip_values_det_limits, add_read_noise, add_stellar_noise, add_initial_bias, progress_bar, threads,
             rng_mode, out_dtype, reference_quirks, exact_samplers, contaminants, charge_traps)
-        if self._prepare_only:
-            self._prepared = (eng, desc, start_time)        # host half done; launch(slot) does the rest
-            return None
-        if slot is not None:
-            # pipelined use (submit / collect): enqueue everything and return; the reads are picked up later
-            eng.ctx.upload(slot, desc)
-            eng.ctx.run(slot)
-            eng.ctx.fetch_async(slot)
-            self._pending = (eng, slot, start_time)
-            return None
         if record is None:
             reads = eng.ctx.synthesize(desc)
         else:
@@ -177,7 +166,9 @@ class ExposureGenerator(object):
             reads = eng.ctx.download(0)
         return self._fill_exposure(reads, start_time)
 
-    def _fill_exposure(self, reads, start_time):
+    def _fill_exposure(self, reads, start_time=None):
+        """The reads of this generator's descriptor -> its Exposure (the arrays are kept, not copied); `start_time`:
+        when the exposure's generation began, for the header's SIM-TIME (None: left as it is)."""
         # read 0 is the zero read (:301-303); reads 1..R carry their timing (:371-382)
         R = len(self.read_times)
         read_dt = self._read_dt
@@ -186,47 +177,41 @@ class ExposureGenerator(object):
             self.exposure.add_read(reads[r + 1], {"cumulative_exp_time": float(self.read_times[r]),
                                                   "read_exp_time": float(read_dt[r]), "CRPIX1": 0})
         assert len(self.exposure.reads) == self.NSAMP                                  # (:397)
-        self.exp_info["sim_time"] = time.time() - start_time
+        if start_time is not None:
+            self.exp_info["sim_time"] = time.time() - start_time
         return self.exposure
 
-    # -- pipelined generation: the host prepares exposure n+1 while the GPU works on n ---------------
-    def submit(self, slot, *args, staring=False, **kw):
-        """Enqueue a scanning (or staring) frame on context slot `slot` -- same arguments as
-        scanning_frame / staring_frame -- and return at once; collect() returns the Exposure."""
-        self._submit_slot = int(slot)
-        try:
-            (self.staring_frame if staring else self.scanning_frame)(*args, **kw)
-        finally:
-            self._submit_slot = None
-        return self
+    def _host_half(self, x_ref, y_ref, x_jitter, y_jitter, wl, stellar_flux, planet_signal,
+                   scan_speed, sample_rate, sample_mid_points=None, sample_durations=None,
+                   read_index=None, ssv_generator=None, noise_mean=False, noise_std=False,
+                   add_dark=True, add_flat=True, cosmic_rate=None, sky_background=1.0,
+                   scale_factor=None, add_gain_variations=True, add_non_linear=True,
+                   clip_values_det_limits=True, add_read_noise=True, add_stellar_noise=True,
+                   add_initial_bias=True, progress_bar=None, threads=2,
+                   rng_mode=_lib.RNG_SPLIT, out_dtype=np.float32, reference_quirks=False,
+                   exact_samplers=False, contaminants=None, charge_traps=None):
+        """scanning_frame's arguments -> (engine, descriptor, start time): the mode's engine (cached after its first
+        use) and build_descriptor.  No GPU call once the engine exists."""
+        start_time = time.time()
+        eng = _engine.get_engine(self.device, self.grism, self.detector, self.calibration, self.NSAMP,
+                                 self.SAMPSEQ, self.SUBARRAY, add_initial_bias, g102_flat_quirk=reference_quirks)
+        desc = self.build_descriptor(
+            eng, x_ref, y_ref, x_jitter, y_jitter, wl, stellar_flux, planet_signal, scan_speed, sample_rate,
+            sample_mid_points, sample_durations, read_index, ssv_generator, noise_mean, noise_std, add_dark,
+            add_flat, cosmic_rate, sky_background, scale_factor, add_gain_variations, add_non_linear,
+            clip_values_det_limits, add_read_noise, add_stellar_noise, add_initial_bias, progress_bar, threads,
+            rng_mode, out_dtype, reference_quirks, exact_samplers, contaminants, charge_traps)
+        return eng, desc, start_time
 
     def prepare(self, *args, staring=False, **kw):
-        """The HOST half of a scanning (or staring) frame -- same arguments -- and nothing else: sample timing, scan
-        positions, jitter draws, the descriptor.  No GPU call, so it may run on another thread than the one that
-        owns the context; launch(slot) then uploads and enqueues it, collect() returns the Exposure."""
-        self._prepare_only = True
-        try:
-            (self.staring_frame if staring else self.scanning_frame)(*args, **kw)
-        finally:
-            self._prepare_only = False
+        """The HOST half of a scanning (or, with `staring`, a staring) frame -- same arguments -- and nothing else:
+        sample timing, scan positions, jitter draws, the descriptor.  It may run on another thread than the one that
+        owns the context (pipeline.run_pipelined): `_prepared` = (engine, descriptor, start time) is what that thread
+        uploads and runs, and _fill_exposure turns its reads into the Exposure."""
+        if staring:
+            args, kw = self._staring_as_scan(*args, **kw)
+        self._prepared = self._host_half(*args, **kw)
         return self
-
-    def launch(self, slot):
-        """Upload a prepared frame into context slot `slot` and enqueue its kernels and the copy of its reads."""
-        eng, desc, start_time = self._prepared
-        self._prepared = None
-        eng.ctx.upload(int(slot), desc)
-        eng.ctx.run(int(slot))
-        eng.ctx.fetch_async(int(slot))
-        self._pending = (eng, int(slot), start_time)
-        return self
-
-    def collect(self):
-        """Wait for a submitted frame -> Exposure (the reads are copied out of the slot's pinned buffer)."""
-        eng, slot, start_time = self._pending
-        self._pending = None
-        reads = np.array(eng.ctx.wait(slot))
-        return self._fill_exposure(reads, start_time)
 
     def build_descriptor(self, eng, x_ref, y_ref, x_jitter, y_jitter, wl, stellar_flux, planet_signal,
                          scan_speed, sample_rate, sample_mid_points=None, sample_durations=None,

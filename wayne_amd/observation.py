@@ -12,7 +12,6 @@ instead of an exodata object.  What changed underneath:
   * exposures are independent (counter-based RNG), so `run_observation` can
     take a (rank, world) pair and generate only its round-robin share.
 """
-import collections
 import os
 
 import numpy as np
@@ -302,94 +301,43 @@ class Observation(object):
         if rank == 0 and not (resume and write_fits and os.path.isfile(os.path.join(self.outdir, "0000_flt.fits"))
                               and self._fits_is_whole(os.path.join(self.outdir, "0000_flt.fits"))):
             frames[0] = self._generate_direct_image(write_fits)
-        # files are written by background threads while the GPU works on the next exposures
-        import sys
-        from .exposure import FitsWriterPool
-        old_interval = sys.getswitchinterval()
-        pool = FitsWriterPool() if write_fits else None
-        # ... and the host prepares exposure n+1.. while the GPU generates n: up to `depth` exposures
-        # in flight on alternating context slots (even / odd slots run on different HIP streams)
-        depth = 3
-        in_flight = collections.deque()
-
-        def finish_oldest():
-            j, gen = in_flight.popleft()
-            frame = gen.collect()
-            if pool is not None:
-                pool.submit(frame, self.outdir, "{:04d}_raw.fits".format(j + 1))
-                frames[j + 1] = None          # on disk; do not keep 64 MB per exposure alive
-            else:
-                frames[j + 1] = frame
-
-        # ... on two host threads: a producer runs the host half of every exposure (sample times, orbit phases, jitter
-        # draws, the descriptor: ExposureGenerator.prepare -- no GPU call), this thread uploads, launches and collects.
-        # Their C calls release the interpreter lock, so the example visit is paced by the device, not by Python.
-        import queue
-        import threading
-        ahead = queue.Queue(maxsize=depth + 1)
         mine = list(range(rank, len(self.exp_start_times), world))
         self.skipped = []
         if resume and write_fits:
             self.skipped = [i for i in mine if self.exposure_file_is_whole(i + 1)]
             done = set(self.skipped)
             mine = [i for i in mine if i not in done]
-        stop = threading.Event()            # set by this thread when it leaves the loop, for whatever reason
-        # The context is created HERE, on the thread that will use it (upload / launch / collect): the producer's
-        # prepare() then finds the engine in the cache instead of building the context, uploading grism and calibration,
-        # on its own thread.
+        # The context is created HERE, on the thread that will use it (upload / run / wait): the producer's prepare()
+        # then finds the engine in the cache instead of building the context, uploading grism and calibration, on its
+        # own thread.
         from . import engine as _engine
         opts = dict(self.frame_options)
-        _engine.get_engine(self.device, self.grism, self.detector, self.calibration, self.NSAMP, self.SAMPSEQ,
-                           self.SUBARRAY, opts.get("add_initial_bias", self.add_initial_bias),
-                           g102_flat_quirk=bool(opts.get("reference_quirks", False)))
+        eng = _engine.get_engine(self.device, self.grism, self.detector, self.calibration, self.NSAMP, self.SAMPSEQ,
+                                 self.SUBARRAY, opts.get("add_initial_bias", self.add_initial_bias),
+                                 g102_flat_quirk=bool(opts.get("reference_quirks", False)))
+        # files are written by background threads while the GPU works on the next exposures
+        from .exposure import FitsWriterPool
+        from .pipeline import run_pipelined
+        pool = FitsWriterPool() if write_fits else None
 
-        def put(item):
-            """Queue.put that gives up when the consumer has gone (returns False)."""
-            while not stop.is_set():
-                try:
-                    ahead.put(item, timeout=0.05)
-                    return True
-                except queue.Full:
-                    pass
-            return False
+        def prepare(i):
+            gen = self._generate_exposure(self.exp_start_times[i], i + 1, write_fits=False, prepare_only=True)
+            return gen._prepared[1], gen
 
-        def produce():
-            try:
-                for i in mine:
-                    if stop.is_set():
-                        return
-                    if not put((i, self._generate_exposure(self.exp_start_times[i], i + 1, write_fits=False,
-                                                           prepare_only=True))):
-                        return
-            except BaseException as e:          # surfaced in the consuming thread
-                put(e)
-                return
-            put(None)
+        def finish(i, gen, reads):
+            frame = gen._fill_exposure(np.array(reads), gen._prepared[2])     # (a copy: the pinned buffer is reused)
+            if pool is not None:
+                pool.submit(frame, self.outdir, "{:04d}_raw.fits".format(i + 1))
+                frames[i + 1] = None          # on disk; do not keep 64 MB per exposure alive
+            else:
+                frames[i + 1] = frame
 
-        producer = threading.Thread(target=produce, daemon=True)
-        sys.setswitchinterval(min(old_interval, 2e-4))
-        producer.start()
         try:
-            n = 0
-            while True:
-                item = ahead.get()
-                if item is None:
-                    break
-                if isinstance(item, BaseException):
-                    raise item
-                i, gen = item
-                if len(in_flight) >= depth:
-                    finish_oldest()
-                in_flight.append((i, gen.launch(n % (depth + 1))))
-                n += 1
-            while in_flight:
-                finish_oldest()
+            # up to 3 exposures in flight on 4 context slots in rotation (even / odd slots run on different HIP streams)
+            run_pipelined(eng.ctx, mine, prepare, finish, depth=3, n_slots=4)
         finally:
-            stop.set()                          # an error or Ctrl-C here: the producer stops after the exposure it is
-            producer.join()                     # preparing, not after the rest of the visit's host work
             if pool is not None:
                 pool.close()
-            sys.setswitchinterval(old_interval)
         return frames
 
     @staticmethod
@@ -397,10 +345,9 @@ class Observation(object):
         from . import fitsio
         return fitsio.scan(path) is not None
 
-    def _generate_exposure(self, expstart, number, write_fits=True, submit_slot=None, prepare_only=False):
-        """observation.py:415-504.  With `submit_slot` the exposure is only enqueued on that context
-        slot and the ExposureGenerator is returned: call its collect() for the Exposure.  With `prepare_only`
-        only its host half runs (ExposureGenerator.prepare): launch(slot) and collect() follow on the context's thread."""
+    def _generate_exposure(self, expstart, number, write_fits=True, prepare_only=False):
+        """observation.py:415-504.  With `prepare_only` only the exposure's host half runs and the ExposureGenerator is
+        returned (ExposureGenerator.prepare): run_observation's loop does the rest on the context's thread."""
         index_number = number - 1
         filename = "{:04d}_raw.fits".format(number)
         exp_gen = ExposureGenerator(self.detector, self.grism, self.NSAMP, self.SAMPSEQ, self.SUBARRAY, self.planet,
@@ -434,8 +381,6 @@ class Observation(object):
                     sample_mid_points, sample_durations, read_index)
         if prepare_only:
             return exp_gen.prepare(*args, staring=not self.spatial_scan, **common)
-        if submit_slot is not None:
-            return exp_gen.submit(submit_slot, *args, staring=not self.spatial_scan, **common)
         exp_frame = exp_gen.scanning_frame(*args, **common) if self.spatial_scan else exp_gen.staring_frame(*args, **common)
         if write_fits:
             exp_frame.generate_fits(self.outdir, filename)

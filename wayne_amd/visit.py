@@ -8,15 +8,13 @@ calibration) and writes its own NNNN_raw.fits files (observation.py:427).
 """
 import hashlib
 import os
-import queue
-import sys
-import threading
 
 import numpy as np
 
 from . import engine as _engine
-from .exposure import Exposure, FitsWriterPool
+from .exposure import FitsWriterPool
 from .exposure_generator import ExposureGenerator
+from .pipeline import run_pipelined
 
 
 def shard(n_exposures, rank, world):
@@ -92,16 +90,29 @@ class VisitRunner(object):
         `on_reads(i, reads)` is called with a view of the pinned buffer (copy it to keep it);
         keep=True returns {index: copy}; FITS files are written when out_dir is set."""
         eng = self.engine()
-        ctx = eng.ctx
         results = {}
-        pending = []                       # [(index, slot, generator)] in flight, oldest first
-        self._pool = FitsWriterPool() if self.out_dir is not None else None
+        pool = FitsWriterPool() if self.out_dir is not None else None
+
+        def prepare(i):
+            gen = self.generator(i)
+            return gen.build_descriptor(eng, out_dtype=self.out_dtype, rng_mode=self.rng_mode,
+                                        **self.frame_kwargs(i)), gen
+
+        def finish(i, gen, reads):
+            if on_reads is not None:
+                on_reads(i, reads)
+            if keep:
+                results[i] = reads.copy()
+            if pool is not None:
+                os.makedirs(self.out_dir, exist_ok=True)
+                # (a copy: the pinned buffer is reused by the next exposure)
+                pool.submit(gen._fill_exposure(reads.copy()), self.out_dir, gen.exp_info["filename"])
+
         try:
-            self._run_pipeline(eng, ctx, indices, results, pending, keep, on_reads)
+            run_pipelined(eng.ctx, indices, prepare, finish, self.DEPTH, self.DEPTH)
         finally:
-            if self._pool is not None:
-                self._pool.close()
-                self._pool = None
+            if pool is not None:
+                pool.close()
         return results
 
     def run_resident(self, n, on_reads=None):
@@ -123,81 +134,3 @@ class VisitRunner(object):
             reads = ctx.wait(s_old)
             if on_reads is not None:
                 on_reads(s_old, reads)
-
-    def _run_pipeline(self, eng, ctx, indices, results, pending, keep, on_reads):
-        # Two host threads.  A producer prepares descriptors (the K-vectors of an exposure: numpy, the Philox host
-        # draws, the light-curve inputs -- no GPU call, no context state); this thread uploads, launches and collects.
-        # The C calls on both sides release the interpreter lock (ctypes), so a descriptor's 0.1 ms of host draws and an
-        # upload's 0.08 ms of table building overlap the other thread's Python: on the reference's example-visit shape
-        # the pipeline is then paced by the device, not by the host.
-        ahead = queue.Queue(maxsize=self.DEPTH)
-        stop = threading.Event()            # set by this thread when it leaves the loop, for whatever reason
-
-        def put(item):
-            """Queue.put that gives up when the consumer has gone (returns False)."""
-            while not stop.is_set():
-                try:
-                    ahead.put(item, timeout=0.05)
-                    return True
-                except queue.Full:
-                    pass
-            return False
-
-        def produce():
-            try:
-                for n, i in enumerate(indices):
-                    if stop.is_set():
-                        return
-                    gen = self.generator(i)
-                    desc = gen.build_descriptor(eng, out_dtype=self.out_dtype, rng_mode=self.rng_mode,
-                                                **self.frame_kwargs(i))
-                    if not put((n, i, gen, desc)):
-                        return
-            except BaseException as e:      # surfaced in the consuming thread
-                put(e)
-                return
-            put(None)
-
-        producer = threading.Thread(target=produce, daemon=True)
-        old_interval = sys.getswitchinterval()
-        sys.setswitchinterval(min(old_interval, 2e-4))   # hand the lock over promptly between the two
-        producer.start()
-        try:
-            while True:
-                item = ahead.get()
-                if item is None:
-                    break
-                if isinstance(item, BaseException):
-                    raise item
-                n, i, gen, desc = item
-                slot = n % self.DEPTH
-                if len(pending) == self.DEPTH:          # the slot about to be reused must be drained first
-                    self._finish(ctx, pending.pop(0), results, keep, on_reads)
-                ctx.upload(slot, desc)
-                ctx.run(slot)                  # asynchronous on the slot's stream
-                ctx.fetch_async(slot)          # ... followed by its copy to pinned host memory
-                pending.append((i, slot, gen))
-            while pending:
-                self._finish(ctx, pending.pop(0), results, keep, on_reads)
-        finally:
-            sys.setswitchinterval(old_interval)
-            stop.set()              # an error or Ctrl-C on this side: the producer stops after the descriptor it is
-            producer.join()         # building, not after the rest of the visit's host work
-
-    def _finish(self, ctx, pending, results, keep, on_reads=None):
-        i, slot, gen = pending
-        reads = ctx.wait(slot)
-        if on_reads is not None:
-            on_reads(i, reads)
-        if keep:
-            results[i] = reads.copy()
-        if self.out_dir is not None:
-            os.makedirs(self.out_dir, exist_ok=True)
-            exp = Exposure(gen.detector, gen.grism, None, gen.exp_info)
-            read_dt = np.diff(np.concatenate([[0.0], gen.read_times]))
-            own = reads.copy()             # the pinned buffer is reused by the next exposure
-            exp.add_read(own[0], {"cumulative_exp_time": 0.0, "read_exp_time": 0.0, "CRPIX1": 0})
-            for r in range(len(gen.read_times)):
-                exp.add_read(own[r + 1], {"cumulative_exp_time": float(gen.read_times[r]),
-                                          "read_exp_time": float(read_dt[r]), "CRPIX1": 0})
-            self._pool.submit(exp, self.out_dir, gen.exp_info["filename"])
