@@ -62,6 +62,9 @@ extern "C" {
 #define WAYNE_F_EXACT_SAMPLERS (1u << 17) /* IEEE divide/sqrt + libm-grade log/exp/sin/cos in the per-pixel
                                              Poisson / normal draws (parity runs) instead of the hardware
                                              approximations (production); same algorithm, same streams */
+#define WAYNE_F_OUT_U16 (1u << 18) /* reads delivered as 16-bit unsigned DN, the ADC's sample type: the float32 read
+                                      rounded half to even and saturated to 0 .. 65535 (NaN -> 0) in the ramp kernel's
+                                      store.  Not together with WAYNE_F_OUT_F64: WAYNE_E_INVALID at upload */
 
 typedef struct wayne_ctx wayne_ctx;
 
@@ -249,12 +252,12 @@ int wayne_exposure_run_checked(wayne_ctx *ctx, int slot);
 int wayne_exposure_status(wayne_ctx *ctx, int slot, int *status);
 unsigned long long wayne_ctx_reruns(const wayne_ctx *ctx);
 /* Copy the NSAMP reads (read 0 = zero read) of `slot` to the host:
- * NSAMP*S*S float32, or float64 when WAYNE_F_OUT_F64 was set.  Synchronises. */
+ * NSAMP*S*S float32, float64 when WAYNE_F_OUT_F64 was set, uint16 when WAYNE_F_OUT_U16 was.  Synchronises. */
 int wayne_exposure_download(wayne_ctx *ctx, int slot, void *out_reads);
 /* Pinned-host delivery for pipelines: wayne_exposure_fetch_async enqueues, on the
  * slot's stream (i.e. after its kernels), the copy of the reads into a pinned host
  * buffer owned by the library and returns at once; wayne_exposure_wait blocks until
- * that slot's work is done and returns the buffer (NSAMP*S*S float32 / float64), which
+ * that slot's work is done and returns the buffer (NSAMP*S*S float32 / float64 / uint16), which
  * stays valid until the slot is uploaded again.  With two slots on the two streams the
  * copy of one exposure overlaps the kernels of the next. */
 int wayne_exposure_fetch_async(wayne_ctx *ctx, int slot);
@@ -294,7 +297,8 @@ int wayne_exposure_run_back(wayne_ctx *ctx, int slot);
  * NUL-terminated) in the form a kernel trace prints it, e.g. "k_ramp<float, true, 1, false, true>": <type of the reads,
  * production (hardware) math, sky sampler 0 direct / 1 alias tables / 2 tables + pieces, gaussian-noise stage, every
  * detector switch on>.  The arithmetic differs between them (float: exact integer sums + an all-float32 per-read
- * chain; double: fp64 cumulative sum), so a measurement names the one it timed (bench.py `dtype`, `roofline.kernel`).
+ * chain; double: fp64 cumulative sum; unsigned short: float's, quantised in the store), so a measurement names the one
+ * it timed (bench.py `dtype`, `roofline.kernel`).
  * No reference counterpart: the reference has one float64 numpy path (exposure_generator.py:407-515). */
 int wayne_exposure_ramp_variant(wayne_ctx *ctx, int slot, char *buf, int cap);
 

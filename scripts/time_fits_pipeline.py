@@ -1,9 +1,10 @@
 #!/usr/bin/env python3
-"""Exposures/s of a visit written to FITS files (float64 SCI extensions, the reference's layout, exposure.py:133-214),
-and where the time of one file goes: device -> pinned host memory (PCIe), float32 -> big-endian float64 (format),
-the write itself (disk).  GPU only.
+"""Exposures/s of a visit written to FITS files (the reference's layout, exposure.py:133-214: float64 SCI extensions,
+or BITPIX 16 ones for uint16 reads), and where the time of one file goes: device -> pinned host memory (PCIe), the
+reads -> big-endian FITS words (format: float32 -> float64, or uint16 -> top bit flipped + byte swap), the write itself
+(disk).  GPU only.
 
-    python scripts/time_fits_pipeline.py [config=cfg4] [exposures=24]
+    python scripts/time_fits_pipeline.py [config=cfg4] [exposures=24] [reads=float32 | float64 | uint16]
 """
 import os
 import shutil
@@ -22,10 +23,12 @@ from wayne_amd.exposure import Exposure  # noqa: E402
 
 name = sys.argv[1] if len(sys.argv) > 1 else "cfg4"
 n = int(sys.argv[2]) if len(sys.argv) > 2 else 24
+dtype = np.dtype(sys.argv[3] if len(sys.argv) > 3 else "float32")
+u16 = dtype == np.uint16
 v = helpers.make_visit(name, n_exposures=n + 2)
 out = tempfile.mkdtemp(prefix="wayne_fits_")
 try:
-    r = wv.VisitRunner(v, 0, out_dir=out)
+    r = wv.VisitRunner(v, 0, out_dir=out, out_dtype=dtype)
     r.run([0, 1])
     t = time.perf_counter()
     r.run(range(2, n + 2))
@@ -36,7 +39,7 @@ try:
         name, n, dt, n / dt, per_file * n / dt / 1e6, len(os.listdir(out)), per_file / 1e6,
         int(os.environ.get("WAYNE_FITS_THREADS", "0")) or min(16, os.cpu_count() or 4)))
     # the parts, one at a time
-    r2 = wv.VisitRunner(v, 0)
+    r2 = wv.VisitRunner(v, 0, out_dtype=dtype)
     t = time.perf_counter()
     got = r2.run(range(2, n + 2), keep=False)
     d_host = (time.perf_counter() - t) / n
@@ -49,9 +52,12 @@ try:
     t_fmt, t_wr = [], []
     for rep in range(5):
         t0 = time.perf_counter()
-        cube = np.empty(reads.shape, dtype=">f8")
+        cube = np.empty(reads.shape, dtype=">i2" if u16 else ">f8")
         for i in range(reads.shape[0]):
-            cube[i] = reads[i]
+            if u16:
+                fitsio.u16_to_stored(reads[i], out=cube[i])
+            else:
+                cube[i] = reads[i]
         t1 = time.perf_counter()
         fitsio.write_pieces(os.path.join(out, "probe_%d.fits" % rep), [memoryview(cube.reshape(-1)).cast("B")])
         t2 = time.perf_counter()
@@ -61,9 +67,9 @@ try:
     for rep in range(3):
         exp.generate_fits(out, "whole_%d.fits" % rep)
     d_file = (time.perf_counter() - t0) / 3
-    print("parts per exposure: device -> pinned host (kernels + PCIe, pipelined) %.1f ms = %.0f/s; float32 -> big-endian "
-          "float64 (one thread) %.1f ms; write of %.0f MB (one thread) %.1f ms = %.2f GB/s; generate_fits whole, one "
-          "thread %.1f ms" % (d_host * 1e3, 1.0 / d_host, np.median(t_fmt) * 1e3, cube.nbytes / 1e6, np.median(t_wr) * 1e3,
-                              cube.nbytes / np.median(t_wr) / 1e9, d_file * 1e3))
+    print("parts per exposure: device -> pinned host (kernels + PCIe, pipelined) %.1f ms = %.0f/s; %s -> big-endian "
+          "%s (one thread) %.1f ms; write of %.0f MB (one thread) %.1f ms = %.2f GB/s; generate_fits whole, one "
+          "thread %.1f ms" % (d_host * 1e3, 1.0 / d_host, dtype.name, "int16" if u16 else "float64", np.median(t_fmt) * 1e3,
+                              cube.nbytes / 1e6, np.median(t_wr) * 1e3, cube.nbytes / np.median(t_wr) / 1e9, d_file * 1e3))
 finally:
     shutil.rmtree(out, ignore_errors=True)

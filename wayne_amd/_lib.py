@@ -25,6 +25,9 @@ F_ADD_STELLAR_NOISE = 1 << 5
 F_ADD_DARK = 1 << 6
 F_ADD_INITIAL_BIAS = 1 << 7
 F_OUT_F64 = 1 << 16
+F_OUT_U16 = 1 << 18
+# the reads' sample types: numpy dtype -> descriptor flag (float32 is the absence of one)
+OUT_FLAGS = {np.dtype(np.float32): 0, np.dtype(np.float64): F_OUT_F64, np.dtype(np.uint16): F_OUT_U16}
 F_EXACT_SAMPLERS = 1 << 17
 PROF_KERNELS = 8
 ABI_VERSION = 7
@@ -192,6 +195,11 @@ def ptr(a, ctype=None):
     return a.ctypes.data_as(C.POINTER(ctype))
 
 
+def out_dtype_of(flags):
+    """The numpy dtype of the reads a descriptor with these flags delivers."""
+    return np.dtype(np.float64 if flags & F_OUT_F64 else np.uint16 if flags & F_OUT_U16 else np.float32)
+
+
 def f64(a):
     return np.ascontiguousarray(a, dtype=np.float64)
 
@@ -243,7 +251,7 @@ class Context(object):
             raise cls(st.value, "wayne_ctx_create(device=%d): %s -- the HIP path is the only path, "
                                 "there is no CPU fallback" % (device, msg))
         self.device = device
-        self._slot_meta = {}     # slot -> (K, W, R, float64 reads) of the descriptor uploaded last
+        self._slot_meta = {}     # slot -> (K, W, R, dtype of the reads) of the descriptor uploaded last
         self._slot_src = {}      # slot -> bins of each of its contaminants
         _live_contexts.add(self)
         for name, value in _knob_defaults.items():
@@ -363,7 +371,7 @@ class Context(object):
         """Stage the descriptor in `slot`; contaminants and charge traps it carries (make_desc(sources=..., traps=...))
         are set with it."""
         self.check(self._L.wayne_exposure_upload(self._h, int(slot), C.byref(desc)))
-        self._slot_meta[slot] = (desc.n_samples, desc.n_wl, desc.n_reads, bool(desc.flags & F_OUT_F64))
+        self._slot_meta[slot] = (desc.n_samples, desc.n_wl, desc.n_reads, out_dtype_of(desc.flags))
         self._slot_src[slot] = ()
         sources = getattr(desc, "_sources", None)
         if sources:
@@ -450,8 +458,8 @@ class Context(object):
         return int(self._L.wayne_ctx_reruns(self._h))
 
     def download(self, slot):
-        K, W, R, f64out = self._slot_meta[slot]
-        out = np.empty((R + 1, self.S, self.S), dtype=np.float64 if f64out else np.float32)
+        K, W, R, dtype = self._slot_meta[slot]
+        out = np.empty((R + 1, self.S, self.S), dtype=dtype)
         self.check(self._L.wayne_exposure_download(self._h, int(slot), ptr(out)))
         return out
 
@@ -462,13 +470,12 @@ class Context(object):
     def wait(self, slot):
         """Block until the slot's work is done -> its reads as a numpy VIEW of the pinned buffer
         (valid until the slot is uploaded again; copy it to keep it)."""
-        K, W, R, f64out = self._slot_meta[slot]
+        K, W, R, dtype = self._slot_meta[slot]
         p = C.c_void_p()
         self.check(self._L.wayne_exposure_wait(self._h, int(slot), C.byref(p)))
-        ct = C.c_double if f64out else C.c_float
         n = (R + 1) * self.S * self.S
-        buf = (ct * n).from_address(p.value)
-        return np.frombuffer(buf, dtype=np.float64 if f64out else np.float32).reshape(R + 1, self.S, self.S)
+        buf = (C.c_ubyte * (n * dtype.itemsize)).from_address(p.value)
+        return np.frombuffer(buf, dtype=dtype).reshape(R + 1, self.S, self.S)
 
     def synthesize(self, desc):
         self.upload(0, desc)

@@ -20,7 +20,7 @@ struct RampArgs {
   const float* dark_sci;     // [R*S*S] or null
   const float* dark_err;
   const double* zero_read;   // [S*S] or null
-  void* out;                 // [(R+1)*S*S] float or double
+  void* out;                 // [(R+1)*S*S] float, double or uint16_t
   // sky background (see sky_draw): alias tables of Poisson(level_j * bg_count) for `sky_levels` levels
   // of the master sky and every distinct read interval, for the reads whose bit is set in alias_mask
   const uint32_t* sky_alias; // [n_tables <= kMaxReads][kSkyAlias] or null
@@ -364,6 +364,11 @@ __device__ __forceinline__ void sky_counts(const RampArgs& a, uint32_t p, int ti
 template <class OutT, bool FAST, int SKY, bool NOISE, bool ALLON, bool TRAP = false>
 __device__ __forceinline__ void ramp_body(const RampArgs& a, const TrapArgs& tr = TrapArgs{}) {
   constexpr bool ALIAS = SKY != 0;
+  // OutT fixes the store; the arithmetic follows ArithT.  uint16 reads (WAYNE_F_OUT_U16) are the float32 reads of the
+  // same instantiation, quantised in st_out: every choice below that float32 reads make, they make
+  constexpr bool U16 = std::is_same<OutT, uint16_t>::value;
+  typedef typename std::conditional<U16, float, OutT>::type ArithT;
+  constexpr bool PROD = std::is_same<ArithT, float>::value && FAST && SKY == 1 && !NOISE;   // the production chain
   typedef typename std::conditional<FAST, FastMath, ExactMath<float> >::type M;
   static_assert(kSkyAlias <= kRampThreads, "the sky tables and the per-thread sky counts share one LDS array");
   // ALIAS: alias tables [table][entry]; else: sky counts [read][thread]
@@ -413,8 +418,14 @@ __device__ __forceinline__ void ramp_body(const RampArgs& a, const TrapArgs& tr 
 #endif
     return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs, off4, (uint32_t)r * f32_plane, kNT));
   };
-  auto st_out = [&](int plane, OutT v) {
-    if (sizeof(OutT) == 4) {
+  auto st_out = [&](int plane, ArithT v) {
+    if constexpr (U16) {
+      // the ADC's law: round half to even, saturate at 0 and 65535, NaN -> 0 (tested for itself: what v_med3_f32 makes of
+      // a NaN depends on the mode register).  q is an integer in [0, 65535]: the conversions are exact
+      const float q = __builtin_amdgcn_fmed3f(__builtin_rintf(v), 0.f, 65535.f);
+      const unsigned short w = (v != v) ? (unsigned short)0 : (unsigned short)(int)q;
+      __builtin_amdgcn_raw_buffer_store_b16(w, rs_out, offo, (uint32_t)plane * out_plane, kNT);
+    } else if constexpr (sizeof(OutT) == 4) {
       __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint((float)v), rs_out, offo, (uint32_t)plane * out_plane, kNT);
     } else {
       const unsigned long long b = (unsigned long long)__double_as_longlong((double)v);
@@ -542,7 +553,7 @@ __device__ __forceinline__ void ramp_body(const RampArgs& a, const TrapArgs& tr 
     rn.next2(w0, w1);
     double v = z;
     if (rdn) { bm_pair<FAST>(w0, w1, zd, zr); v = v + kReadNoise * (double)zr; }
-    st_out(0, (OutT)v);
+    st_out(0, (ArithT)v);
   }
 
   // gain: 2.35 / pfl evaluated in float32 as numpy does for scalar / f32 array
@@ -550,7 +561,7 @@ __device__ __forceinline__ void ramp_body(const RampArgs& a, const TrapArgs& tr 
   // applied as a multiplication by its fp64 reciprocal
   const float g32 = 2.35f / t_pfl;                          // (float32 IEEE division, as numpy's)
   double inv_g = 1.0 / kGain;
-  if (interior && gainvar && !(std::is_same<OutT, float>::value && FAST && SKY == 1 && !NOISE)) inv_g = 1.0 / (double)g32;
+  if (interior && gainvar && !PROD) inv_g = 1.0 / (double)g32;
 
   // charge traps: the pixel's mean collected-charge rate over the exposure -- its accumulators (only the reads whose
   // wave is live load anything) plus its EXPECTED sky -- and from it what its traps hold at the zero read.  Reference
@@ -563,7 +574,7 @@ __device__ __forceinline__ void ramp_body(const RampArgs& a, const TrapArgs& tr 
       for (int r = 0; r < a.R; ++r)
         if (acc_live(r)) qs += ld_acc(r);
       const float sky_px = skyv > 0.f ? skyv : 0.f;
-      if constexpr (std::is_same<OutT, float>::value && FAST && SKY == 1 && !NOISE) {
+      if constexpr (PROD) {
         const float e_acc = fmaf((float)(int)(qs >> 32), 16.0f, (float)(uint32_t)qs * 3.725290298461914e-09f);
         const float fbar = fmaf(sky_px, tr.sum_bg_f, e_acc) * tr.inv_sum_dt_f;
         te_s = trap_start<float>(tr.start_f, tr, 0, fbar);
@@ -586,9 +597,10 @@ __device__ __forceinline__ void ramp_body(const RampArgs& a, const TrapArgs& tr 
   float sky_c = -1.f;
   SkyRem srem;
   srem.m = 0.f; srem.t0 = srem.t1 = srem.t2 = srem.t3 = 0xFFFFFFFFu; srem.c3 = 1.f; srem.term3 = 0.f;
-  if (std::is_same<OutT, float>::value && FAST && SKY == 1 && !NOISE) {
-    // PRODUCTION VARIANT (float32 reads, hardware math, alias-table sky, no gaussian-noise stage): the same stages,
-    // streams and draws as the generic loop below with the arithmetic cut to what a float32 read can tell.
+  if (PROD) {
+    // PRODUCTION VARIANT (float32 reads -- or uint16 reads, quantised from them in st_out --, hardware math, alias-table
+    // sky, no gaussian-noise stage): the same stages, streams and draws as the generic loop below with the arithmetic
+    // cut to what a float32 read can tell.
     //  * what a pixel has collected so far is kept EXACTLY, in integers: Q = the sum of its fixed-point accumulators
     //    (int64; touched only by the waves a read's electrons can reach, ~5 % of them) and ksum = the sum of its sky
     //    counts (int32).  One conversion per read takes it to float32 electrons -- a single rounding of the exact sum,
@@ -682,7 +694,7 @@ __device__ __forceinline__ void ramp_body(const RampArgs& a, const TrapArgs& tr 
         if (!interior) v = 0.f;                            // reference pixels (exposure.py:122-131)
         // + zero read + read noise (exposure.py:94-104, detector.py:193-198)
         const float tail = f_rdn ? fmaf((float)kReadNoise, zr, zf) : zf;
-        st_out(r + 1, (OutT)(v + tail));
+        st_out(r + 1, (ArithT)(v + tail));
       };
       int r = 0;
       if (PF == 1) {
@@ -783,7 +795,7 @@ __device__ __forceinline__ void ramp_body(const RampArgs& a, const TrapArgs& tr 
     }
     v = v + z;                       // add_zero_read (exposure.py:94-104)
     if (rdn) v = v + kReadNoise * (double)zr;   // add_read_noise (detector.py:193-198)
-    st_out(r + 1, (OutT)v);
+    st_out(r + 1, (ArithT)v);
   }
 }
 

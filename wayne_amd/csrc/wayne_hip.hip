@@ -507,6 +507,14 @@ int launch_narrow(wayne_ctx* c, const ThrowArgs& a, bool exact) {
   return WAYNE_OK;
 }
 
+// The reads' sample type of a descriptor: 0 float32, 1 float64 (WAYNE_F_OUT_F64), 2 uint16 (WAYNE_F_OUT_U16), and its
+// size -- the one place the read buffers are sized from
+int out_kind(uint32_t flags) { return (flags & WAYNE_F_OUT_F64) ? 1 : (flags & WAYNE_F_OUT_U16) ? 2 : 0; }
+size_t out_elem_size(uint32_t flags) {
+  const int k = out_kind(flags);
+  return k == 1 ? sizeof(double) : k == 2 ? sizeof(uint16_t) : sizeof(float);
+}
+
 template <class OutT, bool FAST, int SKY, bool NOISE>
 void (*ramp_kernel())(RampArgs) {
   // (pinned to 8 waves per SIMD where that does not spill: see k_ramp / k_ramp_wide)
@@ -520,9 +528,11 @@ void (*ramp_sky(int sky, bool noise))(RampArgs) {
   return sky == 1 ? ramp_noise<OutT, FAST, 1>(noise) : sky == 2 ? ramp_noise<OutT, FAST, 2>(noise) : ramp_noise<OutT, FAST, 0>(noise);
 }
 // k_ramp<reads' type, production / exact math, sky sampler, gaussian-noise stage>
-void (*pick_ramp(bool f64, bool exact, int sky, bool noise))(RampArgs) {
-  return f64 ? (exact ? ramp_sky<double, false>(sky, noise) : ramp_sky<double, true>(sky, noise))
-             : (exact ? ramp_sky<float, false>(sky, noise) : ramp_sky<float, true>(sky, noise));
+// (reads' type: 0 float, 1 double, 2 uint16_t -- out_kind())
+void (*pick_ramp(int out, bool exact, int sky, bool noise))(RampArgs) {
+  return out == 1 ? (exact ? ramp_sky<double, false>(sky, noise) : ramp_sky<double, true>(sky, noise))
+       : out == 2 ? (exact ? ramp_sky<uint16_t, false>(sky, noise) : ramp_sky<uint16_t, true>(sky, noise))
+                  : (exact ? ramp_sky<float, false>(sky, noise) : ramp_sky<float, true>(sky, noise));
 }
 
 template <int FLUSH>
@@ -550,33 +560,36 @@ template <class OutT, bool FAST>
 RampTrapKernel trap_sky(int sky, bool noise) {
   return sky == 1 ? trap_noise<OutT, FAST, 1>(noise) : sky == 2 ? trap_noise<OutT, FAST, 2>(noise) : trap_noise<OutT, FAST, 0>(noise);
 }
-RampTrapKernel pick_ramp_trap(bool f64, bool exact, int sky, bool noise, bool allon) {
-  if (allon) return k_ramp_trap<float, true, 1, false, true>;
-  return f64 ? (exact ? trap_sky<double, false>(sky, noise) : trap_sky<double, true>(sky, noise))
-             : (exact ? trap_sky<float, false>(sky, noise) : trap_sky<float, true>(sky, noise));
+RampTrapKernel pick_ramp_trap(int out, bool exact, int sky, bool noise, bool allon) {
+  if (allon) return out == 2 ? k_ramp_trap<uint16_t, true, 1, false, true> : k_ramp_trap<float, true, 1, false, true>;
+  return out == 1 ? (exact ? trap_sky<double, false>(sky, noise) : trap_sky<double, true>(sky, noise))
+       : out == 2 ? (exact ? trap_sky<uint16_t, false>(sky, noise) : trap_sky<uint16_t, true>(sky, noise))
+                  : (exact ? trap_sky<float, false>(sky, noise) : trap_sky<float, true>(sky, noise));
 }
 
 // The k_ramp instantiation the back half of slot `s` launches, and (if asked) its name as the kernel trace prints it.
 // A slot with charge traps launches k_ramp_trap instead: *trap (when given) is then set, else left null.
 void (*select_ramp(const wayne_ctx* c, const Slot& s, std::string* name, RampTrapKernel* trap = nullptr))(RampArgs) {
   const wayne_exposure_desc& d = s.d;
-  const bool f64 = (d.flags & WAYNE_F_OUT_F64) != 0, exact = (d.flags & WAYNE_F_EXACT_SAMPLERS) != 0;
+  const int out = out_kind(d.flags);
+  const bool f64 = out == 1, exact = (d.flags & WAYNE_F_EXACT_SAMPLERS) != 0;
+  const char* out_name = out == 1 ? "double" : out == 2 ? "unsigned short" : "float";
   const int sky_mode = !s.sky_alias_on ? 0 : (s.sky_pieces ? 2 : 1);
   const bool noise = d.noise_mean != 0. && d.noise_std != 0.;
-  void (*kern)(RampArgs) = pick_ramp(f64, exact, sky_mode, noise);
+  void (*kern)(RampArgs) = pick_ramp(out, exact, sky_mode, noise);
   // the production variant with every detector switch on (the rule) has an instantiation of its own (k_ramp.h, ALLON)
   const uint32_t all_on = WAYNE_F_ADD_DARK | WAYNE_F_ADD_NON_LINEAR | WAYNE_F_CLIP_DET_LIMITS | WAYNE_F_ADD_READ_NOISE;
   const bool allon = !f64 && !exact && sky_mode == 1 && !noise && (d.flags & all_on) == all_on && c->has_dark && c->has_lin;
-  if (allon) kern = k_ramp<float, true, 1, false, true>;
-  if (trap) *trap = s.traps_on ? pick_ramp_trap(f64, exact, sky_mode, noise, allon) : nullptr;
+  if (allon) kern = out == 2 ? k_ramp<uint16_t, true, 1, false, true> : k_ramp<float, true, 1, false, true>;
+  if (trap) *trap = s.traps_on ? pick_ramp_trap(out, exact, sky_mode, noise, allon) : nullptr;
   if (name) {
     const bool pinned = !exact && sky_mode != 0 && !noise;      // ramp_kernel(): k_ramp where it fits 64 registers, else k_ramp_wide
     char buf[96];
     if (s.traps_on)
-      std::snprintf(buf, sizeof buf, "k_ramp_trap<%s, %s, %d, %s, %s>", f64 ? "double" : "float", exact ? "false" : "true",
+      std::snprintf(buf, sizeof buf, "k_ramp_trap<%s, %s, %d, %s, %s>", out_name, exact ? "false" : "true",
                     sky_mode, noise ? "true" : "false", allon ? "true" : "false");
     else
-      std::snprintf(buf, sizeof buf, "%s<%s, %s, %d, %s%s>", pinned ? "k_ramp" : "k_ramp_wide", f64 ? "double" : "float",
+      std::snprintf(buf, sizeof buf, "%s<%s, %s, %d, %s%s>", pinned ? "k_ramp" : "k_ramp_wide", out_name,
                     exact ? "false" : "true", sky_mode, noise ? "true" : "false", pinned ? (allon ? ", true" : ", false") : "");
     *name = buf;
   }
@@ -1033,6 +1046,8 @@ int wayne_exposure_upload(wayne_ctx* c, int slot, const wayne_exposure_desc* d) 
     return fail(c, WAYNE_E_INVALID, "upload: null array");
   if (d->rng_mode != WAYNE_RNG_REPLAY && d->rng_mode != WAYNE_RNG_PHILOX && d->rng_mode != WAYNE_RNG_SPLIT)
     return fail(c, WAYNE_E_INVALID, "upload: rng_mode");
+  if ((d->flags & WAYNE_F_OUT_F64) && (d->flags & WAYNE_F_OUT_U16))
+    return fail(c, WAYNE_E_INVALID, "upload: WAYNE_F_OUT_F64 and WAYNE_F_OUT_U16 are mutually exclusive");
   if (d->rng_mode == WAYNE_RNG_REPLAY && (d->threads_compat <= 0 || !d->replay_seed))
     return fail(c, WAYNE_E_INVALID, "upload: replay mode needs threads_compat >= 1 and replay_seed");
   for (int k = 0; k < K; ++k)
@@ -1102,7 +1117,7 @@ int wayne_exposure_upload(wayne_ctx* c, int slot, const wayne_exposure_desc* d) 
     s.acc_init = true;
     s.acc_dirty = false;
   }
-  const size_t out_elem = (d->flags & WAYNE_F_OUT_F64) ? sizeof(double) : sizeof(float);
+  const size_t out_elem = out_elem_size(d->flags);
   HIP_TRY(c, s.out.reserve((size_t)(R + 1) * SS * out_elem));
   // (no stream synchronisation: the host arrays were copied into the pinned arena above)
   s.d = *d;
@@ -1506,7 +1521,7 @@ int wayne_exposure_download(wayne_ctx* c, int slot, void* out_reads) {
   (void)hipSetDevice(c->device);
   use_slot_stream(c, slot);
   const size_t SS = (size_t)c->S * c->S;
-  const size_t out_elem = (s.d.flags & WAYNE_F_OUT_F64) ? sizeof(double) : sizeof(float);
+  const size_t out_elem = out_elem_size(s.d.flags);
   HIP_TRY(c, hipMemcpyAsync(out_reads, s.out.p, (size_t)(s.R + 1) * SS * out_elem, hipMemcpyDeviceToHost, c->stream));
   bool reran = false;
   int rc = look_at_status(c, slot, nullptr, wayne_exposure_run, &reran);
@@ -1523,7 +1538,7 @@ int wayne_exposure_fetch_async(wayne_ctx* c, int slot) {
   (void)hipSetDevice(c->device);
   use_slot_stream(c, slot);
   const size_t SS = (size_t)c->S * c->S;
-  const size_t bytes = (size_t)(s.R + 1) * SS * ((s.d.flags & WAYNE_F_OUT_F64) ? sizeof(double) : sizeof(float));
+  const size_t bytes = (size_t)(s.R + 1) * SS * out_elem_size(s.d.flags);
   const size_t tail = align64(bytes);
   s.pinned_misc = nullptr;
   if (!s.pinned.reserve(tail + 64)) return fail(c, WAYNE_E_NOMEM, "fetch_async: pinned host allocation failed");

@@ -150,7 +150,7 @@ class Exposure(object):
 
     def generate_fits(self, out_dir="", filename=None, ldcoeffs=None):
         """Write the HST-style file (exposure.py:133-214): primary header, then for each
-        read in REVERSE time order a float64 SCI image with SAMPNUM / SAMPTIME / DELTATIM /
+        read in REVERSE time order a float64 SCI image (an unsigned 16-bit one when every read is uint16) with SAMPNUM / SAMPTIME / DELTATIM /
         CRPIX1 followed by four data-less ERR, DQ, SAMP, TIME extensions, so that read r
         sits at HDU 1 + 5 (NSAMP - 1 - r) as in a real _raw/_ima file."""
         if filename is None:
@@ -164,11 +164,20 @@ class Exposure(object):
         n = len(self.reads)
         arrs = [np.asarray(d) for d, _ in self.reads]
         same = n > 0 and all(a.shape == arrs[0].shape and a.ndim == 2 for a in arrs)
+        # uint16 reads (out_dtype=np.uint16) go out as the instrument's sample type -- BITPIX 16, BSCALE 1, BZERO 32768 --
+        # with no float64 intermediate: a quarter of the bytes.  Float or mixed reads: the float64 SCI images as ever.
+        u16 = same and all(a.dtype == np.uint16 for a in arrs)
+        code = "u2" if u16 else "f8"
         pieces = [primary]
-        if same:
+        if u16:
+            cube = np.empty((n,) + arrs[0].shape, dtype=">i2")
+            for i, a in enumerate(arrs):
+                fitsio.u16_to_stored(a, out=cube[i])            # top bit flipped + byte swap, one pass each
+        elif same:
             cube = np.empty((n,) + arrs[0].shape, dtype=">f8")
             for i, a in enumerate(arrs):
                 cube[i] = a                                     # cast + byte swap, interpreter lock released
+        if same:
             pad = b"\x00" * ((-cube[0].nbytes) % fitsio.BLOCK)
         for i, (data, hdr) in enumerate(reversed(self.reads)):
             samp = n - 1 - i
@@ -177,8 +186,9 @@ class Exposure(object):
                      ("EXTVER", i + 1, ""), ("BUNIT", "COUNTS", "")]
             if same:
                 shape = arrs[samp].shape
-                pieces.append(fitsio.cached_header_block(("SCI", shape, samp, sampt, delt, type(crpix), crpix, i + 1),
-                                                         cards, data_shape=shape, name="SCI"))
+                pieces.append(fitsio.cached_header_block(("SCI", shape, samp, sampt, delt, type(crpix), crpix, i + 1) +
+                                                         (("u2",) if u16 else ()),
+                                                         cards, data_shape=shape, dtype_code=code, name="SCI"))
                 pieces.append(memoryview(cube[samp].reshape(-1)).cast("B"))
                 if pad:
                     pieces.append(pad)

@@ -136,7 +136,9 @@ class ExposureGenerator(object):
         profiles/r06/visit_science.json) or float64 reads (out_dtype=np.float64, CLI --float64-reads: what the
         reference's Exposure.reads hold, exposure.py:47,106-120 -- a DEVIATION of the default from the reference,
         chosen so that the benchmarked kernel is the one an API user gets; FITS files carry float64 SCI images
-        either way); `reference_quirks` keeps the reference's -5 px frame
+        either way) or uint16 reads (out_dtype=np.uint16, CLI --uint16-reads: the float32 read rounded half to even
+        and saturated to 0 .. 65535 in the kernel's store -- the ADC's 16-bit unsigned DN of a real _raw file, which
+        the FITS files then carry as BITPIX 16 / BZERO 32768 images; any other dtype: ValueError); `reference_quirks` keeps the reference's -5 px frame
         offset at SUBARRAY=1024 (exposure_generator.py:630) and flat-fields G102 exposures with the
         G141 cube as the reference does (grism.py:428,453-454); `record`, if a dict,
         receives the device's intermediate products (counts, x, y per bin and
@@ -226,6 +228,9 @@ class ExposureGenerator(object):
         jitter / seed draws, spectrum crop (exposure_generator.py:247-334) ->
         one wayne_exposure_desc for the device.  Pure host code (`eng` may be
         None when no GPU is involved, e.g. when sharding a visit on the CPU)."""
+        out_dtype = np.dtype(out_dtype)
+        if out_dtype not in _lib.OUT_FLAGS:
+            raise ValueError("out_dtype must be float32, float64 or uint16, not %s" % out_dtype)
         wl = np.asarray(wl, dtype=float)
         stellar_flux = np.asarray(stellar_flux, dtype=float)
         scan_speed_ms = scan_speed / 1000.          # px/s -> px/ms (:247)
@@ -321,7 +326,7 @@ class ExposureGenerator(object):
                         (add_non_linear, _lib.F_ADD_NON_LINEAR), (clip_values_det_limits, _lib.F_CLIP_DET_LIMITS),
                         (add_read_noise, _lib.F_ADD_READ_NOISE), (add_stellar_noise, _lib.F_ADD_STELLAR_NOISE),
                         (add_dark, _lib.F_ADD_DARK), (add_initial_bias, _lib.F_ADD_INITIAL_BIAS),
-                        (np.dtype(out_dtype) == np.float64, _lib.F_OUT_F64),
+                        (True, _lib.OUT_FLAGS[out_dtype]),
                         (exact_samplers, _lib.F_EXACT_SAMPLERS)):
             if on:
                 flags |= bit

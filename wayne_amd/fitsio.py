@@ -18,6 +18,9 @@ import numpy as np
 BLOCK = 2880
 _BITPIX_DTYPE = {8: ">u1", 16: ">i2", 32: ">i4", 64: ">i8", -32: ">f4", -64: ">f8"}
 _DTYPE_BITPIX = {"u1": 8, "i2": 16, "i4": 32, "i8": 64, "f4": -32, "f8": -64}
+# Unsigned 16-bit images (FITS Standard 4.0, section 5.2.5 / table 11): BITPIX = 16 with BSCALE = 1, BZERO = 32768; the
+# stored two's-complement word is value - 32768, i.e. the value with its top bit flipped.  What a WFC3-IR _raw file holds.
+U16_BZERO = 32768
 # BINTABLE TFORM letter -> (numpy type, bytes)
 _TFORM = {"L": ("u1", 1), "B": ("u1", 1), "I": (">i2", 2), "J": (">i4", 4), "K": (">i8", 8),
           "E": (">f4", 4), "D": (">f8", 8), "A": ("S1", 1)}
@@ -179,7 +182,9 @@ def read(path):
                 shape = tuple(h["NAXIS%d" % i] for i in range(h["NAXIS"], 0, -1))
                 data = np.frombuffer(raw, dtype=_BITPIX_DTYPE[h["BITPIX"]]).reshape(shape)
                 bscale, bzero = h.get("BSCALE", 1), h.get("BZERO", 0)
-                if bscale != 1 or bzero != 0:
+                if h["BITPIX"] == 16 and bscale == 1 and bzero == U16_BZERO:
+                    data = (data.astype(np.int16).view(np.uint16) ^ np.uint16(0x8000))   # the unsigned convention, exactly
+                elif bscale != 1 or bzero != 0:
                     data = data * bscale + bzero
         hdus.append(HDU(h, data))
     return hdus
@@ -278,6 +283,10 @@ def _image_hdu_parts(data, extra_cards, primary, name=None):
     else:
         a = np.asarray(data)
         code = a.dtype.kind + str(a.dtype.itemsize)
+        unsigned16 = code == "u2"
+        if unsigned16:
+            a = u16_to_stored(a)                   # big-endian int16 of value - 32768
+            code = "i2"
         if code not in _DTYPE_BITPIX:
             a = a.astype(np.float64)
             code = "f8"
@@ -293,14 +302,27 @@ def _image_hdu_parts(data, extra_cards, primary, name=None):
         cards.append(("EXTEND", True, ""))
     else:
         cards += [("PCOUNT", 0, ""), ("GCOUNT", 1, "")]
-        if name:
-            cards.append(("EXTNAME", name, "extension name"))
     reserved = {"SIMPLE", "XTENSION", "BITPIX", "NAXIS", "EXTEND", "PCOUNT", "GCOUNT", "END"}
+    if data is not None and unsigned16:
+        cards += [("BSCALE", 1, ""), ("BZERO", U16_BZERO, "")]
+        reserved |= {"BSCALE", "BZERO"}
+    if not primary and name:
+        cards.append(("EXTNAME", name, "extension name"))
     for k, v, c in extra_cards:
         if k in reserved or k.startswith("NAXIS") or (k == "EXTNAME" and name):
             continue
         cards.append((k, v, c))
     return [_header_bytes(cards), payload, b"\x00" * ((-nbytes) % BLOCK)]
+
+
+def u16_to_stored(a, out=None):
+    """The FITS words of an unsigned 16-bit image: big-endian int16 of value - 32768 -- the top bit flipped (one pass),
+    then the bytes swapped into `out` (a ">i2" array of a's shape; allocated when None)."""
+    a = np.asarray(a)
+    if out is None:
+        out = np.empty(a.shape, dtype=">i2")
+    out[...] = (a.astype(np.uint16, copy=False) ^ np.uint16(0x8000)).view(np.int16)
+    return out
 
 
 def _write_all(fd, pieces):

@@ -56,7 +56,8 @@ class Observation(object):
         # extra keywords for scanning_frame / staring_frame (rng_mode, out_dtype, exact_samplers, reference_quirks).
         # The visit driver asks for float32 reads: the FITS writer stores them as the reference's float64 SCI images
         # (BITPIX -64) either way, and a full-array exposure is 67 MB instead of 134 MB to bring over PCIe;
-        # frame_options["out_dtype"] = np.float64 (CLI: --float64-reads) keeps the float64 arithmetic to the file.
+        # frame_options["out_dtype"] = np.float64 (CLI: --float64-reads) keeps the float64 arithmetic to the file;
+        # np.uint16 (CLI: --uint16-reads) makes the reads and the files' SCI images 16-bit unsigned DN (BITPIX 16).
         self.frame_options = {"out_dtype": np.float32}
         self.contaminants = []       # field stars on every exposure (setup_contaminants)
         self.charge_traps = None     # per-pixel charge trapping (setup_charge_traps)
@@ -228,7 +229,8 @@ class Observation(object):
         """Is `NNNN_raw.fits` of exposure `number` (1-based) in the output directory, complete, and THIS visit's file?
         Files are written under a temporary name and renamed when finished (fitsio.write_pieces), so a file under its
         final name is whole unless something else truncated it: checked anyway -- the HDU structure is walked header by
-        header (1 + 5 NSAMP HDUs ending exactly at the end of the file, SCI images of the mode's size) and the primary
+        header (1 + 5 NSAMP HDUs ending exactly at the end of the file, SCI images of the mode's size and of the sample
+        type this visit writes) and the primary
         header must carry this exposure's start time and mode."""
         path = os.path.join(self.outdir, "{:04d}_raw.fits".format(number))
         if not os.path.isfile(path):
@@ -247,7 +249,10 @@ class Observation(object):
             return False
         if not (same and self._contaminant_cards_match(p0) and self._trap_cards_match(p0)):
             return False
-        return all(size == S * S * 8 for (h, size) in hdus[1::5])
+        # the visit's sample type too: uint16 reads make BITPIX 16 images, float reads float64 ones -- a file of the
+        # other kind is regenerated, whichever way the visit was switched
+        elem = 2 if np.dtype(self.frame_options.get("out_dtype", np.float32)) == np.uint16 else 8
+        return all(size == S * S * elem for (h, size) in hdus[1::5])
 
     def _contaminant_cards_match(self, p0):
         """The file's NCONTAM / CONTDXn / CONTDYn / CONTFRn cards are this visit's contaminants (absent: none), so that

@@ -167,8 +167,12 @@ def run(argv=None):
     ap.add_argument("--resume", action="store_true",
                     help="skip every exposure whose NNNN_raw.fits is already in the output directory, whole and this "
                          "visit's (restart after a failed rank: only the missing files are generated)")
-    ap.add_argument("--float64-reads", action="store_true",
-                    help="float64 reads from the device (the reference's arithmetic to the file) instead of float32 ones")
+    reads = ap.add_mutually_exclusive_group()
+    reads.add_argument("--float64-reads", action="store_true",
+                       help="float64 reads from the device (the reference's arithmetic to the file) instead of float32 ones")
+    reads.add_argument("--uint16-reads", action="store_true",
+                       help="16-bit unsigned reads, the ADC's sample type: the float32 read rounded and saturated to "
+                            "0 .. 65535 on the device; the _raw files are then BITPIX 16 / BZERO 32768, a quarter the size")
     args = ap.parse_args(argv)
     if args.gpus < 1 or args.ranks_per_gpu < 1:
         raise SystemExit("--gpus and --ranks-per-gpu must be at least 1")
@@ -217,6 +221,8 @@ def run(argv=None):
         obs.exp_start_times = obs.exp_start_times[:args.max_exposures]
     if args.float64_reads:
         obs.frame_options["out_dtype"] = np.float64
+    if args.uint16_reads:
+        obs.frame_options["out_dtype"] = np.uint16
     os.makedirs(obs.outdir, exist_ok=True)
     rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
     if rank == 0:
