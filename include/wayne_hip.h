@@ -367,6 +367,57 @@ typedef struct wayne_trap_desc {
  * not uploaded.  The back half then launches k_ramp_trap<...> (wayne_exposure_ramp_variant names it). */
 int wayne_exposure_set_traps(wayne_ctx *ctx, int slot, const wayne_trap_desc *t);
 
+/* ---- device-side spectral extraction (no reference counterpart) ---------- */
+
+/*
+ * Column spectra of the slot's exposure, formed on the device from the reads k_ramp has just written and the context's
+ * calibration planes: what a light-curve consumer keeps of an exposure (~120 KB) instead of its reads (67 MB).
+ * All coordinates bordered, side S; float64 throughout (a read of any stored type is promoted exactly); an absent
+ * calibration plane counts as 0 (c1..c4, dark, master sky) or as a gain of 2.35 (pixel flat):
+ *   D_r = P_r - P_0,  L_r = D_r (1 + c1 + D_r (c2 + D_r (c3 + c4 D_r))) - dark_r,  L_0 = 0
+ *   I_r = (L_r - L_{r-1}) g,  g = 2.35 / pfl as a float64 divide (2.35 on the 5-px border),  T = master sky (0 on the border)
+ *   product j = 0 .. R-1 (read interval j), rows [row_lo[j], row_hi[j]):  A_j[x] = sum_y I_{j+1}[y,x],  B_j[x] = read_dt_s[j] sum_y T[y,x]
+ *   product R (the last read alone), rows [row_lo[R], row_hi[R]):       A_R[x] = sum_y L_R[y,x] g,   B_R[x] = (sum_j read_dt_s[j]) sum_y T[y,x]
+ *   sky_j = sum_{x in [bg_col_lo, bg_col_hi)} A_j[x] / sum_{x in [bg_col_lo, bg_col_hi)} B_j[x]   (0 when the denominator is 0)
+ *   spectra_j[x] = A_j[x] - sky_j B_j[x],  x = 0 .. S-1
+ * Result: spectra [(R+1)*S] and sky [R+1], float64.  The sums are taken in an order fixed by the plan (chunks of 32
+ * rows of a window, added in ascending order; no atomics): the same exposure gives the same bytes in any slot, on
+ * either stream, in any process.  Channel binning, fits and cosmic-ray rejection stay with the caller.
+ */
+#define WAYNE_X_LINEARISE (1u << 0) /* off: L_r = D_r - dark_r */
+#define WAYNE_X_DARK (1u << 1)      /* off: dark_r = 0 */
+#define WAYNE_X_GAIN (1u << 2)      /* off: g = 1, the result is in DN */
+#define WAYNE_X_SKY (1u << 3)       /* off: sky_j = 0, spectra_j = A_j */
+#define WAYNE_X_LAST_READ (1u << 4) /* off: product R is not formed (zeros); its window is ignored */
+#define WAYNE_X_ALL 31u
+
+typedef struct wayne_extract_desc {
+  uint32_t steps;   /* WAYNE_X_* */
+  int row_lo[17];   /* product j at index j, the last-read product at index R (= n_reads); the rest is ignored */
+  int row_hi[17];
+  int bg_col_lo;    /* columns the sky level is fitted on */
+  int bg_col_hi;
+} wayne_extract_desc;
+
+/* After wayne_exposure_upload, before run: extract the slot's exposure (x = NULL clears; upload clears too, so callers
+ * that never call this get today's exposure and today's launches).  WAYNE_E_INVALID (the slot stays usable, without
+ * extraction) when a window or the background range is not within 0 <= lo < hi <= S or `steps` has unknown bits;
+ * WAYNE_E_STATE on a slot that is not uploaded.  The back half of wayne_exposure_run then enqueues the extraction
+ * behind the ramp kernel on the slot's stream, so every call that runs an exposure a second time re-extracts it. */
+int wayne_exposure_set_extraction(wayne_ctx *ctx, int slot, const wayne_extract_desc *x);
+/* The counterparts of wayne_exposure_fetch_async / _wait for the spectra: only the spectra block and the slot's status
+ * block are copied to pinned memory, never the reads.  *spectra [(R+1)*S] and *sky [R+1] stay valid until the slot is
+ * uploaded again.  The status word is handled as in wayne_exposure_wait (a bin beyond the lanes' reach: run again,
+ * fetch again, look again).  WAYNE_E_STATE when no extraction is set.  wayne_exposure_fetch_async / _wait / _download
+ * keep delivering the reads of the same slot. */
+int wayne_exposure_fetch_spectra_async(wayne_ctx *ctx, int slot);
+int wayne_exposure_wait_spectra(wayne_ctx *ctx, int slot, double **spectra, double **sky);
+/* The blocking form: spectra [(R+1)*S] and sky [R+1] into the caller's arrays.  Synchronises. */
+int wayne_exposure_download_spectra(wayne_ctx *ctx, int slot, double *spectra, double *sky);
+/* HIP-event time of the extraction's kernels while wayne_profile_enable is on, since wayne_profile_reset: launches
+ * (one per extracted exposure) and total milliseconds.  wayne_profile_select's bit 8 selects it.  Synchronises. */
+int wayne_extract_profile(wayne_ctx *ctx, uint64_t *launches, double *ms);
+
 /* ---- measurement ------------------------------------------------------- */
 
 #define WAYNE_PROF_KERNELS 8

@@ -33,6 +33,9 @@ PROF_KERNELS = 8
 ABI_VERSION = 7
 MAX_SOURCES = 8   # contaminants per exposure (WAYNE_MAX_SOURCES)
 MAX_TRAP_RATES = 4096   # points of a charge-trap start table (WAYNE_MAX_TRAP_RATES)
+# wayne_extract_desc.steps (WAYNE_X_*)
+X_LINEARISE, X_DARK, X_GAIN, X_SKY, X_LAST_READ, X_ALL = 1, 2, 4, 8, 16, 31
+EXTRACT_PRODUCTS = 17   # row windows a wayne_extract_desc holds
 
 
 class WayneError(RuntimeError):
@@ -87,6 +90,11 @@ class TrapDesc(C.Structure):
                 ("n_rate", C.c_int), ("rate_lo", C.c_double), ("rate_hi", C.c_double), ("start", _dp * 2)]
 
 
+class ExtractDesc(C.Structure):
+    _fields_ = [("steps", C.c_uint32), ("row_lo", C.c_int * EXTRACT_PRODUCTS), ("row_hi", C.c_int * EXTRACT_PRODUCTS),
+                ("bg_col_lo", C.c_int), ("bg_col_hi", C.c_int)]
+
+
 class Profile(C.Structure):
     _fields_ = [("name", C.c_char_p * PROF_KERNELS), ("launches", C.c_uint64 * PROF_KERNELS),
                 ("ms", C.c_double * PROF_KERNELS), ("electrons", C.c_uint64)]
@@ -133,6 +141,11 @@ SYMBOLS = {
     "wayne_source_seed": (C.c_uint32, [C.c_uint32, C.c_uint32]),
     "wayne_exposure_set_traps": (C.c_int, [_vp, C.c_int, C.POINTER(TrapDesc)]),
     "wayne_exposure_debug_fetch_source": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp]),
+    "wayne_exposure_set_extraction": (C.c_int, [_vp, C.c_int, C.POINTER(ExtractDesc)]),
+    "wayne_exposure_fetch_spectra_async": (C.c_int, [_vp, C.c_int]),
+    "wayne_exposure_wait_spectra": (C.c_int, [_vp, C.c_int, C.POINTER(_dp), C.POINTER(_dp)]),
+    "wayne_exposure_download_spectra": (C.c_int, [_vp, C.c_int, _vp, _vp]),
+    "wayne_extract_profile": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_double)]),
     "wayne_profile_enable": (C.c_int, [_vp, C.c_int]),
     "wayne_profile_select": (C.c_int, [_vp, C.c_uint]),
     "wayne_profile_reset": (C.c_int, [_vp]),
@@ -379,6 +392,46 @@ class Context(object):
         traps = getattr(desc, "_traps", None)
         if traps is not None:
             self.set_traps(slot, traps)
+        extraction = getattr(desc, "_extraction", None)
+        if extraction is not None:
+            self.set_extraction(slot, extraction)
+
+    def set_extraction(self, slot, extraction):
+        """Spectral extraction of the slot's uploaded exposure: an extraction.Extraction (row windows of the R read
+        intervals and of the last read, background columns, step mask) -- None clears.  The back half of every run of
+        the slot then forms spectra [R + 1, S] and sky [R + 1] on the device.  See wayne_exposure_set_extraction."""
+        if extraction is None:
+            self.check(self._L.wayne_exposure_set_extraction(self._h, int(slot), None))
+            return
+        self.check(self._L.wayne_exposure_set_extraction(self._h, int(slot), C.byref(extraction.desc())))
+
+    def fetch_spectra_async(self, slot):
+        """Enqueue the copy of the slot's spectra (never its reads) into pinned host memory (returns at once)."""
+        self.check(self._L.wayne_exposure_fetch_spectra_async(self._h, int(slot)))
+
+    def wait_spectra(self, slot):
+        """Block until the slot's work is done -> (spectra [R + 1, S], sky [R + 1]) as numpy VIEWS of the pinned buffer
+        (valid until the slot is uploaded again; copy them to keep them)."""
+        K, W, R, _ = self._slot_meta[slot]
+        ps, pk = _dp(), _dp()
+        self.check(self._L.wayne_exposure_wait_spectra(self._h, int(slot), C.byref(ps), C.byref(pk)))
+        spectra = np.ctypeslib.as_array(ps, shape=(R + 1, self.S))
+        sky = np.ctypeslib.as_array(pk, shape=(R + 1,))
+        return spectra, sky
+
+    def download_spectra(self, slot):
+        """(spectra [R + 1, S], sky [R + 1]) of the slot, blocking; arrays of the caller's own."""
+        K, W, R, _ = self._slot_meta[slot]
+        spectra = np.empty((R + 1, self.S), dtype=np.float64)
+        sky = np.empty(R + 1, dtype=np.float64)
+        self.check(self._L.wayne_exposure_download_spectra(self._h, int(slot), ptr(spectra), ptr(sky)))
+        return spectra, sky
+
+    def extract_profile(self):
+        """{"launches", "ms"} of the extraction's kernels by HIP events (profile_enable; since profile_reset)."""
+        n, ms = C.c_uint64(0), C.c_double(0.0)
+        self.check(self._L.wayne_extract_profile(self._h, C.byref(n), C.byref(ms)))
+        return {"launches": int(n.value), "ms": float(ms.value)}
 
     def set_traps(self, slot, traps):
         """Charge traps of the slot's uploaded exposure: a traps.ExposureTraps (the model and this exposure's start tables
@@ -510,11 +563,11 @@ class Context(object):
         self.check(self._L.wayne_profile_enable(self._h, 1 if on else 0))
 
     def profile_select(self, names=None):
-        """Time only the named kernels (e.g. ["k_ramp"]); None = all."""
+        """Time only the named kernels (e.g. ["k_ramp"]; "k_extract": the extraction, extract_profile); None = all."""
         if names is None:
             mask = 0xFFFFFFFF
         else:
-            order = list(self.profile_get().keys())
+            order = list(self.profile_get().keys())[:PROF_KERNELS] + ["k_extract"]
             mask = 0
             for n in names:
                 mask |= 1 << order.index(n)
@@ -537,11 +590,12 @@ def make_desc(seed, exposure_index, flags, sub_scale, wl_um, flux, depth, x_ref,
               sample_read, read_dt_s, replay_seed=None, rng_mode=RNG_PHILOX, threads_compat=1,
               sky_ct_s=0.0, cosmic_rate=-1.0, scale_factor=1.0, noise_mean=0.0, noise_std=0.0,
               thrower_margin=0, thrower_splits=0, lc_z=None, lc_hidden=None, lc_rp=None, lc_ld=None, sources=None,
-              traps=None):
+              traps=None, extraction=None):
     """The exposure descriptor.  `sources`: contaminating field stars (sources.Contaminant), carried beside the C struct
     and set by Context.upload (wayne_exposure_set_sources); None or [] = the target alone.  `traps`: charge traps
     (traps.ExposureTraps, or a traps.ChargeTraps whose table is flat at `initial`), set by Context.upload
-    (wayne_exposure_set_traps); None = no trapping."""
+    (wayne_exposure_set_traps); None = no trapping.  `extraction`: the spectral extraction of the exposure
+    (extraction.Extraction), set by Context.upload (wayne_exposure_set_extraction); None = reads only."""
     d = ExposureDesc()
     keep = []
 
@@ -592,6 +646,7 @@ def make_desc(seed, exposure_index, flags, sub_scale, wl_um, flux, depth, x_ref,
         from . import traps as _traps
         traps = _traps.for_exposure(traps)
     d._traps = traps
+    d._extraction = extraction
     return d
 
 

@@ -11,6 +11,7 @@
 //   plan_psf_apply       the host half of wayne_psf_apply: count reduction, N = (int)(counts ratio), routing, clip rectangle
 //   plan_sky             levels of the master sky, alias-table keys, which reads fit a table (k_ramp's sky draw)
 //   build_sky_alias      one Walker / Vose table of Poisson(lam)
+//   extract_desc_error   wayne_exposure_set_extraction's argument check (the windows k_extract walks stay inside the frame)
 //
 // Reference: the reach of the thrower bounds pyparallel_menu.c:87-108 as the device modes implement it; the trace is
 // grism.py:491-506, 779-803 (trace_coeffs, plan_consts.h); the frame offset exposure_generator.py:630-645.
@@ -422,6 +423,27 @@ inline void plan_sky(double sky_ct_s, int R, const double* read_dt_s, bool has_s
   float bg_max = 0.f;
   for (float b : bg) bg_max = std::max(bg_max, b);
   p->pieces = !(gap * bg_max <= kSkyPiece);
+}
+
+// wayne_exposure_set_extraction's argument check (include/wayne_hip.h: wayne_extract_desc) for a frame of side S with R
+// non-zero reads: null when the plan is valid, else what is wrong with it.  Every window -- product j < R at index j,
+// the last read at index R, which is ignored when its step bit is off -- and the background columns must lie within
+// 0 <= lo < hi <= S.  *max_chunks (if given): chunks of kExtractRows rows of the longest window that is used.
+inline const char* extract_desc_error(int S, int R, unsigned steps, const int* row_lo, const int* row_hi, int bg_lo,
+                                      int bg_hi, int* max_chunks = nullptr) {
+  if (S < 1 || S > kExtractMaxS) return "frame side outside 1 .. 1024";
+  if (R < 1 || R > kMaxReads) return "n_reads outside 1 .. 15";
+  if (steps & ~X_ALL) return "unknown bits in steps";
+  if (!row_lo || !row_hi) return "null row windows";
+  if (!(0 <= bg_lo && bg_lo < bg_hi && bg_hi <= S)) return "background columns must satisfy 0 <= lo < hi <= S";
+  int longest = 0;
+  const int n = (steps & X_LAST_READ) ? R + 1 : R;
+  for (int j = 0; j < n; ++j) {
+    if (!(0 <= row_lo[j] && row_lo[j] < row_hi[j] && row_hi[j] <= S)) return "a row window must satisfy 0 <= lo < hi <= S";
+    longest = std::max(longest, row_hi[j] - row_lo[j]);
+  }
+  if (max_chunks) *max_chunks = (longest + kExtractRows - 1) / kExtractRows;
+  return nullptr;
 }
 
 }  // namespace plan

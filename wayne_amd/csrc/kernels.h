@@ -12,6 +12,8 @@
 //                   k_lane_fused   thin exposures: k_lane planning its bins itself (plan_bin of k_prep.h), no k_prep_sub
 //   k_ramp.h        k_ramp         fused up-the-ramp kernel: sky, gain, cumulative, dark, non-linearity,
 //                                  clip, reference pixels, zero read, read noise                          (A13-A15)
+//   k_extract.h     k_extract_rows / k_extract_finish   opt-in: column spectra per read interval from the reads
+//                                  just written (linearise, dark, gain, row sums, sky level), no reference counterpart
 //
 // "A<n>" are the row ids of SURVEY.md section 8(a); reference file:line
 // citations are next to each formula.
@@ -22,3 +24,4 @@
 #include "k_throw.h"
 #include "k_narrow.h"
 #include "k_ramp.h"
+#include "k_extract.h"

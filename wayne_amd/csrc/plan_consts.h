@@ -40,6 +40,14 @@ constexpr int kSkyAlias = 256;    // entries per alias table: alias << 24 | 24-b
 constexpr float kSkyPiece = 16.f; // largest mean drawn by one sequential search
 constexpr int kMaxReads = 15;     // NSAMP <= 16 (detector.py:228)
 
+// ---- device-side spectral extraction (k_extract.h; validated by plan::extract_desc_error) ----
+constexpr int kExtractRows = 32;                  // rows of a chunk of a product's window: a constant of the plan, not of the launch
+constexpr int kExtractProducts = kMaxReads + 2;   // wayne_extract_desc.row_lo / row_hi hold 17: R <= 15 read intervals + the last read
+constexpr int kExtractMaxS = 1024;                // widest frame (k_extract_finish keeps a product's columns in LDS)
+// wayne_extract_desc.steps (include/wayne_hip.h: WAYNE_X_*)
+constexpr unsigned X_LINEARISE = 1u << 0, X_DARK = 1u << 1, X_GAIN = 1u << 2, X_SKY = 1u << 3, X_LAST_READ = 1u << 4;
+constexpr unsigned X_ALL = X_LINEARISE | X_DARK | X_GAIN | X_SKY | X_LAST_READ;
+
 WAYNE_HD void trace_coeffs(const GrismDev& g, double x_ref, double y_ref, double* o) {
   // o = {m_t, c_t, m_w, c_w, m_wl, c_wl}
     // wavelength_calibration_coeffs (grism.py:779-803)

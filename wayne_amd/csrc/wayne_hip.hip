@@ -36,7 +36,9 @@ int fail(wayne_ctx* c, int code, const std::string& msg);   // (keeps `msg` as t
 
 inline size_t align64(size_t n) { return (n + 63) & ~(size_t)63; }
 
-enum ProfKernel { PK_PREP_WL = 0, PK_PREP_SUB, PK_THROW, PK_COSMIC, PK_RAMP, PK_LIGHTCURVE, PK_NARROW, PK_LANE };
+enum ProfKernel { PK_PREP_WL = 0, PK_PREP_SUB, PK_THROW, PK_COSMIC, PK_RAMP, PK_LIGHTCURVE, PK_NARROW, PK_LANE,
+                  PK_EXTRACT };   // (PK_EXTRACT lies beyond wayne_profile's arrays, which the ABI fixes: wayne_extract_profile reports it)
+constexpr int kProfKernels = WAYNE_PROF_KERNELS + 1;
 const char* const kProfNames[WAYNE_PROF_KERNELS] = {"k_prep_wl", "k_prep_sub",   "k_throw",  "k_cosmic",   /* (cosmic rays ride in k_prep_sub: slot kept for the ABI) */
                                                     "k_ramp",    "k_lightcurve", "k_narrow", "k_lane"};
 
@@ -198,6 +200,15 @@ struct Slot : SourceState {
   int trap_G = 0;
   StageArena trap_stage;
   DevBuf trap_d, trap_f;             // views of the float64 / float32 tables
+  // spectral extraction of this exposure (wayne_exposure_set_extraction; cleared by upload): the plan, the partial sums
+  // [2][chunks][R+1][S], the result -- spectra [(R+1)*S] then sky [R+1] -- and its pinned host copy, followed by a
+  // copy of `misc` (fetch_spectra_async / wait_spectra)
+  bool extract_on = false;
+  wayne_extract_desc ex{};
+  int ex_chunks = 0;
+  DevBuf ex_part, ex_out;
+  PinnedBuf ex_pinned;
+  Misc* ex_pinned_misc = nullptr;
   // staging arena of the descriptor's arrays: uploads are enqueued from here, so
   // wayne_exposure_upload returns without waiting for the slot's stream to drain
   StageArena stage;
@@ -309,8 +320,8 @@ struct wayne_ctx : CtxStreams {
   unsigned prof_mask = ~0u;   // kernels timed while prof_on (wayne_profile_select)
   std::vector<ProfRec> prof;
   std::vector<hipEvent_t> ev_pool;
-  uint64_t prof_launches[WAYNE_PROF_KERNELS] = {0};
-  double prof_ms[WAYNE_PROF_KERNELS] = {0};
+  uint64_t prof_launches[kProfKernels] = {0};
+  double prof_ms[kProfKernels] = {0};
   uint64_t electrons = 0;  // thrown through wayne_psf_apply (host-counted)
   uint64_t reruns = 0;     // exposures run a second time because a bin lay beyond what the first launch sequence handles
   DevBuf counters;         // kCounterStripes u64 words, 128 B apart: electrons thrown by exposures (device-counted,
@@ -594,6 +605,44 @@ void (*select_ramp(const wayne_ctx* c, const Slot& s, std::string* name, RampTra
     *name = buf;
   }
   return kern;
+}
+
+// The extraction of slot `s` (wayne_exposure_set_extraction) behind its ramp kernel: the row sums of every product, then
+// the chunks added up, the sky level and the spectra.  The grid follows from the plan alone.
+int launch_extract(wayne_ctx* c, Slot& s) {
+  const int S = c->S, R = s.R;
+  ExtractArgs a{};
+  a.R = R; a.S = S;
+  a.steps = s.ex.steps;
+  a.bg_lo = s.ex.bg_col_lo; a.bg_hi = s.ex.bg_col_hi;
+  a.n_chunks = s.ex_chunks;
+  double sum_dt = 0.;
+  for (int j = 0; j < R; ++j) { a.scale[j] = s.read_dt_host[j]; sum_dt += s.read_dt_host[j]; }
+  a.scale[R] = sum_dt;
+  for (int j = 0; j <= R; ++j) { a.row_lo[j] = s.ex.row_lo[j]; a.row_hi[j] = s.ex.row_hi[j]; }
+  a.reads = s.out.p;
+  a.pfl = c->has_pfl ? c->pfl.as<float>() : nullptr;
+  a.sky = c->has_sky ? c->sky.as<float>() : nullptr;
+  for (int i = 0; i < 4; ++i) a.lin[i] = c->has_lin ? c->lin[i].as<float>() : nullptr;
+  a.dark = c->has_dark ? c->dark_sci.as<float>() : nullptr;
+  a.part = s.ex_part.as<double>();
+  a.spectra = s.ex_out.as<double>();
+  a.sky_out = s.ex_out.as<double>() + (size_t)(R + 1) * S;
+  const int products = (a.steps & X_LAST_READ) ? R + 1 : R;
+  for (int p = 0; p <= kExtractProducts; ++p) a.first_chunk[p] = 0;
+  for (int p = 0; p < products; ++p)
+    a.first_chunk[p + 1] = a.first_chunk[p] + (a.row_hi[p] - a.row_lo[p] + kExtractRows - 1) / kExtractRows;
+  for (int p = products; p < kExtractProducts; ++p) a.first_chunk[p + 1] = a.first_chunk[p];
+  const dim3 grid((unsigned)((S + 63) / 64), (unsigned)a.first_chunk[products]);
+  ProfScope ps(c, PK_EXTRACT);
+  const int out = out_kind(s.d.flags);
+  if (out == 1) hipLaunchKernelGGL((k_extract_rows<double>), grid, dim3(kExtractThreads), 0, c->stream, a);
+  else if (out == 2) hipLaunchKernelGGL((k_extract_rows<uint16_t>), grid, dim3(kExtractThreads), 0, c->stream, a);
+  else hipLaunchKernelGGL((k_extract_rows<float>), grid, dim3(kExtractThreads), 0, c->stream, a);
+  HIP_TRY(c, hipGetLastError());
+  hipLaunchKernelGGL(k_extract_finish, dim3((unsigned)(R + 1)), dim3(kExtractThreads), 0, c->stream, a);
+  HIP_TRY(c, hipGetLastError());
+  return WAYNE_OK;
 }
 
 }  // namespace
@@ -1069,6 +1118,8 @@ int wayne_exposure_upload(wayne_ctx* c, int slot, const wayne_exposure_desc* d) 
   s.fused_last = false;      // (last_prep points into buffers this call may re-allocate)
   s.n_extra = 0;             // a new exposure has no contaminants until wayne_exposure_set_sources says so
   s.traps_on = false;        // ... and no charge traps until wayne_exposure_set_traps says so
+  s.extract_on = false;      // ... and no spectral extraction until wayne_exposure_set_extraction says so
+  s.ex_pinned_misc = nullptr;
   int rc;
   const size_t KW = (size_t)K * W;
   {
@@ -1463,6 +1514,8 @@ int wayne_exposure_run_back(wayne_ctx* c, int slot) {
     }
     HIP_TRY(c, hipGetLastError());
   }
+  if (s.extract_on)
+    if (int rc = launch_extract(c, s)) return rc;   // the spectra of the reads just written, behind them on the stream
   s.acc_dirty = false;
 #ifdef WAYNE_TIMING_KNOBS
   if (ramp_reads_cut) s.acc_dirty = true;     // the next front half starts from cleared accumulators
@@ -1568,6 +1621,8 @@ int wayne_exposure_wait(wayne_ctx* c, int slot, void** host_reads) {
   int rc = look_at_status(c, slot, s.pinned_misc, wayne_exposure_run, &reran);
   if (rc || !reran) return rc;
   if ((rc = wayne_exposure_fetch_async(c, slot))) return rc;     // a bin beyond the lanes' reach: once more, with k_throw
+  // (spectra fetched beside the reads are those of the first run: fetched again too, with the second run's status word)
+  if (s.extract_on && s.ex_pinned_misc && (rc = wayne_exposure_fetch_spectra_async(c, slot))) return rc;
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   return look_at_status(c, slot, s.pinned_misc);
 }
@@ -1813,6 +1868,104 @@ int wayne_exposure_set_traps(wayne_ctx* c, int slot, const wayne_trap_desc* t) {
   return WAYNE_OK;
 }
 
+// ---------------------------------------------------------------------------
+// spectral extraction
+// ---------------------------------------------------------------------------
+
+int wayne_exposure_set_extraction(wayne_ctx* c, int slot, const wayne_extract_desc* x) {
+  if (!c) return WAYNE_E_INVALID;
+  if (slot < 0 || slot >= kSlots) return fail(c, WAYNE_E_INVALID, "set_extraction: slot");
+  Slot& s = c->slots[slot];
+  if (!s.uploaded) return fail(c, WAYNE_E_STATE, "set_extraction: slot not uploaded");
+  s.extract_on = false;           // from here on a refusal leaves the slot usable, without extraction
+  s.ex_pinned_misc = nullptr;
+  if (!x) return WAYNE_OK;
+  int chunks = 0;
+  if (const char* why = plan::extract_desc_error(c->S, s.R, x->steps, x->row_lo, x->row_hi, x->bg_col_lo, x->bg_col_hi, &chunks))
+    return fail(c, WAYNE_E_INVALID, std::string("set_extraction: ") + why);
+  (void)hipSetDevice(c->device);
+  const size_t NP = (size_t)s.R + 1, S = (size_t)c->S;
+  HIP_TRY(c, s.ex_part.reserve((size_t)2 * chunks * NP * S * sizeof(double)));
+  HIP_TRY(c, s.ex_out.reserve(NP * (S + 1) * sizeof(double)));
+  s.ex = *x;
+  s.ex_chunks = chunks;
+  s.extract_on = true;
+  return WAYNE_OK;
+}
+
+// bytes of a slot's spectra block: spectra [(R+1)*S], then sky [R+1]
+static size_t spectra_bytes(const wayne_ctx* c, const Slot& s) { return (size_t)(s.R + 1) * ((size_t)c->S + 1) * sizeof(double); }
+
+int wayne_exposure_fetch_spectra_async(wayne_ctx* c, int slot) {
+  if (!c) return WAYNE_E_INVALID;
+  if (slot < 0 || slot >= kSlots) return fail(c, WAYNE_E_INVALID, "fetch_spectra_async: slot");
+  Slot& s = c->slots[slot];
+  if (!s.uploaded) return fail(c, WAYNE_E_STATE, "fetch_spectra_async: slot not uploaded");
+  if (!s.extract_on) return fail(c, WAYNE_E_STATE, "fetch_spectra_async: no extraction set for the slot");
+  (void)hipSetDevice(c->device);
+  use_slot_stream(c, slot);
+  const size_t bytes = spectra_bytes(c, s), tail = align64(bytes);
+  s.ex_pinned_misc = nullptr;
+  if (!s.ex_pinned.reserve(tail + 64)) return fail(c, WAYNE_E_NOMEM, "fetch_spectra_async: pinned host allocation failed");
+  s.ex_pinned_misc = (Slot::Misc*)(s.ex_pinned.p + tail);
+  // (120 KB behind the slot's kernels on its own stream: nothing here for the other stream to keep out of phase with)
+  HIP_TRY(c, hipMemcpyAsync(s.ex_pinned.p, s.ex_out.p, bytes, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(s.ex_pinned_misc, s.misc.p, sizeof(Slot::Misc), hipMemcpyDeviceToHost, c->stream));
+  return WAYNE_OK;
+}
+
+int wayne_exposure_wait_spectra(wayne_ctx* c, int slot, double** spectra, double** sky) {
+  if (!c || !spectra || !sky) return WAYNE_E_INVALID;
+  if (slot < 0 || slot >= kSlots) return fail(c, WAYNE_E_INVALID, "wait_spectra: slot");
+  Slot& s = c->slots[slot];
+  if (!s.uploaded) return fail(c, WAYNE_E_STATE, "wait_spectra: slot not uploaded");
+  if (!s.extract_on) return fail(c, WAYNE_E_STATE, "wait_spectra: no extraction set for the slot");
+  if (!s.ex_pinned.p || !s.ex_pinned_misc) return fail(c, WAYNE_E_STATE, "wait_spectra: fetch_spectra_async first");
+  (void)hipSetDevice(c->device);
+  use_slot_stream(c, slot);
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  *spectra = (double*)s.ex_pinned.p;
+  *sky = (double*)s.ex_pinned.p + (size_t)(s.R + 1) * c->S;
+  bool reran = false;                        // (the status word came with the spectra)
+  int rc = look_at_status(c, slot, s.ex_pinned_misc, wayne_exposure_run, &reran);
+  if (rc || !reran) return rc;
+  if ((rc = wayne_exposure_fetch_spectra_async(c, slot))) return rc;     // a bin beyond the lanes' reach: once more, with k_throw
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return look_at_status(c, slot, s.ex_pinned_misc);
+}
+
+int wayne_exposure_download_spectra(wayne_ctx* c, int slot, double* spectra, double* sky) {
+  if (!c || !spectra || !sky) return WAYNE_E_INVALID;
+  if (slot < 0 || slot >= kSlots) return fail(c, WAYNE_E_INVALID, "download_spectra: slot");
+  Slot& s = c->slots[slot];
+  if (!s.uploaded) return fail(c, WAYNE_E_STATE, "download_spectra: slot not uploaded");
+  if (!s.extract_on) return fail(c, WAYNE_E_STATE, "download_spectra: no extraction set for the slot");
+  (void)hipSetDevice(c->device);
+  use_slot_stream(c, slot);
+  const size_t n = (size_t)(s.R + 1) * c->S;
+  auto copy = [&]() -> int {
+    HIP_TRY(c, hipMemcpyAsync(spectra, s.ex_out.p, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(sky, s.ex_out.as<double>() + n, (size_t)(s.R + 1) * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    return WAYNE_OK;
+  };
+  int rc = copy();
+  if (rc) return rc;
+  bool reran = false;
+  rc = look_at_status(c, slot, nullptr, wayne_exposure_run, &reran);
+  if (rc || !reran) return rc;
+  if ((rc = copy())) return rc;
+  return look_at_status(c, slot, nullptr);
+}
+
+int wayne_extract_profile(wayne_ctx* c, uint64_t* launches, double* ms) {
+  if (!c) return WAYNE_E_INVALID;
+  int rc = collect_profile(c);
+  if (rc) return rc;
+  if (launches) *launches = c->prof_launches[PK_EXTRACT];
+  if (ms) *ms = c->prof_ms[PK_EXTRACT];
+  return WAYNE_OK;
+}
+
 uint32_t wayne_source_seed(uint32_t seed, uint32_t tag) {
   if (tag == 0) return seed;
   return philox4x32_10(tag, 0u, 0u, 0u, seed, STAGE_SOURCE).v[0];
@@ -1837,7 +1990,7 @@ int wayne_profile_reset(wayne_ctx* c) {
   if (!c) return WAYNE_E_INVALID;
   int rc = collect_profile(c);
   if (rc) return rc;
-  for (int i = 0; i < WAYNE_PROF_KERNELS; ++i) { c->prof_launches[i] = 0; c->prof_ms[i] = 0; }
+  for (int i = 0; i < kProfKernels; ++i) { c->prof_launches[i] = 0; c->prof_ms[i] = 0; }
   c->electrons = 0;
   HIP_TRY(c, hipMemsetAsync(c->counters.p, 0, kCounterBytes, c->streams[0]));
   return sync_all(c);

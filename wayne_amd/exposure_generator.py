@@ -28,6 +28,7 @@ import numpy as np
 
 from . import _lib, engine as _engine, exposure, lightcurve, tools
 from . import traps as _traps
+from . import extraction as _extraction
 from .trend_generators import scan_speed_varations
 
 MS_PER_YEAR = 365.25 * 86400. * 1000.
@@ -122,7 +123,7 @@ class ExposureGenerator(object):
                        clip_values_det_limits=True, add_read_noise=True, add_stellar_noise=True,
                        add_initial_bias=True, progress_bar=None, threads=2,
                        rng_mode=_lib.RNG_SPLIT, out_dtype=np.float32, reference_quirks=False,
-                       record=None, exact_samplers=False, contaminants=None, charge_traps=None):
+                       record=None, exact_samplers=False, contaminants=None, charge_traps=None, extraction=None):
         """Generate a spatially scanned exposure (exposure_generator.py:178-405).
 
         Extra keywords (not in the reference): `rng_mode` -- RNG_SPLIT (default:
@@ -149,24 +150,38 @@ class ExposureGenerator(object):
         spectra land on the same exposure (a list of sources.Contaminant; staring_frame passes it on too);
         `charge_traps` -- per-pixel charge trapping, the ramp effect (traps.ExposureTraps: the model with this exposure's
         start tables from its visit, as Observation.setup_charge_traps passes them; or a traps.ChargeTraps alone, whose
-        traps then start every pixel at `initial`).
+        traps then start every pixel at `initial`); `extraction` -- column spectra formed on the device behind the reads
+        (extraction.Extraction: a plan as it is; True or an extraction.ExtractionOptions: the default plan for this
+        exposure's star position and scan; staring_frame passes it on too): the returned Exposure then carries
+        `spectra` [R + 1, S] and `sky` [R + 1] beside its reads.
         """
         eng, desc, start_time = self._host_half(
             x_ref, y_ref, x_jitter, y_jitter, wl, stellar_flux, planet_signal, scan_speed, sample_rate,
             sample_mid_points, sample_durations, read_index, ssv_generator, noise_mean, noise_std, add_dark,
             add_flat, cosmic_rate, sky_background, scale_factor, add_gain_variations, add_non_linear,
             clip_values_det_limits, add_read_noise, add_stellar_noise, add_initial_bias, progress_bar, threads,
-            rng_mode, out_dtype, reference_quirks, exact_samplers, contaminants, charge_traps)
-        if record is None:
+            rng_mode, out_dtype, reference_quirks, exact_samplers, contaminants, charge_traps, extraction)
+        if record is None and desc._extraction is None:
             reads = eng.ctx.synthesize(desc)
         else:
             eng.ctx.upload(0, desc)
             eng.ctx.run_front(0)
-            record["counts"], record["x"], record["y"], record["acc"] = eng.ctx.debug_fetch(0, acc=True)
-            record.update(self._host_vectors)
+            if record is not None:
+                record["counts"], record["x"], record["y"], record["acc"] = eng.ctx.debug_fetch(0, acc=True)
+                record.update(self._host_vectors)
             eng.ctx.run_back(0)
             reads = eng.ctx.download(0)
-        return self._fill_exposure(reads, start_time)
+        frame = self._fill_exposure(reads, start_time)
+        if desc._extraction is not None:
+            self._fill_spectra(*eng.ctx.download_spectra(0))
+        return frame
+
+    def _fill_spectra(self, spectra, sky):
+        """The device's extraction of this generator's exposure -> Exposure.spectra [R + 1, S] / Exposure.sky [R + 1]
+        (and Exposure.extraction, the plan they were formed with)."""
+        self.exposure.spectra, self.exposure.sky = spectra, sky
+        self.exposure.extraction = self.extraction_plan
+        return self.exposure
 
     def _fill_exposure(self, reads, start_time=None):
         """The reads of this generator's descriptor -> its Exposure (the arrays are kept, not copied); `start_time`:
@@ -191,7 +206,7 @@ class ExposureGenerator(object):
                    clip_values_det_limits=True, add_read_noise=True, add_stellar_noise=True,
                    add_initial_bias=True, progress_bar=None, threads=2,
                    rng_mode=_lib.RNG_SPLIT, out_dtype=np.float32, reference_quirks=False,
-                   exact_samplers=False, contaminants=None, charge_traps=None):
+                   exact_samplers=False, contaminants=None, charge_traps=None, extraction=None):
         """scanning_frame's arguments -> (engine, descriptor, start time): the mode's engine (cached after its first
         use) and build_descriptor.  No GPU call once the engine exists."""
         start_time = time.time()
@@ -202,7 +217,7 @@ class ExposureGenerator(object):
             sample_mid_points, sample_durations, read_index, ssv_generator, noise_mean, noise_std, add_dark,
             add_flat, cosmic_rate, sky_background, scale_factor, add_gain_variations, add_non_linear,
             clip_values_det_limits, add_read_noise, add_stellar_noise, add_initial_bias, progress_bar, threads,
-            rng_mode, out_dtype, reference_quirks, exact_samplers, contaminants, charge_traps)
+            rng_mode, out_dtype, reference_quirks, exact_samplers, contaminants, charge_traps, extraction)
         return eng, desc, start_time
 
     def prepare(self, *args, staring=False, **kw):
@@ -223,7 +238,7 @@ class ExposureGenerator(object):
                          clip_values_det_limits=True, add_read_noise=True, add_stellar_noise=True,
                          add_initial_bias=True, progress_bar=None, threads=2,
                          rng_mode=_lib.RNG_SPLIT, out_dtype=np.float32, reference_quirks=False,
-                         exact_samplers=False, contaminants=None, charge_traps=None):
+                         exact_samplers=False, contaminants=None, charge_traps=None, extraction=None):
         """The host half of scanning_frame: sample timing, scan positions, SSV,
         jitter / seed draws, spectrum crop (exposure_generator.py:247-334) ->
         one wayne_exposure_desc for the device.  Pure host code (`eng` may be
@@ -338,6 +353,9 @@ class ExposureGenerator(object):
 
         if eng is not None:
             eng.check_descriptor(sub_scale)
+        S = (1014 if self.SUBARRAY == 1024 else self.SUBARRAY) + 10
+        self.extraction_plan = _extraction.for_exposure(extraction, self.grism, s_wl, x_ref, y_ref, scan_speed,
+                                                        self.read_times, sub_scale, S)
         self._read_dt = read_dt
         self._host_vectors = {"x_ref": s_x, "y_ref": s_y, "dur": s_dur, "seeds": s_rand_seeds, "read": sample_read}
         return _lib.make_desc(
@@ -347,7 +365,8 @@ class ExposureGenerator(object):
             cosmic_rate=-1.0 if cosmic_rate is None else float(cosmic_rate),
             scale_factor=1.0 if scale_factor is None else float(scale_factor),
             noise_mean=float(noise_mean) if noise_mean else 0.0,
-            noise_std=float(noise_std) if noise_std else 0.0, sources=contaminants, traps=charge_traps, **lc)
+            noise_std=float(noise_std) if noise_std else 0.0, sources=contaminants, traps=charge_traps,
+            extraction=self.extraction_plan, **lc)
 
     def direct_image(self, x_ref, y_ref):
         """The unscaled 2-D gaussian direct image used to calibrate x_ref / y_ref

@@ -1,0 +1,181 @@
+"""Device-side spectral extraction: the plan handed to the device, and the caller's side of what comes back.
+
+An exposure's reads are 67 MB (float32, full array); what a light-curve consumer keeps of them is one column spectrum
+per read interval, ~120 KB.  With an `Extraction` set on a slot (Context.set_extraction, or `extraction=` on
+scanning_frame / staring_frame / VisitRunner / Observation.frame_options) the device forms, behind the ramp kernel,
+
+    spectra[j, x]   j = 0 .. R-1: the electrons of read interval j in column x, summed over the interval's row window,
+                    linearised, dark-subtracted, gain-corrected and sky-subtracted; j = R: the same from the last read
+                    alone over the whole scan's rows
+    sky[j]          the fitted sky level of product j (electrons per second per unit of the master-sky template)
+
+(the law: include/wayne_hip.h, wayne_extract_desc) and only those cross PCIe.  Channel binning stays here: a channel's
+flux is `channel_weights(...) @ spectra[:R].sum(0)` (up the ramp) or `... @ spectra[R]` (last read).  No cosmic-ray
+rejection, no optimal extraction, no direct image.
+"""
+import numpy as np
+
+from . import _lib, tools
+
+LINEARISE, DARK, GAIN, SKY, LAST_READ = _lib.X_LINEARISE, _lib.X_DARK, _lib.X_GAIN, _lib.X_SKY, _lib.X_LAST_READ
+ALL = _lib.X_ALL
+ROW_MARGIN = 14
+BG_COLS = (6, 26)           # bordered columns left of the first-order spectrum
+
+
+class Extraction(object):
+    """The plan of one exposure's extraction: `row_windows` [(lo, hi)] * (R + 1) -- bordered rows, half open, read
+    interval j at index j and the last-read product at index R -- the background columns and the step mask (LINEARISE |
+    DARK | GAIN | SKY | LAST_READ; a step that is off: see the WAYNE_X_* bits)."""
+
+    def __init__(self, row_windows, bg_cols=BG_COLS, steps=ALL):
+        w = np.asarray(row_windows, dtype=np.int64)
+        if w.ndim != 2 or w.shape[1] != 2 or not 2 <= w.shape[0] <= _lib.EXTRACT_PRODUCTS:
+            raise ValueError("row_windows: (lo, hi) for each of the R read intervals and for the last read")
+        self.row_windows = w
+        self.bg_cols = (int(bg_cols[0]), int(bg_cols[1]))
+        self.steps = int(steps)
+
+    @property
+    def row_lo(self):
+        return self.row_windows[:, 0].copy()
+
+    @property
+    def row_hi(self):
+        return self.row_windows[:, 1].copy()
+
+    def desc(self):
+        d = _lib.ExtractDesc()
+        d.steps = self.steps & 0xFFFFFFFF
+        n = self.row_windows.shape[0]
+        d.row_lo[:n] = [int(v) for v in self.row_windows[:, 0]]
+        d.row_hi[:n] = [int(v) for v in self.row_windows[:, 1]]
+        d.bg_col_lo, d.bg_col_hi = self.bg_cols
+        return d
+
+
+class ExtractionOptions(object):
+    """Extraction planned per exposure: what `extraction=` takes where the star moves from exposure to exposure
+    (Observation.frame_options, VisitRunner).  ExposureGenerator turns it into that exposure's Extraction (plan)."""
+
+    def __init__(self, margin=ROW_MARGIN, bg_cols=BG_COLS, steps=ALL):
+        self.margin, self.bg_cols, self.steps = int(margin), (int(bg_cols[0]), int(bg_cols[1])), int(steps)
+
+    def plan(self, grism, wl, x_ref, y_ref, scan_speed, read_times, sub_scale, S):
+        return Extraction(row_windows(grism, wl, x_ref, y_ref, scan_speed, read_times, sub_scale, S, self.margin),
+                          self.bg_cols, self.steps)
+
+
+def for_exposure(extraction, grism, wl, x_ref, y_ref, scan_speed, read_times, sub_scale, S):
+    """`extraction=` of a frame -> that exposure's Extraction: None stays None, an Extraction is taken as it is, True is
+    the default plan and an ExtractionOptions its own."""
+    if extraction is None or extraction is False:
+        return None
+    if isinstance(extraction, Extraction):
+        return extraction
+    if extraction is True:
+        extraction = ExtractionOptions()
+    if not isinstance(extraction, ExtractionOptions):
+        raise TypeError("extraction: None, True, an extraction.Extraction or an extraction.ExtractionOptions")
+    return extraction.plan(grism, wl, x_ref, y_ref, scan_speed, read_times, sub_scale, S)
+
+
+def row_windows(grism, wl, x_ref, y_ref, scan_speed, read_times, sub_scale, S, margin=ROW_MARGIN):
+    """The default plan: for each read interval (t0, t1) the bordered rows the first-order spectrum crosses in it, from
+    floor(y* + dy_min + v t0) - margin to ceil(y* + dy_max + v t1) + margin + 1, clamped to [5, S - 5]; y* = y_ref -
+    sub_scale + 5 and dy_min / dy_max the extremes of the trace's y offset from the star over the wavelength grid cropped
+    to the grism's limits.  The last-read window is that of (0, t_R).  scan_speed in px / s (0: a staring exposure, the
+    same window for every product); read_times in s.  -> int array [R + 1, 2]."""
+    wl = np.asarray(wl, dtype=float)
+    i0, i1 = tools.crop_spectrum_ind(grism.wl_limits[0], grism.wl_limits[1], wl)
+    tr = grism.get_trace(x_ref + 0.5, y_ref + 0.5)
+    dy = np.asarray(tr.wl_to_y(wl[i0:i1]), dtype=float) - (y_ref + 0.5)
+    v = float(scan_speed or 0.0)
+    y0 = y_ref - sub_scale + 5.0 + dy.min()
+    y1 = y_ref - sub_scale + 5.0 + dy.max()
+    read_times = np.asarray(read_times, dtype=float)
+    spans = list(zip(np.concatenate([[0.0], read_times[:-1]]), read_times)) + [(0.0, read_times[-1])]
+    out = np.empty((len(spans), 2), dtype=np.int64)
+    for j, (t0, t1) in enumerate(spans):
+        lo = int(np.floor(y0 + v * t0)) - margin
+        hi = int(np.ceil(y1 + v * t1)) + margin + 1
+        out[j] = max(lo, 5), min(hi, S - 5)
+    return out
+
+
+def channel_weights(x_ref, edges, sub_scale, S):
+    """[len(edges) - 1, S] fractional weights of the bordered columns for star-fixed channels: channel c covers
+    [x* + edges[c], x* + edges[c + 1]) with x* = x_ref - sub_scale + 5, the star's bordered column; `edges` are offsets
+    from the star in pixels."""
+    edges = np.asarray(edges, dtype=float)
+    x_star = x_ref - sub_scale + 5.0
+    cols = np.arange(S, dtype=float)
+    w = np.empty((len(edges) - 1, S))
+    for c in range(len(edges) - 1):
+        lo, hi = x_star + edges[c], x_star + edges[c + 1]
+        w[c] = np.clip(np.minimum(cols + 1.0, hi) - np.maximum(cols, lo), 0.0, 1.0)
+    return w
+
+
+CHUNK_ROWS = 32            # rows of a chunk of a window (kExtractRows): partial sums are kept per chunk
+
+
+def algorithmic_bytes(plan, S, R, read_bytes=4):
+    """Bytes the extraction's kernels must move for `plan` on a frame of side S with R non-zero reads of `read_bytes`
+    a sample: per pixel of product j's window the reads P_{j+1}, P_j, P_0 (P_0 once for j = 0 and for the last read),
+    four coefficient planes, dark_{j+1} and dark_j (float32 each; dark_0 = 0 is not stored), the pixel flat and the
+    master sky; the partial sums written and read once (2 float64 per chunk and column) and the result written."""
+    total = 0
+    steps = plan.steps
+    for p, (lo, hi) in enumerate(plan.row_windows[:R + 1]):
+        if p == R and not steps & LAST_READ:
+            continue
+        first = p == 0 or p == R                    # L_{r-1} = L_0 = 0: one read and one dark plane fewer
+        per_pixel = (2 if first else 3) * read_bytes
+        per_pixel += 16 if steps & LINEARISE else 0
+        per_pixel += (4 if first else 8) if steps & DARK else 0
+        per_pixel += 4 if steps & GAIN else 0
+        per_pixel += 4 if steps & SKY else 0
+        rows = int(hi) - int(lo)
+        chunks = -(-rows // CHUNK_ROWS)
+        total += rows * S * per_pixel + 2 * (2 * chunks * S * 8)
+    return total + (R + 1) * (S + 1) * 8
+
+
+class Delivery(object):
+    """What pipeline.run_pipelined sees of a context when an exposure's spectra are delivered: fetch_async / wait are the
+    spectra calls, and wait hands `finish` (reads or None, spectra, sky) -- views of the slot's pinned buffers.  With
+    `reads` the reads are copied too (both blocks follow the slot's kernels on its stream); without, they never leave
+    the device."""
+
+    def __init__(self, ctx, reads=False):
+        self.ctx, self.reads = ctx, reads
+
+    def upload(self, slot, desc):
+        self.ctx.upload(slot, desc)
+
+    def run(self, slot):
+        self.ctx.run(slot)
+
+    def fetch_async(self, slot):
+        if self.reads:
+            self.ctx.fetch_async(slot)
+        self.ctx.fetch_spectra_async(slot)
+
+    def wait(self, slot):
+        reads = self.ctx.wait(slot) if self.reads else None
+        spectra, sky = self.ctx.wait_spectra(slot)
+        return reads, spectra, sky
+
+
+def save_npz(path, spectra, sky, exposure_index, plans, x_ref, y_ref, read_times, exp_start):
+    """The file --spectra / --spectra-only write: spectra [n, R + 1, S], sky [n, R + 1], exposure_index [n], row_lo /
+    row_hi [n, R + 1], bg_cols [2], x_ref / y_ref [n], read_times [R], exp_start [n]."""
+    n = len(exposure_index)
+    np.savez(path, spectra=np.asarray(spectra, dtype=np.float64), sky=np.asarray(sky, dtype=np.float64),
+             exposure_index=np.asarray(exposure_index, dtype=np.int64),
+             row_lo=np.array([p.row_lo for p in plans], dtype=np.int64).reshape(n, -1),
+             row_hi=np.array([p.row_hi for p in plans], dtype=np.int64).reshape(n, -1),
+             bg_cols=np.asarray(plans[0].bg_cols if plans else BG_COLS, dtype=np.int64),
+             x_ref=np.asarray(x_ref, dtype=np.float64), y_ref=np.asarray(y_ref, dtype=np.float64),
+             read_times=np.asarray(read_times, dtype=np.float64), exp_start=np.asarray(exp_start, dtype=np.float64))

@@ -58,7 +58,14 @@ class Observation(object):
         # (BITPIX -64) either way, and a full-array exposure is 67 MB instead of 134 MB to bring over PCIe;
         # frame_options["out_dtype"] = np.float64 (CLI: --float64-reads) keeps the float64 arithmetic to the file;
         # np.uint16 (CLI: --uint16-reads) makes the reads and the files' SCI images 16-bit unsigned DN (BITPIX 16).
+        # frame_options["extraction"] (True, an extraction.ExtractionOptions or an extraction.Extraction; CLI: --spectra /
+        # --spectra-only): the device extracts every exposure's column spectra behind its reads; run_observation keeps
+        # them in `spectra_result` and writes them to `spectra_out` (an .npz path) when that is set.  `spectra_only`:
+        # the reads are neither copied from the device nor written.
         self.frame_options = {"out_dtype": np.float32}
+        self.spectra_out = None
+        self.spectra_only = False
+        self.spectra_result = None
         self.contaminants = []       # field stars on every exposure (setup_contaminants)
         self.charge_traps = None     # per-pixel charge trapping (setup_charge_traps)
         self._trap_tables = None
@@ -289,7 +296,19 @@ class Observation(object):
         (exposure_file_is_whole), is not generated again -- what is left of a visit after a rank died is then only the
         files that are missing.  Every exposure's random streams are keyed by the visit seed and its own index, so the
         files of a resumed visit are those of an uninterrupted one (the reference, whose exposures share one global
-        numpy stream, has no such restart: it deletes and rewrites, exposure.py:211-213)."""
+        numpy stream, has no such restart: it deletes and rewrites, exposure.py:211-213).
+        With frame_options["extraction"] every exposure's spectra are delivered too (see __init__): `spectra_result`
+        holds them and `spectra_out` names the .npz they are written to -- with world > 1 each rank writes its own,
+        `.rankNN` before the extension.  Not together with `resume` (a skipped exposure has no spectra)."""
+        extraction = self.frame_options.get("extraction")
+        if extraction is None and (self.spectra_only or self.spectra_out):
+            raise ValueError("spectra_out / spectra_only need frame_options['extraction']")
+        if extraction is not None and resume:
+            raise ValueError("spectra are not delivered by a resumed visit: the exposures it skips have none")
+        if self.spectra_only:
+            write_fits_raw = False
+        else:
+            write_fits_raw = write_fits
         if write_fits and self.outdir and not os.path.exists(self.outdir):
             os.makedirs(self.outdir)
         frames = {}
@@ -323,14 +342,22 @@ class Observation(object):
         # files are written by background threads while the GPU works on the next exposures
         from .exposure import FitsWriterPool
         from .pipeline import run_pipelined
-        pool = FitsWriterPool() if write_fits else None
+        pool = FitsWriterPool() if write_fits_raw else None
+        got_spectra = []              # (index, spectra, sky, plan, x_ref, y_ref) of every exposure, in delivery order
 
         def prepare(i):
             gen = self._generate_exposure(self.exp_start_times[i], i + 1, write_fits=False, prepare_only=True)
             return gen._prepared[1], gen
 
         def finish(i, gen, reads):
-            frame = gen._fill_exposure(np.array(reads), gen._prepared[2])     # (a copy: the pinned buffer is reused)
+            frame = None
+            if extraction is not None:
+                reads, spectra, sky = reads
+                spectra, sky = np.array(spectra), np.array(sky)           # (copies: the pinned buffer is reused)
+                got_spectra.append((i, spectra, sky, gen.extraction_plan, gen.exp_info["x_ref"], gen.exp_info["y_ref"]))
+                frame = gen._fill_spectra(spectra, sky)
+            if reads is not None:
+                frame = gen._fill_exposure(np.array(reads), gen._prepared[2])     # (a copy: the pinned buffer is reused)
             if pool is not None:
                 pool.submit(frame, self.outdir, "{:04d}_raw.fits".format(i + 1))
                 frames[i + 1] = None          # on disk; do not keep 64 MB per exposure alive
@@ -339,11 +366,41 @@ class Observation(object):
 
         try:
             # up to 3 exposures in flight on 4 context slots in rotation (even / odd slots run on different HIP streams)
-            run_pipelined(eng.ctx, mine, prepare, finish, depth=3, n_slots=4)
+            ctx = eng.ctx
+            if extraction is not None:
+                from .extraction import Delivery
+                ctx = Delivery(eng.ctx, reads=not self.spectra_only)
+            run_pipelined(ctx, mine, prepare, finish, depth=3, n_slots=4)
         finally:
             if pool is not None:
                 pool.close()
+        if extraction is not None:
+            self._keep_spectra(got_spectra, rank, world)
         return frames
+
+    def _keep_spectra(self, got, rank, world):
+        """What the exposures' extraction delivered -> `spectra_result` (the arrays of extraction.save_npz), written to
+        `spectra_out` when that is set."""
+        from . import extraction as _extraction
+        got = sorted(got, key=lambda g: g[0])
+        idx = [g[0] for g in got]
+        self.spectra_result = dict(
+            spectra=np.array([g[1] for g in got]), sky=np.array([g[2] for g in got]), exposure_index=np.array(idx, dtype=int),
+            plans=[g[3] for g in got], x_ref=np.array([g[4] for g in got], dtype=float),
+            y_ref=np.array([g[5] for g in got], dtype=float),
+            read_times=np.asarray(self.detector.get_read_times(self.NSAMP, self.SUBARRAY, self.SAMPSEQ), dtype=float),
+            exp_start=np.asarray(self.exp_start_times, dtype=float)[idx] if idx else np.zeros(0))
+        if not self.spectra_out:
+            return None
+        path = self.spectra_out
+        if world > 1:
+            root, ext = os.path.splitext(path)
+            path = "%s.rank%02d%s" % (root, rank, ext)
+        r = self.spectra_result
+        with open(path, "wb") as f:
+            _extraction.save_npz(f, r["spectra"], r["sky"], r["exposure_index"], r["plans"], r["x_ref"], r["y_ref"],
+                                 r["read_times"], r["exp_start"])
+        return path
 
     @staticmethod
     def _fits_is_whole(path):

@@ -1,6 +1,7 @@
 """Command line: generate a visit from a YAML parameter file.
 
     python -m wayne_amd.run_visit -p <parameter_file> [--calibration DIR] [--device N] [--max-exposures M] [--gpus G] [--resume]
+                                  [--spectra OUT.npz | --spectra-only OUT.npz]
 
 Accepts the reference's parameter files (wayne/run_visit.py:1-9, example
 examples/hd209458b_12181_simulation_parameters.yml): sections `general`
@@ -22,6 +23,11 @@ examples/hd209458b_12181_simulation_parameters.yml): sections `general`
   * an optional top-level `charge_traps:` section turns on per-pixel charge trapping, the ramp effect
     (wayne_amd/traps.py): `slow` / `fast` mappings of n_traps, efficiency, lifetime_s, initial, orbit_fill; `{}` = the
     defaults, an omitted key its default;
+  * `--spectra OUT.npz`: the device extracts every exposure's column spectra behind its reads (wayne_amd/extraction.py)
+    and they are written to OUT.npz beside the _raw files: spectra [n, NSAMP, S], sky [n, NSAMP], exposure_index, row_lo,
+    row_hi, bg_cols, x_ref, y_ref, read_times, exp_start.  `--spectra-only OUT.npz`: the same file, no _raw files, and
+    the reads never leave the device.  Neither goes with --resume.  With --gpus G > 1 each rank writes its own file,
+    `.rankNN` before the extension; they are not merged;
   * `--gpus G`: the process starts G rank processes itself (one per GPU of this node, before anything touches a
     GPU) and waits for them; under an external launcher (WORLD_SIZE / RANK set, one process per GPU) it is one
     rank.  Each rank generates its round-robin share of the exposures (observation.py:403-405 is the axis) on the
@@ -173,7 +179,15 @@ def run(argv=None):
     reads.add_argument("--uint16-reads", action="store_true",
                        help="16-bit unsigned reads, the ADC's sample type: the float32 read rounded and saturated to "
                             "0 .. 65535 on the device; the _raw files are then BITPIX 16 / BZERO 32768, a quarter the size")
+    spectra = ap.add_mutually_exclusive_group()
+    spectra.add_argument("--spectra", metavar="OUT.npz", default=None,
+                         help="extract every exposure's column spectra on the device and write them to OUT.npz beside "
+                              "the _raw files")
+    spectra.add_argument("--spectra-only", metavar="OUT.npz", default=None,
+                         help="... and write no _raw files: the reads never leave the device")
     args = ap.parse_args(argv)
+    if args.resume and (args.spectra or args.spectra_only):
+        raise SystemExit("--spectra / --spectra-only cannot be combined with --resume (a skipped exposure has no spectra)")
     if args.gpus < 1 or args.ranks_per_gpu < 1:
         raise SystemExit("--gpus and --ranks-per-gpu must be at least 1")
     n_ranks = args.gpus * args.ranks_per_gpu
@@ -223,6 +237,10 @@ def run(argv=None):
         obs.frame_options["out_dtype"] = np.float64
     if args.uint16_reads:
         obs.frame_options["out_dtype"] = np.uint16
+    if args.spectra or args.spectra_only:
+        obs.frame_options["extraction"] = True
+        obs.spectra_out = args.spectra or args.spectra_only
+        obs.spectra_only = bool(args.spectra_only)
     os.makedirs(obs.outdir, exist_ok=True)
     rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
     if rank == 0:

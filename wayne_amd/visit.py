@@ -12,6 +12,7 @@ import os
 import numpy as np
 
 from . import engine as _engine
+from . import extraction as _extraction
 from .exposure import FitsWriterPool
 from .exposure_generator import ExposureGenerator
 from .pipeline import run_pipelined
@@ -83,37 +84,97 @@ class VisitRunner(object):
         return self.generator(i).build_descriptor(eng, out_dtype=self.out_dtype, rng_mode=self.rng_mode,
                                                   **self.frame_kwargs(i))
 
-    def run(self, indices, keep=False, on_reads=None):
+    def run(self, indices, keep=False, on_reads=None, extraction=None, on_spectra=None):
         """Synthesise the given exposures as a pipeline over the context's two HIP streams and pinned
         host buffers: while the kernels of exposure n run on one stream and the device-to-host copy of
         exposure n-1 on the other, the host prepares and uploads exposure n+1 into the next slot.
         `on_reads(i, reads)` is called with a view of the pinned buffer (copy it to keep it);
-        keep=True returns {index: copy}; FITS files are written when out_dir is set."""
+        keep=True returns {index: copy}; FITS files are written when out_dir is set.
+        `extraction` (True, an extraction.ExtractionOptions, or one extraction.Extraction for every exposure): the
+        device extracts each exposure's column spectra behind its reads and both are delivered --
+        `on_spectra(i, spectra, sky)` gets views of the pinned buffer, and keep=True returns
+        {index: (reads, spectra, sky)}."""
         eng = self.engine()
         results = {}
         pool = FitsWriterPool() if self.out_dir is not None else None
 
         def prepare(i):
             gen = self.generator(i)
-            return gen.build_descriptor(eng, out_dtype=self.out_dtype, rng_mode=self.rng_mode,
-                                        **self.frame_kwargs(i)), gen
+            kw = self.frame_kwargs(i)
+            if extraction is not None:
+                kw["extraction"] = extraction
+            return gen.build_descriptor(eng, out_dtype=self.out_dtype, rng_mode=self.rng_mode, **kw), gen
 
-        def finish(i, gen, reads):
+        def finish(i, gen, got):
+            reads = got
+            if extraction is not None:
+                reads, spectra, sky = got
+                if on_spectra is not None:
+                    on_spectra(i, spectra, sky)
             if on_reads is not None:
                 on_reads(i, reads)
             if keep:
-                results[i] = reads.copy()
+                results[i] = reads.copy() if extraction is None else (reads.copy(), spectra.copy(), sky.copy())
             if pool is not None:
                 os.makedirs(self.out_dir, exist_ok=True)
                 # (a copy: the pinned buffer is reused by the next exposure)
                 pool.submit(gen._fill_exposure(reads.copy()), self.out_dir, gen.exp_info["filename"])
 
         try:
-            run_pipelined(eng.ctx, indices, prepare, finish, self.DEPTH, self.DEPTH)
+            ctx = eng.ctx if extraction is None else _extraction.Delivery(eng.ctx, reads=True)
+            run_pipelined(ctx, indices, prepare, finish, self.DEPTH, self.DEPTH)
         finally:
             if pool is not None:
                 pool.close()
         return results
+
+    def run_spectra(self, indices, extraction=True):
+        """The same pipeline with only the spectra delivered: every exposure is synthesised and extracted on the device
+        (`extraction`: as in run) and 8 (R + 1)(S + 1) bytes of it reach the host -- the reads never leave the device.
+        -> (spectra [n, R + 1, S], sky [n, R + 1]) in the order of `indices`; `self.plans` [n]: each exposure's
+        extraction.Extraction."""
+        eng = self.engine()
+        indices = list(indices)
+        where = {i: n for n, i in enumerate(indices)}
+        R, S = eng.ctx.R, eng.ctx.S
+        spectra = np.empty((len(indices), R + 1, S))
+        sky = np.empty((len(indices), R + 1))
+        self.plans = [None] * len(indices)
+
+        def prepare(i):
+            gen = self.generator(i)
+            kw = self.frame_kwargs(i)
+            kw["extraction"] = extraction
+            return gen.build_descriptor(eng, out_dtype=self.out_dtype, rng_mode=self.rng_mode, **kw), gen
+
+        def finish(i, gen, got):
+            _, sp, sk = got
+            spectra[where[i]], sky[where[i]] = sp, sk
+            self.plans[where[i]] = gen.extraction_plan
+
+        run_pipelined(_extraction.Delivery(eng.ctx, reads=False), indices, prepare, finish, self.DEPTH, self.DEPTH)
+        return spectra, sky
+
+    def run_resident_spectra(self, n, on_spectra=None):
+        """run_resident with only the spectra delivered: the descriptors AND their extraction are already in slots
+        0..DEPTH-1; n exposures, kernels + extraction + the copy of the spectra block, no reads copied."""
+        ctx = self.engine().ctx
+        pending = []
+
+        def done(s_old):
+            spectra, sky = ctx.wait_spectra(s_old)
+            if on_spectra is not None:
+                on_spectra(s_old, spectra, sky)
+
+        for j in range(n):
+            slot = j % self.DEPTH
+            if len(pending) == self.DEPTH:
+                done(pending.pop(0))
+            ctx.run(slot)
+            ctx.fetch_spectra_async(slot)
+            pending.append(slot)
+        for s_old in pending:
+            done(s_old)
 
     def run_resident(self, n, on_reads=None):
         """The same pipeline over descriptors that are ALREADY in slots 0..DEPTH-1 (uploaded by the
