@@ -42,6 +42,16 @@ namespace wayne {
 // 0.25 sigma in y and 10 % in sigma of one another (Z >~ 0.8) and <= 2^24
 // electrons; any other group runs a column and a row chain per bin as above.
 // oracle/split_oracle.c (so_group_pools, so_narrow_pooled) is the same procedure.
+//
+// COMPACTED CHAINS (COMPACT = true, knob narrow_compact, the default).  With chain j of group g on lane 16 g + j, only
+// 6-7 of a group's 16 lanes hold a chain at all (sigma_l = 0.5-0.9 px), the light columns are done after 2-4 rows and
+// the wave steps on for its three heavy ones, paying for both branches of binomial() every time.  A chain depends on
+// its own stream (keyed by group and column, not by lane), its start count s_pool[16 g + j] and its group's s_cond, X0
+// and J0 -- all in LDS -- and its deposits are integer atomics, so any lane can run it: after a workgroup barrier the
+// live slots of s_pool (~200 of 512) are listed by a counting sort on the highest set bit of their counts, heaviest
+// first, in the memory of s_q (dead by then), and thread i runs list entry i.  Waves past the list's end skip the
+// phase, and chains of like weight (hence of the same branch of binomial()) share a wave.  Same frames, bit for bit.
+// COMPACT = false keeps step (4) as written above: a group's chains inside its own wave, no barrier.
 // (kNarrowThreads = 512 bins per workgroup: plan_consts.h)
 constexpr int kNarrowCells = 2 * kNarrowR + 1;
 constexpr int kPoolRows = 2 * kNarrowR + 2;   // rows of a group's common window: jc_min - R .. jc_min + R + 1
@@ -72,7 +82,7 @@ __device__ __forceinline__ float upper_tail(float t) {
   return (t > kTailCut) ? 0.f : (0.5f * u) * M::exp_(p);
 }
 
-template <int FLUSH, bool FAST>
+template <int FLUSH, bool FAST, bool COMPACT>
 __global__ __launch_bounds__(kNarrowThreads) void k_narrow(ThrowArgs a) {
   typedef typename std::conditional<FAST, FastMath, ExactMath<float> >::type M;
   __shared__ int tile[kNarrowTile];
@@ -83,7 +93,10 @@ __global__ __launch_bounds__(kNarrowThreads) void k_narrow(ThrowArgs a) {
   __shared__ float s_cond[kNarrowThreads];              // [group][i]: conditional probability of the i-th row visited by a pooled chain
   __shared__ int s_box[4];
   __shared__ float s_fc[10];                            // stirling_tail(0..9), indexed per lane in the rejection sampler
+  // COMPACT: X0 and J0 of the 32 groups; the live chains by the highest set bit of their start count
+  __shared__ int s_gx[COMPACT ? kNarrowThreads / 16 : 1], s_gj[COMPACT ? kNarrowThreads / 16 : 1], s_hist[COMPACT ? 32 : 1];
   if (threadIdx.x < 10) s_fc[threadIdx.x] = (float)kStirlingSmall[threadIdx.x];
+  if (COMPACT && threadIdx.x < 32) s_hist[threadIdx.x] = 0;
   const int k = blockIdx.x;                                    // (sub-sample fastest: see ThrowArgs::chunk_order)
   const int tid = threadIdx.x;
   // (the workgroup's chunk by a scalar load of the argument word that holds its byte; the bin's count, position and
@@ -298,7 +311,7 @@ __global__ __launch_bounds__(kNarrowThreads) void k_narrow(ThrowArgs a) {
       }
     }
     // the pooled columns' rows: lane j of a group takes column X0 + j
-    if (__any(pool)) {
+    if (!COMPACT && __any(pool)) {
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
       __builtin_amdgcn_wave_barrier();
       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -315,6 +328,55 @@ __global__ __launch_bounds__(kNarrowThreads) void k_narrow(ThrowArgs a) {
           if (m > 0.f) {
             const int u = (i + 1) >> 1;
             deposit(X0 + gl, J0 + ((i & 1) ? kNarrowR + u : kNarrowR - u), (int)m);
+          }
+        }
+      }
+    }
+  }
+  if (COMPACT) {
+    // the pooled columns' rows, compacted: the workgroup's live chains -- slots t of s_pool with electrons, ~200 of 512 --
+    // are listed heaviest first and thread i takes chain i (see COMPACTED CHAINS above).  Every thread of the workgroup
+    // gets here, whatever its wave ran above, and the barriers below stand under a workgroup-uniform condition only.
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    const int mine = pool ? s_pool[tid] : 0;                   // (added to by the slot's own wave only)
+    if (gl == 0) { s_gx[tid >> 4] = X0; s_gj[tid >> 4] = J0; }
+    if (__syncthreads_or(mine > 0)) {                          // (s_q is free from here on)
+      // counting sort on the highest set bit of the count (<= 2^24: classes 0..24), order within a class as it comes
+      int* const list = reinterpret_cast<int*>(&s_q[0][0]);
+      const int cls = (mine > 0) ? 31 - __clz(mine) : 0;
+      int rank = 0;
+      if (mine > 0) rank = atomicAdd(&s_hist[cls], 1);
+      __syncthreads();
+      // every wave for itself: lane l < 32 holds the chains of class 31 - l, summed over the lanes before it
+      const int lane = tid & 63;
+      const int h = (lane < 32) ? s_hist[31 - lane] : 0;
+      int incl = h;
+#pragma unroll
+      for (int off = 1; off < 32; off <<= 1) {
+        const int v = __shfl_up(incl, off);
+        if (lane >= off) incl += v;
+      }
+      const int first = __shfl(incl - h, 31 - cls), n_live = __shfl(incl, 31);
+      if (mine > 0) list[first + rank] = tid;
+      __syncthreads();
+      if ((tid & ~63) < n_live) {                              // (waves past the end of the list have nothing to do)
+        const int slot = (tid < n_live) ? list[tid] : 0;
+        float left = (tid < n_live) ? (float)s_pool[slot] : 0.f;
+        const int cgrp = slot & ~15, cl = slot & 15;
+        const int cX = s_gx[slot >> 4] + cl, cJ0 = s_gj[slot >> 4];
+        SeededStream rp(a.seed, STAGE_POOL, (uint32_t)(w - tid + slot) >> 4, (uint32_t)k + a.subsample0, a.exposure, (uint32_t)cl);
+        for (int i = 0; i < kPoolRows; ++i) {
+          if (!__any(left > 0.f)) break;
+          float m = 0.f;
+          if (left > 0.f) {
+            m = binomial<M>(left, s_cond[cgrp + i], rp, s_fc);
+            left -= m;
+          }
+          if (m > 0.f) {
+            const int u = (i + 1) >> 1;
+            deposit(cX, cJ0 + ((i & 1) ? kNarrowR + u : kNarrowR - u), (int)m);
           }
         }
       }

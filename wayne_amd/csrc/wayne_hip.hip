@@ -244,6 +244,7 @@ struct Knobs {
   long long fork_narrow = -1;    // 1: k_narrow on a side stream beside k_lane
   long long streams = -1;        // 1: every slot on one stream
   long long upload_timing = -1;  // 1: wayne_ctx_destroy prints the host time of wayne_exposure_upload by part
+  long long narrow_compact = -1; // 0: k_narrow's pooled row chains stay on their groups' lanes (default: compacted across the workgroup)
   long long ramp_reads = -1;     // TIMING BUILDS (-DWAYNE_TIMING_KNOBS) only: k_ramp works through the first n reads
 };
 struct KnobName { const char* name; const char* env; long long Knobs::*field; };
@@ -254,6 +255,7 @@ const KnobName kKnobNames[] = {
     {"keep_narrow", "WAYNE_KEEP_NARROW", &Knobs::keep_narrow}, {"no_fuse", "WAYNE_NO_FUSE", &Knobs::no_fuse},
     {"fork_narrow", "WAYNE_FORK_NARROW", &Knobs::fork_narrow}, {"streams", "WAYNE_STREAMS", &Knobs::streams},
     {"upload_timing", "WAYNE_UPLOAD_TIMING", &Knobs::upload_timing}, {"ramp_reads", "WAYNE_RAMP_READS", &Knobs::ramp_reads},
+    {"narrow_compact", "WAYNE_NARROW_COMPACT", &Knobs::narrow_compact},
 };
 constexpr size_t kMiscBytes = 64;   // status block of a slot: [0] electrons (u64), [8] status (int); k_prep_wl clears all of it
 
@@ -512,8 +514,10 @@ int launch_throw(wayne_ctx* c, const ThrowArgs& a, int lds_ints) {
 template <int FLUSH>
 int launch_narrow(wayne_ctx* c, const ThrowArgs& a, bool exact) {
   const dim3 grid((unsigned)a.K, (unsigned)((a.W + kNarrowThreads - 1) / kNarrowThreads));
-  if (exact) hipLaunchKernelGGL((k_narrow<FLUSH, false>), grid, dim3(kNarrowThreads), 0, c->stream, a);
-  else hipLaunchKernelGGL((k_narrow<FLUSH, true>), grid, dim3(kNarrowThreads), 0, c->stream, a);
+  const bool compact = c->knobs.narrow_compact != 0;   // (knob narrow_compact: the same frames either way)
+  void (*kern)(ThrowArgs) = exact ? (compact ? k_narrow<FLUSH, false, true> : k_narrow<FLUSH, false, false>)
+                                  : (compact ? k_narrow<FLUSH, true, true> : k_narrow<FLUSH, true, false>);
+  hipLaunchKernelGGL(kern, grid, dim3(kNarrowThreads), 0, c->stream, a);
   HIP_TRY(c, hipGetLastError());
   return WAYNE_OK;
 }
