@@ -96,8 +96,8 @@ int wayne_ctx_synchronize(wayne_ctx *ctx);
  * other entry point looks at the environment, so editing it from another thread cannot change what a live context
  * launches.  Afterwards only this call changes a knob (value < 0: back to the library's own choice).  Names:
  * tile_ints, batch, thin, no_acc_box, lane_reach, throw_wgs, keep_narrow, no_fuse, fork_narrow, streams,
- * upload_timing, narrow_compact, ramp_reads (timing builds only).  None changes a frame (integer accumulation commutes); they change
- * launch shapes.  WAYNE_E_INVALID for an unknown name. */
+ * upload_timing, narrow_compact, lane_tight_tile, ramp_reads (timing builds only).  None changes a frame (integer
+ * accumulation commutes); they change launch shapes.  WAYNE_E_INVALID for an unknown name. */
 int wayne_ctx_set_knob(wayne_ctx *ctx, const char *name, long long value);
 int wayne_ctx_get_knob(const wayne_ctx *ctx, const char *name, long long *value);
 /* The context's hipStream_t (as void*), for callers that interoperate. */

@@ -226,7 +226,7 @@ def i32(a):
 
 
 KNOBS = ("tile_ints", "batch", "thin", "no_acc_box", "lane_reach", "throw_wgs", "keep_narrow", "no_fuse", "fork_narrow",
-         "streams", "upload_timing", "ramp_reads", "narrow_compact")
+         "streams", "upload_timing", "ramp_reads", "narrow_compact", "lane_tight_tile")
 _live_contexts = weakref.WeakSet()
 _knob_defaults = {}
 

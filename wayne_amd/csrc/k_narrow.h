@@ -409,12 +409,32 @@ __global__ __launch_bounds__(kNarrowThreads) void k_narrow(ThrowArgs a) {
 // 63 lanes of the wave idle).  At a margin of 22 px (3.7 sigma_h) 3 % of the wave-iterations had such a lane and
 // the kernel ran at 220 cycles per iteration instead of ~135; 30 px is 5 sigma_h.
 //
-// Better still, the tile can hold EVERY electron: the radius' uniform is >= 2^-34 (see the electron loop), so an
-// electron lands within sigma sqrt(2 ln 2^34) = 6.87 sigma of its bin.  A workgroup whose tile -- the bins' bounding
-// box +- (6.9 sigma_max + 1) px -- fits the LDS budget and lies inside the frame needs no bounds test at all: the deposit is
-// cvt, cvt, lshl_add, mad, ds_add (the tile origin folded into one scalar), four vector instructions fewer per
-// electron and no branch in the loop.  Other workgroups (frame edge, huge sigma, wild positions) keep the test and
-// the fixed margin.
+// Better still, the tile can hold EVERY electron that is thrown without a test.  The radius' uniform is >= 2^-34 (see
+// the electron loop), so an electron lands within sigma sqrt(2 ln 2^34) = 6.87 sigma of its bin -- but that reach
+// belongs to the REFINED radius, drawn only when the radius half-word h is 0: one electron in 65536.  Every other
+// electron has u = (h + 1/2) / 2^16 >= 1.5 / 65536 and lands within kLaneR16 sigma (below).  A workgroup whose tile --
+// the bins' bounding box +- (kLaneR16 sigma_max + 1) px -- fits the LDS budget and lies inside the frame throws those
+// without a bounds test: the deposit is cvt, cvt, lshl_add, mad, ds_add (the tile origin folded into one scalar), four
+// vector instructions fewer per electron.  A wave in which a lane draws h = 0 leaves the test-free loop body by a scalar
+// branch -- one per pair of electrons, where the branch around the refinement stood once per electron -- and throws that
+// pair by the checked rule of throw_one: tile if inside, the global path if on the frame (sure_loop).  128 draws per
+// pair-iteration of a wave x 2^-16: one iteration in 512 takes the checked body, and ~0.1 of the far electrons lie
+// beyond the tile: 2e-4 of the iterations at ~2800 cycles each, under 1 % of the loop.  Other workgroups (frame edge,
+// huge sigma, wild positions) keep the test and the fixed margin.
+// Sized for 6.9 sigma (the rule until knob lane_tight_tile; 0 brings it back) the tile served 0.0015 % of the electrons
+// and could not be test-free at all for sigma_h >~ 5.9 px -- (20 + 2 x 43) x (2 + 2 x 43) > kLaneTile: the two reddest
+// chunks of nine, 22 % of the flagship workload's workgroups, ran the bounds-tested loop.  With kLaneR16 the margin at
+// sigma_h = 6.8 px is 33 px and the tile ~86 x 69, and the mean test-free tile of that workload falls from 7548 to 4238
+// cells to clear, scan and flush.  Measured: k_lane 165.9 -> 161.4 us (profiles/lane_tight_tile.json).
+//
+// kLaneR16: the largest radius, in sigmas, of an electron whose radius is NOT refined.  h >= 1, so
+// u >= 1.5 / 65536 = 1 / 43690.7 and R <= sqrt(2 ln 43690.7) = 4.6228.  As the loop computes it in float32 --
+// sqrt(fma(c, log2(h + 0.5), c16)) / sigma, largest at h = 1 -- it is 4.62275 (tests/test_lane_reach_bound.py restates
+// it over h = 1 ... 65535); the hardware's log2 and sqrt are good to 1 ulp, ~1e-7 relative, against the 1.6e-3 between
+// 4.62275 and 4.63, and v_cos_f32 / v_sin_f32 do not exceed 1 in magnitude, so neither offset exceeds the radius.  The
+// smallest REFINED radius is sqrt(2 ln 65536) = 4.71 sigma.
+constexpr float kLaneR16 = 4.63f;
+constexpr float kLaneR34 = 6.9f;        // reach of the refined radius (6.87 sigma): the tile rule with lane_tight_tile = 0
 constexpr int kLaneMargin = 30;
 constexpr int kLaneReachMax = 48;       // largest margin of a test-free tile (sigma_h up to 6.8 px)
 constexpr int kLaneTile = 9216;         // ints of LDS (36 KB): 512 bins span ~20 px of the trace, + 2 x margin, by 2 x margin + a few rows
@@ -447,7 +467,7 @@ __device__ __forceinline__ void lane_body(const ThrowArgs& a, const PrepArgs& p,
   __shared__ unsigned short s_list[THIN ? kLaneListCap : 1];
   __shared__ int s_cnt[2];                // THIN: cells on the flush list; two counters used in turn (see the flush)
   __shared__ int s_box[4];
-  __shared__ int s_reach;                 // max over the lanes of 6.9 sigma + 1 (float bits; 0x7F800000 if a lane is not sane)
+  __shared__ int s_reach;                 // max over the lanes of reach_sigmas x sigma + 1 (float bits; 0x7F800000 if a lane is not sane)
   // (sub-sample fastest: see ThrowArgs::chunk_order; BATCH = false: one sub-sample, as k_narrow)
   const int k0 = BATCH ? (int)blockIdx.x * a.kb : (int)blockIdx.x, k1 = BATCH ? min(k0 + a.kb, a.K) : k0 + 1;
   const int tid = threadIdx.x;
@@ -533,7 +553,7 @@ __device__ __forceinline__ void lane_body(const ThrowArgs& a, const PrepArgs& p,
       // (each sigma the bin uses on its own: fmaxf would step over a NaN)
       const bool sig_ok = (nw > 0 ? (sh >= 0.f && sh < 1e6f) : true) && (n > nw ? (sl >= 0.f && sl < 1e6f) : true);
       const float smax = fmaxf(nw > 0 ? sh : 0.f, n > nw ? sl : 0.f);
-      float r = sig_ok ? 6.9f * smax + 1.f : __int_as_float(0x7F800000);
+      float r = sig_ok ? a.lane_reach_sigmas * smax + 1.f : __int_as_float(0x7F800000);
       if (sane) {
         constexpr int spare = FUSED ? 1 : 0;
         x_lo = min(x_lo, ic - spare); x_hi = max(x_hi, ic + spare); y_lo = min(y_lo, jc - spare); y_hi = max(y_hi, jc + spare);
@@ -559,7 +579,7 @@ __device__ __forceinline__ void lane_body(const ThrowArgs& a, const PrepArgs& p,
   }
   __syncthreads();
   const float reach_wg = __int_as_float(s_reach);
-  bool sure = reach_wg <= (float)kLaneReachMax;               // every electron within `margin` of its bin
+  bool sure = reach_wg <= (float)kLaneReachMax;               // every electron with h != 0 within `margin` of its bin
   const int margin = sure ? (int)ceilf(reach_wg) : kLaneMargin;
   const int bx0 = s_box[0] - margin, bx1 = s_box[1] + margin + 1, by0 = s_box[2] - margin, by1 = s_box[3] + margin + 1;
   int tx0 = max(bx0, 1), tx1 = min(bx1, a.N), ty0 = max(by0, 1), ty1 = min(by1, a.N);
@@ -656,10 +676,30 @@ __device__ __forceinline__ void lane_body(const ThrowArgs& a, const PrepArgs& p,
     vx = fmaf(__builtin_amdgcn_cosf(rev), Rs, px);            // offset + the bin's fraction of a pixel (:91-92; bin_local)
     vy = fmaf(__builtin_amdgcn_sinf(rev), Rs, py);
   };
-  // (test-free tile) every live electron is inside the tile and on the frame
-  auto throw_sure = [&](SeededStream& rng, uint32_t wd, float c, float c16, bool live) {
-    float vx, vy;
-    draw(rng, wd, c, c16, x, y, vx, vy);
+  // the checked deposit: the electron's cell counted from the tile's corner: floor of the sum + the bin's pixel
+  // relative to that corner, in unsigned arithmetic -- a dead lane's -1e30 saturates the conversion and wraps to a cell
+  // off every frame.  As many instructions as the truncating convert and the subtraction of the corner they replace.
+  const uint32_t oxl = (uint32_t)ox - (uint32_t)tx0, oyl = (uint32_t)oy - (uint32_t)ty0;
+  auto deposit_checked = [&](float vx, float vy) {
+    uint32_t lx, ly;
+    asm("v_cvt_flr_i32_f32 %0, %2\n\tv_cvt_flr_i32_f32 %1, %3\n\tv_add_u32 %0, %0, %4\n\tv_add_u32 %1, %1, %5"
+        : "=&v"(lx), "=&v"(ly) : "v"(vx), "v"(vy), "v"(oxl), "v"(oyl));
+    if (lx < (uint32_t)tw && ly < (uint32_t)th) {
+      tile_add(__umul24(ly, tw4) + (lx << 2));
+    } else {
+      const int xi = (int)(lx + (uint32_t)tx0), yi = (int)(ly + (uint32_t)ty0);
+      if (xi > 0 && xi < a.N && yi > 0 && yi < a.N) deposit_global<FLUSH>(a, si, xi, yi, 1);               // (:93)
+    }
+  };
+  // (test-free tile) every live electron whose radius is not refined (h != 0) is inside the tile and on the frame.  The
+  // one in 65536 with h = 0 reaches up to 6.87 sigma, beyond a tile sized for kLaneR16: a wave with such a lane (one
+  // pair-iteration in 512) takes that pair of electrons through throw_one, the checked rule, by a scalar branch
+  // (sure_loop) -- one per pair where the branch around the refinement stood once per electron; the common path is
+  // the sequence it was, without the refinement.
+  auto throw_sure = [&](uint32_t wd, float c, float c16, bool live) {
+    const float rev = __uint_as_float(__builtin_amdgcn_alignbit(0x7Fu, wd, 9));     // (see draw)
+    const float Rs = __builtin_amdgcn_sqrtf(fmaf(c, __builtin_amdgcn_logf((float)(wd & 0xFFFFu) + 0.5f), c16));
+    const float vx = fmaf(__builtin_amdgcn_cosf(rev), Rs, x), vy = fmaf(__builtin_amdgcn_sinf(rev), Rs, y);
     // byte address = j * tw4 + (i * 4 + origin), (i, j) = floor(vx, vy) within +-kLaneReachMax: v_cvt_flr_i32_f32 twice,
     // v_lshl_add_u32, v_mad_i32_i24 (the compiler's own choice is a floor, a convert, a multiply, a shift and a
     // three-operand add)
@@ -669,21 +709,30 @@ __device__ __forceinline__ void lane_body(const ThrowArgs& a, const PrepArgs& p,
         : "=&v"(addr), "=&v"(j) : "v"(vx), "v"(vy), "v"(origin), "s"(tw4));
     if (live) tile_add(addr);
   };
-  // (tile with the bounds test) the electron's cell counted from the tile's corner: floor of the sum + the bin's pixel
-  // relative to that corner, in unsigned arithmetic -- a dead lane's -1e30 saturates the conversion and wraps to a cell
-  // off every frame.  As many instructions as the truncating convert and the subtraction of the corner they replace.
-  const uint32_t oxl = (uint32_t)ox - (uint32_t)tx0, oyl = (uint32_t)oy - (uint32_t)ty0;
+  // (tile with the bounds test)
   auto throw_one = [&](SeededStream& rng, uint32_t wd, float c, float c16, float px, float py) {
     float vx, vy;
     draw(rng, wd, c, c16, px, py, vx, vy);
-    uint32_t lx, ly;
-    asm("v_cvt_flr_i32_f32 %0, %2\n\tv_cvt_flr_i32_f32 %1, %3\n\tv_add_u32 %0, %0, %4\n\tv_add_u32 %1, %1, %5"
-        : "=&v"(lx), "=&v"(ly) : "v"(vx), "v"(vy), "v"(oxl), "v"(oyl));
-    if (lx < (uint32_t)tw && ly < (uint32_t)th) {
-      tile_add(__umul24(ly, tw4) + (lx << 2));
-    } else {
-      const int xi = (int)(lx + (uint32_t)tx0), yi = (int)(ly + (uint32_t)ty0);
-      if (xi > 0 && xi < a.N && yi > 0 && yi < a.N) deposit_global<FLUSH>(a, si, xi, yi, 1);               // (:93)
+    deposit_checked(vx, vy);
+  };
+  const float ch16 = -16.f * ch, cl16 = -16.f * cl;
+  // electrons [j0, j1) of the wave's lanes on a test-free tile: the inner loop runs until a lane draws h = 0, that pair of
+  // electrons goes through throw_one, and the inner loop takes over again.  `refine` changes outside the inner loop only.
+  // wide(j): electron j takes sigma_h; alive(j): the lane has an electron j
+  auto sure_loop = [&](SeededStream& rng, int j0, int j1, auto wide, auto alive) {
+    for (int j = j0; j < j1; j += 2) {
+      uint32_t wa, wb;
+      for (;;) {
+        rng.next2(wa, wb);
+        if (__builtin_expect(__any(((wa & 0xFFFFu) == 0u) | ((wb & 0xFFFFu) == 0u)), 0)) break;
+        throw_sure(wa, wide(j) ? ch : cl, wide(j) ? ch16 : cl16, alive(j));
+        throw_sure(wb, wide(j + 1) ? ch : cl, wide(j + 1) ? ch16 : cl16, alive(j + 1));
+        j += 2;
+        if (j >= j1) return;
+      }
+      const bool la = alive(j), lb = alive(j + 1);
+      throw_one(rng, wa, wide(j) ? ch : cl, wide(j) ? ch16 : cl16, la ? x : -1e30f, la ? y : -1e30f);
+      throw_one(rng, wb, wide(j + 1) ? ch : cl, wide(j + 1) ? ch16 : cl16, lb ? x : -1e30f, lb ? y : -1e30f);
     }
   };
   int cmin = n, cmax = n;
@@ -702,7 +751,6 @@ __device__ __forceinline__ void lane_body(const ThrowArgs& a, const PrepArgs& p,
     const int lo = bad_h ? nw : 0, hi = bad_l ? min(nw, n) : n;
     const bool odd_wave = __any(n > 0 && (bad_h || bad_l));
     const int cmin2 = cmin & ~1;                             // electrons 2i and 2i + 1 share pair i
-    const float ch16 = -16.f * ch, cl16 = -16.f * cl;
     uint32_t wa, wb;
     if (odd_wave) {
       // (a wave with such a lane -- its workgroup's tile is never test-free: the reach of a sigma that is not finite is
@@ -715,14 +763,10 @@ __device__ __forceinline__ void lane_body(const ThrowArgs& a, const PrepArgs& p,
       }
     } else if (sure) {
       if (one_sigma) {
-        for (int j = 0; j < cmin2; j += 2) { rng.next2(wa, wb); throw_sure(rng, wa, ch, ch16, true); throw_sure(rng, wb, ch, ch16, true); }
-        for (int j = cmin2; j < cmax; j += 2) { rng.next2(wa, wb); throw_sure(rng, wa, ch, ch16, j < n); throw_sure(rng, wb, ch, ch16, j + 1 < n); }
+        sure_loop(rng, 0, cmin2, [](int) { return true; }, [](int) { return true; });
+        sure_loop(rng, cmin2, cmax, [](int) { return true; }, [&](int j) { return j < n; });
       } else {
-        for (int j = 0; j < cmax; j += 2) {
-          rng.next2(wa, wb);
-          throw_sure(rng, wa, (j < nw) ? ch : cl, (j < nw) ? ch16 : cl16, j < n);
-          throw_sure(rng, wb, (j + 1 < nw) ? ch : cl, (j + 1 < nw) ? ch16 : cl16, j + 1 < n);
-        }
+        sure_loop(rng, 0, cmax, [&](int j) { return j < nw; }, [&](int j) { return j < n; });
       }
     } else if (one_sigma) {
       for (int j = 0; j < cmin2; j += 2) { rng.next2(wa, wb); throw_one(rng, wa, ch, ch16, x, y); throw_one(rng, wb, ch, ch16, x, y); }

@@ -51,6 +51,7 @@ struct ThrowArgs {
   uint32_t flags;
   int margin, lds_ints;    // per-workgroup tile: margin around its slice of the trace, LDS capacity
   int flat_off;            // (1014 - N) / 2  (grism.py:363)
+  float lane_reach_sigmas; // k_lane: a test-free tile is the bins' box +- (this x sigma_max + 1) px (kLaneR16; knob lane_tight_tile)
   double flat_wmin, flat_wmax, flat_inv_range;   // inv_range = 1 / (wmax - wmin)
   const SubInfo* sub;      // [K]
   const uint32_t* prefix;  // [K*(W+1)]

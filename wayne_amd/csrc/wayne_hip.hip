@@ -245,6 +245,7 @@ struct Knobs {
   long long streams = -1;        // 1: every slot on one stream
   long long upload_timing = -1;  // 1: wayne_ctx_destroy prints the host time of wayne_exposure_upload by part
   long long narrow_compact = -1; // 0: k_narrow's pooled row chains stay on their groups' lanes (default: compacted across the workgroup)
+  long long lane_tight_tile = -1; // 0: k_lane sizes its test-free tiles for the refined radius, 6.9 sigma (default: kLaneR16, the 16-bit radius)
   long long ramp_reads = -1;     // TIMING BUILDS (-DWAYNE_TIMING_KNOBS) only: k_ramp works through the first n reads
 };
 struct KnobName { const char* name; const char* env; long long Knobs::*field; };
@@ -256,6 +257,7 @@ const KnobName kKnobNames[] = {
     {"fork_narrow", "WAYNE_FORK_NARROW", &Knobs::fork_narrow}, {"streams", "WAYNE_STREAMS", &Knobs::streams},
     {"upload_timing", "WAYNE_UPLOAD_TIMING", &Knobs::upload_timing}, {"ramp_reads", "WAYNE_RAMP_READS", &Knobs::ramp_reads},
     {"narrow_compact", "WAYNE_NARROW_COMPACT", &Knobs::narrow_compact},
+    {"lane_tight_tile", "WAYNE_LANE_TIGHT_TILE", &Knobs::lane_tight_tile},
 };
 constexpr size_t kMiscBytes = 64;   // status block of a slot: [0] electrons (u64), [8] status (int); k_prep_wl clears all of it
 
@@ -549,6 +551,10 @@ void (*pick_ramp(int out, bool exact, int sky, bool noise))(RampArgs) {
        : out == 2 ? (exact ? ramp_sky<uint16_t, false>(sky, noise) : ramp_sky<uint16_t, true>(sky, noise))
                   : (exact ? ramp_sky<float, false>(sky, noise) : ramp_sky<float, true>(sky, noise));
 }
+
+// k_lane's tile reach in sigmas (knob lane_tight_tile: the same frames either way -- an electron beyond the tile takes
+// the global path)
+float lane_reach_sigmas(const wayne_ctx* c) { return c->knobs.lane_tight_tile != 0 ? kLaneR16 : kLaneR34; }
 
 template <int FLUSH>
 int launch_lane(wayne_ctx* c, const ThrowArgs& a, bool thin, const PrepArgs* fused_prep = nullptr, const CosmicArgs* fused_cosmic = nullptr) {
@@ -946,6 +952,7 @@ int wayne_psf_apply_ex(wayne_ctx* c, const int32_t* counts, int size, const doub
 
     ThrowArgs a{};
     a.W = size; a.K = 1; a.N = N; a.S = N + 2 * kBorder; a.kb = 1;
+    a.lane_reach_sigmas = lane_reach_sigmas(c);
     // enough workgroups to fill the chip when the call is big, one when small
     a.splits = (int)std::min<long long>(512, std::max<long long>(1, total / (64LL * kThrowThreads)));
     a.min_wgs = a.splits;   // one call, one sub-sample: share the electrons among all launched workgroups
@@ -1299,6 +1306,7 @@ static int front_source(wayne_ctx* c, int slot, Slot& s, SourceState& ss, int sr
     ThrowArgs a{};
     a.W = W; a.K = K; a.N = N; a.S = S;
     a.kb = ss.kb;
+    a.lane_reach_sigmas = lane_reach_sigmas(c);
     // grid: one unit (128 electrons; 1 in replay mode) per lane of the workgroups of a sub-sample, from
     // the host's estimate of the electrons + 8 %, but at least ~4 workgroups per CU over the launch
     // (knob `throw_wgs` / desc.thrower_splits override); k_throw shares out what it actually finds
