@@ -414,6 +414,37 @@ int wayne_exposure_fetch_spectra_async(wayne_ctx *ctx, int slot);
 int wayne_exposure_wait_spectra(wayne_ctx *ctx, int slot, double **spectra, double **sky);
 /* The blocking form: spectra [(R+1)*S] and sky [R+1] into the caller's arrays.  Synchronises. */
 int wayne_exposure_download_spectra(wayne_ctx *ctx, int slot, double *spectra, double *sky);
+/*
+ * Cosmic-ray rejection on the extraction's difference images (opt-in; without it nothing above changes).  I_r and g are
+ * the extraction law's.  For read interval j = 0 .. R-1 let I = I_{j+1}.  A pixel (y, x) is TESTED iff 7 <= y < S-7,
+ * 7 <= x < S-7 and y lies in the mask rows [min_p row_lo[p], max_p row_hi[p]) over the products that are formed:
+ *   m8 = max of the eight stencil pixels I[y+-1,x], I[y+-2,x], I[y,x+-1], I[y,x+-2]
+ *   d  = I[y,x] - m8
+ *   flag_j[y,x]  <=>  d > 0  and  d d > k^2 (rn^2 + max(m8, 0))        (no square root, no division)
+ *   repl_j[y,x]  =  0.5 (b + c),  b <= c the middle two of I[y,x-2], I[y,x-1], I[y,x+1], I[y,x+2]   (the same row)
+ * A flag is a strict local maximum over the plus-shaped stencil by k sigma of a Poisson + read-noise model in electrons
+ * (hence WAYNE_X_GAIN); the replacement is taken along the dispersion, never along the scan.
+ *   product j < R:  A_j[x] sums  flag_j ? repl_j : I_{j+1}  over its window
+ *   product R:      A_R[x] sums  L_R g - sum_j flag_j (I_{j+1} - repl_j)
+ * B, the sky level and the spectra follow as above (the background columns are cleaned too).  n_rejected[p] is the
+ * number of flags in product p's window; for p = R it counts (pixel, interval) pairs.  Defaults of the Python layer:
+ * k = 8, read_noise_e = 20 (sqrt(2) x 14.1 e-, the noise of a difference of two reads as the ramp kernel adds it).
+ * Not covered: hits on adjacent pixels of one interval (they shield each other) and the 7-pixel frame margin.
+ */
+typedef struct wayne_crrej_desc {
+  double k;            /* threshold in sigma: finite, > 0 */
+  double read_noise_e; /* rn (e-): finite, >= 0 */
+} wayne_crrej_desc;
+
+/* After wayne_exposure_set_extraction, before run: reject cosmic rays in the slot's extraction (r = NULL clears; upload
+ * and set_extraction clear it too).  WAYNE_E_STATE when no extraction is set on the slot; WAYNE_E_INVALID (the slot stays
+ * usable, extracting without rejection) for a bad k or read_noise_e or when WAYNE_X_GAIN is off. */
+int wayne_exposure_set_crrej(wayne_ctx *ctx, int slot, const wayne_crrej_desc *r);
+/* After wayne_exposure_wait_spectra / _download_spectra of a slot with rejection: *n_rejected [R+1], valid until the
+ * slot's spectra are fetched or the slot is uploaded again.  WAYNE_E_STATE before any fetch or without rejection. */
+int wayne_exposure_rejected(wayne_ctx *ctx, int slot, const uint32_t **n_rejected);
+/* The flag plane of the slot's last run, blocking: mask [S*S], bit j = flag_j, 0 outside the mask rows. */
+int wayne_exposure_download_crmask(wayne_ctx *ctx, int slot, uint16_t *mask);
 /* HIP-event time of the extraction's kernels while wayne_profile_enable is on, since wayne_profile_reset: launches
  * (one per extracted exposure) and total milliseconds.  wayne_profile_select's bit 8 selects it.  Synchronises. */
 int wayne_extract_profile(wayne_ctx *ctx, uint64_t *launches, double *ms);

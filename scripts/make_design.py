@@ -14,6 +14,8 @@ template, filled from ONE source file under profiles/<round>/:
     a   ab_bin_local.json     the A/B of the bin-local coordinates on one box (scripts/ab_summary.py)
     e   kernel_stats_thrower_electron.json   kernel averages of `bench.py --thrower electron` under rocprofv3
     n   visit_science_test.json    what tests/test_visit_science_gpu.py measured (negative control, injected difference)
+    x   ../extract.json       scripts/bench_extract.py (not a round's file)
+    c   ../crrej.json         scripts/bench_crrej.py (nor this)
     d   (derived)             computed here: d.traffic_over_algorithmic (t over b), and the fit lines of
                               thrower_vs_electrons.txt (d.lane_t0_us, d.lane_us_per_1e9, d.narrow_t0_us)
 so the document cannot drift from the measurements: tests/test_design_doc.py renders the template again and compares
@@ -30,7 +32,8 @@ OUT = os.path.join(ROOT, "DESIGN.md")
 FILES = {"b": "bench.json", "s": "visit_science.json", "k": "kernel_stats.json", "t": "k_ramp_traffic.json",
          "v": "valu_issue.json", "a": "ab_bin_local.json", "e": "kernel_stats_thrower_electron.json",
          "n": "visit_science_test.json",
-         "x": os.path.join("..", "extract.json")}        # (not a round's file: scripts/bench_extract.py)
+         "x": os.path.join("..", "extract.json"),        # (not a round's file: scripts/bench_extract.py)
+         "c": os.path.join("..", "crrej.json")}          # (nor this: scripts/bench_crrej.py)
 PLACEHOLDER = re.compile(r"\{\{([a-z])\.([^|*}]+)(?:\*([0-9.eE+-]+))?\|([^}]*)\}\}")
 
 

@@ -95,6 +95,10 @@ class ExtractDesc(C.Structure):
                 ("bg_col_lo", C.c_int), ("bg_col_hi", C.c_int)]
 
 
+class CrrejDesc(C.Structure):
+    _fields_ = [("k", C.c_double), ("read_noise_e", C.c_double)]
+
+
 class Profile(C.Structure):
     _fields_ = [("name", C.c_char_p * PROF_KERNELS), ("launches", C.c_uint64 * PROF_KERNELS),
                 ("ms", C.c_double * PROF_KERNELS), ("electrons", C.c_uint64)]
@@ -145,6 +149,9 @@ SYMBOLS = {
     "wayne_exposure_fetch_spectra_async": (C.c_int, [_vp, C.c_int]),
     "wayne_exposure_wait_spectra": (C.c_int, [_vp, C.c_int, C.POINTER(_dp), C.POINTER(_dp)]),
     "wayne_exposure_download_spectra": (C.c_int, [_vp, C.c_int, _vp, _vp]),
+    "wayne_exposure_set_crrej": (C.c_int, [_vp, C.c_int, C.POINTER(CrrejDesc)]),
+    "wayne_exposure_rejected": (C.c_int, [_vp, C.c_int, C.POINTER(C.POINTER(C.c_uint32))]),
+    "wayne_exposure_download_crmask": (C.c_int, [_vp, C.c_int, _vp]),
     "wayne_extract_profile": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_double)]),
     "wayne_profile_enable": (C.c_int, [_vp, C.c_int]),
     "wayne_profile_select": (C.c_int, [_vp, C.c_uint]),
@@ -266,6 +273,7 @@ class Context(object):
         self.device = device
         self._slot_meta = {}     # slot -> (K, W, R, dtype of the reads) of the descriptor uploaded last
         self._slot_src = {}      # slot -> bins of each of its contaminants
+        self._slot_crrej = set() # slots whose extraction rejects cosmic rays
         _live_contexts.add(self)
         for name, value in _knob_defaults.items():
             self.set_knob(name, value)
@@ -386,6 +394,7 @@ class Context(object):
         self.check(self._L.wayne_exposure_upload(self._h, int(slot), C.byref(desc)))
         self._slot_meta[slot] = (desc.n_samples, desc.n_wl, desc.n_reads, out_dtype_of(desc.flags))
         self._slot_src[slot] = ()
+        self._slot_crrej.discard(slot)
         sources = getattr(desc, "_sources", None)
         if sources:
             self.set_sources(slot, sources)
@@ -396,14 +405,46 @@ class Context(object):
         if extraction is not None:
             self.set_extraction(slot, extraction)
 
+    def set_crrej(self, slot, crrej):
+        """Cosmic-ray rejection of the slot's extraction: an extraction.CosmicRejection (k, read_noise) -- None clears;
+        after set_extraction, which clears it too.  See wayne_exposure_set_crrej."""
+        self._slot_crrej.discard(slot)           # (a refusal leaves the slot extracting without rejection)
+        if crrej is None:
+            self.check(self._L.wayne_exposure_set_crrej(self._h, int(slot), None))
+            return
+        self.check(self._L.wayne_exposure_set_crrej(self._h, int(slot), C.byref(crrej.desc())))
+        self._slot_crrej.add(slot)
+
+    def has_crrej(self, slot):
+        """Whether the slot's extraction rejects cosmic rays (set_crrej succeeded since its last set_extraction)."""
+        return slot in self._slot_crrej
+
+    def rejected(self, slot):
+        """n_rejected [R + 1] (uint32; a copy) of the slot's last wait_spectra / download_spectra: the flags in each
+        product's window, (pixel, interval) pairs for the last-read product."""
+        K, W, R, _ = self._slot_meta[slot]
+        pn = C.POINTER(C.c_uint32)()
+        self.check(self._L.wayne_exposure_rejected(self._h, int(slot), C.byref(pn)))
+        return np.ctypeslib.as_array(pn, shape=(R + 1,)).copy()
+
+    def download_crmask(self, slot):
+        """The flag plane [S, S] (uint16, bit j = read interval j) of the slot's last run, blocking; 0 outside the mask
+        rows."""
+        mask = np.empty((self.S, self.S), dtype=np.uint16)
+        self.check(self._L.wayne_exposure_download_crmask(self._h, int(slot), ptr(mask)))
+        return mask
+
     def set_extraction(self, slot, extraction):
         """Spectral extraction of the slot's uploaded exposure: an extraction.Extraction (row windows of the R read
-        intervals and of the last read, background columns, step mask) -- None clears.  The back half of every run of
+        intervals and of the last read, background columns, step mask; its `crrej`, if any, is set with it) -- None clears.  The back half of every run of
         the slot then forms spectra [R + 1, S] and sky [R + 1] on the device.  See wayne_exposure_set_extraction."""
+        self._slot_crrej.discard(slot)
         if extraction is None:
             self.check(self._L.wayne_exposure_set_extraction(self._h, int(slot), None))
             return
         self.check(self._L.wayne_exposure_set_extraction(self._h, int(slot), C.byref(extraction.desc())))
+        if getattr(extraction, "crrej", None) is not None:
+            self.set_crrej(slot, extraction.crrej)
 
     def fetch_spectra_async(self, slot):
         """Enqueue the copy of the slot's spectra (never its reads) into pinned host memory (returns at once)."""

@@ -12,6 +12,7 @@
 //   plan_sky             levels of the master sky, alias-table keys, which reads fit a table (k_ramp's sky draw)
 //   build_sky_alias      one Walker / Vose table of Poisson(lam)
 //   extract_desc_error   wayne_exposure_set_extraction's argument check (the windows k_extract walks stay inside the frame)
+//   crrej_desc_error     wayne_exposure_set_crrej's argument check; crrej_mask_rows: the rows k_extract_crmask writes
 //
 // Reference: the reach of the thrower bounds pyparallel_menu.c:87-108 as the device modes implement it; the trace is
 // grism.py:491-506, 779-803 (trace_coeffs, plan_consts.h); the frame offset exposure_generator.py:630-645.
@@ -444,6 +445,26 @@ inline const char* extract_desc_error(int S, int R, unsigned steps, const int* r
   }
   if (max_chunks) *max_chunks = (longest + kExtractRows - 1) / kExtractRows;
   return nullptr;
+}
+
+// wayne_exposure_set_crrej's argument check (include/wayne_hip.h: wayne_crrej_desc) against the extraction's `steps`:
+// null when valid.  The noise model is in electrons, so the gain step must be on.
+inline const char* crrej_desc_error(unsigned steps, double k, double read_noise_e) {
+  if (!(std::isfinite(k) && k > 0.)) return "k must be finite and > 0";
+  if (!(std::isfinite(read_noise_e) && read_noise_e >= 0.)) return "read_noise_e must be finite and >= 0";
+  if (!(steps & X_GAIN)) return "rejection needs WAYNE_X_GAIN: its noise model is in electrons";
+  return nullptr;
+}
+
+// The mask rows of a valid extraction plan: [min_p row_lo[p], max_p row_hi[p]) over the products that are formed.
+inline void crrej_mask_rows(int R, unsigned steps, const int* row_lo, const int* row_hi, int* lo, int* hi) {
+  const int n = (steps & X_LAST_READ) ? R + 1 : R;
+  *lo = row_lo[0];
+  *hi = row_hi[0];
+  for (int j = 1; j < n; ++j) {
+    *lo = std::min(*lo, row_lo[j]);
+    *hi = std::max(*hi, row_hi[j]);
+  }
 }
 
 }  // namespace plan

@@ -17,6 +17,21 @@
 // partial sums go to the slot's scratch [A | T][chunk][product][S]; k_extract_finish (one workgroup per product) adds
 // the chunks in ascending order, forms sky_j and writes spectra and sky.
 //
+// Cosmic-ray rejection (wayne_exposure_set_crrej; off unless asked for -- the instantiations launched without it are
+// those of the lines above).  For read interval j, I = I_{j+1}; a pixel is tested iff it lies kCrMargin pixels inside the
+// frame and in the mask rows [min_p lo_p, max_p hi_p):
+//   m8 = max of I[y+-1, x], I[y+-2, x], I[y, x+-1], I[y, x+-2],   d = I[y, x] - m8
+//   flag_j[y, x] <=> d > 0 and d d > k^2 (rn^2 + max(m8, 0))
+//   repl_j[y, x] = 0.5 (b + c), b <= c the middle two of I[y, x-2], I[y, x-1], I[y, x+1], I[y, x+2]
+//   A_j sums flag_j ? repl_j : I_{j+1};   A_R sums L_R g - sum_j flag_j (I_{j+1} - repl_j)
+// k_extract_crmask<T>: one workgroup per (64-column tile, 32-row chunk of the mask rows).  A thread keeps P_0, c1..c4, g
+// and L_{r-1} of its (at most 5) pixels of the tile and its 2-pixel halo in registers over the loop on r; I_r of the tile
+// goes to LDS (two buffers, so one barrier per read), then 4 pixels per thread are tested.  Every read plane is loaded
+// once.  Bit j of the slot's uint16 plane is flag_j; every pixel of the mask rows is stored, so a second run rewrites the
+// plane.  k_extract_rows<T, true> loads the pixel's mask word; a set bit is the rare, divergent path that forms repl_j
+// from the row neighbours' I_{j+1}.  The flags of a chunk are counted per column beside the partial sums and
+// k_extract_finish<true> adds them up: n_rejected[p], behind sky.
+//
 // The file is compiled without FMA contraction (wayne_amd/build.py), so a pixel's chain rounds as the numpy statement
 // of it does; what differs from numpy is the order of the row sums alone.
 #pragma once
@@ -44,6 +59,12 @@ struct ExtractArgs {
   double* part;                      // [2][n_chunks][R+1][S]: sums of A, then sums of T
   double* spectra;                   // [(R+1)*S]
   double* sky_out;                   // [R+1]
+  // cosmic-ray rejection (null / 0 without it)
+  uint16_t* mask;                    // [S*S]: bit j = flag_j; written on the mask rows [m_lo, m_hi) only
+  unsigned* part_n;                  // [n_chunks][R+1][S]: flags of a chunk's column
+  unsigned* n_rej;                   // [R+1]
+  int m_lo, m_hi;
+  double k2, rn2;                    // k^2, rn^2
 };
 
 // L_r of one pixel (r >= 1); `lin`: the four coefficients are in c[]
@@ -56,7 +77,115 @@ __device__ __forceinline__ double extract_linear(const ExtractArgs& a, const T* 
   return L;
 }
 
+// I_{j+1} of one pixel, everything loaded here (the rare path of a flagged pixel and of its row neighbours)
 template <class T>
+__device__ double extract_interval(const ExtractArgs& a, const T* reads, size_t SS, size_t pix, int j, bool lin, bool gain) {
+  const double p0 = (double)reads[pix];
+  double c[4] = {0., 0., 0., 0.};
+  if (lin)
+    for (int i = 0; i < 4; ++i) c[i] = (double)a.lin[i][pix];
+  const double Lh = extract_linear<T>(a, reads, SS, pix, j + 1, p0, lin, c);
+  const double Ll = j > 0 ? extract_linear<T>(a, reads, SS, pix, j, p0, lin, c) : 0.;
+  const double g = (a.steps & X_GAIN) ? (gain ? 2.35 / (double)a.pfl[pix] : 2.35) : 1.0;
+  return (Lh - Ll) * g;
+}
+
+// half the sum of the middle two of four values
+__device__ __forceinline__ double middle_two_mean(double a0, double a1, double a2, double a3) {
+  const double lo1 = fmin(a0, a1), hi1 = fmax(a0, a1), lo2 = fmin(a2, a3), hi2 = fmax(a2, a3);
+  return 0.5 * (fmax(lo1, lo2) + fmin(hi1, hi2));
+}
+
+// repl_j of a flagged pixel (it is tested, so x -+ 2 lie inside the frame)
+template <class T>
+__device__ double extract_repl(const ExtractArgs& a, const T* reads, size_t SS, size_t pix, int j, bool lin, bool gain) {
+  return middle_two_mean(extract_interval<T>(a, reads, SS, pix - 2, j, lin, gain), extract_interval<T>(a, reads, SS, pix - 1, j, lin, gain),
+                         extract_interval<T>(a, reads, SS, pix + 1, j, lin, gain), extract_interval<T>(a, reads, SS, pix + 2, j, lin, gain));
+}
+
+constexpr int kCrW = kCrTileCols + 2 * kCrHalo, kCrH = kCrTileRows + 2 * kCrHalo;   // the tile and its halo: 68 x 36
+constexpr int kCrOwn = (kCrW * kCrH + kExtractThreads - 1) / kExtractThreads;        // pixels a thread carries: 5
+static_assert(kCrTileCols == 64 && kCrTileRows % kExtractWaves == 0, "k_extract_crmask: a wave tests rows of 64 pixels");
+
+template <class T>
+__global__ void __launch_bounds__(kExtractThreads) k_extract_crmask(ExtractArgs a) {
+  const int S = a.S, R = a.R, tid = (int)threadIdx.x;
+  const size_t SS = (size_t)S * S;
+  const T* reads = (const T*)a.reads;
+  const int x0 = (int)blockIdx.x * kCrTileCols - kCrHalo;
+  const int y_lo = a.m_lo + (int)blockIdx.y * kCrTileRows, y_hi = min(y_lo + kCrTileRows, a.m_hi);   // the rows stored
+  const int y0 = y_lo - kCrHalo;
+  const bool lin = (a.steps & X_LINEARISE) && a.lin[0];
+  const bool dark = (a.steps & X_DARK) && a.dark;
+  __shared__ double sh[2][kCrH * kCrW];
+  // the thread's pixels of tile + halo: element tid + i * kExtractThreads, row-major
+  size_t pix[kCrOwn];
+  bool in[kCrOwn];
+  double p0[kCrOwn], g[kCrOwn], Lp[kCrOwn];
+  float cf[kCrOwn][4];               // (float32 planes: promoted at use, exactly)
+#pragma unroll
+  for (int i = 0; i < kCrOwn; ++i) {
+    const int e = tid + i * kExtractThreads, ty = e / kCrW, tx = e - ty * kCrW;
+    const int y = y0 + ty, x = x0 + tx;
+    in[i] = e < kCrW * kCrH && y >= 0 && y < min(y_hi + kCrHalo, S) && x >= 0 && x < S;
+    pix[i] = in[i] ? (size_t)y * S + x : 0;
+    p0[i] = 0.; g[i] = 2.35; Lp[i] = 0.;
+    for (int q = 0; q < 4; ++q) cf[i][q] = 0.f;
+    if (in[i]) {
+      p0[i] = (double)reads[pix[i]];
+      if (lin)
+        for (int q = 0; q < 4; ++q) cf[i][q] = a.lin[q][pix[i]];
+      if (a.pfl) g[i] = 2.35 / (double)a.pfl[pix[i]];
+    }
+  }
+  // the thread's tested pixels: rows wave, wave + 8, ... of the tile, column lane
+  const int wave = tid >> 6, lane = tid & 63;
+  const int x = x0 + kCrHalo + lane;
+  const bool x_tested = x >= kCrMargin && x < S - kCrMargin;
+  constexpr int kTest = kCrTileRows / kExtractWaves;
+  unsigned bits[kTest];
+#pragma unroll
+  for (int i = 0; i < kTest; ++i) bits[i] = 0u;
+  for (int r = 1; r <= R; ++r) {
+    double* I = sh[r & 1];
+#pragma unroll
+    for (int i = 0; i < kCrOwn; ++i) {
+      const int e = tid + i * kExtractThreads;
+      if (e < kCrW * kCrH) {
+        double v = 0.;
+        if (in[i]) {
+          const double D = (double)reads[(size_t)r * SS + pix[i]] - p0[i];
+          double L = lin ? D * (1.0 + (double)cf[i][0] + D * ((double)cf[i][1] + D * ((double)cf[i][2] + (double)cf[i][3] * D))) : D;
+          if (dark) L -= (double)a.dark[(size_t)(r - 1) * SS + pix[i]];
+          v = (L - Lp[i]) * g[i];
+          Lp[i] = L;
+        }
+        I[e] = v;
+      }
+    }
+    __syncthreads();       // (one barrier per read: the next read fills the other buffer)
+#pragma unroll
+    for (int i = 0; i < kTest; ++i) {
+      const int ty = kCrHalo + wave + i * kExtractWaves, y = y0 + ty;
+      if (x_tested && y < y_hi && y >= kCrMargin && y < S - kCrMargin) {
+        const double* at = I + ty * kCrW + kCrHalo + lane;
+        double m8 = fmax(fmax(at[-kCrW], at[kCrW]), fmax(at[-2 * kCrW], at[2 * kCrW]));
+        m8 = fmax(m8, fmax(fmax(at[-1], at[1]), fmax(at[-2], at[2])));
+        const double d = at[0] - m8;
+        if (d > 0. && d * d > a.k2 * (a.rn2 + fmax(m8, 0.))) bits[i] |= 1u << (r - 1);
+      }
+    }
+  }
+  if (x < S) {
+#pragma unroll
+    for (int i = 0; i < kTest; ++i) {
+      const int y = y_lo + wave + i * kExtractWaves;
+      if (y < y_hi) a.mask[(size_t)y * S + x] = (uint16_t)bits[i];
+    }
+  }
+}
+
+template <class T, bool CR>
 __global__ void __launch_bounds__(kExtractThreads) k_extract_rows(ExtractArgs a) {
   int p = 0;
   while (p < a.R && (int)blockIdx.y >= a.first_chunk[p + 1]) ++p;     // (wave-uniform: at most R steps)
@@ -73,6 +202,7 @@ __global__ void __launch_bounds__(kExtractThreads) k_extract_rows(ExtractArgs a)
   const bool lin = (a.steps & X_LINEARISE) && a.lin[0];
   const bool gain = (a.steps & X_GAIN) && a.pfl, sky = (a.steps & X_SKY) && a.sky;
   double sA = 0., sT = 0.;
+  unsigned n_flag = 0u;
   if (x < S) {
     for (int y = lo + wave; y < hi; y += kExtractWaves) {
       const size_t pix = (size_t)y * S + x;
@@ -83,13 +213,32 @@ __global__ void __launch_bounds__(kExtractThreads) k_extract_rows(ExtractArgs a)
       const double Lh = extract_linear<T>(a, reads, SS, pix, r_hi, p0, lin, c);
       const double Ll = r_lo > 0 ? extract_linear<T>(a, reads, SS, pix, r_lo, p0, lin, c) : 0.;
       const double g = (a.steps & X_GAIN) ? (gain ? 2.35 / (double)a.pfl[pix] : 2.35) : 1.0;
-      sA += (Lh - Ll) * g;
+      if constexpr (CR) {
+        double v = (Lh - Ll) * g;
+        const unsigned m = a.mask[pix];
+        if (p < a.R) {
+          if ((m >> p) & 1u) { v = extract_repl<T>(a, reads, SS, pix, p, lin, gain); ++n_flag; }
+        } else if (m) {
+          double corr = 0.;
+          for (unsigned b = m; b; b &= b - 1u) {               // the set bits, ascending
+            const int j = __ffs((int)b) - 1;
+            corr += extract_interval<T>(a, reads, SS, pix, j, lin, gain) - extract_repl<T>(a, reads, SS, pix, j, lin, gain);
+            ++n_flag;
+          }
+          v -= corr;
+        }
+        sA += v;
+      } else {
+        sA += (Lh - Ll) * g;
+      }
       if (sky) sT += (double)a.sky[pix];
     }
   }
   __shared__ double sh[2][kExtractWaves][64];
   sh[0][wave][lane] = sA;
   sh[1][wave][lane] = sT;
+  __shared__ unsigned sh_n[CR ? kExtractWaves : 1][64];
+  if constexpr (CR) sh_n[wave][lane] = n_flag;
   __syncthreads();
   if (wave == 0 && x < S) {
     double tA = sh[0][0][lane], tT = sh[1][0][lane];
@@ -98,15 +247,22 @@ __global__ void __launch_bounds__(kExtractThreads) k_extract_rows(ExtractArgs a)
     const size_t at = ((size_t)chunk * NP + p) * S + x;
     a.part[at] = tA;
     a.part[(size_t)a.n_chunks * NP * S + at] = tT;
+    if constexpr (CR) {
+      unsigned n = 0u;
+      for (int w = 0; w < kExtractWaves; ++w) n += sh_n[w][lane];
+      a.part_n[at] = n;
+    }
   }
 }
 
+template <bool CR>
 __global__ void __launch_bounds__(kExtractThreads) k_extract_finish(ExtractArgs a) {
   const int p = (int)blockIdx.x, S = a.S, NP = a.R + 1;
   const int tid = (int)threadIdx.x;
   if (p == a.R && !(a.steps & X_LAST_READ)) {            // the last-read product was not asked for: zeros
     for (int x = tid; x < S; x += kExtractThreads) a.spectra[(size_t)p * S + x] = 0.;
     if (tid == 0) a.sky_out[p] = 0.;
+    if (CR && tid == 0) a.n_rej[p] = 0u;
     return;
   }
   __shared__ double shA[kExtractMaxS], shB[kExtractMaxS];
@@ -115,16 +271,20 @@ __global__ void __launch_bounds__(kExtractThreads) k_extract_finish(ExtractArgs 
   const int rows = a.row_hi[p] - a.row_lo[p];
   const int chunks = (rows + kExtractRows - 1) / kExtractRows;
   const size_t half = (size_t)a.n_chunks * NP * S;
+  unsigned n_flag = 0u;
   for (int x = tid; x < S; x += kExtractThreads) {
     double A = 0., T = 0.;
     for (int c = 0; c < chunks; ++c) {                   // ascending chunks
       const size_t at = ((size_t)c * NP + p) * S + x;
       A += a.part[at];
       T += a.part[half + at];
+      if constexpr (CR) n_flag += a.part_n[at];
     }
     shA[x] = A;
     shB[x] = a.scale[p] * T;
   }
+  __shared__ unsigned shN[CR ? kExtractThreads : 1];
+  if constexpr (CR) shN[tid] = n_flag;
   __syncthreads();
   if (tid < 64) {
     double sa = 0., sb = 0.;
@@ -138,6 +298,11 @@ __global__ void __launch_bounds__(kExtractThreads) k_extract_finish(ExtractArgs 
     for (int l = 0; l < 64; ++l) { sa += shR[0][l]; sb += shR[1][l]; }
     sh_sky = ((a.steps & X_SKY) && sb != 0.) ? sa / sb : 0.;
     a.sky_out[p] = sh_sky;
+    if constexpr (CR) {
+      unsigned n = 0u;
+      for (int t = 0; t < kExtractThreads; ++t) n += shN[t];
+      a.n_rej[p] = n;
+    }
   }
   __syncthreads();
   const double s = sh_sky;

@@ -14,6 +14,7 @@
 //                                  clip, reference pixels, zero read, read noise                          (A13-A15)
 //   k_extract.h     k_extract_rows / k_extract_finish   opt-in: column spectra per read interval from the reads
 //                                  just written (linearise, dark, gain, row sums, sky level), no reference counterpart
+//                   k_extract_crmask                    opt-in on top of it: the cosmic-ray flag plane of the difference images
 //
 // "A<n>" are the row ids of SURVEY.md section 8(a); reference file:line
 // citations are next to each formula.

@@ -47,6 +47,10 @@ constexpr int kExtractMaxS = 1024;                // widest frame (k_extract_fin
 // wayne_extract_desc.steps (include/wayne_hip.h: WAYNE_X_*)
 constexpr unsigned X_LINEARISE = 1u << 0, X_DARK = 1u << 1, X_GAIN = 1u << 2, X_SKY = 1u << 3, X_LAST_READ = 1u << 4;
 constexpr unsigned X_ALL = X_LINEARISE | X_DARK | X_GAIN | X_SKY | X_LAST_READ;
+// cosmic-ray rejection of the extraction (k_extract_crmask; validated by plan::crrej_desc_error)
+constexpr int kCrMargin = 7;                      // pixels of the frame's edge that are never tested
+constexpr int kCrHalo = 2;                        // reach of the plus-shaped stencil
+constexpr int kCrTileCols = 64, kCrTileRows = kExtractRows;   // pixels of a k_extract_crmask workgroup
 
 WAYNE_HD void trace_coeffs(const GrismDev& g, double x_ref, double y_ref, double* o) {
   // o = {m_t, c_t, m_w, c_w, m_wl, c_wl}

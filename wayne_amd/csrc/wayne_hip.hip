@@ -209,6 +209,15 @@ struct Slot : SourceState {
   DevBuf ex_part, ex_out;
   PinnedBuf ex_pinned;
   Misc* ex_pinned_misc = nullptr;
+  // cosmic-ray rejection of the extraction (wayne_exposure_set_crrej; cleared by upload and set_extraction): the flag
+  // plane [S*S] uint16, the chunks' flag counts [chunks][R+1][S], and n_rejected [R+1] behind sky in ex_out.  `ex_rej`:
+  // the counts the last wait_spectra / download_spectra brought back (null before any)
+  bool crrej_on = false;
+  double cr_k = 0., cr_rn = 0.;
+  int cr_lo = 0, cr_hi = 0;          // the mask rows
+  DevBuf cr_mask, ex_part_n;
+  const uint32_t* ex_rej = nullptr;
+  std::vector<uint32_t> ex_rej_host;
   // staging arena of the descriptor's arrays: uploads are enqueued from here, so
   // wayne_exposure_upload returns without waiting for the slot's stream to drain
   StageArena stage;
@@ -638,6 +647,14 @@ int launch_extract(wayne_ctx* c, Slot& s) {
   a.part = s.ex_part.as<double>();
   a.spectra = s.ex_out.as<double>();
   a.sky_out = s.ex_out.as<double>() + (size_t)(R + 1) * S;
+  const bool cr = s.crrej_on;
+  if (cr) {
+    a.mask = s.cr_mask.as<uint16_t>();
+    a.part_n = s.ex_part_n.as<unsigned>();
+    a.n_rej = (unsigned*)(a.sky_out + (R + 1));
+    a.m_lo = s.cr_lo; a.m_hi = s.cr_hi;
+    a.k2 = s.cr_k * s.cr_k; a.rn2 = s.cr_rn * s.cr_rn;
+  }
   const int products = (a.steps & X_LAST_READ) ? R + 1 : R;
   for (int p = 0; p <= kExtractProducts; ++p) a.first_chunk[p] = 0;
   for (int p = 0; p < products; ++p)
@@ -646,11 +663,27 @@ int launch_extract(wayne_ctx* c, Slot& s) {
   const dim3 grid((unsigned)((S + 63) / 64), (unsigned)a.first_chunk[products]);
   ProfScope ps(c, PK_EXTRACT);
   const int out = out_kind(s.d.flags);
-  if (out == 1) hipLaunchKernelGGL((k_extract_rows<double>), grid, dim3(kExtractThreads), 0, c->stream, a);
-  else if (out == 2) hipLaunchKernelGGL((k_extract_rows<uint16_t>), grid, dim3(kExtractThreads), 0, c->stream, a);
-  else hipLaunchKernelGGL((k_extract_rows<float>), grid, dim3(kExtractThreads), 0, c->stream, a);
+  const dim3 block(kExtractThreads), products_grid((unsigned)(R + 1));
+  if (cr) {
+    // the flag plane first: tiles of the mask rows
+    const dim3 tiles((unsigned)((S + kCrTileCols - 1) / kCrTileCols), (unsigned)((a.m_hi - a.m_lo + kCrTileRows - 1) / kCrTileRows));
+    if (out == 1) hipLaunchKernelGGL((k_extract_crmask<double>), tiles, block, 0, c->stream, a);
+    else if (out == 2) hipLaunchKernelGGL((k_extract_crmask<uint16_t>), tiles, block, 0, c->stream, a);
+    else hipLaunchKernelGGL((k_extract_crmask<float>), tiles, block, 0, c->stream, a);
+    HIP_TRY(c, hipGetLastError());
+    if (out == 1) hipLaunchKernelGGL((k_extract_rows<double, true>), grid, block, 0, c->stream, a);
+    else if (out == 2) hipLaunchKernelGGL((k_extract_rows<uint16_t, true>), grid, block, 0, c->stream, a);
+    else hipLaunchKernelGGL((k_extract_rows<float, true>), grid, block, 0, c->stream, a);
+    HIP_TRY(c, hipGetLastError());
+    hipLaunchKernelGGL(k_extract_finish<true>, products_grid, block, 0, c->stream, a);
+    HIP_TRY(c, hipGetLastError());
+    return WAYNE_OK;
+  }
+  if (out == 1) hipLaunchKernelGGL((k_extract_rows<double, false>), grid, block, 0, c->stream, a);
+  else if (out == 2) hipLaunchKernelGGL((k_extract_rows<uint16_t, false>), grid, block, 0, c->stream, a);
+  else hipLaunchKernelGGL((k_extract_rows<float, false>), grid, block, 0, c->stream, a);
   HIP_TRY(c, hipGetLastError());
-  hipLaunchKernelGGL(k_extract_finish, dim3((unsigned)(R + 1)), dim3(kExtractThreads), 0, c->stream, a);
+  hipLaunchKernelGGL(k_extract_finish<false>, products_grid, block, 0, c->stream, a);
   HIP_TRY(c, hipGetLastError());
   return WAYNE_OK;
 }
@@ -1131,6 +1164,8 @@ int wayne_exposure_upload(wayne_ctx* c, int slot, const wayne_exposure_desc* d) 
   s.traps_on = false;        // ... and no charge traps until wayne_exposure_set_traps says so
   s.extract_on = false;      // ... and no spectral extraction until wayne_exposure_set_extraction says so
   s.ex_pinned_misc = nullptr;
+  s.crrej_on = false;        // ... whose cosmic-ray rejection waits for wayne_exposure_set_crrej
+  s.ex_rej = nullptr;
   int rc;
   const size_t KW = (size_t)K * W;
   {
@@ -1891,6 +1926,8 @@ int wayne_exposure_set_extraction(wayne_ctx* c, int slot, const wayne_extract_de
   if (!s.uploaded) return fail(c, WAYNE_E_STATE, "set_extraction: slot not uploaded");
   s.extract_on = false;           // from here on a refusal leaves the slot usable, without extraction
   s.ex_pinned_misc = nullptr;
+  s.crrej_on = false;
+  s.ex_rej = nullptr;
   if (!x) return WAYNE_OK;
   int chunks = 0;
   if (const char* why = plan::extract_desc_error(c->S, s.R, x->steps, x->row_lo, x->row_hi, x->bg_col_lo, x->bg_col_hi, &chunks))
@@ -1898,15 +1935,39 @@ int wayne_exposure_set_extraction(wayne_ctx* c, int slot, const wayne_extract_de
   (void)hipSetDevice(c->device);
   const size_t NP = (size_t)s.R + 1, S = (size_t)c->S;
   HIP_TRY(c, s.ex_part.reserve((size_t)2 * chunks * NP * S * sizeof(double)));
-  HIP_TRY(c, s.ex_out.reserve(NP * (S + 1) * sizeof(double)));
+  HIP_TRY(c, s.ex_out.reserve(NP * (S + 1) * sizeof(double) + NP * sizeof(uint32_t)));   // (room for set_crrej's counts)
   s.ex = *x;
   s.ex_chunks = chunks;
   s.extract_on = true;
   return WAYNE_OK;
 }
 
-// bytes of a slot's spectra block: spectra [(R+1)*S], then sky [R+1]
-static size_t spectra_bytes(const wayne_ctx* c, const Slot& s) { return (size_t)(s.R + 1) * ((size_t)c->S + 1) * sizeof(double); }
+int wayne_exposure_set_crrej(wayne_ctx* c, int slot, const wayne_crrej_desc* r) {
+  if (!c) return WAYNE_E_INVALID;
+  if (slot < 0 || slot >= kSlots) return fail(c, WAYNE_E_INVALID, "set_crrej: slot");
+  Slot& s = c->slots[slot];
+  if (!s.uploaded || !s.extract_on) return fail(c, WAYNE_E_STATE, "set_crrej: no extraction set for the slot");
+  s.crrej_on = false;             // from here on a refusal leaves the slot extracting, without rejection
+  s.ex_rej = nullptr;
+  s.ex_pinned_misc = nullptr;     // (a fetched block has the other layout)
+  if (!r) return WAYNE_OK;
+  if (const char* why = plan::crrej_desc_error(s.ex.steps, r->k, r->read_noise_e))
+    return fail(c, WAYNE_E_INVALID, std::string("set_crrej: ") + why);
+  (void)hipSetDevice(c->device);
+  const size_t NP = (size_t)s.R + 1, S = (size_t)c->S;
+  HIP_TRY(c, s.cr_mask.reserve(S * S * sizeof(uint16_t)));
+  HIP_TRY(c, s.ex_part_n.reserve((size_t)s.ex_chunks * NP * S * sizeof(unsigned)));
+  plan::crrej_mask_rows(s.R, s.ex.steps, s.ex.row_lo, s.ex.row_hi, &s.cr_lo, &s.cr_hi);
+  s.cr_k = r->k;
+  s.cr_rn = r->read_noise_e;
+  s.crrej_on = true;
+  return WAYNE_OK;
+}
+
+// bytes of a slot's spectra block: spectra [(R+1)*S], then sky [R+1]; with rejection, n_rejected [R+1] (uint32) behind them
+static size_t spectra_bytes(const wayne_ctx* c, const Slot& s) {
+  return (size_t)(s.R + 1) * ((size_t)c->S + 1) * sizeof(double) + (s.crrej_on ? (size_t)(s.R + 1) * sizeof(uint32_t) : 0);
+}
 
 int wayne_exposure_fetch_spectra_async(wayne_ctx* c, int slot) {
   if (!c) return WAYNE_E_INVALID;
@@ -1938,6 +1999,7 @@ int wayne_exposure_wait_spectra(wayne_ctx* c, int slot, double** spectra, double
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   *spectra = (double*)s.ex_pinned.p;
   *sky = (double*)s.ex_pinned.p + (size_t)(s.R + 1) * c->S;
+  s.ex_rej = s.crrej_on ? (const uint32_t*)(*sky + (s.R + 1)) : nullptr;
   bool reran = false;                        // (the status word came with the spectra)
   int rc = look_at_status(c, slot, s.ex_pinned_misc, wayne_exposure_run, &reran);
   if (rc || !reran) return rc;
@@ -1958,8 +2020,16 @@ int wayne_exposure_download_spectra(wayne_ctx* c, int slot, double* spectra, dou
   auto copy = [&]() -> int {
     HIP_TRY(c, hipMemcpyAsync(spectra, s.ex_out.p, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipMemcpyAsync(sky, s.ex_out.as<double>() + n, (size_t)(s.R + 1) * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (s.crrej_on)
+      HIP_TRY(c, hipMemcpyAsync(s.ex_rej_host.data(), s.ex_out.as<double>() + n + (s.R + 1), (size_t)(s.R + 1) * sizeof(uint32_t),
+                                hipMemcpyDeviceToHost, c->stream));
     return WAYNE_OK;
   };
+  s.ex_rej = nullptr;
+  if (s.crrej_on) {
+    s.ex_rej_host.assign((size_t)s.R + 1, 0u);
+    s.ex_rej = s.ex_rej_host.data();
+  }
   int rc = copy();
   if (rc) return rc;
   bool reran = false;
@@ -1967,6 +2037,31 @@ int wayne_exposure_download_spectra(wayne_ctx* c, int slot, double* spectra, dou
   if (rc || !reran) return rc;
   if ((rc = copy())) return rc;
   return look_at_status(c, slot, nullptr);
+}
+
+int wayne_exposure_rejected(wayne_ctx* c, int slot, const uint32_t** n_rejected) {
+  if (!c || !n_rejected) return WAYNE_E_INVALID;
+  if (slot < 0 || slot >= kSlots) return fail(c, WAYNE_E_INVALID, "rejected: slot");
+  Slot& s = c->slots[slot];
+  if (!s.uploaded || !s.extract_on || !s.crrej_on) return fail(c, WAYNE_E_STATE, "rejected: no rejection set for the slot");
+  if (!s.ex_rej) return fail(c, WAYNE_E_STATE, "rejected: wait_spectra or download_spectra first");
+  *n_rejected = s.ex_rej;
+  return WAYNE_OK;
+}
+
+int wayne_exposure_download_crmask(wayne_ctx* c, int slot, uint16_t* mask) {
+  if (!c || !mask) return WAYNE_E_INVALID;
+  if (slot < 0 || slot >= kSlots) return fail(c, WAYNE_E_INVALID, "download_crmask: slot");
+  Slot& s = c->slots[slot];
+  if (!s.uploaded || !s.extract_on || !s.crrej_on) return fail(c, WAYNE_E_STATE, "download_crmask: no rejection set for the slot");
+  (void)hipSetDevice(c->device);
+  use_slot_stream(c, slot);
+  const size_t S = (size_t)c->S;
+  std::memset(mask, 0, S * S * sizeof(uint16_t));
+  HIP_TRY(c, hipMemcpyAsync(mask + (size_t)s.cr_lo * S, s.cr_mask.as<uint16_t>() + (size_t)s.cr_lo * S,
+                            (size_t)(s.cr_hi - s.cr_lo) * S * sizeof(uint16_t), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return WAYNE_OK;
 }
 
 int wayne_extract_profile(wayne_ctx* c, uint64_t* launches, double* ms) {

@@ -123,7 +123,8 @@ class ExposureGenerator(object):
                        clip_values_det_limits=True, add_read_noise=True, add_stellar_noise=True,
                        add_initial_bias=True, progress_bar=None, threads=2,
                        rng_mode=_lib.RNG_SPLIT, out_dtype=np.float32, reference_quirks=False,
-                       record=None, exact_samplers=False, contaminants=None, charge_traps=None, extraction=None):
+                       record=None, exact_samplers=False, contaminants=None, charge_traps=None, extraction=None,
+                       crrej=None):
         """Generate a spatially scanned exposure (exposure_generator.py:178-405).
 
         Extra keywords (not in the reference): `rng_mode` -- RNG_SPLIT (default:
@@ -153,14 +154,16 @@ class ExposureGenerator(object):
         traps then start every pixel at `initial`); `extraction` -- column spectra formed on the device behind the reads
         (extraction.Extraction: a plan as it is; True or an extraction.ExtractionOptions: the default plan for this
         exposure's star position and scan; staring_frame passes it on too): the returned Exposure then carries
-        `spectra` [R + 1, S] and `sky` [R + 1] beside its reads.
+        `spectra` [R + 1, S] and `sky` [R + 1] beside its reads; `crrej` -- cosmic-ray rejection of that extraction
+        (True or an extraction.CosmicRejection; it replaces the `crrej` the extraction carries): the Exposure then
+        carries `rejected` [R + 1] too.
         """
         eng, desc, start_time = self._host_half(
             x_ref, y_ref, x_jitter, y_jitter, wl, stellar_flux, planet_signal, scan_speed, sample_rate,
             sample_mid_points, sample_durations, read_index, ssv_generator, noise_mean, noise_std, add_dark,
             add_flat, cosmic_rate, sky_background, scale_factor, add_gain_variations, add_non_linear,
             clip_values_det_limits, add_read_noise, add_stellar_noise, add_initial_bias, progress_bar, threads,
-            rng_mode, out_dtype, reference_quirks, exact_samplers, contaminants, charge_traps, extraction)
+            rng_mode, out_dtype, reference_quirks, exact_samplers, contaminants, charge_traps, extraction, crrej)
         if record is None and desc._extraction is None:
             reads = eng.ctx.synthesize(desc)
         else:
@@ -173,14 +176,18 @@ class ExposureGenerator(object):
             reads = eng.ctx.download(0)
         frame = self._fill_exposure(reads, start_time)
         if desc._extraction is not None:
-            self._fill_spectra(*eng.ctx.download_spectra(0))
+            spectra, sky = eng.ctx.download_spectra(0)
+            self._fill_spectra(spectra, sky, eng.ctx.rejected(0) if desc._extraction.crrej is not None else None)
         return frame
 
-    def _fill_spectra(self, spectra, sky):
+    def _fill_spectra(self, spectra, sky, rejected=None):
         """The device's extraction of this generator's exposure -> Exposure.spectra [R + 1, S] / Exposure.sky [R + 1]
-        (and Exposure.extraction, the plan they were formed with)."""
+        (and Exposure.extraction, the plan they were formed with; Exposure.rejected [R + 1] when it rejects cosmic
+        rays)."""
         self.exposure.spectra, self.exposure.sky = spectra, sky
         self.exposure.extraction = self.extraction_plan
+        if rejected is not None:
+            self.exposure.rejected = rejected
         return self.exposure
 
     def _fill_exposure(self, reads, start_time=None):
@@ -206,7 +213,8 @@ class ExposureGenerator(object):
                    clip_values_det_limits=True, add_read_noise=True, add_stellar_noise=True,
                    add_initial_bias=True, progress_bar=None, threads=2,
                    rng_mode=_lib.RNG_SPLIT, out_dtype=np.float32, reference_quirks=False,
-                   exact_samplers=False, contaminants=None, charge_traps=None, extraction=None):
+                   exact_samplers=False, contaminants=None, charge_traps=None, extraction=None,
+                       crrej=None):
         """scanning_frame's arguments -> (engine, descriptor, start time): the mode's engine (cached after its first
         use) and build_descriptor.  No GPU call once the engine exists."""
         start_time = time.time()
@@ -217,7 +225,7 @@ class ExposureGenerator(object):
             sample_mid_points, sample_durations, read_index, ssv_generator, noise_mean, noise_std, add_dark,
             add_flat, cosmic_rate, sky_background, scale_factor, add_gain_variations, add_non_linear,
             clip_values_det_limits, add_read_noise, add_stellar_noise, add_initial_bias, progress_bar, threads,
-            rng_mode, out_dtype, reference_quirks, exact_samplers, contaminants, charge_traps, extraction)
+            rng_mode, out_dtype, reference_quirks, exact_samplers, contaminants, charge_traps, extraction, crrej)
         return eng, desc, start_time
 
     def prepare(self, *args, staring=False, **kw):
@@ -238,7 +246,8 @@ class ExposureGenerator(object):
                          clip_values_det_limits=True, add_read_noise=True, add_stellar_noise=True,
                          add_initial_bias=True, progress_bar=None, threads=2,
                          rng_mode=_lib.RNG_SPLIT, out_dtype=np.float32, reference_quirks=False,
-                         exact_samplers=False, contaminants=None, charge_traps=None, extraction=None):
+                         exact_samplers=False, contaminants=None, charge_traps=None, extraction=None,
+                       crrej=None):
         """The host half of scanning_frame: sample timing, scan positions, SSV,
         jitter / seed draws, spectrum crop (exposure_generator.py:247-334) ->
         one wayne_exposure_desc for the device.  Pure host code (`eng` may be
@@ -355,7 +364,7 @@ class ExposureGenerator(object):
             eng.check_descriptor(sub_scale)
         S = (1014 if self.SUBARRAY == 1024 else self.SUBARRAY) + 10
         self.extraction_plan = _extraction.for_exposure(extraction, self.grism, s_wl, x_ref, y_ref, scan_speed,
-                                                        self.read_times, sub_scale, S)
+                                                        self.read_times, sub_scale, S, crrej)
         self._read_dt = read_dt
         self._host_vectors = {"x_ref": s_x, "y_ref": s_y, "dur": s_dur, "seeds": s_rand_seeds, "read": sample_read}
         return _lib.make_desc(

@@ -61,7 +61,9 @@ class Observation(object):
         # frame_options["extraction"] (True, an extraction.ExtractionOptions or an extraction.Extraction; CLI: --spectra /
         # --spectra-only): the device extracts every exposure's column spectra behind its reads; run_observation keeps
         # them in `spectra_result` and writes them to `spectra_out` (an .npz path) when that is set.  `spectra_only`:
-        # the reads are neither copied from the device nor written.
+        # the reads are neither copied from the device nor written.  frame_options["crrej"] (True or an
+        # extraction.CosmicRejection; CLI: --reject-cosmics) rejects cosmic rays in that extraction:
+        # `spectra_result["rejected"]` and the .npz's n_rejected then hold each exposure's flag counts.
         self.frame_options = {"out_dtype": np.float32}
         self.spectra_out = None
         self.spectra_only = False
@@ -343,7 +345,7 @@ class Observation(object):
         from .exposure import FitsWriterPool
         from .pipeline import run_pipelined
         pool = FitsWriterPool() if write_fits_raw else None
-        got_spectra = []              # (index, spectra, sky, plan, x_ref, y_ref) of every exposure, in delivery order
+        got_spectra = []              # (index, spectra, sky, plan, x_ref, y_ref, n_rejected or None) of every exposure, in delivery order
 
         def prepare(i):
             gen = self._generate_exposure(self.exp_start_times[i], i + 1, write_fits=False, prepare_only=True)
@@ -354,8 +356,9 @@ class Observation(object):
             if extraction is not None:
                 reads, spectra, sky = reads
                 spectra, sky = np.array(spectra), np.array(sky)           # (copies: the pinned buffer is reused)
-                got_spectra.append((i, spectra, sky, gen.extraction_plan, gen.exp_info["x_ref"], gen.exp_info["y_ref"]))
-                frame = gen._fill_spectra(spectra, sky)
+                got_spectra.append((i, spectra, sky, gen.extraction_plan, gen.exp_info["x_ref"], gen.exp_info["y_ref"],
+                                    ctx.rejected))
+                frame = gen._fill_spectra(spectra, sky, ctx.rejected)
             if reads is not None:
                 frame = gen._fill_exposure(np.array(reads), gen._prepared[2])     # (a copy: the pinned buffer is reused)
             if pool is not None:
@@ -390,6 +393,8 @@ class Observation(object):
             y_ref=np.array([g[5] for g in got], dtype=float),
             read_times=np.asarray(self.detector.get_read_times(self.NSAMP, self.SUBARRAY, self.SAMPSEQ), dtype=float),
             exp_start=np.asarray(self.exp_start_times, dtype=float)[idx] if idx else np.zeros(0))
+        if got and all(g[6] is not None for g in got):        # extracted with cosmic-ray rejection: the flag counts
+            self.spectra_result["rejected"] = np.array([g[6] for g in got], dtype=np.uint32)
         if not self.spectra_out:
             return None
         path = self.spectra_out
@@ -399,7 +404,7 @@ class Observation(object):
         r = self.spectra_result
         with open(path, "wb") as f:
             _extraction.save_npz(f, r["spectra"], r["sky"], r["exposure_index"], r["plans"], r["x_ref"], r["y_ref"],
-                                 r["read_times"], r["exp_start"])
+                                 r["read_times"], r["exp_start"], rejected=r.get("rejected"))
         return path
 
     @staticmethod

@@ -1,7 +1,7 @@
 """Command line: generate a visit from a YAML parameter file.
 
     python -m wayne_amd.run_visit -p <parameter_file> [--calibration DIR] [--device N] [--max-exposures M] [--gpus G] [--resume]
-                                  [--spectra OUT.npz | --spectra-only OUT.npz]
+                                  [--spectra OUT.npz | --spectra-only OUT.npz] [--reject-cosmics [K]]
 
 Accepts the reference's parameter files (wayne/run_visit.py:1-9, example
 examples/hd209458b_12181_simulation_parameters.yml): sections `general`
@@ -27,7 +27,10 @@ examples/hd209458b_12181_simulation_parameters.yml): sections `general`
     and they are written to OUT.npz beside the _raw files: spectra [n, NSAMP, S], sky [n, NSAMP], exposure_index, row_lo,
     row_hi, bg_cols, x_ref, y_ref, read_times, exp_start.  `--spectra-only OUT.npz`: the same file, no _raw files, and
     the reads never leave the device.  Neither goes with --resume.  With --gpus G > 1 each rank writes its own file,
-    `.rankNN` before the extension; they are not merged;
+    `.rankNN` before the extension; they are not merged.  `--reject-cosmics [K]` (with either): cosmic rays are
+    rejected on the difference images first, K sigma (default 8) above a pixel's stencil neighbours; OUT.npz then also
+    holds n_rejected [n, NSAMP] -- the pixels replaced in each read interval's window and, last, the (pixel, interval)
+    pairs corrected in the last-read product -- crrej_k and crrej_read_noise;
   * `--gpus G`: the process starts G rank processes itself (one per GPU of this node, before anything touches a
     GPU) and waits for them; under an external launcher (WORLD_SIZE / RANK set, one process per GPU) it is one
     rank.  Each rank generates its round-robin share of the exposures (observation.py:403-405 is the axis) on the
@@ -185,7 +188,16 @@ def run(argv=None):
                               "the _raw files")
     spectra.add_argument("--spectra-only", metavar="OUT.npz", default=None,
                          help="... and write no _raw files: the reads never leave the device")
+    ap.add_argument("--reject-cosmics", metavar="K", nargs="?", type=float, const=8.0, default=None,
+                    help="with --spectra / --spectra-only: reject cosmic rays on the difference images before the column "
+                         "sums, K sigma (default 8) above the largest stencil neighbour; OUT.npz then also holds n_rejected, "
+                         "crrej_k and crrej_read_noise")
     args = ap.parse_args(argv)
+    if args.reject_cosmics is not None:
+        if not (args.spectra or args.spectra_only):
+            raise SystemExit("--reject-cosmics needs --spectra or --spectra-only")
+        if not (np.isfinite(args.reject_cosmics) and args.reject_cosmics > 0):
+            raise SystemExit("--reject-cosmics: K must be finite and > 0")
     if args.resume and (args.spectra or args.spectra_only):
         raise SystemExit("--spectra / --spectra-only cannot be combined with --resume (a skipped exposure has no spectra)")
     if args.gpus < 1 or args.ranks_per_gpu < 1:
@@ -239,6 +251,9 @@ def run(argv=None):
         obs.frame_options["out_dtype"] = np.uint16
     if args.spectra or args.spectra_only:
         obs.frame_options["extraction"] = True
+        if args.reject_cosmics is not None:
+            from .extraction import CosmicRejection
+            obs.frame_options["crrej"] = CosmicRejection(k=args.reject_cosmics)
         obs.spectra_out = args.spectra or args.spectra_only
         obs.spectra_only = bool(args.spectra_only)
     os.makedirs(obs.outdir, exist_ok=True)

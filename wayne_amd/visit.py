@@ -132,7 +132,8 @@ class VisitRunner(object):
         """The same pipeline with only the spectra delivered: every exposure is synthesised and extracted on the device
         (`extraction`: as in run) and 8 (R + 1)(S + 1) bytes of it reach the host -- the reads never leave the device.
         -> (spectra [n, R + 1, S], sky [n, R + 1]) in the order of `indices`; `self.plans` [n]: each exposure's
-        extraction.Extraction."""
+        extraction.Extraction; `self.rejected` [n, R + 1]: the flag counts of an extraction that rejects cosmic rays
+        (None otherwise)."""
         eng = self.engine()
         indices = list(indices)
         where = {i: n for n, i in enumerate(indices)}
@@ -140,6 +141,8 @@ class VisitRunner(object):
         spectra = np.empty((len(indices), R + 1, S))
         sky = np.empty((len(indices), R + 1))
         self.plans = [None] * len(indices)
+        counts = [None] * len(indices)
+        delivery = _extraction.Delivery(eng.ctx, reads=False)
 
         def prepare(i):
             gen = self.generator(i)
@@ -151,8 +154,10 @@ class VisitRunner(object):
             _, sp, sk = got
             spectra[where[i]], sky[where[i]] = sp, sk
             self.plans[where[i]] = gen.extraction_plan
+            counts[where[i]] = delivery.rejected
 
-        run_pipelined(_extraction.Delivery(eng.ctx, reads=False), indices, prepare, finish, self.DEPTH, self.DEPTH)
+        run_pipelined(delivery, indices, prepare, finish, self.DEPTH, self.DEPTH)
+        self.rejected = None if any(n is None for n in counts) or not counts else np.array(counts, dtype=np.uint32)
         return spectra, sky
 
     def run_resident_spectra(self, n, on_spectra=None):
