@@ -382,7 +382,8 @@ int wayne_exposure_set_traps(wayne_ctx *ctx, int slot, const wayne_trap_desc *t)
  *   spectra_j[x] = A_j[x] - sky_j B_j[x],  x = 0 .. S-1
  * Result: spectra [(R+1)*S] and sky [R+1], float64.  The sums are taken in an order fixed by the plan (chunks of 32
  * rows of a window, added in ascending order; no atomics): the same exposure gives the same bytes in any slot, on
- * either stream, in any process.  Channel binning, fits and cosmic-ray rejection stay with the caller.
+ * either stream, in any process.  Cosmic-ray rejection and wavelength-binned channels are opt-in (below); fits stay
+ * with the caller.
  */
 #define WAYNE_X_LINEARISE (1u << 0) /* off: L_r = D_r - dark_r */
 #define WAYNE_X_DARK (1u << 1)      /* off: dark_r = 0 */
@@ -445,8 +446,56 @@ int wayne_exposure_set_crrej(wayne_ctx *ctx, int slot, const wayne_crrej_desc *r
 int wayne_exposure_rejected(wayne_ctx *ctx, int slot, const uint32_t **n_rejected);
 /* The flag plane of the slot's last run, blocking: mask [S*S], bit j = flag_j, 0 outside the mask rows. */
 int wayne_exposure_download_crmask(wayne_ctx *ctx, int slot, uint16_t *mask);
-/* HIP-event time of the extraction's kernels while wayne_profile_enable is on, since wayne_profile_reset: launches
- * (one per extracted exposure) and total milliseconds.  wayne_profile_select's bit 8 selects it.  Synchronises. */
+/*
+ * Wavelength-binned channel fluxes of the extraction, flat-fielded (opt-in; without it nothing above changes).  Added
+ * within WAYNE_ABI_VERSION 7: new symbols and a new struct only, so a caller built against the earlier header runs
+ * unchanged.  Conventions as above: bordered coordinates, side S, float64 throughout.  C channels with edges
+ * e[0] < ... < e[C] (um); per bordered row y the wavelength at bordered column coordinate u (pixel x covers [x, x+1)) is
+ *   lambda_y(u) = wl_a[y] + wl_b[y] u   (um)
+ * For product p and pixel (y, x) of its window let v be the term A_p[x] sums for that pixel (I_{p+1}, or its cleaned
+ * value under wayne_exposure_set_crrej; for p = R: L_R g minus the rejection's corrections), t = T[y, x] (0 on the
+ * border, when the plane is absent or WAYNE_X_SKY is off), scale_p = read_dt_s[p] (sum_j read_dt_s[j] for p = R) and
+ * sky_p the level of the column extraction, unchanged and not flat-fielded:
+ *   ua_b(y)  = (e[b] - wl_a[y]) / wl_b[y]                         (one float64 subtract, one divide)
+ *   w_b(y,x) = min(max(min(x+1, ua_{b+1}) - max(x, ua_b), 0), 1)
+ *   F(y,x)   = 1, unless WAYNE_C_FLAT is set, the context holds a flat cube and (y, x) is not a border pixel; then, with
+ *              tau = (1e4 (wl_a[y] + wl_b[y] x) - flat_wmin) / (flat_wmax - flat_wmin)  (lambda at the pixel's integer
+ *              coordinate, as the thrower's flat evaluates it), F = (double)(float)(f0 + f1 tau + f2 tau^2 + f3 tau^3) on
+ *              frame pixel (y-5, x-5), tau^2 = tau tau, tau^3 = tau^2 tau, the terms added left to right; F := 1 where
+ *              that is not > 0
+ *   P_p[b] = sum_y sum_x w_b(y,x) (v / F)        Q_p[b] = scale_p sum_y sum_x w_b(y,x) (t / F)
+ *   channels_p[b] = P_p[b] - sky_p Q_p[b]        p = 0 .. R   (zeros for p = R when WAYNE_X_LAST_READ is off)
+ * Result: channels [(R+1)*C], float64.  Every sum is taken in an order fixed by the plan (a row's columns ascending, then
+ * the 8 rows of a group, the 4 groups of a 32-row chunk and the chunks of a window, each ascending; no atomics): the same exposure gives the same
+ * bytes in any slot, on either stream, after a second run and in any process.  The work falls on the column hull
+ * [min_y floor(ua_0(y)), max_y ceil(ua_C(y))) over the rows of the formed windows, clamped to [0, S].
+ * Not covered: optimal extraction, resampling in y, other grism orders, the direct image, a flat-fielded sky fit.
+ */
+#define WAYNE_C_FLAT (1u << 0)   /* divide by the flat cube at the pixel's wavelength */
+#define WAYNE_MAX_CHANNELS 256
+#define WAYNE_MAX_CHANNEL_HULL 384 /* widest column hull a plan may have */
+
+typedef struct wayne_channels_desc {
+  int n_channels;         /* C: 1 .. WAYNE_MAX_CHANNELS */
+  const double *edges_um; /* [C + 1], finite and increasing */
+  const double *wl_a;     /* [S] um; finite on every row of a formed window */
+  const double *wl_b;     /* [S] um / px; finite and > 0 on every row of a formed window */
+  uint32_t flags;         /* WAYNE_C_* */
+} wayne_channels_desc;
+
+/* After wayne_exposure_set_extraction, before run: bin the slot's extraction into channels (d = NULL clears; upload and
+ * set_extraction clear it too, set_crrej does not).  The arrays are copied before the call returns.  WAYNE_E_STATE when no
+ * extraction is set on the slot; WAYNE_E_INVALID (the slot stays usable, extracting without channels) for n_channels
+ * outside 1 .. 256, non-finite or non-increasing edges, a bad wl_a / wl_b on a row of a formed window, unknown flag bits
+ * or a hull wider than WAYNE_MAX_CHANNEL_HULL.  The channels ride in the same copy as the spectra
+ * (wayne_exposure_fetch_spectra_async / _wait_spectra / _download_spectra). */
+int wayne_exposure_set_channels(wayne_ctx *ctx, int slot, const wayne_channels_desc *d);
+/* After wayne_exposure_wait_spectra / _download_spectra of a slot with channels: *channels [(R+1)*C], valid until the
+ * slot's spectra are fetched or the slot is uploaded again.  WAYNE_E_STATE before any fetch or without channels. */
+int wayne_exposure_channels(wayne_ctx *ctx, int slot, const double **channels);
+/* HIP-event time of the extraction's kernels (the channels' included) while wayne_profile_enable is on, since
+ * wayne_profile_reset: launches (one per extracted exposure) and total milliseconds.  wayne_profile_select's bit 8
+ * selects it.  Synchronises. */
 int wayne_extract_profile(wayne_ctx *ctx, uint64_t *launches, double *ms);
 
 /* ---- measurement ------------------------------------------------------- */

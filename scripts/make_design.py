@@ -16,6 +16,7 @@ template, filled from ONE source file under profiles/<round>/:
     n   visit_science_test.json    what tests/test_visit_science_gpu.py measured (negative control, injected difference)
     x   ../extract.json       scripts/bench_extract.py (not a round's file)
     c   ../crrej.json         scripts/bench_crrej.py (nor this)
+    h   ../channels.json      scripts/bench_channels.py (nor this)
     d   (derived)             computed here: d.traffic_over_algorithmic (t over b), and the fit lines of
                               thrower_vs_electrons.txt (d.lane_t0_us, d.lane_us_per_1e9, d.narrow_t0_us)
 so the document cannot drift from the measurements: tests/test_design_doc.py renders the template again and compares
@@ -33,7 +34,8 @@ FILES = {"b": "bench.json", "s": "visit_science.json", "k": "kernel_stats.json",
          "v": "valu_issue.json", "a": "ab_bin_local.json", "e": "kernel_stats_thrower_electron.json",
          "n": "visit_science_test.json",
          "x": os.path.join("..", "extract.json"),        # (not a round's file: scripts/bench_extract.py)
-         "c": os.path.join("..", "crrej.json")}          # (nor this: scripts/bench_crrej.py)
+         "c": os.path.join("..", "crrej.json"),          # (nor this: scripts/bench_crrej.py)
+         "h": os.path.join("..", "channels.json")}       # (nor this: scripts/bench_channels.py)
 PLACEHOLDER = re.compile(r"\{\{([a-z])\.([^|*}]+)(?:\*([0-9.eE+-]+))?\|([^}]*)\}\}")
 
 

@@ -36,6 +36,9 @@ MAX_TRAP_RATES = 4096   # points of a charge-trap start table (WAYNE_MAX_TRAP_RA
 # wayne_extract_desc.steps (WAYNE_X_*)
 X_LINEARISE, X_DARK, X_GAIN, X_SKY, X_LAST_READ, X_ALL = 1, 2, 4, 8, 16, 31
 EXTRACT_PRODUCTS = 17   # row windows a wayne_extract_desc holds
+C_FLAT = 1              # wayne_channels_desc.flags (WAYNE_C_*)
+MAX_CHANNELS = 256      # WAYNE_MAX_CHANNELS
+MAX_CHANNEL_HULL = 384  # WAYNE_MAX_CHANNEL_HULL
 
 
 class WayneError(RuntimeError):
@@ -99,6 +102,10 @@ class CrrejDesc(C.Structure):
     _fields_ = [("k", C.c_double), ("read_noise_e", C.c_double)]
 
 
+class ChannelsDesc(C.Structure):
+    _fields_ = [("n_channels", C.c_int), ("edges_um", _dp), ("wl_a", _dp), ("wl_b", _dp), ("flags", C.c_uint32)]
+
+
 class Profile(C.Structure):
     _fields_ = [("name", C.c_char_p * PROF_KERNELS), ("launches", C.c_uint64 * PROF_KERNELS),
                 ("ms", C.c_double * PROF_KERNELS), ("electrons", C.c_uint64)]
@@ -152,6 +159,8 @@ SYMBOLS = {
     "wayne_exposure_set_crrej": (C.c_int, [_vp, C.c_int, C.POINTER(CrrejDesc)]),
     "wayne_exposure_rejected": (C.c_int, [_vp, C.c_int, C.POINTER(C.POINTER(C.c_uint32))]),
     "wayne_exposure_download_crmask": (C.c_int, [_vp, C.c_int, _vp]),
+    "wayne_exposure_set_channels": (C.c_int, [_vp, C.c_int, C.POINTER(ChannelsDesc)]),
+    "wayne_exposure_channels": (C.c_int, [_vp, C.c_int, C.POINTER(_dp)]),
     "wayne_extract_profile": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_double)]),
     "wayne_profile_enable": (C.c_int, [_vp, C.c_int]),
     "wayne_profile_select": (C.c_int, [_vp, C.c_uint]),
@@ -274,6 +283,7 @@ class Context(object):
         self._slot_meta = {}     # slot -> (K, W, R, dtype of the reads) of the descriptor uploaded last
         self._slot_src = {}      # slot -> bins of each of its contaminants
         self._slot_crrej = set() # slots whose extraction rejects cosmic rays
+        self._slot_chan = {}     # slot -> channels of its extraction (set_channels succeeded)
         _live_contexts.add(self)
         for name, value in _knob_defaults.items():
             self.set_knob(name, value)
@@ -395,6 +405,7 @@ class Context(object):
         self._slot_meta[slot] = (desc.n_samples, desc.n_wl, desc.n_reads, out_dtype_of(desc.flags))
         self._slot_src[slot] = ()
         self._slot_crrej.discard(slot)
+        self._slot_chan.pop(slot, None)
         sources = getattr(desc, "_sources", None)
         if sources:
             self.set_sources(slot, sources)
@@ -439,12 +450,52 @@ class Context(object):
         intervals and of the last read, background columns, step mask; its `crrej`, if any, is set with it) -- None clears.  The back half of every run of
         the slot then forms spectra [R + 1, S] and sky [R + 1] on the device.  See wayne_exposure_set_extraction."""
         self._slot_crrej.discard(slot)
+        self._slot_chan.pop(slot, None)
         if extraction is None:
             self.check(self._L.wayne_exposure_set_extraction(self._h, int(slot), None))
             return
         self.check(self._L.wayne_exposure_set_extraction(self._h, int(slot), C.byref(extraction.desc())))
         if getattr(extraction, "crrej", None) is not None:
             self.set_crrej(slot, extraction.crrej)
+        if getattr(extraction, "channels", None) is not None:
+            self.set_channels(slot, extraction.channels, extraction.row_solution)
+
+    def set_channels(self, slot, channels, row_solution=None):
+        """Wavelength-binned channels of the slot's extraction: an extraction.Channels (edges in um, flat on / off) and
+        the rows' wavelength solution (wl_a [S], wl_b [S]): lambda_y(u) = wl_a[y] + wl_b[y] u at bordered column
+        coordinate u -- None clears; after set_extraction, which clears it too (set_crrej does not).  The arrays are
+        copied.  See wayne_exposure_set_channels."""
+        self._slot_chan.pop(slot, None)          # (a refusal leaves the slot extracting without channels)
+        if channels is None:
+            self.check(self._L.wayne_exposure_set_channels(self._h, int(slot), None))
+            return
+        if row_solution is None:
+            raise ValueError("set_channels: the rows' wavelength solution (wl_a, wl_b) is needed")
+        edges = np.ascontiguousarray(channels.edges_um, dtype=np.float64)
+        wl_a = np.ascontiguousarray(row_solution[0], dtype=np.float64)
+        wl_b = np.ascontiguousarray(row_solution[1], dtype=np.float64)
+        if wl_a.shape != (self.S,) or wl_b.shape != (self.S,):
+            raise ValueError("set_channels: wl_a and wl_b must have one entry per bordered row (%d)" % self.S)
+        d = ChannelsDesc()
+        d.n_channels = len(edges) - 1
+        d.edges_um, d.wl_a, d.wl_b = edges.ctypes.data_as(_dp), wl_a.ctypes.data_as(_dp), wl_b.ctypes.data_as(_dp)
+        d.flags = C_FLAT if channels.flat else 0
+        self.check(self._L.wayne_exposure_set_channels(self._h, int(slot), C.byref(d)))
+        self._slot_chan[slot] = d.n_channels
+
+    def has_channels(self, slot):
+        """Whether the slot's extraction is binned into channels (set_channels succeeded since its last set_extraction)."""
+        return slot in self._slot_chan
+
+    def channels(self, slot):
+        """channels [R + 1, C] (float64; a copy) of the slot's last wait_spectra / download_spectra."""
+        K, W, R, _ = self._slot_meta[slot]
+        pc = _dp()
+        self.check(self._L.wayne_exposure_channels(self._h, int(slot), C.byref(pc)))
+        n_ch = self._slot_chan.get(slot)
+        if n_ch is None:
+            raise WayneError(-7, "channels: no channels set for the slot")
+        return np.ctypeslib.as_array(pc, shape=(R + 1, n_ch)).copy()
 
     def fetch_spectra_async(self, slot):
         """Enqueue the copy of the slot's spectra (never its reads) into pinned host memory (returns at once)."""

@@ -13,6 +13,7 @@
 //   build_sky_alias      one Walker / Vose table of Poisson(lam)
 //   extract_desc_error   wayne_exposure_set_extraction's argument check (the windows k_extract walks stay inside the frame)
 //   crrej_desc_error     wayne_exposure_set_crrej's argument check; crrej_mask_rows: the rows k_extract_crmask writes
+//   channels_desc_error  wayne_exposure_set_channels' argument check, and the column hull k_extract_bins walks
 //
 // Reference: the reach of the thrower bounds pyparallel_menu.c:87-108 as the device modes implement it; the trace is
 // grism.py:491-506, 779-803 (trace_coeffs, plan_consts.h); the frame offset exposure_generator.py:630-645.
@@ -465,6 +466,40 @@ inline void crrej_mask_rows(int R, unsigned steps, const int* row_lo, const int*
     *lo = std::min(*lo, row_lo[j]);
     *hi = std::max(*hi, row_hi[j]);
   }
+}
+
+// wayne_exposure_set_channels' argument check (include/wayne_hip.h: wayne_channels_desc) against a valid extraction plan:
+// null when valid.  The rows looked at are those of the windows that are formed, the only rows k_extract_bins reads
+// wl_a / wl_b of.  *u_lo, *u_hi (if given): the column hull [min_y floor(ua_0(y)), max_y ceil(ua_C(y))) over those rows,
+// ua_b(y) = (e[b] - wl_a[y]) / wl_b[y], clamped to [0, S] (u_lo = u_hi: no channel touches the frame).
+inline const char* channels_desc_error(int S, int R, unsigned steps, const int* row_lo, const int* row_hi, int n_channels,
+                                       const double* edges, const double* wl_a, const double* wl_b, unsigned flags,
+                                       int* u_lo = nullptr, int* u_hi = nullptr) {
+  static_assert(kChanMaxChannels == 256 && kChanMaxHull == 384, "the messages below name the caps");
+  if (n_channels < 1 || n_channels > kChanMaxChannels) return "n_channels outside 1 .. 256";
+  if (!edges || !wl_a || !wl_b) return "null edges or row solution";
+  if (flags & ~C_ALL) return "unknown bits in flags";
+  for (int b = 0; b <= n_channels; ++b) {
+    if (!std::isfinite(edges[b])) return "channel edges must be finite";
+    if (b > 0 && !(edges[b] > edges[b - 1])) return "channel edges must increase";
+  }
+  const int n = (steps & X_LAST_READ) ? R + 1 : R;
+  double lo = (double)S, hi = 0.;
+  for (int j = 0; j < n; ++j)
+    for (int y = row_lo[j]; y < row_hi[j]; ++y) {
+      if (!std::isfinite(wl_a[y])) return "wl_a must be finite on every row of a window";
+      if (!(std::isfinite(wl_b[y]) && wl_b[y] > 0.)) return "wl_b must be finite and > 0 on every row of a window";
+      const double ua0 = (edges[0] - wl_a[y]) / wl_b[y], uaC = (edges[n_channels] - wl_a[y]) / wl_b[y];
+      if (!std::isfinite(ua0) || !std::isfinite(uaC)) return "a channel edge has no finite column on a row of a window";
+      lo = std::min(lo, std::floor(ua0));
+      hi = std::max(hi, std::ceil(uaC));
+    }
+  lo = std::min(std::max(lo, 0.), (double)S);
+  hi = std::min(std::max(hi, lo), (double)S);
+  if (hi - lo > (double)kChanMaxHull) return "the channels' column hull is wider than 384 columns";
+  if (u_lo) *u_lo = (int)lo;
+  if (u_hi) *u_hi = (int)hi;
+  return nullptr;
 }
 
 }  // namespace plan

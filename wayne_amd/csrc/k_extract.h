@@ -32,6 +32,18 @@
 // from the row neighbours' I_{j+1}.  The flags of a chunk are counted per column beside the partial sums and
 // k_extract_finish<true> adds them up: n_rejected[p], behind sky.
 //
+// Wavelength-binned channels (wayne_exposure_set_channels; off unless asked for -- the three kernels above are launched
+// as before and are not touched by it).  With v the term A_p sums for a pixel, t = T[y, x], C channels with edges e[] (um)
+// and the row's wavelength solution lambda_y(u) = wl_a[y] + wl_b[y] u:
+//   ua_b(y) = (e[b] - wl_a[y]) / wl_b[y],   w_b(y, x) = min(max(min(x + 1, ua_{b+1}) - max(x, ua_b), 0), 1)
+//   F(y, x) = the flat cube's cubic at lambda_y(x), rounded to float32 (1 without WAYNE_C_FLAT, on the border, where <= 0)
+//   P_p[b] = sum_y sum_x w_b (v / F),   Q_p[b] = scale_p sum_y sum_x w_b (t / F),   channels_p[b] = P_p[b] - sky_p Q_p[b]
+// k_extract_bins<T, CR>: one workgroup per (chunk of the list above, group of 8 consecutive rows of it) -- a chunk alone
+// gives too few workgroups for the device (68 for the first order on the full array); wave w takes row w of the group,
+// walks it over the column hull [u_lo, u_hi) of the plan in 64-column strips into LDS, then lane = channel gathers its
+// columns in ascending x; the waves are added in wave order -> scratch [chunk][group][p][2][C].  k_extract_bins_finish,
+// behind k_extract_finish for sky_p, adds the groups of a chunk and then the chunks in ascending order.
+//
 // The file is compiled without FMA contraction (wayne_amd/build.py), so a pixel's chain rounds as the numpy statement
 // of it does; what differs from numpy is the order of the row sums alone.
 #pragma once
@@ -307,6 +319,165 @@ __global__ void __launch_bounds__(kExtractThreads) k_extract_finish(ExtractArgs 
   __syncthreads();
   const double s = sh_sky;
   for (int x = tid; x < S; x += kExtractThreads) a.spectra[(size_t)p * S + x] = shA[x] - s * shB[x];
+}
+
+// ---- wavelength-binned channels (wayne_exposure_set_channels) ----
+
+struct ChannelArgs {
+  int C;                             // channels, 1 .. kChanMaxChannels
+  int u_lo, u_hi;                    // the column hull (plan::channels_desc_error): u_hi - u_lo <= kChanMaxHull
+  bool flat;                         // WAYNE_C_FLAT is set and the context holds a flat cube
+  int N;                             // side of the flat planes: S - 2 kBorder
+  double flat_wmin, flat_wmax;
+  const double* edges;               // [C + 1] um
+  const double* wl_a;                // [S]
+  const double* wl_b;                // [S]
+  const float* cube[4];              // [N*N] each, or null
+  double* part;                      // [n_chunks][kChanGroups][R+1][2][C]: a row group's P, then its Q / scale
+  double* channels;                  // [(R+1)*C]
+};
+
+// the term k_extract_rows adds to A_p[x] for pixel `pix` = y S + x (the same operations in the same order)
+template <class T, bool CR>
+__device__ __forceinline__ double extract_term(const ExtractArgs& a, const T* reads, size_t SS, size_t pix, int p, int r_hi,
+                                               int r_lo, bool lin, bool gain) {
+  const double p0 = (double)reads[pix];
+  double c[4] = {0., 0., 0., 0.};
+  if (lin)
+    for (int i = 0; i < 4; ++i) c[i] = (double)a.lin[i][pix];
+  const double Lh = extract_linear<T>(a, reads, SS, pix, r_hi, p0, lin, c);
+  const double Ll = r_lo > 0 ? extract_linear<T>(a, reads, SS, pix, r_lo, p0, lin, c) : 0.;
+  const double g = (a.steps & X_GAIN) ? (gain ? 2.35 / (double)a.pfl[pix] : 2.35) : 1.0;
+  double v = (Lh - Ll) * g;
+  if constexpr (CR) {
+    const unsigned m = a.mask[pix];
+    if (p < a.R) {
+      if ((m >> p) & 1u) v = extract_repl<T>(a, reads, SS, pix, p, lin, gain);
+    } else if (m) {
+      double corr = 0.;
+      for (unsigned b = m; b; b &= b - 1u) {                 // the set bits, ascending
+        const int j = __ffs((int)b) - 1;
+        corr += extract_interval<T>(a, reads, SS, pix, j, lin, gain) - extract_repl<T>(a, reads, SS, pix, j, lin, gain);
+      }
+      v -= corr;
+    }
+  }
+  return v;
+}
+
+constexpr int kChanPasses = (kChanMaxChannels + 63) / 64;             // channels a lane carries: 4
+constexpr int kChanGroups = kExtractRows / kExtractWaves;            // groups of 8 rows (one per wave) in a chunk: 4
+static_assert(kExtractRows % kExtractWaves == 0, "k_extract_bins: a chunk is a whole number of row groups");
+// the waves' sums red[kExtractWaves][2][C] reuse the row buffers buf[kExtractWaves][2][kChanMaxHull]
+static_assert(kExtractWaves * 2 * kChanMaxChannels <= kExtractWaves * 2 * kChanMaxHull,
+              "k_extract_bins: the waves' sums of the widest channel plan must fit the row buffers they reuse");
+
+// One workgroup per (chunk of a product's window -- the chunk list of k_extract_rows -- , group blockIdx.y of 8 rows of
+// it).  Wave w takes row w of the group: it writes v / F and t / F of the hull's columns into its row buffers, 64 columns
+// at a time, then lane = channel (kChanPasses passes) gathers [ua_b, ua_{b+1}) from them in ascending x.  A row past
+// the window's end adds nothing (its group still writes its zeros), so the barriers are uniform.
+template <class T, bool CR>
+__global__ void __launch_bounds__(kExtractThreads) k_extract_bins(ExtractArgs a, ChannelArgs ch) {
+  int p = 0;
+  while (p < a.R && (int)blockIdx.x >= a.first_chunk[p + 1]) ++p;
+  const int chunk = (int)blockIdx.x - a.first_chunk[p];
+  const int lo = a.row_lo[p] + chunk * kExtractRows, hi = min(lo + kExtractRows, a.row_hi[p]);
+  const int wave = (int)threadIdx.x >> 6, lane = (int)threadIdx.x & 63;
+  const int S = a.S, C = ch.C, W = ch.u_hi - ch.u_lo;
+  const size_t SS = (size_t)S * S;
+  const T* reads = (const T*)a.reads;
+  const int r_hi = p < a.R ? p + 1 : a.R, r_lo = p < a.R ? p : 0;
+  const bool lin = (a.steps & X_LINEARISE) && a.lin[0];
+  const bool gain = (a.steps & X_GAIN) && a.pfl, sky = (a.steps & X_SKY) && a.sky;
+  __shared__ double buf[kExtractWaves][2][kChanMaxHull];
+  double* bv = buf[wave][0];
+  double* bt = buf[wave][1];
+  double P[kChanPasses], Q[kChanPasses], e0[kChanPasses], e1[kChanPasses];
+#pragma unroll
+  for (int k = 0; k < kChanPasses; ++k) {
+    const int b = k * 64 + lane;
+    P[k] = 0.; Q[k] = 0.;
+    e0[k] = b < C ? ch.edges[b] : 0.;
+    e1[k] = b < C ? ch.edges[b + 1] : 0.;
+  }
+  const int group = (int)blockIdx.y;
+  const int y = lo + wave + group * kExtractWaves;
+  const bool row = y < hi;                                 // (wave-uniform)
+  double wa = 0., wb = 1.;
+  if (row) {
+    wa = ch.wl_a[y]; wb = ch.wl_b[y];
+    const bool y_in = y >= kBorder && y < S - kBorder;
+    for (int o = lane; o < W; o += 64) {
+      const int x = ch.u_lo + o;
+      const size_t pix = (size_t)y * S + x;
+      const double v = extract_term<T, CR>(a, reads, SS, pix, p, r_hi, r_lo, lin, gain);
+      const double t = sky ? (double)a.sky[pix] : 0.;
+      double F = 1.;
+      if (ch.flat && y_in && x >= kBorder && x < S - kBorder) {
+        const double tau = (1e4 * (wa + wb * (double)x) - ch.flat_wmin) / (ch.flat_wmax - ch.flat_wmin);
+        const double t2 = tau * tau, t3 = t2 * tau;
+        const size_t fi = (size_t)(y - kBorder) * ch.N + (x - kBorder);
+        const double f = (double)ch.cube[0][fi] + ((double)ch.cube[1][fi] * tau) + ((double)ch.cube[2][fi] * t2) +
+                         ((double)ch.cube[3][fi] * t3);
+        F = (double)(float)f;
+        if (!(F > 0.)) F = 1.;
+      }
+      bv[o] = v / F;
+      bt[o] = t / F;
+    }
+  }
+  __syncthreads();
+  if (row) {
+#pragma unroll
+    for (int k = 0; k < kChanPasses; ++k) {
+      if (k * 64 + lane < C) {
+        const double ua0 = (e0[k] - wa) / wb, ua1 = (e1[k] - wa) / wb;
+        // the columns [floor(ua0), ceil(ua1)) of the hull (clamped as float64: an edge may lie far outside the frame)
+        const int xs = (int)fmin(fmax(floor(ua0), (double)ch.u_lo), (double)ch.u_hi);
+        const int xe = (int)fmin(fmax(ceil(ua1), (double)ch.u_lo), (double)ch.u_hi);
+        for (int x = xs; x < xe; ++x) {
+          const double w = fmin(fmax(fmin((double)x + 1.0, ua1) - fmax((double)x, ua0), 0.), 1.);
+          P[k] += w * bv[x - ch.u_lo];
+          Q[k] += w * bt[x - ch.u_lo];
+        }
+      }
+    }
+  }
+  __syncthreads();
+  // the waves' sums, added in wave order: the row buffers are free now (the barrier above)
+  double* red = &buf[0][0][0];                               // [kExtractWaves][2][C]
+#pragma unroll
+  for (int k = 0; k < kChanPasses; ++k) {
+    const int b = k * 64 + lane;
+    if (b < C) {
+      red[((size_t)wave * 2 + 0) * C + b] = P[k];
+      red[((size_t)wave * 2 + 1) * C + b] = Q[k];
+    }
+  }
+  __syncthreads();
+  const int NP = a.R + 1;
+  for (int i = (int)threadIdx.x; i < 2 * C; i += kExtractThreads) {
+    double t = red[i];
+    for (int w = 1; w < kExtractWaves; ++w) t += red[(size_t)w * 2 * C + i];
+    ch.part[(((size_t)chunk * kChanGroups + group) * NP + p) * 2 * C + i] = t;
+  }
+}
+
+// Behind k_extract_finish (it reads sky_p): one workgroup per product adds the row groups in ascending order and writes
+// channels_p[b] = P_p[b] - sky_p (scale_p Q_p[b]).
+__global__ void __launch_bounds__(kChanMaxChannels) k_extract_bins_finish(ExtractArgs a, ChannelArgs ch) {
+  const int p = (int)blockIdx.x, b = (int)threadIdx.x, C = ch.C, NP = a.R + 1;
+  if (b >= C) return;
+  if (p == a.R && !(a.steps & X_LAST_READ)) { ch.channels[(size_t)p * C + b] = 0.; return; }
+  const int rows = a.row_hi[p] - a.row_lo[p];
+  const int chunks = (rows + kExtractRows - 1) / kExtractRows;
+  double P = 0., Q = 0.;
+  for (int c = 0; c < chunks * kChanGroups; ++c) {           // ascending chunks, ascending groups of a chunk
+    const size_t at = ((size_t)c * NP + p) * 2 * C;
+    P += ch.part[at + b];
+    Q += ch.part[at + C + b];
+  }
+  ch.channels[(size_t)p * C + b] = P - a.sky_out[p] * (a.scale[p] * Q);
 }
 
 }  // namespace wayne

@@ -51,6 +51,10 @@ constexpr unsigned X_ALL = X_LINEARISE | X_DARK | X_GAIN | X_SKY | X_LAST_READ;
 constexpr int kCrMargin = 7;                      // pixels of the frame's edge that are never tested
 constexpr int kCrHalo = 2;                        // reach of the plus-shaped stencil
 constexpr int kCrTileCols = 64, kCrTileRows = kExtractRows;   // pixels of a k_extract_crmask workgroup
+// wavelength-binned channels of the extraction (k_extract_bins; validated by plan::channels_desc_error)
+constexpr int kChanMaxChannels = 256;             // WAYNE_MAX_CHANNELS
+constexpr int kChanMaxHull = 384;                 // widest column hull: 8 waves x 2 row buffers x 384 float64 = 48 KB of LDS
+constexpr unsigned C_FLAT = 1u << 0, C_ALL = C_FLAT;   // wayne_channels_desc.flags (WAYNE_C_*)
 
 WAYNE_HD void trace_coeffs(const GrismDev& g, double x_ref, double y_ref, double* o) {
   // o = {m_t, c_t, m_w, c_w, m_wl, c_wl}

@@ -218,6 +218,17 @@ struct Slot : SourceState {
   DevBuf cr_mask, ex_part_n;
   const uint32_t* ex_rej = nullptr;
   std::vector<uint32_t> ex_rej_host;
+  // wavelength-binned channels of the extraction (wayne_exposure_set_channels; cleared by upload and set_extraction, not
+  // by set_crrej): edges [C+1], wl_a [S], wl_b [S] in an arena of their own, the row groups' sums [chunks][4][R+1][2][C], and
+  // channels [(R+1)*C] behind sky / n_rejected in ex_out, 8-byte aligned.  `ch_res`: what the last wait_spectra /
+  // download_spectra brought back (null before any)
+  bool chan_on = false;
+  int ch_C = 0, ch_lo = 0, ch_hi = 0;
+  uint32_t ch_flags = 0;
+  StageArena ch_stage;
+  DevBuf ch_edges, ch_wa, ch_wb, ch_part;
+  const double* ch_res = nullptr;
+  std::vector<double> ch_host;
   // staging arena of the descriptor's arrays: uploads are enqueued from here, so
   // wayne_exposure_upload returns without waiting for the slot's stream to drain
   StageArena stage;
@@ -626,6 +637,45 @@ void (*select_ramp(const wayne_ctx* c, const Slot& s, std::string* name, RampTra
   return kern;
 }
 
+static_assert(WAYNE_MAX_CHANNELS == kChanMaxChannels && WAYNE_MAX_CHANNEL_HULL == kChanMaxHull && WAYNE_C_FLAT == C_FLAT,
+              "include/wayne_hip.h and plan_consts.h must agree on the channels' caps and flag");
+
+// Where channels [(R+1)*C] begin in a slot's spectra block: behind spectra, sky and (with rejection) n_rejected, on the
+// next multiple of 8 bytes.
+size_t channels_offset(const wayne_ctx* c, const Slot& s) {
+  const size_t b = (size_t)(s.R + 1) * ((size_t)c->S + 1) * sizeof(double) + (s.crrej_on ? (size_t)(s.R + 1) * sizeof(uint32_t) : 0);
+  return (b + 7) & ~(size_t)7;
+}
+
+// The channels of slot `s` (wayne_exposure_set_channels) behind k_extract_finish, from `a` as launch_extract filled it.
+int launch_channels(wayne_ctx* c, Slot& s, const ExtractArgs& a, int blocks, int out, bool cr) {
+  ChannelArgs ch{};
+  ch.C = s.ch_C; ch.u_lo = s.ch_lo; ch.u_hi = s.ch_hi;
+  ch.flat = (s.ch_flags & C_FLAT) && c->has_flat;
+  ch.N = c->S - 2 * kBorder;
+  ch.flat_wmin = c->g.flat_wmin; ch.flat_wmax = c->g.flat_wmax;
+  ch.edges = s.ch_edges.as<double>(); ch.wl_a = s.ch_wa.as<double>(); ch.wl_b = s.ch_wb.as<double>();
+  for (int i = 0; i < 4; ++i) ch.cube[i] = c->has_flat ? c->flat[i].as<float>() : nullptr;
+  ch.part = s.ch_part.as<double>();
+  ch.channels = (double*)((char*)s.ex_out.p + channels_offset(c, s));
+  const dim3 grid((unsigned)blocks, (unsigned)kChanGroups), block(kExtractThreads);
+  if (blocks > 0) {
+    if (cr) {
+      if (out == 1) hipLaunchKernelGGL((k_extract_bins<double, true>), grid, block, 0, c->stream, a, ch);
+      else if (out == 2) hipLaunchKernelGGL((k_extract_bins<uint16_t, true>), grid, block, 0, c->stream, a, ch);
+      else hipLaunchKernelGGL((k_extract_bins<float, true>), grid, block, 0, c->stream, a, ch);
+    } else {
+      if (out == 1) hipLaunchKernelGGL((k_extract_bins<double, false>), grid, block, 0, c->stream, a, ch);
+      else if (out == 2) hipLaunchKernelGGL((k_extract_bins<uint16_t, false>), grid, block, 0, c->stream, a, ch);
+      else hipLaunchKernelGGL((k_extract_bins<float, false>), grid, block, 0, c->stream, a, ch);
+    }
+    HIP_TRY(c, hipGetLastError());
+  }
+  hipLaunchKernelGGL(k_extract_bins_finish, dim3((unsigned)(a.R + 1)), dim3(kChanMaxChannels), 0, c->stream, a, ch);
+  HIP_TRY(c, hipGetLastError());
+  return WAYNE_OK;
+}
+
 // The extraction of slot `s` (wayne_exposure_set_extraction) behind its ramp kernel: the row sums of every product, then
 // the chunks added up, the sky level and the spectra.  The grid follows from the plan alone.
 int launch_extract(wayne_ctx* c, Slot& s) {
@@ -677,7 +727,7 @@ int launch_extract(wayne_ctx* c, Slot& s) {
     HIP_TRY(c, hipGetLastError());
     hipLaunchKernelGGL(k_extract_finish<true>, products_grid, block, 0, c->stream, a);
     HIP_TRY(c, hipGetLastError());
-    return WAYNE_OK;
+    return s.chan_on ? launch_channels(c, s, a, a.first_chunk[products], out, true) : WAYNE_OK;
   }
   if (out == 1) hipLaunchKernelGGL((k_extract_rows<double, false>), grid, block, 0, c->stream, a);
   else if (out == 2) hipLaunchKernelGGL((k_extract_rows<uint16_t, false>), grid, block, 0, c->stream, a);
@@ -685,7 +735,7 @@ int launch_extract(wayne_ctx* c, Slot& s) {
   HIP_TRY(c, hipGetLastError());
   hipLaunchKernelGGL(k_extract_finish<false>, products_grid, block, 0, c->stream, a);
   HIP_TRY(c, hipGetLastError());
-  return WAYNE_OK;
+  return s.chan_on ? launch_channels(c, s, a, a.first_chunk[products], out, false) : WAYNE_OK;
 }
 
 }  // namespace
@@ -1166,6 +1216,8 @@ int wayne_exposure_upload(wayne_ctx* c, int slot, const wayne_exposure_desc* d) 
   s.ex_pinned_misc = nullptr;
   s.crrej_on = false;        // ... whose cosmic-ray rejection waits for wayne_exposure_set_crrej
   s.ex_rej = nullptr;
+  s.chan_on = false;         // ... and whose channels wait for wayne_exposure_set_channels
+  s.ch_res = nullptr;
   int rc;
   const size_t KW = (size_t)K * W;
   {
@@ -1928,6 +1980,8 @@ int wayne_exposure_set_extraction(wayne_ctx* c, int slot, const wayne_extract_de
   s.ex_pinned_misc = nullptr;
   s.crrej_on = false;
   s.ex_rej = nullptr;
+  s.chan_on = false;
+  s.ch_res = nullptr;
   if (!x) return WAYNE_OK;
   int chunks = 0;
   if (const char* why = plan::extract_desc_error(c->S, s.R, x->steps, x->row_lo, x->row_hi, x->bg_col_lo, x->bg_col_hi, &chunks))
@@ -1949,6 +2003,7 @@ int wayne_exposure_set_crrej(wayne_ctx* c, int slot, const wayne_crrej_desc* r) 
   if (!s.uploaded || !s.extract_on) return fail(c, WAYNE_E_STATE, "set_crrej: no extraction set for the slot");
   s.crrej_on = false;             // from here on a refusal leaves the slot extracting, without rejection
   s.ex_rej = nullptr;
+  s.ch_res = nullptr;
   s.ex_pinned_misc = nullptr;     // (a fetched block has the other layout)
   if (!r) return WAYNE_OK;
   if (const char* why = plan::crrej_desc_error(s.ex.steps, r->k, r->read_noise_e))
@@ -1964,8 +2019,42 @@ int wayne_exposure_set_crrej(wayne_ctx* c, int slot, const wayne_crrej_desc* r) 
   return WAYNE_OK;
 }
 
-// bytes of a slot's spectra block: spectra [(R+1)*S], then sky [R+1]; with rejection, n_rejected [R+1] (uint32) behind them
+int wayne_exposure_set_channels(wayne_ctx* c, int slot, const wayne_channels_desc* d) {
+  if (!c) return WAYNE_E_INVALID;
+  if (slot < 0 || slot >= kSlots) return fail(c, WAYNE_E_INVALID, "set_channels: slot");
+  Slot& s = c->slots[slot];
+  if (!s.uploaded || !s.extract_on) return fail(c, WAYNE_E_STATE, "set_channels: no extraction set for the slot");
+  s.chan_on = false;              // from here on a refusal leaves the slot extracting, without channels
+  s.ch_res = nullptr;
+  s.ex_pinned_misc = nullptr;     // (a fetched block has the other layout)
+  if (!d) return WAYNE_OK;
+  int u_lo = 0, u_hi = 0;
+  if (const char* why = plan::channels_desc_error(c->S, s.R, s.ex.steps, s.ex.row_lo, s.ex.row_hi, d->n_channels, d->edges_um,
+                                                  d->wl_a, d->wl_b, d->flags, &u_lo, &u_hi))
+    return fail(c, WAYNE_E_INVALID, std::string("set_channels: ") + why);
+  (void)hipSetDevice(c->device);
+  use_slot_stream(c, slot);
+  const size_t NP = (size_t)s.R + 1, S = (size_t)c->S, C = (size_t)d->n_channels;
+  HIP_TRY(c, s.ch_part.reserve((size_t)s.ex_chunks * kChanGroups * NP * 2 * C * sizeof(double)));
+  // the spectra block grows by the channels, 8-byte aligned behind sky and (set_crrej may come before or after) the counts;
+  // nothing of it is kept: the next run writes all of it
+  HIP_TRY(c, s.ex_out.reserve(NP * (S + 1) * sizeof(double) + NP * sizeof(uint32_t) + 8 + NP * C * sizeof(double)));
+  if (int rc = s.ch_stage.begin(c, 3 * 64 + (2 * S + C + 1) * sizeof(double), "set_channels: pinned host allocation failed")) return rc;
+  if (!s.ch_stage.put(s.ch_edges, d->edges_um, (C + 1) * sizeof(double)) || !s.ch_stage.put(s.ch_wa, d->wl_a, S * sizeof(double)) ||
+      !s.ch_stage.put(s.ch_wb, d->wl_b, S * sizeof(double)))
+    return fail(c, WAYNE_E_NOMEM, "set_channels: staging arena too small");
+  if (int rc = s.ch_stage.commit(c, c->stream)) return rc;
+  s.ch_C = d->n_channels;
+  s.ch_lo = u_lo; s.ch_hi = u_hi;
+  s.ch_flags = d->flags;
+  s.chan_on = true;
+  return WAYNE_OK;
+}
+
+// bytes of a slot's spectra block: spectra [(R+1)*S], then sky [R+1]; with rejection, n_rejected [R+1] (uint32) behind
+// them; with channels, channels [(R+1)*C] behind those on the next multiple of 8 bytes
 static size_t spectra_bytes(const wayne_ctx* c, const Slot& s) {
+  if (s.chan_on) return channels_offset(c, s) + (size_t)(s.R + 1) * s.ch_C * sizeof(double);
   return (size_t)(s.R + 1) * ((size_t)c->S + 1) * sizeof(double) + (s.crrej_on ? (size_t)(s.R + 1) * sizeof(uint32_t) : 0);
 }
 
@@ -2000,6 +2089,7 @@ int wayne_exposure_wait_spectra(wayne_ctx* c, int slot, double** spectra, double
   *spectra = (double*)s.ex_pinned.p;
   *sky = (double*)s.ex_pinned.p + (size_t)(s.R + 1) * c->S;
   s.ex_rej = s.crrej_on ? (const uint32_t*)(*sky + (s.R + 1)) : nullptr;
+  s.ch_res = s.chan_on ? (const double*)(s.ex_pinned.p + channels_offset(c, s)) : nullptr;
   bool reran = false;                        // (the status word came with the spectra)
   int rc = look_at_status(c, slot, s.ex_pinned_misc, wayne_exposure_run, &reran);
   if (rc || !reran) return rc;
@@ -2023,8 +2113,16 @@ int wayne_exposure_download_spectra(wayne_ctx* c, int slot, double* spectra, dou
     if (s.crrej_on)
       HIP_TRY(c, hipMemcpyAsync(s.ex_rej_host.data(), s.ex_out.as<double>() + n + (s.R + 1), (size_t)(s.R + 1) * sizeof(uint32_t),
                                 hipMemcpyDeviceToHost, c->stream));
+    if (s.chan_on)
+      HIP_TRY(c, hipMemcpyAsync(s.ch_host.data(), (const char*)s.ex_out.p + channels_offset(c, s), s.ch_host.size() * sizeof(double),
+                                hipMemcpyDeviceToHost, c->stream));
     return WAYNE_OK;
   };
+  s.ch_res = nullptr;
+  if (s.chan_on) {
+    s.ch_host.assign((size_t)(s.R + 1) * s.ch_C, 0.);
+    s.ch_res = s.ch_host.data();
+  }
   s.ex_rej = nullptr;
   if (s.crrej_on) {
     s.ex_rej_host.assign((size_t)s.R + 1, 0u);
@@ -2046,6 +2144,16 @@ int wayne_exposure_rejected(wayne_ctx* c, int slot, const uint32_t** n_rejected)
   if (!s.uploaded || !s.extract_on || !s.crrej_on) return fail(c, WAYNE_E_STATE, "rejected: no rejection set for the slot");
   if (!s.ex_rej) return fail(c, WAYNE_E_STATE, "rejected: wait_spectra or download_spectra first");
   *n_rejected = s.ex_rej;
+  return WAYNE_OK;
+}
+
+int wayne_exposure_channels(wayne_ctx* c, int slot, const double** channels) {
+  if (!c || !channels) return WAYNE_E_INVALID;
+  if (slot < 0 || slot >= kSlots) return fail(c, WAYNE_E_INVALID, "channels: slot");
+  Slot& s = c->slots[slot];
+  if (!s.uploaded || !s.extract_on || !s.chan_on) return fail(c, WAYNE_E_STATE, "channels: no channels set for the slot");
+  if (!s.ch_res) return fail(c, WAYNE_E_STATE, "channels: wait_spectra or download_spectra first");
+  *channels = s.ch_res;
   return WAYNE_OK;
 }
 

@@ -9,8 +9,19 @@ scanning_frame / staring_frame / VisitRunner / Observation.frame_options) the de
                     alone over the whole scan's rows
     sky[j]          the fitted sky level of product j (electrons per second per unit of the master-sky template)
 
-(the law: include/wayne_hip.h, wayne_extract_desc) and only those cross PCIe.  Channel binning stays here: a channel's
-flux is `channel_weights(...) @ spectra[:R].sum(0)` (up the ramp) or `... @ spectra[R]` (last read).
+(the law: include/wayne_hip.h, wayne_extract_desc) and only those cross PCIe.  Star-fixed column channels can still be
+formed here: `channel_weights(...) @ spectra[:R].sum(0)` (up the ramp) or `... @ spectra[R]` (last read).
+
+Wavelength-binned channels are opt-in (`channels=` of Extraction / ExtractionOptions / the frames, CLI --channels
+LO:HI:N): the grism's dispersion depends on the star's height, and during a scan every detector row is lit while the star
+sits at another height, so lines of constant wavelength are slanted against the columns -- one column-to-wavelength
+solution for all rows errs by up to 104 A (2.3 px) over +-200 px on G141, a linear solution per row (`row_solution`) by
+0.41 A (G102: 60 A and 0.28 A).  With `Channels(edges_um)` and that per-row solution lambda_y(u) = wl_a[y] + wl_b[y] u the device bins every
+window pixel into the channels by fractional column coverage, dividing it first (flat=True, the default) by the flat
+cube evaluated at the pixel's wavelength -- the factor the simulator multiplied in -- and hands back
+`channels` [R + 1, C] with the spectra (the law: include/wayne_hip.h, wayne_channels_desc).  The sky level is the column
+extraction's.  Not covered: optimal extraction, resampling in y, other grism orders, the direct image, merging per-rank
+.npz files, a flat-fielded sky fit.  Fitting stays with the caller.
 
 Cosmic-ray rejection is opt-in (`crrej=` of Extraction / ExtractionOptions / the frames, CLI --reject-cosmics): on each
 read interval's difference image I a pixel at least 7 px inside the frame and in the plan's rows is flagged when it
@@ -26,6 +37,7 @@ pixels of one interval (they shield each other), the 7-pixel frame margin, optim
 import numpy as np
 
 from . import _lib, tools
+from . import grism as grism_mod
 
 LINEARISE, DARK, GAIN, SKY, LAST_READ = _lib.X_LINEARISE, _lib.X_DARK, _lib.X_GAIN, _lib.X_SKY, _lib.X_LAST_READ
 ALL = _lib.X_ALL
@@ -62,13 +74,89 @@ class CosmicRejection(object):
         return d
 
 
+MAX_CHANNELS = _lib.MAX_CHANNELS
+MAX_HULL = _lib.MAX_CHANNEL_HULL      # widest column hull of a channel plan (kChanMaxHull)
+
+
+class Channels(object):
+    """Wavelength channels of an extraction (wayne_channels_desc): `edges_um` [C + 1], finite and increasing, 1 <= C <=
+    256; `flat`: divide every pixel by the flat cube at its wavelength (WAYNE_C_FLAT)."""
+
+    def __init__(self, edges_um, flat=True):
+        e = np.array(edges_um, dtype=np.float64)
+        if e.ndim != 1 or not 2 <= e.size <= MAX_CHANNELS + 1:
+            raise ValueError("Channels: between 1 and %d channels (edges_um holds one more)" % MAX_CHANNELS)
+        if not np.isfinite(e).all():
+            raise ValueError("Channels: edges_um must be finite")
+        if not (np.diff(e) > 0.0).all():
+            raise ValueError("Channels: edges_um must increase")
+        self.edges_um, self.flat = e, bool(flat)
+
+    @staticmethod
+    def linear(lo_um, hi_um, n):
+        """`n` channels of equal width between lo_um and hi_um."""
+        n = int(n)
+        if n < 1:
+            raise ValueError("Channels: between 1 and %d channels" % MAX_CHANNELS)
+        return Channels(np.linspace(float(lo_um), float(hi_um), n + 1))
+
+    @staticmethod
+    def coerce(channels):
+        """`channels=` -> a Channels or None: None and False are off."""
+        if channels is None or channels is False:
+            return None
+        if not isinstance(channels, Channels):
+            raise TypeError("channels: None or an extraction.Channels")
+        return channels
+
+    def with_flat(self, flat):
+        return Channels(self.edges_um, flat)
+
+    @property
+    def n(self):
+        return self.edges_um.size - 1
+
+
+def channel_hull(channels, row_solution, row_windows, steps=ALL):
+    """The bordered columns [u_lo, u_hi) the channels can touch on the rows of the windows that are formed (as
+    plan::channels_desc_error computes them): min_y floor(ua_0(y)) to max_y ceil(ua_C(y)), clamped to [0, S].  Raises
+    ValueError for what wayne_exposure_set_channels refuses."""
+    wl_a, wl_b = (np.asarray(v, dtype=np.float64) for v in row_solution)
+    if wl_a.ndim != 1 or wl_a.shape != wl_b.shape:
+        raise ValueError("row_solution: (wl_a [S], wl_b [S])")
+    S = wl_a.size
+    w = np.asarray(row_windows)
+    w = w if steps & LAST_READ else w[:-1]
+    rows = np.zeros(S, dtype=bool)
+    for lo, hi in w:
+        rows[int(lo):int(hi)] = True
+    a, b = wl_a[rows], wl_b[rows]
+    if not np.isfinite(a).all():
+        raise ValueError("row_solution: wl_a must be finite on every row of a window")
+    if not (np.isfinite(b) & (b > 0.0)).all():
+        raise ValueError("row_solution: wl_b must be finite and > 0 on every row of a window")
+    with np.errstate(over="ignore", invalid="ignore"):
+        ua0, uaC = (channels.edges_um[0] - a) / b, (channels.edges_um[-1] - a) / b
+    if not (np.isfinite(ua0).all() and np.isfinite(uaC).all()):
+        raise ValueError("row_solution: a channel edge has no finite column on a row of a window")
+    lo = min(float(S), float(np.floor(ua0).min())) if a.size else float(S)
+    hi = max(0.0, float(np.ceil(uaC).max())) if a.size else 0.0
+    lo = min(max(lo, 0.0), float(S))
+    hi = min(max(hi, lo), float(S))
+    if hi - lo > MAX_HULL:
+        raise ValueError("channels: the column hull is wider than %d columns" % MAX_HULL)
+    return int(lo), int(hi)
+
+
 class Extraction(object):
     """The plan of one exposure's extraction: `row_windows` [(lo, hi)] * (R + 1) -- bordered rows, half open, read
     interval j at index j and the last-read product at index R -- the background columns and the step mask (LINEARISE |
     DARK | GAIN | SKY | LAST_READ; a step that is off: see the WAYNE_X_* bits).  `crrej` (None, True or a
-    CosmicRejection): cosmic rays are rejected on the difference images first; it needs the GAIN step."""
+    CosmicRejection): cosmic rays are rejected on the difference images first; it needs the GAIN step.  `channels` (None
+    or a Channels) with `row_solution` = (wl_a [S], wl_b [S]): the window pixels are also binned into wavelength
+    channels, row y by lambda_y(u) = wl_a[y] + wl_b[y] u at bordered column coordinate u."""
 
-    def __init__(self, row_windows, bg_cols=BG_COLS, steps=ALL, crrej=None):
+    def __init__(self, row_windows, bg_cols=BG_COLS, steps=ALL, crrej=None, channels=None, row_solution=None):
         w = np.asarray(row_windows, dtype=np.int64)
         if w.ndim != 2 or w.shape[1] != 2 or not 2 <= w.shape[0] <= _lib.EXTRACT_PRODUCTS:
             raise ValueError("row_windows: (lo, hi) for each of the R read intervals and for the last read")
@@ -76,10 +164,23 @@ class Extraction(object):
         self.bg_cols = (int(bg_cols[0]), int(bg_cols[1]))
         self.steps = int(steps)
         self.crrej = CosmicRejection.coerce(crrej)
+        self.channels = Channels.coerce(channels)
+        self.row_solution = None
+        self.hull = None              # (u_lo, u_hi): the bordered columns the channels can touch
+        if self.channels is not None:
+            if row_solution is None:
+                raise ValueError("channels need a row_solution (wl_a, wl_b)")
+            self.row_solution = tuple(np.array(v, dtype=np.float64) for v in row_solution)
+            self.hull = channel_hull(self.channels, self.row_solution, w, self.steps)
 
     def with_crrej(self, crrej):
         """The same plan with another `crrej`."""
-        return Extraction(self.row_windows, self.bg_cols, self.steps, crrej)
+        return Extraction(self.row_windows, self.bg_cols, self.steps, crrej, self.channels, self.row_solution)
+
+    def with_channels(self, channels, row_solution=None):
+        """The same plan with other `channels` (None: without); `row_solution` defaults to the plan's own."""
+        return Extraction(self.row_windows, self.bg_cols, self.steps, self.crrej, channels,
+                          self.row_solution if row_solution is None else row_solution)
 
     @property
     def mask_rows(self):
@@ -105,26 +206,48 @@ class Extraction(object):
         return d
 
 
+OWN = object()             # `channels=` of ExtractionOptions.plan: the options' own
+
+
 class ExtractionOptions(object):
     """Extraction planned per exposure: what `extraction=` takes where the star moves from exposure to exposure
     (Observation.frame_options, VisitRunner).  ExposureGenerator turns it into that exposure's Extraction (plan)."""
 
-    def __init__(self, margin=ROW_MARGIN, bg_cols=BG_COLS, steps=ALL, crrej=None):
+    def __init__(self, margin=ROW_MARGIN, bg_cols=BG_COLS, steps=ALL, crrej=None, channels=None):
         self.margin, self.bg_cols, self.steps = int(margin), (int(bg_cols[0]), int(bg_cols[1])), int(steps)
         self.crrej = CosmicRejection.coerce(crrej)
+        self.channels = Channels.coerce(channels)
 
-    def plan(self, grism, wl, x_ref, y_ref, scan_speed, read_times, sub_scale, S):
+    def plan(self, grism, wl, x_ref, y_ref, scan_speed, read_times, sub_scale, S, channels=OWN):
+        """This exposure's Extraction; `channels` (a Channels or None) replaces the options' own."""
+        channels = self.channels if channels is OWN else Channels.coerce(channels)
+        sol = None if channels is None else row_solution(grism, x_ref, y_ref, sub_scale, S)
         return Extraction(row_windows(grism, wl, x_ref, y_ref, scan_speed, read_times, sub_scale, S, self.margin),
-                          self.bg_cols, self.steps, self.crrej)
+                          self.bg_cols, self.steps, self.crrej, channels, sol)
 
 
-def for_exposure(extraction, grism, wl, x_ref, y_ref, scan_speed, read_times, sub_scale, S, crrej=None):
+def for_exposure(extraction, grism, wl, x_ref, y_ref, scan_speed, read_times, sub_scale, S, crrej=None, channels=None):
     """`extraction=` of a frame -> that exposure's Extraction: None stays None, an Extraction is taken as it is, True is
-    the default plan and an ExtractionOptions its own.  `crrej=` of the frame, when given, replaces the plan's."""
+    the default plan and an ExtractionOptions its own.  `crrej=` of the frame, when given, replaces the plan's; so does
+    `channels=` (a Channels), with the row solution planned for this exposure."""
     if extraction is None or extraction is False:
         if crrej is not None and crrej is not False:
             raise ValueError("crrej needs an extraction")
+        if channels is not None and channels is not False:
+            raise ValueError("channels need an extraction")
         return None
+    if channels is not None:
+        # the replaced channels are never planned: only the ones asked for here are, by the one planner
+        channels = Channels.coerce(channels)
+        if isinstance(extraction, Extraction):
+            plan = extraction.with_channels(channels, None if channels is None else row_solution(grism, x_ref, y_ref, sub_scale, S))
+        else:
+            if extraction is True:
+                extraction = ExtractionOptions()
+            if not isinstance(extraction, ExtractionOptions):
+                raise TypeError("extraction: None, True, an extraction.Extraction or an extraction.ExtractionOptions")
+            plan = extraction.plan(grism, wl, x_ref, y_ref, scan_speed, read_times, sub_scale, S, channels=channels)
+        return plan if crrej is None else plan.with_crrej(crrej)
     if crrej is not None:
         plan = for_exposure(extraction, grism, wl, x_ref, y_ref, scan_speed, read_times, sub_scale, S)
         return plan.with_crrej(crrej)
@@ -160,6 +283,41 @@ def row_windows(grism, wl, x_ref, y_ref, scan_speed, read_times, sub_scale, S, m
     return out
 
 
+def row_solution(grism, x_ref, y_ref, sub_scale, S):
+    """The per-row wavelength solution of a spatial scan -> (wl_a [S], wl_b [S]) in um and um / px: at bordered column
+    coordinate u of bordered row y the first order carries lambda_y(u) = wl_a[y] + wl_b[y] u.  The grism's dispersion
+    depends on the star's height, and row y is lit while the star is at the height y_s at which the trace crosses the
+    row: with the row's centre in detector coordinates Y = y - 5 + sub_scale + 0.5, y_s solves
+    get_trace(x_ref, y_s).wl_to_y(lambda_c) = Y at the centre lambda_c of the grism's [min_lambda, max_lambda] (fixed-point
+    iteration; the trace is 1-2 px off the star's row and almost independent of y_s, so four steps converge far below
+    1e-6 px).  Then wl_b = m_wl and wl_a = c_wl + m_wl (sub_scale - 5) of that trace: bordered u is detector column
+    u - 5 + sub_scale.  `x_ref` is the exposure's nominal one (an observer does not know the jitter); the solution is a
+    function of the detector row alone, so `y_ref` -- where the scan starts -- does not enter it.  Against the
+    simulator's own bin positions over +-200 px the solution errs by 0.41 A (G141; G102 0.28 A): the term quadratic in
+    x that a line omits, plus planning at the row's centre."""
+    tr0 = grism.get_trace(x_ref, y_ref)
+    coeff, wlsol = tr0.trace_coeff, tr0.wl_solution
+    lam_c = 0.5 * (grism.min_lambda + grism.max_lambda)
+    Y = np.arange(int(S), dtype=np.float64) - 5.0 + sub_scale + 0.5
+
+    def lines(y_s):
+        # _SpectrumTrace for an array of star heights: (m_t, c_t, m_wl, c_wl)
+        m_t, c_t, m_w, c_w = grism_mod.wavelength_calibration_coeffs(x_ref, y_s, coeff, wlsol)
+        xa, xb = x_ref + 10, x_ref + 20
+        ya, yb = m_t * (xa - x_ref) + c_t + y_s, m_t * (xb - x_ref) + c_t + y_s
+        wa = (m_w * np.sqrt((ya - y_s) ** 2 + (xa - x_ref) ** 2) + c_w) * 1e-4
+        wb = (m_w * np.sqrt((yb - y_s) ** 2 + (xb - x_ref) ** 2) + c_w) * 1e-4
+        m_wl = (wb - wa) / (xb - xa)
+        return m_t, c_t, m_wl, wa - m_wl * xa
+
+    y_s = Y.copy()
+    for _ in range(4):
+        m_t, c_t, m_wl, c_wl = lines(y_s)
+        y_s = y_s + (Y - (m_t * ((lam_c - c_wl) / m_wl - x_ref) + c_t + y_s))
+    m_t, c_t, m_wl, c_wl = lines(y_s)
+    return c_wl + m_wl * (sub_scale - 5.0), m_wl * np.ones_like(Y)
+
+
 def channel_weights(x_ref, edges, sub_scale, S):
     """[len(edges) - 1, S] fractional weights of the bordered columns for star-fixed channels: channel c covers
     [x* + edges[c], x* + edges[c + 1]) with x* = x_ref - sub_scale + 5, the star's bordered column; `edges` are offsets
@@ -177,7 +335,7 @@ def channel_weights(x_ref, edges, sub_scale, S):
 CHUNK_ROWS = 32            # rows of a chunk of a window (kExtractRows): partial sums are kept per chunk
 
 
-def algorithmic_bytes(plan, S, R, read_bytes=4, crrej=False):
+def algorithmic_bytes(plan, S, R, read_bytes=4, crrej=False, channels=False):
     """Bytes the extraction's kernels must move for `plan` on a frame of side S with R non-zero reads of `read_bytes`
     a sample: per pixel of product j's window the reads P_{j+1}, P_j, P_0 (P_0 once for j = 0 and for the last read),
     four coefficient planes, dark_{j+1} and dark_j (float32 each; dark_0 = 0 is not stored), the pixel flat and the
@@ -185,8 +343,13 @@ def algorithmic_bytes(plan, S, R, read_bytes=4, crrej=False):
     `crrej`: plus the mask kernel's -- per pixel of the mask rows the R + 1 reads, R dark planes, four coefficient planes
     and the pixel flat read once and the 2-byte flag word written; the word read again per window pixel; the chunks'
     counts (uint32 per chunk and column) written and read, and R + 1 counts written.  (The halo a tile re-reads and the
-    neighbours of a flagged pixel are not algorithmic.)"""
+    neighbours of a flagged pixel are not algorithmic.)  `channels` (the plan carries them): plus k_extract_bins' -- per
+    window pixel of the plan's column hull the same planes as above (and the flag word under `crrej`), four float32 flat
+    planes when the flat is divided out, the row's wl_a / wl_b (2 float64 per row); the chunks' sums (2 C float64 per
+    chunk) written and read once and channels [(R + 1) C] written."""
     total = 0
+    hull = (plan.hull[1] - plan.hull[0]) if channels and plan.channels is not None else 0
+    n_ch = plan.channels.n if hull or (channels and plan.channels is not None) else 0
     if crrej:
         lo, hi = plan.mask_rows
         total += (hi - lo) * S * ((R + 1) * read_bytes + 4 * R + 16 + 4 + 2) + (R + 1) * 4
@@ -205,7 +368,10 @@ def algorithmic_bytes(plan, S, R, read_bytes=4, crrej=False):
         total += rows * S * per_pixel + 2 * (2 * chunks * S * 8)
         if crrej:
             total += rows * S * 2 + 2 * (chunks * S * 4)
-    return total + (R + 1) * (S + 1) * 8
+        if n_ch:
+            total += rows * hull * (per_pixel + (2 if crrej else 0) + (16 if plan.channels.flat else 0))
+            total += rows * 16 + 2 * (chunks * 2 * n_ch * 8)
+    return total + (R + 1) * (S + 1) * 8 + (R + 1) * n_ch * 8
 
 
 class Delivery(object):
@@ -217,6 +383,7 @@ class Delivery(object):
     def __init__(self, ctx, reads=False):
         self.ctx, self.reads = ctx, reads
         self.rejected = None      # n_rejected [R + 1] of the last wait (None: that slot extracts without rejection)
+        self.channels = None      # channels [R + 1, C] of the last wait (None: that slot extracts without channels)
 
     def upload(self, slot, desc):
         self.ctx.upload(slot, desc)
@@ -233,20 +400,29 @@ class Delivery(object):
         reads = self.ctx.wait(slot) if self.reads else None
         spectra, sky = self.ctx.wait_spectra(slot)
         self.rejected = self.ctx.rejected(slot) if self.ctx.has_crrej(slot) else None
+        self.channels = self.ctx.channels(slot) if self.ctx.has_channels(slot) else None
         return reads, spectra, sky
 
 
-def save_npz(path, spectra, sky, exposure_index, plans, x_ref, y_ref, read_times, exp_start, rejected=None):
+def save_npz(path, spectra, sky, exposure_index, plans, x_ref, y_ref, read_times, exp_start, rejected=None, channels=None):
     """The file --spectra / --spectra-only write: spectra [n, R + 1, S], sky [n, R + 1], exposure_index [n], row_lo /
     row_hi [n, R + 1], bg_cols [2], x_ref / y_ref [n], read_times [R], exp_start [n].  With `rejected` [n, R + 1] (the
     exposures were extracted with cosmic-ray rejection) also n_rejected [n, R + 1] -- flags in each product's window,
-    (pixel, interval) pairs for the last-read product -- crrej_k and crrej_read_noise."""
+    (pixel, interval) pairs for the last-read product -- crrej_k and crrej_read_noise.  With `channels` [n, R + 1, C]
+    (the exposures were binned into wavelength channels) also channels, channel_edges_um [C + 1], channel_flat and the
+    rows' wavelength solutions wl_a / wl_b [n, S]."""
     n = len(exposure_index)
     more = {}
     if rejected is not None:
         cr = plans[0].crrej
         more = dict(n_rejected=np.asarray(rejected, dtype=np.uint32).reshape(n, -1), crrej_k=np.float64(cr.k),
                     crrej_read_noise=np.float64(cr.read_noise))
+    if channels is not None:
+        ch = plans[0].channels
+        more.update(channels=np.asarray(channels, dtype=np.float64), channel_edges_um=ch.edges_um.copy(),
+                    channel_flat=np.bool_(ch.flat),
+                    wl_a=np.array([p.row_solution[0] for p in plans], dtype=np.float64).reshape(n, -1),
+                    wl_b=np.array([p.row_solution[1] for p in plans], dtype=np.float64).reshape(n, -1))
     np.savez(path, **more, spectra=np.asarray(spectra, dtype=np.float64), sky=np.asarray(sky, dtype=np.float64),
              exposure_index=np.asarray(exposure_index, dtype=np.int64),
              row_lo=np.array([p.row_lo for p in plans], dtype=np.int64).reshape(n, -1),

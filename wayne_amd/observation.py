@@ -64,6 +64,8 @@ class Observation(object):
         # the reads are neither copied from the device nor written.  frame_options["crrej"] (True or an
         # extraction.CosmicRejection; CLI: --reject-cosmics) rejects cosmic rays in that extraction:
         # `spectra_result["rejected"]` and the .npz's n_rejected then hold each exposure's flag counts.
+        # frame_options["channels"] (an extraction.Channels; CLI: --channels LO:HI:N) bins that extraction into
+        # flat-fielded wavelength channels: `spectra_result["channels"]` [n, R + 1, C] and the .npz's channels.
         self.frame_options = {"out_dtype": np.float32}
         self.spectra_out = None
         self.spectra_only = False
@@ -345,7 +347,7 @@ class Observation(object):
         from .exposure import FitsWriterPool
         from .pipeline import run_pipelined
         pool = FitsWriterPool() if write_fits_raw else None
-        got_spectra = []              # (index, spectra, sky, plan, x_ref, y_ref, n_rejected or None) of every exposure, in delivery order
+        got_spectra = []              # (index, spectra, sky, plan, x_ref, y_ref, n_rejected or None, channels or None) of every exposure, in delivery order
 
         def prepare(i):
             gen = self._generate_exposure(self.exp_start_times[i], i + 1, write_fits=False, prepare_only=True)
@@ -357,8 +359,8 @@ class Observation(object):
                 reads, spectra, sky = reads
                 spectra, sky = np.array(spectra), np.array(sky)           # (copies: the pinned buffer is reused)
                 got_spectra.append((i, spectra, sky, gen.extraction_plan, gen.exp_info["x_ref"], gen.exp_info["y_ref"],
-                                    ctx.rejected))
-                frame = gen._fill_spectra(spectra, sky, ctx.rejected)
+                                    ctx.rejected, ctx.channels))
+                frame = gen._fill_spectra(spectra, sky, ctx.rejected, ctx.channels)
             if reads is not None:
                 frame = gen._fill_exposure(np.array(reads), gen._prepared[2])     # (a copy: the pinned buffer is reused)
             if pool is not None:
@@ -395,6 +397,8 @@ class Observation(object):
             exp_start=np.asarray(self.exp_start_times, dtype=float)[idx] if idx else np.zeros(0))
         if got and all(g[6] is not None for g in got):        # extracted with cosmic-ray rejection: the flag counts
             self.spectra_result["rejected"] = np.array([g[6] for g in got], dtype=np.uint32)
+        if got and all(g[7] is not None for g in got):        # binned into wavelength channels
+            self.spectra_result["channels"] = np.array([g[7] for g in got], dtype=np.float64)
         if not self.spectra_out:
             return None
         path = self.spectra_out
@@ -404,7 +408,7 @@ class Observation(object):
         r = self.spectra_result
         with open(path, "wb") as f:
             _extraction.save_npz(f, r["spectra"], r["sky"], r["exposure_index"], r["plans"], r["x_ref"], r["y_ref"],
-                                 r["read_times"], r["exp_start"], rejected=r.get("rejected"))
+                                 r["read_times"], r["exp_start"], rejected=r.get("rejected"), channels=r.get("channels"))
         return path
 
     @staticmethod

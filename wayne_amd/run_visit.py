@@ -2,6 +2,7 @@
 
     python -m wayne_amd.run_visit -p <parameter_file> [--calibration DIR] [--device N] [--max-exposures M] [--gpus G] [--resume]
                                   [--spectra OUT.npz | --spectra-only OUT.npz] [--reject-cosmics [K]]
+                                  [--channels LO:HI:N] [--no-channel-flat]
 
 Accepts the reference's parameter files (wayne/run_visit.py:1-9, example
 examples/hd209458b_12181_simulation_parameters.yml): sections `general`
@@ -30,7 +31,11 @@ examples/hd209458b_12181_simulation_parameters.yml): sections `general`
     `.rankNN` before the extension; they are not merged.  `--reject-cosmics [K]` (with either): cosmic rays are
     rejected on the difference images first, K sigma (default 8) above a pixel's stencil neighbours; OUT.npz then also
     holds n_rejected [n, NSAMP] -- the pixels replaced in each read interval's window and, last, the (pixel, interval)
-    pairs corrected in the last-read product -- crrej_k and crrej_read_noise;
+    pairs corrected in the last-read product -- crrej_k and crrej_read_noise.  `--channels LO:HI:N` (with either): every
+    exposure is also binned on the device into N wavelength channels of equal width between LO and HI um, each row by
+    its own wavelength solution and each pixel divided by the flat cube at its wavelength (`--no-channel-flat`: not
+    divided); OUT.npz then also holds channels [n, NSAMP, N], channel_edges_um [N + 1], channel_flat and the rows'
+    solutions wl_a / wl_b [n, S];
   * `--gpus G`: the process starts G rank processes itself (one per GPU of this node, before anything touches a
     GPU) and waits for them; under an external launcher (WORLD_SIZE / RANK set, one process per GPU) it is one
     rank.  Each rank generates its round-robin share of the exposures (observation.py:403-405 is the axis) on the
@@ -192,7 +197,25 @@ def run(argv=None):
                     help="with --spectra / --spectra-only: reject cosmic rays on the difference images before the column "
                          "sums, K sigma (default 8) above the largest stencil neighbour; OUT.npz then also holds n_rejected, "
                          "crrej_k and crrej_read_noise")
+    ap.add_argument("--channels", metavar="LO:HI:N", default=None,
+                    help="with --spectra / --spectra-only: also bin every exposure on the device into N wavelength channels "
+                         "of equal width between LO and HI um (flat-fielded at each pixel's wavelength); OUT.npz then also "
+                         "holds channels, channel_edges_um, channel_flat, wl_a and wl_b")
+    ap.add_argument("--no-channel-flat", action="store_true",
+                    help="with --channels: do not divide by the wavelength-dependent flat")
     args = ap.parse_args(argv)
+    channels = None
+    if args.no_channel_flat and args.channels is None:
+        raise SystemExit("--no-channel-flat needs --channels")
+    if args.channels is not None:
+        if not (args.spectra or args.spectra_only):
+            raise SystemExit("--channels needs --spectra or --spectra-only")
+        from .extraction import Channels
+        try:
+            lo, hi, n = args.channels.split(":")
+            channels = Channels.linear(float(lo), float(hi), int(n)).with_flat(not args.no_channel_flat)
+        except ValueError as e:
+            raise SystemExit("--channels LO:HI:N (um, um, 1 .. 256): %s" % e)
     if args.reject_cosmics is not None:
         if not (args.spectra or args.spectra_only):
             raise SystemExit("--reject-cosmics needs --spectra or --spectra-only")
@@ -254,6 +277,8 @@ def run(argv=None):
         if args.reject_cosmics is not None:
             from .extraction import CosmicRejection
             obs.frame_options["crrej"] = CosmicRejection(k=args.reject_cosmics)
+        if channels is not None:
+            obs.frame_options["channels"] = channels
         obs.spectra_out = args.spectra or args.spectra_only
         obs.spectra_only = bool(args.spectra_only)
     os.makedirs(obs.outdir, exist_ok=True)

@@ -133,7 +133,8 @@ class VisitRunner(object):
         (`extraction`: as in run) and 8 (R + 1)(S + 1) bytes of it reach the host -- the reads never leave the device.
         -> (spectra [n, R + 1, S], sky [n, R + 1]) in the order of `indices`; `self.plans` [n]: each exposure's
         extraction.Extraction; `self.rejected` [n, R + 1]: the flag counts of an extraction that rejects cosmic rays
-        (None otherwise)."""
+        (None otherwise); `self.channels` [n, R + 1, C]: the channel fluxes of an extraction that bins into wavelength
+        channels (None otherwise)."""
         eng = self.engine()
         indices = list(indices)
         where = {i: n for n, i in enumerate(indices)}
@@ -142,6 +143,7 @@ class VisitRunner(object):
         sky = np.empty((len(indices), R + 1))
         self.plans = [None] * len(indices)
         counts = [None] * len(indices)
+        binned = [None] * len(indices)
         delivery = _extraction.Delivery(eng.ctx, reads=False)
 
         def prepare(i):
@@ -155,9 +157,11 @@ class VisitRunner(object):
             spectra[where[i]], sky[where[i]] = sp, sk
             self.plans[where[i]] = gen.extraction_plan
             counts[where[i]] = delivery.rejected
+            binned[where[i]] = delivery.channels
 
         run_pipelined(delivery, indices, prepare, finish, self.DEPTH, self.DEPTH)
         self.rejected = None if any(n is None for n in counts) or not counts else np.array(counts, dtype=np.uint32)
+        self.channels = None if any(c is None for c in binned) or not binned else np.array(binned, dtype=np.float64)
         return spectra, sky
 
     def run_resident_spectra(self, n, on_spectra=None):
