@@ -493,7 +493,46 @@ int wayne_exposure_set_channels(wayne_ctx *ctx, int slot, const wayne_channels_d
 /* After wayne_exposure_wait_spectra / _download_spectra of a slot with channels: *channels [(R+1)*C], valid until the
  * slot's spectra are fetched or the slot is uploaded again.  WAYNE_E_STATE before any fetch or without channels. */
 int wayne_exposure_channels(wayne_ctx *ctx, int slot, const double **channels);
-/* HIP-event time of the extraction's kernels (the channels' included) while wayne_profile_enable is on, since
+/*
+ * Variances of the spectra, the sky levels and the channels (opt-in; without it nothing above changes: every launch and
+ * every byte of the spectra block stay as they are).  Added within WAYNE_ABI_VERSION 7: new symbols and a new struct only.
+ * Float64 throughout.  For product p and pixel (y, x) of its window let v be the term A_p[x] sums for that pixel (as
+ * for the channels above), g the extraction's gain factor, q = g / 2.35 (1 / pfl; 1 on the border) and rn = read_noise,
+ * the noise of a difference of two reads in electrons -- every product is one (wayne_crrej_desc.read_noise_e has the
+ * same meaning and the same default, 20):
+ *   var_p(y,x)        = max(v, 0) + rn^2 (q q)
+ *   VA_p[x]           = sum_{y in window p} var_p(y,x)
+ *   sky_var_p         = sum_{x in bg} VA_p[x] / (sum_{x in bg} B_p[x])^2       (0 where sky_p is 0 by its rule)
+ *   spectra_var_p[x]  = VA_p[x] + (B_p[x] B_p[x]) sky_var_p
+ *   VP_p[b]           = sum_y sum_x (w_b w_b) (var_p(y,x) / (F F))
+ *   channels_var_p[b] = VP_p[b] + (Q_p[b] Q_p[b]) sky_var_p
+ * with w_b, F, B_p, Q_p, the windows, the hull and the background columns of the laws above.  Zeros for p = R when
+ * WAYNE_X_LAST_READ is off; sky_var = 0 when WAYNE_X_SKY is off.  The sums follow the order of the flux sums (no
+ * atomics): the same exposure gives the same bytes in any slot, on either stream, after a second run.  No plane is read a
+ * second time: a pixel's variance is formed beside its flux.
+ * Left out: the covariance between a background column's own flux and the sky level (such a column's variance counts
+ * its own pixels twice, once through sky_var_p); the correlation between neighbouring channels that share a pixel, and
+ * through the common sky level; the correlation of read intervals through the read they share -- in a sum over
+ * consecutive intervals the Poisson parts add, but the read noise is that of the first and the last read alone, i.e. of
+ * the last-read product over the same rows, not R times it; the variance of a rejected pixel's replacement, which is
+ * taken from the replacement's own value as if it were a measured pixel.
+ */
+typedef struct wayne_variance_desc {
+  double read_noise; /* rn (e-) of a difference of two reads: finite, >= 0 */
+} wayne_variance_desc;
+
+/* After wayne_exposure_set_extraction, before run: deliver variances with the slot's extraction (v = NULL clears; upload
+ * and set_extraction clear it too, set_crrej and set_channels do not -- with channels, before or after, channels_var is
+ * delivered too).  WAYNE_E_STATE when no extraction is set on the slot; WAYNE_E_INVALID (the slot stays usable,
+ * extracting without variances) for a negative or non-finite read_noise or when WAYNE_X_GAIN is off: a variance is in
+ * electrons^2.  The variances ride in the same copy as the spectra, behind the channels. */
+int wayne_exposure_set_variance(wayne_ctx *ctx, int slot, const wayne_variance_desc *v);
+/* After wayne_exposure_wait_spectra / _download_spectra of a slot with variances: *spectra_var [(R+1)*S], *sky_var [R+1]
+ * and *channels_var [(R+1)*C] (NULL without channels), valid until the slot's spectra are fetched or the slot is uploaded
+ * again.  WAYNE_E_STATE before any fetch or without variances. */
+int wayne_exposure_variances(wayne_ctx *ctx, int slot, const double **spectra_var, const double **sky_var,
+                             const double **channels_var);
+/* HIP-event time of the extraction's kernels (the channels' and the variances' included) while wayne_profile_enable is on, since
  * wayne_profile_reset: launches (one per extracted exposure) and total milliseconds.  wayne_profile_select's bit 8
  * selects it.  Synchronises. */
 int wayne_extract_profile(wayne_ctx *ctx, uint64_t *launches, double *ms);

@@ -106,6 +106,10 @@ class ChannelsDesc(C.Structure):
     _fields_ = [("n_channels", C.c_int), ("edges_um", _dp), ("wl_a", _dp), ("wl_b", _dp), ("flags", C.c_uint32)]
 
 
+class VarianceDesc(C.Structure):
+    _fields_ = [("read_noise", C.c_double)]
+
+
 class Profile(C.Structure):
     _fields_ = [("name", C.c_char_p * PROF_KERNELS), ("launches", C.c_uint64 * PROF_KERNELS),
                 ("ms", C.c_double * PROF_KERNELS), ("electrons", C.c_uint64)]
@@ -161,6 +165,8 @@ SYMBOLS = {
     "wayne_exposure_download_crmask": (C.c_int, [_vp, C.c_int, _vp]),
     "wayne_exposure_set_channels": (C.c_int, [_vp, C.c_int, C.POINTER(ChannelsDesc)]),
     "wayne_exposure_channels": (C.c_int, [_vp, C.c_int, C.POINTER(_dp)]),
+    "wayne_exposure_set_variance": (C.c_int, [_vp, C.c_int, C.POINTER(VarianceDesc)]),
+    "wayne_exposure_variances": (C.c_int, [_vp, C.c_int, C.POINTER(_dp), C.POINTER(_dp), C.POINTER(_dp)]),
     "wayne_extract_profile": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_double)]),
     "wayne_profile_enable": (C.c_int, [_vp, C.c_int]),
     "wayne_profile_select": (C.c_int, [_vp, C.c_uint]),
@@ -284,6 +290,7 @@ class Context(object):
         self._slot_src = {}      # slot -> bins of each of its contaminants
         self._slot_crrej = set() # slots whose extraction rejects cosmic rays
         self._slot_chan = {}     # slot -> channels of its extraction (set_channels succeeded)
+        self._slot_var = set()   # slots whose extraction delivers variances (set_variance succeeded)
         _live_contexts.add(self)
         for name, value in _knob_defaults.items():
             self.set_knob(name, value)
@@ -406,6 +413,7 @@ class Context(object):
         self._slot_src[slot] = ()
         self._slot_crrej.discard(slot)
         self._slot_chan.pop(slot, None)
+        self._slot_var.discard(slot)
         sources = getattr(desc, "_sources", None)
         if sources:
             self.set_sources(slot, sources)
@@ -451,6 +459,7 @@ class Context(object):
         the slot then forms spectra [R + 1, S] and sky [R + 1] on the device.  See wayne_exposure_set_extraction."""
         self._slot_crrej.discard(slot)
         self._slot_chan.pop(slot, None)
+        self._slot_var.discard(slot)
         if extraction is None:
             self.check(self._L.wayne_exposure_set_extraction(self._h, int(slot), None))
             return
@@ -459,6 +468,39 @@ class Context(object):
             self.set_crrej(slot, extraction.crrej)
         if getattr(extraction, "channels", None) is not None:
             self.set_channels(slot, extraction.channels, extraction.row_solution)
+        if getattr(extraction, "variance", None) is not None:
+            self.set_variance(slot, extraction.variance)
+
+    def set_variance(self, slot, variance):
+        """Variances with the slot's extraction: an extraction.Variances (the read noise of a difference of two reads, in
+        electrons) or True for its default -- None clears; after set_extraction, which clears it too (set_crrej and
+        set_channels do not).  See wayne_exposure_set_variance."""
+        self._slot_var.discard(slot)             # (a refusal leaves the slot extracting without variances)
+        if variance is None or variance is False:
+            self.check(self._L.wayne_exposure_set_variance(self._h, int(slot), None))
+            return
+        if variance is True:
+            d = VarianceDesc(20.0)
+        else:
+            d = variance.desc() if hasattr(variance, "desc") else VarianceDesc(float(variance))
+        self.check(self._L.wayne_exposure_set_variance(self._h, int(slot), C.byref(d)))
+        self._slot_var.add(slot)
+
+    def has_variance(self, slot):
+        """Whether the slot's extraction delivers variances (set_variance succeeded since its last set_extraction)."""
+        return slot in self._slot_var
+
+    def variances(self, slot):
+        """(spectra_var [R + 1, S], sky_var [R + 1], channels_var [R + 1, C] or None without channels) -- float64 copies --
+        of the slot's last wait_spectra / download_spectra."""
+        K, W, R, _ = self._slot_meta[slot]
+        ps, pk, pc = _dp(), _dp(), _dp()
+        self.check(self._L.wayne_exposure_variances(self._h, int(slot), C.byref(ps), C.byref(pk), C.byref(pc)))
+        spectra_var = np.ctypeslib.as_array(ps, shape=(R + 1, self.S)).copy()
+        sky_var = np.ctypeslib.as_array(pk, shape=(R + 1,)).copy()
+        n_ch = self._slot_chan.get(slot)
+        channels_var = np.ctypeslib.as_array(pc, shape=(R + 1, n_ch)).copy() if (pc and n_ch) else None
+        return spectra_var, sky_var, channels_var
 
     def set_channels(self, slot, channels, row_solution=None):
         """Wavelength-binned channels of the slot's extraction: an extraction.Channels (edges in um, flat on / off) and

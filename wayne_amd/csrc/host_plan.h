@@ -14,6 +14,7 @@
 //   extract_desc_error   wayne_exposure_set_extraction's argument check (the windows k_extract walks stay inside the frame)
 //   crrej_desc_error     wayne_exposure_set_crrej's argument check; crrej_mask_rows: the rows k_extract_crmask writes
 //   channels_desc_error  wayne_exposure_set_channels' argument check, and the column hull k_extract_bins walks
+//   variance_desc_error  wayne_exposure_set_variance's argument check
 //
 // Reference: the reach of the thrower bounds pyparallel_menu.c:87-108 as the device modes implement it; the trace is
 // grism.py:491-506, 779-803 (trace_coeffs, plan_consts.h); the frame offset exposure_generator.py:630-645.
@@ -454,6 +455,14 @@ inline const char* crrej_desc_error(unsigned steps, double k, double read_noise_
   if (!(std::isfinite(k) && k > 0.)) return "k must be finite and > 0";
   if (!(std::isfinite(read_noise_e) && read_noise_e >= 0.)) return "read_noise_e must be finite and >= 0";
   if (!(steps & X_GAIN)) return "rejection needs WAYNE_X_GAIN: its noise model is in electrons";
+  return nullptr;
+}
+
+// wayne_exposure_set_variance's argument check (include/wayne_hip.h: wayne_variance_desc) against the extraction's
+// `steps`: null when valid.  A variance is in electrons^2, so the gain step must be on.
+inline const char* variance_desc_error(unsigned steps, double read_noise) {
+  if (!(std::isfinite(read_noise) && read_noise >= 0.)) return "read_noise must be finite and >= 0";
+  if (!(steps & X_GAIN)) return "variances need WAYNE_X_GAIN: they are in electrons";
   return nullptr;
 }
 

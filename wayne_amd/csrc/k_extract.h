@@ -44,6 +44,22 @@
 // columns in ascending x; the waves are added in wave order -> scratch [chunk][group][p][2][C].  k_extract_bins_finish,
 // behind k_extract_finish for sky_p, adds the groups of a chunk and then the chunks in ascending order.
 //
+// Variances (wayne_exposure_set_variance; off unless asked for -- VAR = false gives the instantiations of the lines above,
+// and those are the ones launched without it).  With v as above, g the gain factor, q = g / 2.35 and rn the read noise of
+// a difference of two reads (every product is one):
+//   var_p(y, x) = max(v, 0) + rn^2 (q q)
+//   VA_p[x] = sum_y var_p,   sky_var_p = sum_{x in bg} VA_p[x] / (sum_{x in bg} B_p[x])^2  (0 where sky_p is 0 by its rule)
+//   spectra_var_p[x] = VA_p[x] + (B_p[x] B_p[x]) sky_var_p
+//   VP_p[b] = sum_y sum_x (w_b w_b) (var_p / (F F)),   channels_var_p[b] = VP_p[b] + (Q_p[b] Q_p[b]) sky_var_p
+// No plane is read for them: a pixel's variance is formed from the v and g its flux was formed from, and summed in the
+// order of the flux sums (k_extract_rows / _finish: a third sum beside A and T -> part_v [chunk][product][S]).
+// k_extract_bins<.., true> keeps the 48 KB of LDS, and with them three workgroups per CU: a lane holds var / F^2 of its
+// (at most 6) columns of the row in registers while the channels gather v / F and t / F, then the wave writes them over
+// its v / F buffer and the channels gather them with w^2 -- one more pair of barriers and the weights formed twice, against
+// a third 24 KB row buffer that would leave two workgroups per CU.  The waves' sums [wave][C] lie behind [wave][2][C].
+// With rejection the row's chain is the register peak, so the VAR instantiations load the channel edges behind it: 117
+// VGPRs, 4 waves / SIMD as without variances (loaded ahead of it: 137 and 3).  No instantiation uses scratch memory.
+//
 // The file is compiled without FMA contraction (wayne_amd/build.py), so a pixel's chain rounds as the numpy statement
 // of it does; what differs from numpy is the order of the row sums alone.
 #pragma once
@@ -77,7 +93,18 @@ struct ExtractArgs {
   unsigned* n_rej;                   // [R+1]
   int m_lo, m_hi;
   double k2, rn2;                    // k^2, rn^2
+  // variances (null / 0 without them)
+  double vrn2;                       // rn^2 of the variance law
+  double* part_v;                    // [n_chunks][R+1][S]: sums of var
+  double* spectra_var;               // [(R+1)*S]
+  double* sky_var;                   // [R+1]
 };
+
+// var_p of one pixel from the term v its flux sums and its gain factor g
+__device__ __forceinline__ double extract_var(double v, double g, double rn2) {
+  const double q = g / 2.35;
+  return fmax(v, 0.) + rn2 * (q * q);
+}
 
 // L_r of one pixel (r >= 1); `lin`: the four coefficients are in c[]
 template <class T>
@@ -197,7 +224,7 @@ __global__ void __launch_bounds__(kExtractThreads) k_extract_crmask(ExtractArgs 
   }
 }
 
-template <class T, bool CR>
+template <class T, bool CR, bool VAR>
 __global__ void __launch_bounds__(kExtractThreads) k_extract_rows(ExtractArgs a) {
   int p = 0;
   while (p < a.R && (int)blockIdx.y >= a.first_chunk[p + 1]) ++p;     // (wave-uniform: at most R steps)
@@ -214,6 +241,7 @@ __global__ void __launch_bounds__(kExtractThreads) k_extract_rows(ExtractArgs a)
   const bool lin = (a.steps & X_LINEARISE) && a.lin[0];
   const bool gain = (a.steps & X_GAIN) && a.pfl, sky = (a.steps & X_SKY) && a.sky;
   double sA = 0., sT = 0.;
+  [[maybe_unused]] double sV = 0.;
   unsigned n_flag = 0u;
   if (x < S) {
     for (int y = lo + wave; y < hi; y += kExtractWaves) {
@@ -240,6 +268,11 @@ __global__ void __launch_bounds__(kExtractThreads) k_extract_rows(ExtractArgs a)
           v -= corr;
         }
         sA += v;
+        if constexpr (VAR) sV += extract_var(v, g, a.vrn2);
+      } else if constexpr (VAR) {
+        const double v = (Lh - Ll) * g;
+        sA += v;
+        sV += extract_var(v, g, a.vrn2);
       } else {
         sA += (Lh - Ll) * g;
       }
@@ -251,6 +284,8 @@ __global__ void __launch_bounds__(kExtractThreads) k_extract_rows(ExtractArgs a)
   sh[1][wave][lane] = sT;
   __shared__ unsigned sh_n[CR ? kExtractWaves : 1][64];
   if constexpr (CR) sh_n[wave][lane] = n_flag;
+  __shared__ double sh_v[VAR ? kExtractWaves : 1][64];
+  if constexpr (VAR) sh_v[wave][lane] = sV;
   __syncthreads();
   if (wave == 0 && x < S) {
     double tA = sh[0][0][lane], tT = sh[1][0][lane];
@@ -264,10 +299,15 @@ __global__ void __launch_bounds__(kExtractThreads) k_extract_rows(ExtractArgs a)
       for (int w = 0; w < kExtractWaves; ++w) n += sh_n[w][lane];
       a.part_n[at] = n;
     }
+    if constexpr (VAR) {
+      double tV = sh_v[0][lane];
+      for (int w = 1; w < kExtractWaves; ++w) tV += sh_v[w][lane];
+      a.part_v[at] = tV;
+    }
   }
 }
 
-template <bool CR>
+template <bool CR, bool VAR>
 __global__ void __launch_bounds__(kExtractThreads) k_extract_finish(ExtractArgs a) {
   const int p = (int)blockIdx.x, S = a.S, NP = a.R + 1;
   const int tid = (int)threadIdx.x;
@@ -275,25 +315,34 @@ __global__ void __launch_bounds__(kExtractThreads) k_extract_finish(ExtractArgs 
     for (int x = tid; x < S; x += kExtractThreads) a.spectra[(size_t)p * S + x] = 0.;
     if (tid == 0) a.sky_out[p] = 0.;
     if (CR && tid == 0) a.n_rej[p] = 0u;
+    if constexpr (VAR) {
+      for (int x = tid; x < S; x += kExtractThreads) a.spectra_var[(size_t)p * S + x] = 0.;
+      if (tid == 0) a.sky_var[p] = 0.;
+    }
     return;
   }
   __shared__ double shA[kExtractMaxS], shB[kExtractMaxS];
   __shared__ double shR[2][64];
   __shared__ double sh_sky;
+  __shared__ double shV[VAR ? kExtractMaxS : 1], shRV[VAR ? 64 : 1];
+  __shared__ double sh_skyvar;
   const int rows = a.row_hi[p] - a.row_lo[p];
   const int chunks = (rows + kExtractRows - 1) / kExtractRows;
   const size_t half = (size_t)a.n_chunks * NP * S;
   unsigned n_flag = 0u;
   for (int x = tid; x < S; x += kExtractThreads) {
     double A = 0., T = 0.;
+    [[maybe_unused]] double V = 0.;
     for (int c = 0; c < chunks; ++c) {                   // ascending chunks
       const size_t at = ((size_t)c * NP + p) * S + x;
       A += a.part[at];
       T += a.part[half + at];
       if constexpr (CR) n_flag += a.part_n[at];
+      if constexpr (VAR) V += a.part_v[at];
     }
     shA[x] = A;
     shB[x] = a.scale[p] * T;
+    if constexpr (VAR) shV[x] = V;
   }
   __shared__ unsigned shN[CR ? kExtractThreads : 1];
   if constexpr (CR) shN[tid] = n_flag;
@@ -303,6 +352,11 @@ __global__ void __launch_bounds__(kExtractThreads) k_extract_finish(ExtractArgs 
     for (int x = a.bg_lo + tid; x < a.bg_hi; x += 64) { sa += shA[x]; sb += shB[x]; }
     shR[0][tid] = sa;
     shR[1][tid] = sb;
+    if constexpr (VAR) {
+      double sv = 0.;
+      for (int x = a.bg_lo + tid; x < a.bg_hi; x += 64) sv += shV[x];
+      shRV[tid] = sv;
+    }
   }
   __syncthreads();
   if (tid == 0) {
@@ -310,6 +364,12 @@ __global__ void __launch_bounds__(kExtractThreads) k_extract_finish(ExtractArgs 
     for (int l = 0; l < 64; ++l) { sa += shR[0][l]; sb += shR[1][l]; }
     sh_sky = ((a.steps & X_SKY) && sb != 0.) ? sa / sb : 0.;
     a.sky_out[p] = sh_sky;
+    if constexpr (VAR) {
+      double sv = 0.;
+      for (int l = 0; l < 64; ++l) sv += shRV[l];
+      sh_skyvar = ((a.steps & X_SKY) && sb != 0.) ? sv / (sb * sb) : 0.;
+      a.sky_var[p] = sh_skyvar;
+    }
     if constexpr (CR) {
       unsigned n = 0u;
       for (int t = 0; t < kExtractThreads; ++t) n += shN[t];
@@ -319,6 +379,10 @@ __global__ void __launch_bounds__(kExtractThreads) k_extract_finish(ExtractArgs 
   __syncthreads();
   const double s = sh_sky;
   for (int x = tid; x < S; x += kExtractThreads) a.spectra[(size_t)p * S + x] = shA[x] - s * shB[x];
+  if constexpr (VAR) {
+    const double sv = sh_skyvar;
+    for (int x = tid; x < S; x += kExtractThreads) a.spectra_var[(size_t)p * S + x] = shV[x] + (shB[x] * shB[x]) * sv;
+  }
 }
 
 // ---- wavelength-binned channels (wayne_exposure_set_channels) ----
@@ -335,12 +399,15 @@ struct ChannelArgs {
   const float* cube[4];              // [N*N] each, or null
   double* part;                      // [n_chunks][kChanGroups][R+1][2][C]: a row group's P, then its Q / scale
   double* channels;                  // [(R+1)*C]
+  // variances (null without them)
+  double* part_v;                    // [n_chunks][kChanGroups][R+1][C]: a row group's VP
+  double* channels_var;              // [(R+1)*C]
 };
 
 // the term k_extract_rows adds to A_p[x] for pixel `pix` = y S + x (the same operations in the same order)
 template <class T, bool CR>
 __device__ __forceinline__ double extract_term(const ExtractArgs& a, const T* reads, size_t SS, size_t pix, int p, int r_hi,
-                                               int r_lo, bool lin, bool gain) {
+                                               int r_lo, bool lin, bool gain, double* g_out = nullptr) {
   const double p0 = (double)reads[pix];
   double c[4] = {0., 0., 0., 0.};
   if (lin)
@@ -348,6 +415,7 @@ __device__ __forceinline__ double extract_term(const ExtractArgs& a, const T* re
   const double Lh = extract_linear<T>(a, reads, SS, pix, r_hi, p0, lin, c);
   const double Ll = r_lo > 0 ? extract_linear<T>(a, reads, SS, pix, r_lo, p0, lin, c) : 0.;
   const double g = (a.steps & X_GAIN) ? (gain ? 2.35 / (double)a.pfl[pix] : 2.35) : 1.0;
+  if (g_out) *g_out = g;
   double v = (Lh - Ll) * g;
   if constexpr (CR) {
     const unsigned m = a.mask[pix];
@@ -365,18 +433,40 @@ __device__ __forceinline__ double extract_term(const ExtractArgs& a, const T* re
   return v;
 }
 
+// F(y, x) of the channels' law (`y_in`: the row is no border row)
+__device__ __forceinline__ double chan_flat(const ChannelArgs& ch, int y, int x, double wa, double wb, bool y_in, int S) {
+  double F = 1.;
+  if (ch.flat && y_in && x >= kBorder && x < S - kBorder) {
+    const double tau = (1e4 * (wa + wb * (double)x) - ch.flat_wmin) / (ch.flat_wmax - ch.flat_wmin);
+    const double t2 = tau * tau, t3 = t2 * tau;
+    const size_t fi = (size_t)(y - kBorder) * ch.N + (x - kBorder);
+    const double f = (double)ch.cube[0][fi] + ((double)ch.cube[1][fi] * tau) + ((double)ch.cube[2][fi] * t2) +
+                     ((double)ch.cube[3][fi] * t3);
+    F = (double)(float)f;
+    if (!(F > 0.)) F = 1.;
+  }
+  return F;
+}
+
 constexpr int kChanPasses = (kChanMaxChannels + 63) / 64;             // channels a lane carries: 4
 constexpr int kChanGroups = kExtractRows / kExtractWaves;            // groups of 8 rows (one per wave) in a chunk: 4
 static_assert(kExtractRows % kExtractWaves == 0, "k_extract_bins: a chunk is a whole number of row groups");
 // the waves' sums red[kExtractWaves][2][C] reuse the row buffers buf[kExtractWaves][2][kChanMaxHull]
 static_assert(kExtractWaves * 2 * kChanMaxChannels <= kExtractWaves * 2 * kChanMaxHull,
               "k_extract_bins: the waves' sums of the widest channel plan must fit the row buffers they reuse");
+constexpr int kChanStrips = kChanMaxHull / 64;                       // 64-column strips of the widest hull: 6
+static_assert(kChanMaxHull % 64 == 0, "k_extract_bins: a lane keeps one value per 64-column strip of the hull");
+// with variances the waves' sums are red[kExtractWaves][2][C], then redv[kExtractWaves][C]
+static_assert(kExtractWaves * 3 * kChanMaxChannels <= kExtractWaves * 2 * kChanMaxHull,
+              "k_extract_bins: the waves' sums with variances must fit the row buffers they reuse");
 
 // One workgroup per (chunk of a product's window -- the chunk list of k_extract_rows -- , group blockIdx.y of 8 rows of
 // it).  Wave w takes row w of the group: it writes v / F and t / F of the hull's columns into its row buffers, 64 columns
 // at a time, then lane = channel (kChanPasses passes) gathers [ua_b, ua_{b+1}) from them in ascending x.  A row past
-// the window's end adds nothing (its group still writes its zeros), so the barriers are uniform.
-template <class T, bool CR>
+// the window's end adds nothing (its group still writes its zeros), so the barriers are uniform.  VAR: a lane keeps
+// var / F^2 of its columns (one per strip) in registers meanwhile; the wave then writes them over its v / F buffer and the
+// channels gather them with w^2.
+template <class T, bool CR, bool VAR>
 __global__ void __launch_bounds__(kExtractThreads) k_extract_bins(ExtractArgs a, ChannelArgs ch) {
   int p = 0;
   while (p < a.R && (int)blockIdx.x >= a.first_chunk[p + 1]) ++p;
@@ -397,33 +487,54 @@ __global__ void __launch_bounds__(kExtractThreads) k_extract_bins(ExtractArgs a,
   for (int k = 0; k < kChanPasses; ++k) {
     const int b = k * 64 + lane;
     P[k] = 0.; Q[k] = 0.;
-    e0[k] = b < C ? ch.edges[b] : 0.;
-    e1[k] = b < C ? ch.edges[b + 1] : 0.;
+    if constexpr (!VAR) {
+      e0[k] = b < C ? ch.edges[b] : 0.;
+      e1[k] = b < C ? ch.edges[b + 1] : 0.;
+    }
   }
   const int group = (int)blockIdx.y;
   const int y = lo + wave + group * kExtractWaves;
   const bool row = y < hi;                                 // (wave-uniform)
   double wa = 0., wb = 1.;
+  [[maybe_unused]] double vr[VAR ? kChanStrips : 1];           // var / F^2 of column lane + 64 s of the hull
   if (row) {
     wa = ch.wl_a[y]; wb = ch.wl_b[y];
     const bool y_in = y >= kBorder && y < S - kBorder;
-    for (int o = lane; o < W; o += 64) {
-      const int x = ch.u_lo + o;
-      const size_t pix = (size_t)y * S + x;
-      const double v = extract_term<T, CR>(a, reads, SS, pix, p, r_hi, r_lo, lin, gain);
-      const double t = sky ? (double)a.sky[pix] : 0.;
-      double F = 1.;
-      if (ch.flat && y_in && x >= kBorder && x < S - kBorder) {
-        const double tau = (1e4 * (wa + wb * (double)x) - ch.flat_wmin) / (ch.flat_wmax - ch.flat_wmin);
-        const double t2 = tau * tau, t3 = t2 * tau;
-        const size_t fi = (size_t)(y - kBorder) * ch.N + (x - kBorder);
-        const double f = (double)ch.cube[0][fi] + ((double)ch.cube[1][fi] * tau) + ((double)ch.cube[2][fi] * t2) +
-                         ((double)ch.cube[3][fi] * t3);
-        F = (double)(float)f;
-        if (!(F > 0.)) F = 1.;
+    if constexpr (VAR) {
+#pragma unroll
+      for (int s = 0; s < kChanStrips; ++s) {
+        const int o = lane + 64 * s;
+        vr[s] = 0.;
+        if (o < W) {
+          const int x = ch.u_lo + o;
+          const size_t pix = (size_t)y * S + x;
+          double g;
+          const double v = extract_term<T, CR>(a, reads, SS, pix, p, r_hi, r_lo, lin, gain, &g);
+          const double t = sky ? (double)a.sky[pix] : 0.;
+          const double F = chan_flat(ch, y, x, wa, wb, y_in, S);
+          bv[o] = v / F;
+          bt[o] = t / F;
+          vr[s] = extract_var(v, g, a.vrn2) / (F * F);
+        }
       }
-      bv[o] = v / F;
-      bt[o] = t / F;
+    } else {
+      for (int o = lane; o < W; o += 64) {
+        const int x = ch.u_lo + o;
+        const size_t pix = (size_t)y * S + x;
+        const double v = extract_term<T, CR>(a, reads, SS, pix, p, r_hi, r_lo, lin, gain);
+        const double t = sky ? (double)a.sky[pix] : 0.;
+        const double F = chan_flat(ch, y, x, wa, wb, y_in, S);
+        bv[o] = v / F;
+        bt[o] = t / F;
+      }
+    }
+  }
+  if constexpr (VAR) {                                       // (the edges only now: the row's chain needs the registers)
+#pragma unroll
+    for (int k = 0; k < kChanPasses; ++k) {
+      const int b = k * 64 + lane;
+      e0[k] = b < C ? ch.edges[b] : 0.;
+      e1[k] = b < C ? ch.edges[b + 1] : 0.;
     }
   }
   __syncthreads();
@@ -443,15 +554,42 @@ __global__ void __launch_bounds__(kExtractThreads) k_extract_bins(ExtractArgs a,
       }
     }
   }
+  [[maybe_unused]] double V[VAR ? kChanPasses : 1];
+  if constexpr (VAR) {
+    __syncthreads();                                         // v / F has been gathered: the buffer takes var / F^2
+    if (row) {
+#pragma unroll
+      for (int s = 0; s < kChanStrips; ++s) {
+        const int o = lane + 64 * s;
+        if (o < W) bv[o] = vr[s];
+      }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < kChanPasses; ++k) {
+      V[k] = 0.;
+      if (row && k * 64 + lane < C) {
+        const double ua0 = (e0[k] - wa) / wb, ua1 = (e1[k] - wa) / wb;
+        const int xs = (int)fmin(fmax(floor(ua0), (double)ch.u_lo), (double)ch.u_hi);
+        const int xe = (int)fmin(fmax(ceil(ua1), (double)ch.u_lo), (double)ch.u_hi);
+        for (int x = xs; x < xe; ++x) {
+          const double w = fmin(fmax(fmin((double)x + 1.0, ua1) - fmax((double)x, ua0), 0.), 1.);
+          V[k] += (w * w) * bv[x - ch.u_lo];
+        }
+      }
+    }
+  }
   __syncthreads();
   // the waves' sums, added in wave order: the row buffers are free now (the barrier above)
   double* red = &buf[0][0][0];                               // [kExtractWaves][2][C]
+  [[maybe_unused]] double* redv = red + (size_t)kExtractWaves * 2 * C;   // [kExtractWaves][C] (VAR)
 #pragma unroll
   for (int k = 0; k < kChanPasses; ++k) {
     const int b = k * 64 + lane;
     if (b < C) {
       red[((size_t)wave * 2 + 0) * C + b] = P[k];
       red[((size_t)wave * 2 + 1) * C + b] = Q[k];
+      if constexpr (VAR) redv[(size_t)wave * C + b] = V[k];
     }
   }
   __syncthreads();
@@ -461,14 +599,26 @@ __global__ void __launch_bounds__(kExtractThreads) k_extract_bins(ExtractArgs a,
     for (int w = 1; w < kExtractWaves; ++w) t += red[(size_t)w * 2 * C + i];
     ch.part[(((size_t)chunk * kChanGroups + group) * NP + p) * 2 * C + i] = t;
   }
+  if constexpr (VAR) {
+    for (int i = (int)threadIdx.x; i < C; i += kExtractThreads) {
+      double t = redv[i];
+      for (int w = 1; w < kExtractWaves; ++w) t += redv[(size_t)w * C + i];
+      ch.part_v[(((size_t)chunk * kChanGroups + group) * NP + p) * C + i] = t;
+    }
+  }
 }
 
 // Behind k_extract_finish (it reads sky_p): one workgroup per product adds the row groups in ascending order and writes
-// channels_p[b] = P_p[b] - sky_p (scale_p Q_p[b]).
+// channels_p[b] = P_p[b] - sky_p (scale_p Q_p[b]); VAR: and channels_var_p[b] = VP_p[b] + (scale_p Q_p[b])^2 sky_var_p.
+template <bool VAR>
 __global__ void __launch_bounds__(kChanMaxChannels) k_extract_bins_finish(ExtractArgs a, ChannelArgs ch) {
   const int p = (int)blockIdx.x, b = (int)threadIdx.x, C = ch.C, NP = a.R + 1;
   if (b >= C) return;
-  if (p == a.R && !(a.steps & X_LAST_READ)) { ch.channels[(size_t)p * C + b] = 0.; return; }
+  if (p == a.R && !(a.steps & X_LAST_READ)) {
+    ch.channels[(size_t)p * C + b] = 0.;
+    if constexpr (VAR) ch.channels_var[(size_t)p * C + b] = 0.;
+    return;
+  }
   const int rows = a.row_hi[p] - a.row_lo[p];
   const int chunks = (rows + kExtractRows - 1) / kExtractRows;
   double P = 0., Q = 0.;
@@ -478,6 +628,12 @@ __global__ void __launch_bounds__(kChanMaxChannels) k_extract_bins_finish(Extrac
     Q += ch.part[at + C + b];
   }
   ch.channels[(size_t)p * C + b] = P - a.sky_out[p] * (a.scale[p] * Q);
+  if constexpr (VAR) {
+    double V = 0.;
+    for (int c = 0; c < chunks * kChanGroups; ++c) V += ch.part_v[((size_t)c * NP + p) * C + b];
+    const double Qs = a.scale[p] * Q;
+    ch.channels_var[(size_t)p * C + b] = V + (Qs * Qs) * a.sky_var[p];
+  }
 }
 
 }  // namespace wayne

@@ -229,6 +229,15 @@ struct Slot : SourceState {
   DevBuf ch_edges, ch_wa, ch_wb, ch_part;
   const double* ch_res = nullptr;
   std::vector<double> ch_host;
+  // variances of the extraction (wayne_exposure_set_variance; cleared by upload and set_extraction, not by set_crrej or
+  // set_channels): the chunks' sums [chunks][R+1][S] and, with channels, the row groups' [chunks][4][R+1][C]; the result --
+  // spectra_var [(R+1)*S], sky_var [R+1] and, with channels, channels_var [(R+1)*C] -- behind everything else in ex_out,
+  // 8-byte aligned.  `var_res`: that block as the last wait_spectra / download_spectra brought it back (null before any)
+  bool var_on = false;
+  double var_rn = 0.;
+  DevBuf ex_part_v, ch_part_v;
+  const double* var_res = nullptr;
+  std::vector<double> var_host;
   // staging arena of the descriptor's arrays: uploads are enqueued from here, so
   // wayne_exposure_upload returns without waiting for the slot's stream to drain
   StageArena stage;
@@ -647,6 +656,29 @@ size_t channels_offset(const wayne_ctx* c, const Slot& s) {
   return (b + 7) & ~(size_t)7;
 }
 
+// Where the variances begin in a slot's spectra block: behind everything else (the channels, if any), on a multiple of
+// 8 bytes; and their doubles: spectra_var [(R+1)*S], sky_var [R+1], with channels channels_var [(R+1)*C].
+size_t variance_offset(const wayne_ctx* c, const Slot& s) {
+  return channels_offset(c, s) + (s.chan_on ? (size_t)(s.R + 1) * s.ch_C * sizeof(double) : 0);
+}
+size_t variance_count(const wayne_ctx* c, const Slot& s) {
+  return (size_t)(s.R + 1) * ((size_t)c->S + 1 + (s.chan_on ? (size_t)s.ch_C : 0));
+}
+
+template <bool CR, bool VAR>
+void launch_bins(int out, dim3 grid, dim3 block, hipStream_t st, const ExtractArgs& a, const ChannelArgs& ch) {
+  if (out == 1) hipLaunchKernelGGL((k_extract_bins<double, CR, VAR>), grid, block, 0, st, a, ch);
+  else if (out == 2) hipLaunchKernelGGL((k_extract_bins<uint16_t, CR, VAR>), grid, block, 0, st, a, ch);
+  else hipLaunchKernelGGL((k_extract_bins<float, CR, VAR>), grid, block, 0, st, a, ch);
+}
+
+template <bool CR, bool VAR>
+void launch_rows(int out, dim3 grid, dim3 block, hipStream_t st, const ExtractArgs& a) {
+  if (out == 1) hipLaunchKernelGGL((k_extract_rows<double, CR, VAR>), grid, block, 0, st, a);
+  else if (out == 2) hipLaunchKernelGGL((k_extract_rows<uint16_t, CR, VAR>), grid, block, 0, st, a);
+  else hipLaunchKernelGGL((k_extract_rows<float, CR, VAR>), grid, block, 0, st, a);
+}
+
 // The channels of slot `s` (wayne_exposure_set_channels) behind k_extract_finish, from `a` as launch_extract filled it.
 int launch_channels(wayne_ctx* c, Slot& s, const ExtractArgs& a, int blocks, int out, bool cr) {
   ChannelArgs ch{};
@@ -658,20 +690,25 @@ int launch_channels(wayne_ctx* c, Slot& s, const ExtractArgs& a, int blocks, int
   for (int i = 0; i < 4; ++i) ch.cube[i] = c->has_flat ? c->flat[i].as<float>() : nullptr;
   ch.part = s.ch_part.as<double>();
   ch.channels = (double*)((char*)s.ex_out.p + channels_offset(c, s));
+  const bool var = s.var_on;
+  if (var) {
+    ch.part_v = s.ch_part_v.as<double>();
+    ch.channels_var = a.sky_var + (a.R + 1);
+  }
   const dim3 grid((unsigned)blocks, (unsigned)kChanGroups), block(kExtractThreads);
   if (blocks > 0) {
     if (cr) {
-      if (out == 1) hipLaunchKernelGGL((k_extract_bins<double, true>), grid, block, 0, c->stream, a, ch);
-      else if (out == 2) hipLaunchKernelGGL((k_extract_bins<uint16_t, true>), grid, block, 0, c->stream, a, ch);
-      else hipLaunchKernelGGL((k_extract_bins<float, true>), grid, block, 0, c->stream, a, ch);
+      if (var) launch_bins<true, true>(out, grid, block, c->stream, a, ch);
+      else launch_bins<true, false>(out, grid, block, c->stream, a, ch);
     } else {
-      if (out == 1) hipLaunchKernelGGL((k_extract_bins<double, false>), grid, block, 0, c->stream, a, ch);
-      else if (out == 2) hipLaunchKernelGGL((k_extract_bins<uint16_t, false>), grid, block, 0, c->stream, a, ch);
-      else hipLaunchKernelGGL((k_extract_bins<float, false>), grid, block, 0, c->stream, a, ch);
+      if (var) launch_bins<false, true>(out, grid, block, c->stream, a, ch);
+      else launch_bins<false, false>(out, grid, block, c->stream, a, ch);
     }
     HIP_TRY(c, hipGetLastError());
   }
-  hipLaunchKernelGGL(k_extract_bins_finish, dim3((unsigned)(a.R + 1)), dim3(kChanMaxChannels), 0, c->stream, a, ch);
+  const dim3 products_grid((unsigned)(a.R + 1)), channels_block(kChanMaxChannels);
+  if (var) hipLaunchKernelGGL(k_extract_bins_finish<true>, products_grid, channels_block, 0, c->stream, a, ch);
+  else hipLaunchKernelGGL(k_extract_bins_finish<false>, products_grid, channels_block, 0, c->stream, a, ch);
   HIP_TRY(c, hipGetLastError());
   return WAYNE_OK;
 }
@@ -705,6 +742,13 @@ int launch_extract(wayne_ctx* c, Slot& s) {
     a.m_lo = s.cr_lo; a.m_hi = s.cr_hi;
     a.k2 = s.cr_k * s.cr_k; a.rn2 = s.cr_rn * s.cr_rn;
   }
+  const bool var = s.var_on;
+  if (var) {
+    a.vrn2 = s.var_rn * s.var_rn;
+    a.part_v = s.ex_part_v.as<double>();
+    a.spectra_var = (double*)((char*)s.ex_out.p + variance_offset(c, s));
+    a.sky_var = a.spectra_var + (size_t)(R + 1) * S;
+  }
   const int products = (a.steps & X_LAST_READ) ? R + 1 : R;
   for (int p = 0; p <= kExtractProducts; ++p) a.first_chunk[p] = 0;
   for (int p = 0; p < products; ++p)
@@ -721,19 +765,19 @@ int launch_extract(wayne_ctx* c, Slot& s) {
     else if (out == 2) hipLaunchKernelGGL((k_extract_crmask<uint16_t>), tiles, block, 0, c->stream, a);
     else hipLaunchKernelGGL((k_extract_crmask<float>), tiles, block, 0, c->stream, a);
     HIP_TRY(c, hipGetLastError());
-    if (out == 1) hipLaunchKernelGGL((k_extract_rows<double, true>), grid, block, 0, c->stream, a);
-    else if (out == 2) hipLaunchKernelGGL((k_extract_rows<uint16_t, true>), grid, block, 0, c->stream, a);
-    else hipLaunchKernelGGL((k_extract_rows<float, true>), grid, block, 0, c->stream, a);
+    if (var) launch_rows<true, true>(out, grid, block, c->stream, a);
+    else launch_rows<true, false>(out, grid, block, c->stream, a);
     HIP_TRY(c, hipGetLastError());
-    hipLaunchKernelGGL(k_extract_finish<true>, products_grid, block, 0, c->stream, a);
+    if (var) hipLaunchKernelGGL((k_extract_finish<true, true>), products_grid, block, 0, c->stream, a);
+    else hipLaunchKernelGGL((k_extract_finish<true, false>), products_grid, block, 0, c->stream, a);
     HIP_TRY(c, hipGetLastError());
     return s.chan_on ? launch_channels(c, s, a, a.first_chunk[products], out, true) : WAYNE_OK;
   }
-  if (out == 1) hipLaunchKernelGGL((k_extract_rows<double, false>), grid, block, 0, c->stream, a);
-  else if (out == 2) hipLaunchKernelGGL((k_extract_rows<uint16_t, false>), grid, block, 0, c->stream, a);
-  else hipLaunchKernelGGL((k_extract_rows<float, false>), grid, block, 0, c->stream, a);
+  if (var) launch_rows<false, true>(out, grid, block, c->stream, a);
+  else launch_rows<false, false>(out, grid, block, c->stream, a);
   HIP_TRY(c, hipGetLastError());
-  hipLaunchKernelGGL(k_extract_finish<false>, products_grid, block, 0, c->stream, a);
+  if (var) hipLaunchKernelGGL((k_extract_finish<false, true>), products_grid, block, 0, c->stream, a);
+  else hipLaunchKernelGGL((k_extract_finish<false, false>), products_grid, block, 0, c->stream, a);
   HIP_TRY(c, hipGetLastError());
   return s.chan_on ? launch_channels(c, s, a, a.first_chunk[products], out, false) : WAYNE_OK;
 }
@@ -1218,6 +1262,8 @@ int wayne_exposure_upload(wayne_ctx* c, int slot, const wayne_exposure_desc* d) 
   s.ex_rej = nullptr;
   s.chan_on = false;         // ... and whose channels wait for wayne_exposure_set_channels
   s.ch_res = nullptr;
+  s.var_on = false;          // ... and whose variances wait for wayne_exposure_set_variance
+  s.var_res = nullptr;
   int rc;
   const size_t KW = (size_t)K * W;
   {
@@ -1982,6 +2028,8 @@ int wayne_exposure_set_extraction(wayne_ctx* c, int slot, const wayne_extract_de
   s.ex_rej = nullptr;
   s.chan_on = false;
   s.ch_res = nullptr;
+  s.var_on = false;
+  s.var_res = nullptr;
   if (!x) return WAYNE_OK;
   int chunks = 0;
   if (const char* why = plan::extract_desc_error(c->S, s.R, x->steps, x->row_lo, x->row_hi, x->bg_col_lo, x->bg_col_hi, &chunks))
@@ -2004,6 +2052,7 @@ int wayne_exposure_set_crrej(wayne_ctx* c, int slot, const wayne_crrej_desc* r) 
   s.crrej_on = false;             // from here on a refusal leaves the slot extracting, without rejection
   s.ex_rej = nullptr;
   s.ch_res = nullptr;
+  s.var_res = nullptr;
   s.ex_pinned_misc = nullptr;     // (a fetched block has the other layout)
   if (!r) return WAYNE_OK;
   if (const char* why = plan::crrej_desc_error(s.ex.steps, r->k, r->read_noise_e))
@@ -2026,6 +2075,7 @@ int wayne_exposure_set_channels(wayne_ctx* c, int slot, const wayne_channels_des
   if (!s.uploaded || !s.extract_on) return fail(c, WAYNE_E_STATE, "set_channels: no extraction set for the slot");
   s.chan_on = false;              // from here on a refusal leaves the slot extracting, without channels
   s.ch_res = nullptr;
+  s.var_res = nullptr;
   s.ex_pinned_misc = nullptr;     // (a fetched block has the other layout)
   if (!d) return WAYNE_OK;
   int u_lo = 0, u_hi = 0;
@@ -2038,7 +2088,10 @@ int wayne_exposure_set_channels(wayne_ctx* c, int slot, const wayne_channels_des
   HIP_TRY(c, s.ch_part.reserve((size_t)s.ex_chunks * kChanGroups * NP * 2 * C * sizeof(double)));
   // the spectra block grows by the channels, 8-byte aligned behind sky and (set_crrej may come before or after) the counts;
   // nothing of it is kept: the next run writes all of it
-  HIP_TRY(c, s.ex_out.reserve(NP * (S + 1) * sizeof(double) + NP * sizeof(uint32_t) + 8 + NP * C * sizeof(double)));
+  // (and by the variances, when set_variance came first: they lie behind the channels and take on channels_var)
+  HIP_TRY(c, s.ex_out.reserve(NP * (S + 1) * sizeof(double) + NP * sizeof(uint32_t) + 8 + NP * C * sizeof(double) +
+                              (s.var_on ? NP * (S + 1 + C) * sizeof(double) : 0)));
+  if (s.var_on) HIP_TRY(c, s.ch_part_v.reserve((size_t)s.ex_chunks * kChanGroups * NP * C * sizeof(double)));
   if (int rc = s.ch_stage.begin(c, 3 * 64 + (2 * S + C + 1) * sizeof(double), "set_channels: pinned host allocation failed")) return rc;
   if (!s.ch_stage.put(s.ch_edges, d->edges_um, (C + 1) * sizeof(double)) || !s.ch_stage.put(s.ch_wa, d->wl_a, S * sizeof(double)) ||
       !s.ch_stage.put(s.ch_wb, d->wl_b, S * sizeof(double)))
@@ -2051,9 +2104,34 @@ int wayne_exposure_set_channels(wayne_ctx* c, int slot, const wayne_channels_des
   return WAYNE_OK;
 }
 
+int wayne_exposure_set_variance(wayne_ctx* c, int slot, const wayne_variance_desc* v) {
+  if (!c) return WAYNE_E_INVALID;
+  if (slot < 0 || slot >= kSlots) return fail(c, WAYNE_E_INVALID, "set_variance: slot");
+  Slot& s = c->slots[slot];
+  if (!s.uploaded || !s.extract_on) return fail(c, WAYNE_E_STATE, "set_variance: no extraction set for the slot");
+  s.var_on = false;               // from here on a refusal leaves the slot extracting, without variances
+  s.var_res = nullptr;
+  s.ex_pinned_misc = nullptr;     // (a fetched block has the other layout)
+  if (!v) return WAYNE_OK;
+  if (const char* why = plan::variance_desc_error(s.ex.steps, v->read_noise))
+    return fail(c, WAYNE_E_INVALID, std::string("set_variance: ") + why);
+  (void)hipSetDevice(c->device);
+  const size_t NP = (size_t)s.R + 1, S = (size_t)c->S, C = s.chan_on ? (size_t)s.ch_C : 0;
+  HIP_TRY(c, s.ex_part_v.reserve((size_t)s.ex_chunks * NP * S * sizeof(double)));
+  if (s.chan_on) HIP_TRY(c, s.ch_part_v.reserve((size_t)s.ex_chunks * kChanGroups * NP * C * sizeof(double)));
+  // the spectra block grows by the variances, behind the counts' room and the channels; nothing of it is kept
+  HIP_TRY(c, s.ex_out.reserve(NP * (S + 1) * sizeof(double) + NP * sizeof(uint32_t) + 8 + NP * C * sizeof(double) +
+                              NP * (S + 1 + C) * sizeof(double)));
+  s.var_rn = v->read_noise;
+  s.var_on = true;
+  return WAYNE_OK;
+}
+
 // bytes of a slot's spectra block: spectra [(R+1)*S], then sky [R+1]; with rejection, n_rejected [R+1] (uint32) behind
-// them; with channels, channels [(R+1)*C] behind those on the next multiple of 8 bytes
+// them; with channels, channels [(R+1)*C] behind those on the next multiple of 8 bytes; with variances, those behind
+// everything else
 static size_t spectra_bytes(const wayne_ctx* c, const Slot& s) {
+  if (s.var_on) return variance_offset(c, s) + variance_count(c, s) * sizeof(double);
   if (s.chan_on) return channels_offset(c, s) + (size_t)(s.R + 1) * s.ch_C * sizeof(double);
   return (size_t)(s.R + 1) * ((size_t)c->S + 1) * sizeof(double) + (s.crrej_on ? (size_t)(s.R + 1) * sizeof(uint32_t) : 0);
 }
@@ -2090,6 +2168,7 @@ int wayne_exposure_wait_spectra(wayne_ctx* c, int slot, double** spectra, double
   *sky = (double*)s.ex_pinned.p + (size_t)(s.R + 1) * c->S;
   s.ex_rej = s.crrej_on ? (const uint32_t*)(*sky + (s.R + 1)) : nullptr;
   s.ch_res = s.chan_on ? (const double*)(s.ex_pinned.p + channels_offset(c, s)) : nullptr;
+  s.var_res = s.var_on ? (const double*)(s.ex_pinned.p + variance_offset(c, s)) : nullptr;
   bool reran = false;                        // (the status word came with the spectra)
   int rc = look_at_status(c, slot, s.ex_pinned_misc, wayne_exposure_run, &reran);
   if (rc || !reran) return rc;
@@ -2116,8 +2195,16 @@ int wayne_exposure_download_spectra(wayne_ctx* c, int slot, double* spectra, dou
     if (s.chan_on)
       HIP_TRY(c, hipMemcpyAsync(s.ch_host.data(), (const char*)s.ex_out.p + channels_offset(c, s), s.ch_host.size() * sizeof(double),
                                 hipMemcpyDeviceToHost, c->stream));
+    if (s.var_on)
+      HIP_TRY(c, hipMemcpyAsync(s.var_host.data(), (const char*)s.ex_out.p + variance_offset(c, s), s.var_host.size() * sizeof(double),
+                                hipMemcpyDeviceToHost, c->stream));
     return WAYNE_OK;
   };
+  s.var_res = nullptr;
+  if (s.var_on) {
+    s.var_host.assign(variance_count(c, s), 0.);
+    s.var_res = s.var_host.data();
+  }
   s.ch_res = nullptr;
   if (s.chan_on) {
     s.ch_host.assign((size_t)(s.R + 1) * s.ch_C, 0.);
@@ -2154,6 +2241,18 @@ int wayne_exposure_channels(wayne_ctx* c, int slot, const double** channels) {
   if (!s.uploaded || !s.extract_on || !s.chan_on) return fail(c, WAYNE_E_STATE, "channels: no channels set for the slot");
   if (!s.ch_res) return fail(c, WAYNE_E_STATE, "channels: wait_spectra or download_spectra first");
   *channels = s.ch_res;
+  return WAYNE_OK;
+}
+
+int wayne_exposure_variances(wayne_ctx* c, int slot, const double** spectra_var, const double** sky_var, const double** channels_var) {
+  if (!c || !spectra_var || !sky_var || !channels_var) return WAYNE_E_INVALID;
+  if (slot < 0 || slot >= kSlots) return fail(c, WAYNE_E_INVALID, "variances: slot");
+  Slot& s = c->slots[slot];
+  if (!s.uploaded || !s.extract_on || !s.var_on) return fail(c, WAYNE_E_STATE, "variances: no variances set for the slot");
+  if (!s.var_res) return fail(c, WAYNE_E_STATE, "variances: wait_spectra or download_spectra first");
+  *spectra_var = s.var_res;
+  *sky_var = s.var_res + (size_t)(s.R + 1) * c->S;
+  *channels_var = s.chan_on ? *sky_var + (s.R + 1) : nullptr;
   return WAYNE_OK;
 }
 

@@ -23,6 +23,20 @@ cube evaluated at the pixel's wavelength -- the factor the simulator multiplied 
 extraction's.  Not covered: optimal extraction, resampling in y, other grism orders, the direct image, merging per-rank
 .npz files, a flat-fielded sky fit.  Fitting stays with the caller.
 
+Variances are opt-in (`variance=` of Extraction / ExtractionOptions / the frames, CLI --variances [RN]): every pixel
+of a window carries var = max(v, 0) + rn^2 q^2 -- Poisson on its own electrons v (the term the extraction sums, cleaned
+under rejection) plus the read noise rn of a difference of two reads (20 e- by default, as CosmicRejection.read_noise)
+through its own gain factor q = 1 / pfl -- and the device, which alone sees the pixels, sums it beside the flux, in the
+same order and from the same loads: `spectra_var` [R + 1, S], `sky_var` [R + 1] and, with channels, `channels_var`
+[R + 1, C] come back with the spectra (the law: include/wayne_hip.h, wayne_variance_desc).  The sky level's variance
+enters a column as B^2 sky_var and a channel as Q^2 sky_var.  Left out: the covariance between a background column's
+own flux and the sky level; the correlation between neighbouring channels that share a pixel (and the sky level); the
+correlation of read intervals through the read they share -- in a sum over consecutive intervals the Poisson parts add
+but the read noise is that of the first and the last read alone, so the variance of `channels[:R].sum(0)` is
+`channels_var[:R].sum(0)` with its read-noise part replaced by the last-read product's (with a second extraction at
+read_noise = 0: cv0[:R].sum(0) + cv[R] - cv0[R]); the variance of a rejected pixel's replacement, taken from the
+replacement's own value.  Optimal extraction is not covered; it builds on these variances.
+
 Cosmic-ray rejection is opt-in (`crrej=` of Extraction / ExtractionOptions / the frames, CLI --reject-cosmics): on each
 read interval's difference image I a pixel at least 7 px inside the frame and in the plan's rows is flagged when it
 exceeds the largest of its eight plus-shaped stencil neighbours (y+-1, y+-2, x+-1, x+-2), m8, by d > 0 with
@@ -71,6 +85,33 @@ class CosmicRejection(object):
     def desc(self):
         d = _lib.CrrejDesc()
         d.k, d.read_noise_e = self.k, self.read_noise
+        return d
+
+
+class Variances(object):
+    """Variances of an extraction's spectra, sky levels and channels (wayne_variance_desc): `read_noise`, the noise of a
+    difference of two reads in electrons (finite, >= 0; the meaning and default of CosmicRejection.read_noise)."""
+
+    def __init__(self, read_noise=20.0):
+        read_noise = float(read_noise)
+        if not (np.isfinite(read_noise) and read_noise >= 0.0):
+            raise ValueError("Variances: read_noise must be finite and >= 0")
+        self.read_noise = read_noise
+
+    @staticmethod
+    def coerce(variance):
+        """`variance=` -> a Variances or None: None and False are off, True the defaults."""
+        if variance is None or variance is False:
+            return None
+        if variance is True:
+            return Variances()
+        if not isinstance(variance, Variances):
+            raise TypeError("variance: None, True or an extraction.Variances")
+        return variance
+
+    def desc(self):
+        d = _lib.VarianceDesc()
+        d.read_noise = self.read_noise
         return d
 
 
@@ -154,9 +195,11 @@ class Extraction(object):
     DARK | GAIN | SKY | LAST_READ; a step that is off: see the WAYNE_X_* bits).  `crrej` (None, True or a
     CosmicRejection): cosmic rays are rejected on the difference images first; it needs the GAIN step.  `channels` (None
     or a Channels) with `row_solution` = (wl_a [S], wl_b [S]): the window pixels are also binned into wavelength
-    channels, row y by lambda_y(u) = wl_a[y] + wl_b[y] u at bordered column coordinate u."""
+    channels, row y by lambda_y(u) = wl_a[y] + wl_b[y] u at bordered column coordinate u.  `variance` (None, True or a
+    Variances): variances come back with the spectra, the sky levels and the channels; it needs the GAIN step."""
 
-    def __init__(self, row_windows, bg_cols=BG_COLS, steps=ALL, crrej=None, channels=None, row_solution=None):
+    def __init__(self, row_windows, bg_cols=BG_COLS, steps=ALL, crrej=None, channels=None, row_solution=None,
+                 variance=None):
         w = np.asarray(row_windows, dtype=np.int64)
         if w.ndim != 2 or w.shape[1] != 2 or not 2 <= w.shape[0] <= _lib.EXTRACT_PRODUCTS:
             raise ValueError("row_windows: (lo, hi) for each of the R read intervals and for the last read")
@@ -165,6 +208,9 @@ class Extraction(object):
         self.steps = int(steps)
         self.crrej = CosmicRejection.coerce(crrej)
         self.channels = Channels.coerce(channels)
+        self.variance = Variances.coerce(variance)
+        if self.variance is not None and not self.steps & GAIN:
+            raise ValueError("variance needs the GAIN step: a variance is in electrons^2")
         self.row_solution = None
         self.hull = None              # (u_lo, u_hi): the bordered columns the channels can touch
         if self.channels is not None:
@@ -175,12 +221,18 @@ class Extraction(object):
 
     def with_crrej(self, crrej):
         """The same plan with another `crrej`."""
-        return Extraction(self.row_windows, self.bg_cols, self.steps, crrej, self.channels, self.row_solution)
+        return Extraction(self.row_windows, self.bg_cols, self.steps, crrej, self.channels, self.row_solution,
+                          self.variance)
 
     def with_channels(self, channels, row_solution=None):
         """The same plan with other `channels` (None: without); `row_solution` defaults to the plan's own."""
         return Extraction(self.row_windows, self.bg_cols, self.steps, self.crrej, channels,
-                          self.row_solution if row_solution is None else row_solution)
+                          self.row_solution if row_solution is None else row_solution, self.variance)
+
+    def with_variance(self, variance):
+        """The same plan with another `variance`."""
+        return Extraction(self.row_windows, self.bg_cols, self.steps, self.crrej, self.channels, self.row_solution,
+                          variance)
 
     @property
     def mask_rows(self):
@@ -213,23 +265,33 @@ class ExtractionOptions(object):
     """Extraction planned per exposure: what `extraction=` takes where the star moves from exposure to exposure
     (Observation.frame_options, VisitRunner).  ExposureGenerator turns it into that exposure's Extraction (plan)."""
 
-    def __init__(self, margin=ROW_MARGIN, bg_cols=BG_COLS, steps=ALL, crrej=None, channels=None):
+    def __init__(self, margin=ROW_MARGIN, bg_cols=BG_COLS, steps=ALL, crrej=None, channels=None, variance=None):
         self.margin, self.bg_cols, self.steps = int(margin), (int(bg_cols[0]), int(bg_cols[1])), int(steps)
         self.crrej = CosmicRejection.coerce(crrej)
         self.channels = Channels.coerce(channels)
+        self.variance = Variances.coerce(variance)
 
     def plan(self, grism, wl, x_ref, y_ref, scan_speed, read_times, sub_scale, S, channels=OWN):
         """This exposure's Extraction; `channels` (a Channels or None) replaces the options' own."""
         channels = self.channels if channels is OWN else Channels.coerce(channels)
         sol = None if channels is None else row_solution(grism, x_ref, y_ref, sub_scale, S)
         return Extraction(row_windows(grism, wl, x_ref, y_ref, scan_speed, read_times, sub_scale, S, self.margin),
-                          self.bg_cols, self.steps, self.crrej, channels, sol)
+                          self.bg_cols, self.steps, self.crrej, channels, sol, self.variance)
 
 
-def for_exposure(extraction, grism, wl, x_ref, y_ref, scan_speed, read_times, sub_scale, S, crrej=None, channels=None):
+def for_exposure(extraction, grism, wl, x_ref, y_ref, scan_speed, read_times, sub_scale, S, crrej=None, channels=None,
+                 variance=None):
     """`extraction=` of a frame -> that exposure's Extraction: None stays None, an Extraction is taken as it is, True is
     the default plan and an ExtractionOptions its own.  `crrej=` of the frame, when given, replaces the plan's; so does
-    `channels=` (a Channels), with the row solution planned for this exposure."""
+    `channels=` (a Channels), with the row solution planned for this exposure, and so does `variance=` (True or a
+    Variances)."""
+    if variance is not None:
+        if extraction is None or extraction is False:
+            if variance is not False:
+                raise ValueError("variance needs an extraction")
+            return for_exposure(extraction, grism, wl, x_ref, y_ref, scan_speed, read_times, sub_scale, S, crrej, channels)
+        return for_exposure(extraction, grism, wl, x_ref, y_ref, scan_speed, read_times, sub_scale, S, crrej,
+                            channels).with_variance(variance)
     if extraction is None or extraction is False:
         if crrej is not None and crrej is not False:
             raise ValueError("crrej needs an extraction")
@@ -335,7 +397,7 @@ def channel_weights(x_ref, edges, sub_scale, S):
 CHUNK_ROWS = 32            # rows of a chunk of a window (kExtractRows): partial sums are kept per chunk
 
 
-def algorithmic_bytes(plan, S, R, read_bytes=4, crrej=False, channels=False):
+def algorithmic_bytes(plan, S, R, read_bytes=4, crrej=False, channels=False, variance=False):
     """Bytes the extraction's kernels must move for `plan` on a frame of side S with R non-zero reads of `read_bytes`
     a sample: per pixel of product j's window the reads P_{j+1}, P_j, P_0 (P_0 once for j = 0 and for the last read),
     four coefficient planes, dark_{j+1} and dark_j (float32 each; dark_0 = 0 is not stored), the pixel flat and the
@@ -346,7 +408,9 @@ def algorithmic_bytes(plan, S, R, read_bytes=4, crrej=False, channels=False):
     neighbours of a flagged pixel are not algorithmic.)  `channels` (the plan carries them): plus k_extract_bins' -- per
     window pixel of the plan's column hull the same planes as above (and the flag word under `crrej`), four float32 flat
     planes when the flat is divided out, the row's wl_a / wl_b (2 float64 per row); the chunks' sums (2 C float64 per
-    chunk) written and read once and channels [(R + 1) C] written."""
+    chunk) written and read once and channels [(R + 1) C] written.  `variance`: no plane is read for it -- plus the chunks'
+    variance sums (a float64 per chunk and column; with `channels`, C float64 per chunk) written and read once and
+    spectra_var, sky_var [(R + 1)(S + 1)] and, with `channels`, channels_var [(R + 1) C] written."""
     total = 0
     hull = (plan.hull[1] - plan.hull[0]) if channels and plan.channels is not None else 0
     n_ch = plan.channels.n if hull or (channels and plan.channels is not None) else 0
@@ -371,6 +435,10 @@ def algorithmic_bytes(plan, S, R, read_bytes=4, crrej=False, channels=False):
         if n_ch:
             total += rows * hull * (per_pixel + (2 if crrej else 0) + (16 if plan.channels.flat else 0))
             total += rows * 16 + 2 * (chunks * 2 * n_ch * 8)
+        if variance:
+            total += 2 * (chunks * S * 8) + 2 * (chunks * n_ch * 8)
+    if variance:
+        total += (R + 1) * (S + 1) * 8 + (R + 1) * n_ch * 8
     return total + (R + 1) * (S + 1) * 8 + (R + 1) * n_ch * 8
 
 
@@ -384,6 +452,7 @@ class Delivery(object):
         self.ctx, self.reads = ctx, reads
         self.rejected = None      # n_rejected [R + 1] of the last wait (None: that slot extracts without rejection)
         self.channels = None      # channels [R + 1, C] of the last wait (None: that slot extracts without channels)
+        self.variances = None     # (spectra_var, sky_var, channels_var or None) of the last wait (None: without variances)
 
     def upload(self, slot, desc):
         self.ctx.upload(slot, desc)
@@ -401,16 +470,20 @@ class Delivery(object):
         spectra, sky = self.ctx.wait_spectra(slot)
         self.rejected = self.ctx.rejected(slot) if self.ctx.has_crrej(slot) else None
         self.channels = self.ctx.channels(slot) if self.ctx.has_channels(slot) else None
+        self.variances = self.ctx.variances(slot) if self.ctx.has_variance(slot) else None
         return reads, spectra, sky
 
 
-def save_npz(path, spectra, sky, exposure_index, plans, x_ref, y_ref, read_times, exp_start, rejected=None, channels=None):
+def save_npz(path, spectra, sky, exposure_index, plans, x_ref, y_ref, read_times, exp_start, rejected=None, channels=None,
+             variances=None):
     """The file --spectra / --spectra-only write: spectra [n, R + 1, S], sky [n, R + 1], exposure_index [n], row_lo /
     row_hi [n, R + 1], bg_cols [2], x_ref / y_ref [n], read_times [R], exp_start [n].  With `rejected` [n, R + 1] (the
     exposures were extracted with cosmic-ray rejection) also n_rejected [n, R + 1] -- flags in each product's window,
     (pixel, interval) pairs for the last-read product -- crrej_k and crrej_read_noise.  With `channels` [n, R + 1, C]
     (the exposures were binned into wavelength channels) also channels, channel_edges_um [C + 1], channel_flat and the
-    rows' wavelength solutions wl_a / wl_b [n, S]."""
+    rows' wavelength solutions wl_a / wl_b [n, S].  With `variances` = (spectra_var [n, R + 1, S], sky_var [n, R + 1],
+    channels_var [n, R + 1, C] or None) (the exposures were extracted with variances) also spectra_var, sky_var,
+    channels_var (with channels) and variance_read_noise."""
     n = len(exposure_index)
     more = {}
     if rejected is not None:
@@ -423,6 +496,11 @@ def save_npz(path, spectra, sky, exposure_index, plans, x_ref, y_ref, read_times
                     channel_flat=np.bool_(ch.flat),
                     wl_a=np.array([p.row_solution[0] for p in plans], dtype=np.float64).reshape(n, -1),
                     wl_b=np.array([p.row_solution[1] for p in plans], dtype=np.float64).reshape(n, -1))
+    if variances is not None:
+        more.update(spectra_var=np.asarray(variances[0], dtype=np.float64), sky_var=np.asarray(variances[1], dtype=np.float64),
+                    variance_read_noise=np.float64(plans[0].variance.read_noise))
+        if variances[2] is not None:
+            more["channels_var"] = np.asarray(variances[2], dtype=np.float64)
     np.savez(path, **more, spectra=np.asarray(spectra, dtype=np.float64), sky=np.asarray(sky, dtype=np.float64),
              exposure_index=np.asarray(exposure_index, dtype=np.int64),
              row_lo=np.array([p.row_lo for p in plans], dtype=np.int64).reshape(n, -1),

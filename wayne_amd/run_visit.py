@@ -2,7 +2,7 @@
 
     python -m wayne_amd.run_visit -p <parameter_file> [--calibration DIR] [--device N] [--max-exposures M] [--gpus G] [--resume]
                                   [--spectra OUT.npz | --spectra-only OUT.npz] [--reject-cosmics [K]]
-                                  [--channels LO:HI:N] [--no-channel-flat]
+                                  [--channels LO:HI:N] [--no-channel-flat] [--variances [RN]]
 
 Accepts the reference's parameter files (wayne/run_visit.py:1-9, example
 examples/hd209458b_12181_simulation_parameters.yml): sections `general`
@@ -35,7 +35,10 @@ examples/hd209458b_12181_simulation_parameters.yml): sections `general`
     exposure is also binned on the device into N wavelength channels of equal width between LO and HI um, each row by
     its own wavelength solution and each pixel divided by the flat cube at its wavelength (`--no-channel-flat`: not
     divided); OUT.npz then also holds channels [n, NSAMP, N], channel_edges_um [N + 1], channel_flat and the rows'
-    solutions wl_a / wl_b [n, S];
+    solutions wl_a / wl_b [n, S].  `--variances [RN]` (with either): the device also sums every window pixel's variance
+    -- Poisson on its own electrons plus the read noise RN of a difference of two reads (default 20 e-) through its own
+    gain -- beside its flux; OUT.npz then also holds spectra_var [n, NSAMP, S], sky_var [n, NSAMP], with --channels
+    channels_var [n, NSAMP, N], and variance_read_noise;
   * `--gpus G`: the process starts G rank processes itself (one per GPU of this node, before anything touches a
     GPU) and waits for them; under an external launcher (WORLD_SIZE / RANK set, one process per GPU) it is one
     rank.  Each rank generates its round-robin share of the exposures (observation.py:403-405 is the axis) on the
@@ -203,7 +206,20 @@ def run(argv=None):
                          "holds channels, channel_edges_um, channel_flat, wl_a and wl_b")
     ap.add_argument("--no-channel-flat", action="store_true",
                     help="with --channels: do not divide by the wavelength-dependent flat")
+    ap.add_argument("--variances", nargs="?", type=float, const=20.0, default=None, metavar="RN",
+                    help="with --spectra / --spectra-only: also deliver the variances of the spectra, the sky levels and "
+                         "the channels, RN e- (default 20) the read noise of a difference of two reads; OUT.npz then also "
+                         "holds spectra_var, sky_var, channels_var (with --channels) and variance_read_noise")
     args = ap.parse_args(argv)
+    variance = None
+    if args.variances is not None:
+        if not (args.spectra or args.spectra_only):
+            raise SystemExit("--variances needs --spectra or --spectra-only")
+        from .extraction import Variances
+        try:
+            variance = Variances(read_noise=args.variances)
+        except ValueError as e:
+            raise SystemExit("--variances [RN] (e-, finite and >= 0): %s" % e)
     channels = None
     if args.no_channel_flat and args.channels is None:
         raise SystemExit("--no-channel-flat needs --channels")
@@ -279,6 +295,8 @@ def run(argv=None):
             obs.frame_options["crrej"] = CosmicRejection(k=args.reject_cosmics)
         if channels is not None:
             obs.frame_options["channels"] = channels
+        if variance is not None:
+            obs.frame_options["variance"] = variance
         obs.spectra_out = args.spectra or args.spectra_only
         obs.spectra_only = bool(args.spectra_only)
     os.makedirs(obs.outdir, exist_ok=True)

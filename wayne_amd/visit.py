@@ -93,9 +93,11 @@ class VisitRunner(object):
         `extraction` (True, an extraction.ExtractionOptions, or one extraction.Extraction for every exposure): the
         device extracts each exposure's column spectra behind its reads and both are delivered --
         `on_spectra(i, spectra, sky)` gets views of the pinned buffer, and keep=True returns
-        {index: (reads, spectra, sky)}."""
+        {index: (reads, spectra, sky)}.  When the extraction delivers variances, `self.spectra_var`, `self.sky_var` and
+        -- with channels -- `self.channels_var` are {index: array} of every exposure run (None otherwise)."""
         eng = self.engine()
         results = {}
+        self.spectra_var = self.sky_var = self.channels_var = None
         pool = FitsWriterPool() if self.out_dir is not None else None
 
         def prepare(i):
@@ -109,6 +111,13 @@ class VisitRunner(object):
             reads = got
             if extraction is not None:
                 reads, spectra, sky = got
+                if ctx.variances is not None:
+                    if self.spectra_var is None:
+                        self.spectra_var, self.sky_var = {}, {}
+                        self.channels_var = {} if ctx.variances[2] is not None else None
+                    self.spectra_var[i], self.sky_var[i] = ctx.variances[0], ctx.variances[1]
+                    if self.channels_var is not None:
+                        self.channels_var[i] = ctx.variances[2]
                 if on_spectra is not None:
                     on_spectra(i, spectra, sky)
             if on_reads is not None:
@@ -120,8 +129,8 @@ class VisitRunner(object):
                 # (a copy: the pinned buffer is reused by the next exposure)
                 pool.submit(gen._fill_exposure(reads.copy()), self.out_dir, gen.exp_info["filename"])
 
+        ctx = eng.ctx if extraction is None else _extraction.Delivery(eng.ctx, reads=True)
         try:
-            ctx = eng.ctx if extraction is None else _extraction.Delivery(eng.ctx, reads=True)
             run_pipelined(ctx, indices, prepare, finish, self.DEPTH, self.DEPTH)
         finally:
             if pool is not None:
@@ -134,7 +143,8 @@ class VisitRunner(object):
         -> (spectra [n, R + 1, S], sky [n, R + 1]) in the order of `indices`; `self.plans` [n]: each exposure's
         extraction.Extraction; `self.rejected` [n, R + 1]: the flag counts of an extraction that rejects cosmic rays
         (None otherwise); `self.channels` [n, R + 1, C]: the channel fluxes of an extraction that bins into wavelength
-        channels (None otherwise)."""
+        channels (None otherwise); `self.spectra_var` [n, R + 1, S], `self.sky_var` [n, R + 1] and -- with channels --
+        `self.channels_var` [n, R + 1, C]: the variances of an extraction that delivers them (None otherwise)."""
         eng = self.engine()
         indices = list(indices)
         where = {i: n for n, i in enumerate(indices)}
@@ -144,6 +154,7 @@ class VisitRunner(object):
         self.plans = [None] * len(indices)
         counts = [None] * len(indices)
         binned = [None] * len(indices)
+        varis = [None] * len(indices)
         delivery = _extraction.Delivery(eng.ctx, reads=False)
 
         def prepare(i):
@@ -158,10 +169,17 @@ class VisitRunner(object):
             self.plans[where[i]] = gen.extraction_plan
             counts[where[i]] = delivery.rejected
             binned[where[i]] = delivery.channels
+            varis[where[i]] = delivery.variances
 
         run_pipelined(delivery, indices, prepare, finish, self.DEPTH, self.DEPTH)
         self.rejected = None if any(n is None for n in counts) or not counts else np.array(counts, dtype=np.uint32)
         self.channels = None if any(c is None for c in binned) or not binned else np.array(binned, dtype=np.float64)
+        self.spectra_var = self.sky_var = self.channels_var = None
+        if varis and not any(v is None for v in varis):
+            self.spectra_var = np.array([v[0] for v in varis], dtype=np.float64)
+            self.sky_var = np.array([v[1] for v in varis], dtype=np.float64)
+            if not any(v[2] is None for v in varis):
+                self.channels_var = np.array([v[2] for v in varis], dtype=np.float64)
         return spectra, sky
 
     def run_resident_spectra(self, n, on_spectra=None):
