@@ -39,6 +39,7 @@ EXTRACT_PRODUCTS = 17   # row windows a wayne_extract_desc holds
 C_FLAT = 1              # wayne_channels_desc.flags (WAYNE_C_*)
 MAX_CHANNELS = 256      # WAYNE_MAX_CHANNELS
 MAX_CHANNEL_HULL = 384  # WAYNE_MAX_CHANNEL_HULL
+MAX_OPTIMAL_HALF_WIDTH = 16  # WAYNE_MAX_OPTIMAL_HALF_WIDTH
 
 
 class WayneError(RuntimeError):
@@ -110,6 +111,10 @@ class VarianceDesc(C.Structure):
     _fields_ = [("read_noise", C.c_double)]
 
 
+class OptimalDesc(C.Structure):
+    _fields_ = [("half_width", C.c_int)]
+
+
 class Profile(C.Structure):
     _fields_ = [("name", C.c_char_p * PROF_KERNELS), ("launches", C.c_uint64 * PROF_KERNELS),
                 ("ms", C.c_double * PROF_KERNELS), ("electrons", C.c_uint64)]
@@ -167,6 +172,8 @@ SYMBOLS = {
     "wayne_exposure_channels": (C.c_int, [_vp, C.c_int, C.POINTER(_dp)]),
     "wayne_exposure_set_variance": (C.c_int, [_vp, C.c_int, C.POINTER(VarianceDesc)]),
     "wayne_exposure_variances": (C.c_int, [_vp, C.c_int, C.POINTER(_dp), C.POINTER(_dp), C.POINTER(_dp)]),
+    "wayne_exposure_set_optimal": (C.c_int, [_vp, C.c_int, C.POINTER(OptimalDesc)]),
+    "wayne_exposure_optimal": (C.c_int, [_vp, C.c_int, C.POINTER(_dp), C.POINTER(_dp)]),
     "wayne_extract_profile": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_double)]),
     "wayne_profile_enable": (C.c_int, [_vp, C.c_int]),
     "wayne_profile_select": (C.c_int, [_vp, C.c_uint]),
@@ -291,6 +298,7 @@ class Context(object):
         self._slot_crrej = set() # slots whose extraction rejects cosmic rays
         self._slot_chan = {}     # slot -> channels of its extraction (set_channels succeeded)
         self._slot_var = set()   # slots whose extraction delivers variances (set_variance succeeded)
+        self._slot_opt = set()   # slots whose extraction delivers the optimal values too (set_optimal succeeded)
         _live_contexts.add(self)
         for name, value in _knob_defaults.items():
             self.set_knob(name, value)
@@ -414,6 +422,7 @@ class Context(object):
         self._slot_crrej.discard(slot)
         self._slot_chan.pop(slot, None)
         self._slot_var.discard(slot)
+        self._slot_opt.discard(slot)
         sources = getattr(desc, "_sources", None)
         if sources:
             self.set_sources(slot, sources)
@@ -460,6 +469,7 @@ class Context(object):
         self._slot_crrej.discard(slot)
         self._slot_chan.pop(slot, None)
         self._slot_var.discard(slot)
+        self._slot_opt.discard(slot)
         if extraction is None:
             self.check(self._L.wayne_exposure_set_extraction(self._h, int(slot), None))
             return
@@ -470,12 +480,15 @@ class Context(object):
             self.set_channels(slot, extraction.channels, extraction.row_solution)
         if getattr(extraction, "variance", None) is not None:
             self.set_variance(slot, extraction.variance)
+        if getattr(extraction, "optimal", None) is not None:
+            self.set_optimal(slot, extraction.optimal)
 
     def set_variance(self, slot, variance):
         """Variances with the slot's extraction: an extraction.Variances (the read noise of a difference of two reads, in
         electrons) or True for its default -- None clears; after set_extraction, which clears it too (set_crrej and
         set_channels do not).  See wayne_exposure_set_variance."""
         self._slot_var.discard(slot)             # (a refusal leaves the slot extracting without variances)
+        self._slot_opt.discard(slot)             # (the optimal extraction stands on them: set_optimal comes after)
         if variance is None or variance is False:
             self.check(self._L.wayne_exposure_set_variance(self._h, int(slot), None))
             return
@@ -501,6 +514,34 @@ class Context(object):
         n_ch = self._slot_chan.get(slot)
         channels_var = np.ctypeslib.as_array(pc, shape=(R + 1, n_ch)).copy() if (pc and n_ch) else None
         return spectra_var, sky_var, channels_var
+
+    def set_optimal(self, slot, optimal):
+        """Optimal (profile-weighted) extraction beside the slot's box extraction: an extraction.Optimal (the profile's
+        half width in columns), True for its default or an int -- None clears; after set_variance, which clears it too
+        (set_crrej and set_channels do not).  See wayne_exposure_set_optimal."""
+        self._slot_opt.discard(slot)             # (a refusal leaves the slot extracting without it)
+        if optimal is None or optimal is False:
+            self.check(self._L.wayne_exposure_set_optimal(self._h, int(slot), None))
+            return
+        if optimal is True:
+            d = OptimalDesc(8)
+        else:
+            d = optimal.desc() if hasattr(optimal, "desc") else OptimalDesc(int(optimal))
+        self.check(self._L.wayne_exposure_set_optimal(self._h, int(slot), C.byref(d)))
+        self._slot_opt.add(slot)
+
+    def has_optimal(self, slot):
+        """Whether the slot's extraction delivers the optimal values (set_optimal succeeded since its last set_variance)."""
+        return slot in self._slot_opt
+
+    def optimal(self, slot):
+        """(optimal [R + 1, S], optimal_var [R + 1, S]) -- float64 copies -- of the slot's last wait_spectra /
+        download_spectra."""
+        K, W, R, _ = self._slot_meta[slot]
+        po, pv = _dp(), _dp()
+        self.check(self._L.wayne_exposure_optimal(self._h, int(slot), C.byref(po), C.byref(pv)))
+        return (np.ctypeslib.as_array(po, shape=(R + 1, self.S)).copy(),
+                np.ctypeslib.as_array(pv, shape=(R + 1, self.S)).copy())
 
     def set_channels(self, slot, channels, row_solution=None):
         """Wavelength-binned channels of the slot's extraction: an extraction.Channels (edges in um, flat on / off) and

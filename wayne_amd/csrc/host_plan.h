@@ -15,6 +15,7 @@
 //   crrej_desc_error     wayne_exposure_set_crrej's argument check; crrej_mask_rows: the rows k_extract_crmask writes
 //   channels_desc_error  wayne_exposure_set_channels' argument check, and the column hull k_extract_bins walks
 //   variance_desc_error  wayne_exposure_set_variance's argument check
+//   optimal_desc_error   wayne_exposure_set_optimal's argument check
 //
 // Reference: the reach of the thrower bounds pyparallel_menu.c:87-108 as the device modes implement it; the trace is
 // grism.py:491-506, 779-803 (trace_coeffs, plan_consts.h); the frame offset exposure_generator.py:630-645.
@@ -463,6 +464,13 @@ inline const char* crrej_desc_error(unsigned steps, double k, double read_noise_
 inline const char* variance_desc_error(unsigned steps, double read_noise) {
   if (!(std::isfinite(read_noise) && read_noise >= 0.)) return "read_noise must be finite and >= 0";
   if (!(steps & X_GAIN)) return "variances need WAYNE_X_GAIN: they are in electrons";
+  return nullptr;
+}
+
+// wayne_exposure_set_optimal's argument check (include/wayne_hip.h: wayne_optimal_desc): null when valid.  The half width
+// is bounded by the halo k_extract_optimal keeps beside a tile.
+inline const char* optimal_desc_error(int half_width) {
+  if (half_width < 1 || half_width > kOptMaxH) return "half_width must lie in 1 .. 16";
   return nullptr;
 }
 

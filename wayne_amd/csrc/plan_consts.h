@@ -55,6 +55,8 @@ constexpr int kCrTileCols = 64, kCrTileRows = kExtractRows;   // pixels of a k_e
 constexpr int kChanMaxChannels = 256;             // WAYNE_MAX_CHANNELS
 constexpr int kChanMaxHull = 384;                 // widest column hull: 8 waves x 2 row buffers x 384 float64 = 48 KB of LDS
 constexpr unsigned C_FLAT = 1u << 0, C_ALL = C_FLAT;   // wayne_channels_desc.flags (WAYNE_C_*)
+// optimal extraction (k_extract_optimal; validated by plan::optimal_desc_error)
+constexpr int kOptMaxH = 16;                      // WAYNE_MAX_OPTIMAL_HALF_WIDTH: the halo of a 64-column tile on either side
 
 WAYNE_HD void trace_coeffs(const GrismDev& g, double x_ref, double y_ref, double* o) {
   // o = {m_t, c_t, m_w, c_w, m_wl, c_wl}

@@ -238,6 +238,14 @@ struct Slot : SourceState {
   DevBuf ex_part_v, ch_part_v;
   const double* var_res = nullptr;
   std::vector<double> var_host;
+  // optimal extraction on top of the variances (wayne_exposure_set_optimal; cleared by what clears the variances): the
+  // chunks' sums [3][chunks][R+1][S]; the result -- optimal [(R+1)*S], optimal_var [(R+1)*S] -- behind the variances in
+  // ex_out.  `opt_res`: that block as the last wait_spectra / download_spectra brought it back (null before any)
+  bool opt_on = false;
+  int opt_H = 0;
+  DevBuf opt_part;
+  const double* opt_res = nullptr;
+  std::vector<double> opt_host;
   // staging arena of the descriptor's arrays: uploads are enqueued from here, so
   // wayne_exposure_upload returns without waiting for the slot's stream to drain
   StageArena stage;
@@ -665,6 +673,12 @@ size_t variance_count(const wayne_ctx* c, const Slot& s) {
   return (size_t)(s.R + 1) * ((size_t)c->S + 1 + (s.chan_on ? (size_t)s.ch_C : 0));
 }
 
+// Where optimal and optimal_var [(R+1)*S each] begin in a slot's spectra block: behind the variances.
+size_t optimal_offset(const wayne_ctx* c, const Slot& s) {
+  return variance_offset(c, s) + variance_count(c, s) * sizeof(double);
+}
+size_t optimal_count(const wayne_ctx* c, const Slot& s) { return (size_t)2 * (s.R + 1) * (size_t)c->S; }
+
 template <bool CR, bool VAR>
 void launch_bins(int out, dim3 grid, dim3 block, hipStream_t st, const ExtractArgs& a, const ChannelArgs& ch) {
   if (out == 1) hipLaunchKernelGGL((k_extract_bins<double, CR, VAR>), grid, block, 0, st, a, ch);
@@ -709,6 +723,29 @@ int launch_channels(wayne_ctx* c, Slot& s, const ExtractArgs& a, int blocks, int
   const dim3 products_grid((unsigned)(a.R + 1)), channels_block(kChanMaxChannels);
   if (var) hipLaunchKernelGGL(k_extract_bins_finish<true>, products_grid, channels_block, 0, c->stream, a, ch);
   else hipLaunchKernelGGL(k_extract_bins_finish<false>, products_grid, channels_block, 0, c->stream, a, ch);
+  HIP_TRY(c, hipGetLastError());
+  return WAYNE_OK;
+}
+
+static_assert(WAYNE_MAX_OPTIMAL_HALF_WIDTH == kOptMaxH, "include/wayne_hip.h and plan_consts.h must agree on the widest profile");
+
+// The optimal extraction of slot `s` (wayne_exposure_set_optimal) behind k_extract_finish, from `a` as launch_extract
+// filled it: k_extract_optimal on the grid of k_extract_rows, then one workgroup per product.
+template <bool CR>
+int launch_optimal(wayne_ctx* c, Slot& s, const ExtractArgs& a, dim3 grid, int out) {
+  OptimalArgs o{};
+  o.H = s.opt_H;
+  o.part = s.opt_part.as<double>();
+  o.optimal = (double*)((char*)s.ex_out.p + optimal_offset(c, s));
+  o.optimal_var = o.optimal + (size_t)(a.R + 1) * a.S;
+  const dim3 block(kExtractThreads);
+  if (grid.y > 0) {
+    if (out == 1) hipLaunchKernelGGL((k_extract_optimal<double, CR>), grid, block, 0, c->stream, a, o);
+    else if (out == 2) hipLaunchKernelGGL((k_extract_optimal<uint16_t, CR>), grid, block, 0, c->stream, a, o);
+    else hipLaunchKernelGGL((k_extract_optimal<float, CR>), grid, block, 0, c->stream, a, o);
+    HIP_TRY(c, hipGetLastError());
+  }
+  hipLaunchKernelGGL(k_extract_optimal_finish, dim3((unsigned)(a.R + 1)), block, 0, c->stream, a, o);
   HIP_TRY(c, hipGetLastError());
   return WAYNE_OK;
 }
@@ -771,6 +808,8 @@ int launch_extract(wayne_ctx* c, Slot& s) {
     if (var) hipLaunchKernelGGL((k_extract_finish<true, true>), products_grid, block, 0, c->stream, a);
     else hipLaunchKernelGGL((k_extract_finish<true, false>), products_grid, block, 0, c->stream, a);
     HIP_TRY(c, hipGetLastError());
+    if (s.opt_on)
+      if (int rc = launch_optimal<true>(c, s, a, grid, out)) return rc;
     return s.chan_on ? launch_channels(c, s, a, a.first_chunk[products], out, true) : WAYNE_OK;
   }
   if (var) launch_rows<false, true>(out, grid, block, c->stream, a);
@@ -779,6 +818,8 @@ int launch_extract(wayne_ctx* c, Slot& s) {
   if (var) hipLaunchKernelGGL((k_extract_finish<false, true>), products_grid, block, 0, c->stream, a);
   else hipLaunchKernelGGL((k_extract_finish<false, false>), products_grid, block, 0, c->stream, a);
   HIP_TRY(c, hipGetLastError());
+  if (s.opt_on)
+    if (int rc = launch_optimal<false>(c, s, a, grid, out)) return rc;
   return s.chan_on ? launch_channels(c, s, a, a.first_chunk[products], out, false) : WAYNE_OK;
 }
 
@@ -1264,6 +1305,8 @@ int wayne_exposure_upload(wayne_ctx* c, int slot, const wayne_exposure_desc* d) 
   s.ch_res = nullptr;
   s.var_on = false;          // ... and whose variances wait for wayne_exposure_set_variance
   s.var_res = nullptr;
+  s.opt_on = false;          // ... and whose optimal extraction waits for wayne_exposure_set_optimal
+  s.opt_res = nullptr;
   int rc;
   const size_t KW = (size_t)K * W;
   {
@@ -2030,6 +2073,8 @@ int wayne_exposure_set_extraction(wayne_ctx* c, int slot, const wayne_extract_de
   s.ch_res = nullptr;
   s.var_on = false;
   s.var_res = nullptr;
+  s.opt_on = false;
+  s.opt_res = nullptr;
   if (!x) return WAYNE_OK;
   int chunks = 0;
   if (const char* why = plan::extract_desc_error(c->S, s.R, x->steps, x->row_lo, x->row_hi, x->bg_col_lo, x->bg_col_hi, &chunks))
@@ -2053,6 +2098,7 @@ int wayne_exposure_set_crrej(wayne_ctx* c, int slot, const wayne_crrej_desc* r) 
   s.ex_rej = nullptr;
   s.ch_res = nullptr;
   s.var_res = nullptr;
+  s.opt_res = nullptr;
   s.ex_pinned_misc = nullptr;     // (a fetched block has the other layout)
   if (!r) return WAYNE_OK;
   if (const char* why = plan::crrej_desc_error(s.ex.steps, r->k, r->read_noise_e))
@@ -2076,6 +2122,7 @@ int wayne_exposure_set_channels(wayne_ctx* c, int slot, const wayne_channels_des
   s.chan_on = false;              // from here on a refusal leaves the slot extracting, without channels
   s.ch_res = nullptr;
   s.var_res = nullptr;
+  s.opt_res = nullptr;
   s.ex_pinned_misc = nullptr;     // (a fetched block has the other layout)
   if (!d) return WAYNE_OK;
   int u_lo = 0, u_hi = 0;
@@ -2090,7 +2137,7 @@ int wayne_exposure_set_channels(wayne_ctx* c, int slot, const wayne_channels_des
   // nothing of it is kept: the next run writes all of it
   // (and by the variances, when set_variance came first: they lie behind the channels and take on channels_var)
   HIP_TRY(c, s.ex_out.reserve(NP * (S + 1) * sizeof(double) + NP * sizeof(uint32_t) + 8 + NP * C * sizeof(double) +
-                              (s.var_on ? NP * (S + 1 + C) * sizeof(double) : 0)));
+                              (s.var_on ? NP * (S + 1 + C) * sizeof(double) : 0) + (s.opt_on ? 2 * NP * S * sizeof(double) : 0)));
   if (s.var_on) HIP_TRY(c, s.ch_part_v.reserve((size_t)s.ex_chunks * kChanGroups * NP * C * sizeof(double)));
   if (int rc = s.ch_stage.begin(c, 3 * 64 + (2 * S + C + 1) * sizeof(double), "set_channels: pinned host allocation failed")) return rc;
   if (!s.ch_stage.put(s.ch_edges, d->edges_um, (C + 1) * sizeof(double)) || !s.ch_stage.put(s.ch_wa, d->wl_a, S * sizeof(double)) ||
@@ -2111,6 +2158,8 @@ int wayne_exposure_set_variance(wayne_ctx* c, int slot, const wayne_variance_des
   if (!s.uploaded || !s.extract_on) return fail(c, WAYNE_E_STATE, "set_variance: no extraction set for the slot");
   s.var_on = false;               // from here on a refusal leaves the slot extracting, without variances
   s.var_res = nullptr;
+  s.opt_on = false;               // (the optimal extraction stands on the variances: set_optimal comes after this call)
+  s.opt_res = nullptr;
   s.ex_pinned_misc = nullptr;     // (a fetched block has the other layout)
   if (!v) return WAYNE_OK;
   if (const char* why = plan::variance_desc_error(s.ex.steps, v->read_noise))
@@ -2127,10 +2176,33 @@ int wayne_exposure_set_variance(wayne_ctx* c, int slot, const wayne_variance_des
   return WAYNE_OK;
 }
 
+int wayne_exposure_set_optimal(wayne_ctx* c, int slot, const wayne_optimal_desc* d) {
+  if (!c) return WAYNE_E_INVALID;
+  if (slot < 0 || slot >= kSlots) return fail(c, WAYNE_E_INVALID, "set_optimal: slot");
+  Slot& s = c->slots[slot];
+  if (!s.uploaded || !s.extract_on || !s.var_on) return fail(c, WAYNE_E_STATE, "set_optimal: no variances set for the slot");
+  s.opt_on = false;               // from here on a refusal leaves the slot extracting with variances, without the optimal values
+  s.opt_res = nullptr;
+  s.ex_pinned_misc = nullptr;     // (a fetched block has the other length)
+  if (!d) return WAYNE_OK;
+  if (const char* why = plan::optimal_desc_error(d->half_width))
+    return fail(c, WAYNE_E_INVALID, std::string("set_optimal: ") + why);
+  (void)hipSetDevice(c->device);
+  const size_t NP = (size_t)s.R + 1, S = (size_t)c->S, C = s.chan_on ? (size_t)s.ch_C : 0;
+  HIP_TRY(c, s.opt_part.reserve((size_t)3 * s.ex_chunks * NP * S * sizeof(double)));
+  // the spectra block grows by optimal and optimal_var, behind the variances; nothing of it is kept
+  HIP_TRY(c, s.ex_out.reserve(NP * (S + 1) * sizeof(double) + NP * sizeof(uint32_t) + 8 + NP * C * sizeof(double) +
+                              NP * (S + 1 + C) * sizeof(double) + 2 * NP * S * sizeof(double)));
+  s.opt_H = d->half_width;
+  s.opt_on = true;
+  return WAYNE_OK;
+}
+
 // bytes of a slot's spectra block: spectra [(R+1)*S], then sky [R+1]; with rejection, n_rejected [R+1] (uint32) behind
 // them; with channels, channels [(R+1)*C] behind those on the next multiple of 8 bytes; with variances, those behind
-// everything else
+// everything else -- but for optimal and optimal_var, which lie behind the variances
 static size_t spectra_bytes(const wayne_ctx* c, const Slot& s) {
+  if (s.opt_on) return optimal_offset(c, s) + optimal_count(c, s) * sizeof(double);
   if (s.var_on) return variance_offset(c, s) + variance_count(c, s) * sizeof(double);
   if (s.chan_on) return channels_offset(c, s) + (size_t)(s.R + 1) * s.ch_C * sizeof(double);
   return (size_t)(s.R + 1) * ((size_t)c->S + 1) * sizeof(double) + (s.crrej_on ? (size_t)(s.R + 1) * sizeof(uint32_t) : 0);
@@ -2169,6 +2241,7 @@ int wayne_exposure_wait_spectra(wayne_ctx* c, int slot, double** spectra, double
   s.ex_rej = s.crrej_on ? (const uint32_t*)(*sky + (s.R + 1)) : nullptr;
   s.ch_res = s.chan_on ? (const double*)(s.ex_pinned.p + channels_offset(c, s)) : nullptr;
   s.var_res = s.var_on ? (const double*)(s.ex_pinned.p + variance_offset(c, s)) : nullptr;
+  s.opt_res = s.opt_on ? (const double*)(s.ex_pinned.p + optimal_offset(c, s)) : nullptr;
   bool reran = false;                        // (the status word came with the spectra)
   int rc = look_at_status(c, slot, s.ex_pinned_misc, wayne_exposure_run, &reran);
   if (rc || !reran) return rc;
@@ -2198,8 +2271,16 @@ int wayne_exposure_download_spectra(wayne_ctx* c, int slot, double* spectra, dou
     if (s.var_on)
       HIP_TRY(c, hipMemcpyAsync(s.var_host.data(), (const char*)s.ex_out.p + variance_offset(c, s), s.var_host.size() * sizeof(double),
                                 hipMemcpyDeviceToHost, c->stream));
+    if (s.opt_on)
+      HIP_TRY(c, hipMemcpyAsync(s.opt_host.data(), (const char*)s.ex_out.p + optimal_offset(c, s), s.opt_host.size() * sizeof(double),
+                                hipMemcpyDeviceToHost, c->stream));
     return WAYNE_OK;
   };
+  s.opt_res = nullptr;
+  if (s.opt_on) {
+    s.opt_host.assign(optimal_count(c, s), 0.);
+    s.opt_res = s.opt_host.data();
+  }
   s.var_res = nullptr;
   if (s.var_on) {
     s.var_host.assign(variance_count(c, s), 0.);
@@ -2253,6 +2334,18 @@ int wayne_exposure_variances(wayne_ctx* c, int slot, const double** spectra_var,
   *spectra_var = s.var_res;
   *sky_var = s.var_res + (size_t)(s.R + 1) * c->S;
   *channels_var = s.chan_on ? *sky_var + (s.R + 1) : nullptr;
+  return WAYNE_OK;
+}
+
+int wayne_exposure_optimal(wayne_ctx* c, int slot, const double** optimal, const double** optimal_var) {
+  if (!c || !optimal || !optimal_var) return WAYNE_E_INVALID;
+  if (slot < 0 || slot >= kSlots) return fail(c, WAYNE_E_INVALID, "optimal: slot");
+  Slot& s = c->slots[slot];
+  if (!s.uploaded || !s.extract_on || !s.var_on || !s.opt_on)
+    return fail(c, WAYNE_E_STATE, "optimal: no optimal extraction set for the slot");
+  if (!s.opt_res) return fail(c, WAYNE_E_STATE, "optimal: wait_spectra or download_spectra first");
+  *optimal = s.opt_res;
+  *optimal_var = s.opt_res + (size_t)(s.R + 1) * c->S;
   return WAYNE_OK;
 }
 

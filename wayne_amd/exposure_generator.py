@@ -124,7 +124,7 @@ class ExposureGenerator(object):
                        add_initial_bias=True, progress_bar=None, threads=2,
                        rng_mode=_lib.RNG_SPLIT, out_dtype=np.float32, reference_quirks=False,
                        record=None, exact_samplers=False, contaminants=None, charge_traps=None, extraction=None,
-                       crrej=None, channels=None, variance=None):
+                       crrej=None, channels=None, variance=None, optimal=None):
         """Generate a spatially scanned exposure (exposure_generator.py:178-405).
 
         Extra keywords (not in the reference): `rng_mode` -- RNG_SPLIT (default:
@@ -160,14 +160,16 @@ class ExposureGenerator(object):
         (an extraction.Channels; it replaces the `channels` the extraction carries, with the rows' wavelength solution
         planned for this exposure): the Exposure then carries `channels` [R + 1, C] too; `variance` -- variances of that
         extraction (True or an extraction.Variances; it replaces the `variance` the extraction carries): the Exposure
-        then carries `spectra_var` [R + 1, S], `sky_var` [R + 1] and, with channels, `channels_var` [R + 1, C] too.
+        then carries `spectra_var` [R + 1, S], `sky_var` [R + 1] and, with channels, `channels_var` [R + 1, C] too;
+        `optimal` -- the optimal (profile-weighted) extraction on top of those variances (True or an extraction.Optimal; it
+        replaces the `optimal` the extraction carries): the Exposure then carries `optimal` and `optimal_var` [R + 1, S] too.
         """
         eng, desc, start_time = self._host_half(
             x_ref, y_ref, x_jitter, y_jitter, wl, stellar_flux, planet_signal, scan_speed, sample_rate,
             sample_mid_points, sample_durations, read_index, ssv_generator, noise_mean, noise_std, add_dark,
             add_flat, cosmic_rate, sky_background, scale_factor, add_gain_variations, add_non_linear,
             clip_values_det_limits, add_read_noise, add_stellar_noise, add_initial_bias, progress_bar, threads,
-            rng_mode, out_dtype, reference_quirks, exact_samplers, contaminants, charge_traps, extraction, crrej, channels, variance)
+            rng_mode, out_dtype, reference_quirks, exact_samplers, contaminants, charge_traps, extraction, crrej, channels, variance, optimal)
         if record is None and desc._extraction is None:
             reads = eng.ctx.synthesize(desc)
         else:
@@ -183,14 +185,16 @@ class ExposureGenerator(object):
             spectra, sky = eng.ctx.download_spectra(0)
             self._fill_spectra(spectra, sky, eng.ctx.rejected(0) if desc._extraction.crrej is not None else None,
                                eng.ctx.channels(0) if desc._extraction.channels is not None else None,
-                               eng.ctx.variances(0) if desc._extraction.variance is not None else None)
+                               eng.ctx.variances(0) if desc._extraction.variance is not None else None,
+                               eng.ctx.optimal(0) if desc._extraction.optimal is not None else None)
         return frame
 
-    def _fill_spectra(self, spectra, sky, rejected=None, channels=None, variances=None):
+    def _fill_spectra(self, spectra, sky, rejected=None, channels=None, variances=None, optimal=None):
         """The device's extraction of this generator's exposure -> Exposure.spectra [R + 1, S] / Exposure.sky [R + 1]
         (and Exposure.extraction, the plan they were formed with; Exposure.rejected [R + 1] when it rejects cosmic
         rays; Exposure.channels [R + 1, C] when it bins into wavelength channels; Exposure.spectra_var / .sky_var /
-        .channels_var -- the last None without channels -- when it delivers variances)."""
+        .channels_var -- the last None without channels -- when it delivers variances; Exposure.optimal / .optimal_var
+        when it extracts optimally too)."""
         self.exposure.spectra, self.exposure.sky = spectra, sky
         self.exposure.extraction = self.extraction_plan
         if rejected is not None:
@@ -199,6 +203,8 @@ class ExposureGenerator(object):
             self.exposure.channels = channels
         if variances is not None:
             self.exposure.spectra_var, self.exposure.sky_var, self.exposure.channels_var = variances
+        if optimal is not None:
+            self.exposure.optimal, self.exposure.optimal_var = optimal
         return self.exposure
 
     def _fill_exposure(self, reads, start_time=None):
@@ -225,7 +231,7 @@ class ExposureGenerator(object):
                    add_initial_bias=True, progress_bar=None, threads=2,
                    rng_mode=_lib.RNG_SPLIT, out_dtype=np.float32, reference_quirks=False,
                    exact_samplers=False, contaminants=None, charge_traps=None, extraction=None,
-                       crrej=None, channels=None, variance=None):
+                       crrej=None, channels=None, variance=None, optimal=None):
         """scanning_frame's arguments -> (engine, descriptor, start time): the mode's engine (cached after its first
         use) and build_descriptor.  No GPU call once the engine exists."""
         start_time = time.time()
@@ -236,7 +242,7 @@ class ExposureGenerator(object):
             sample_mid_points, sample_durations, read_index, ssv_generator, noise_mean, noise_std, add_dark,
             add_flat, cosmic_rate, sky_background, scale_factor, add_gain_variations, add_non_linear,
             clip_values_det_limits, add_read_noise, add_stellar_noise, add_initial_bias, progress_bar, threads,
-            rng_mode, out_dtype, reference_quirks, exact_samplers, contaminants, charge_traps, extraction, crrej, channels, variance)
+            rng_mode, out_dtype, reference_quirks, exact_samplers, contaminants, charge_traps, extraction, crrej, channels, variance, optimal)
         return eng, desc, start_time
 
     def prepare(self, *args, staring=False, **kw):
@@ -258,7 +264,7 @@ class ExposureGenerator(object):
                          add_initial_bias=True, progress_bar=None, threads=2,
                          rng_mode=_lib.RNG_SPLIT, out_dtype=np.float32, reference_quirks=False,
                          exact_samplers=False, contaminants=None, charge_traps=None, extraction=None,
-                       crrej=None, channels=None, variance=None):
+                       crrej=None, channels=None, variance=None, optimal=None):
         """The host half of scanning_frame: sample timing, scan positions, SSV,
         jitter / seed draws, spectrum crop (exposure_generator.py:247-334) ->
         one wayne_exposure_desc for the device.  Pure host code (`eng` may be
@@ -375,7 +381,7 @@ class ExposureGenerator(object):
             eng.check_descriptor(sub_scale)
         S = (1014 if self.SUBARRAY == 1024 else self.SUBARRAY) + 10
         self.extraction_plan = _extraction.for_exposure(extraction, self.grism, s_wl, x_ref, y_ref, scan_speed,
-                                                        self.read_times, sub_scale, S, crrej, channels, variance)
+                                                        self.read_times, sub_scale, S, crrej, channels, variance, optimal)
         self._read_dt = read_dt
         self._host_vectors = {"x_ref": s_x, "y_ref": s_y, "dur": s_dur, "seeds": s_rand_seeds, "read": sample_read}
         return _lib.make_desc(

@@ -20,7 +20,7 @@ solution for all rows errs by up to 104 A (2.3 px) over +-200 px on G141, a line
 window pixel into the channels by fractional column coverage, dividing it first (flat=True, the default) by the flat
 cube evaluated at the pixel's wavelength -- the factor the simulator multiplied in -- and hands back
 `channels` [R + 1, C] with the spectra (the law: include/wayne_hip.h, wayne_channels_desc).  The sky level is the column
-extraction's.  Not covered: optimal extraction, resampling in y, other grism orders, the direct image, merging per-rank
+extraction's.  Not covered: resampling in y, other grism orders, the direct image, merging per-rank
 .npz files, a flat-fielded sky fit.  Fitting stays with the caller.
 
 Variances are opt-in (`variance=` of Extraction / ExtractionOptions / the frames, CLI --variances [RN]): every pixel
@@ -35,7 +35,20 @@ correlation of read intervals through the read they share -- in a sum over conse
 but the read noise is that of the first and the last read alone, so the variance of `channels[:R].sum(0)` is
 `channels_var[:R].sum(0)` with its read-noise part replaced by the last-read product's (with a second extraction at
 read_noise = 0: cv0[:R].sum(0) + cv[R] - cv0[R]); the variance of a rejected pixel's replacement, taken from the
-replacement's own value.  Optimal extraction is not covered; it builds on these variances.
+replacement's own value.
+
+Optimal (profile-weighted) extraction is opt-in on top of the variances (`optimal=` of Extraction / ExtractionOptions /
+the frames, CLI --optimal [H]): the box extraction sums every row of a window, the margin rows that hold only read noise
+and sky included; `optimal` [R + 1, S] weighs a pixel by the share P of the column's light the window's own profile over
+2H + 1 columns (H = 8 by default, 1 .. 16) gives it, against the variance V of that model: sum(P d / V) / sum(P P / V),
+with `optimal_var` [R + 1, S] = 1 / sum(P P / V) plus the sky level's share (the law: include/wayne_hip.h,
+wayne_optimal_desc).  A column without a 3-sigma source over its 2H + 1 columns keeps the box values to the bit.  V is a
+model variance (a data variance biased the flux by -0.09 %) and P is clamped at 0 but not renormalised (renormalising
+turned the margin rows' noise into flux: +0.16 %, +9.5 % on a nearly unlit interval).  Limits: the profile's own noise is
+not in optimal_var, which is too small on a nearly unlit interval (an ensemble showed 1.64 times it); the intervals'
+correlation through shared reads is as for spectra_var.  Not covered: optimal wavelength-binned channels
+(`channel_weights(...) @ optimal` serves star-fixed columns), a profile from a PSF model or a polynomial fit along the
+dispersion, iterating the profile, rejecting on the optimal residuals, the direct image.
 
 Cosmic-ray rejection is opt-in (`crrej=` of Extraction / ExtractionOptions / the frames, CLI --reject-cosmics): on each
 read interval's difference image I a pixel at least 7 px inside the frame and in the plan's rows is flagged when it
@@ -112,6 +125,35 @@ class Variances(object):
     def desc(self):
         d = _lib.VarianceDesc()
         d.read_noise = self.read_noise
+        return d
+
+
+class Optimal(object):
+    """Optimal (profile-weighted) extraction beside the box extraction (wayne_optimal_desc): `half_width`, the columns on
+    either side of a column whose light forms its profile (an integer in 1 .. 16).  It needs the variances."""
+
+    def __init__(self, half_width=8):
+        if isinstance(half_width, bool) or int(half_width) != half_width:
+            raise ValueError("Optimal: half_width must be an integer")
+        half_width = int(half_width)
+        if not 1 <= half_width <= _lib.MAX_OPTIMAL_HALF_WIDTH:
+            raise ValueError("Optimal: half_width must lie in 1 .. %d" % _lib.MAX_OPTIMAL_HALF_WIDTH)
+        self.half_width = half_width
+
+    @staticmethod
+    def coerce(optimal):
+        """`optimal=` -> an Optimal or None: None and False are off, True the defaults."""
+        if optimal is None or optimal is False:
+            return None
+        if optimal is True:
+            return Optimal()
+        if not isinstance(optimal, Optimal):
+            raise TypeError("optimal: None, True or an extraction.Optimal")
+        return optimal
+
+    def desc(self):
+        d = _lib.OptimalDesc()
+        d.half_width = self.half_width
         return d
 
 
@@ -196,10 +238,11 @@ class Extraction(object):
     CosmicRejection): cosmic rays are rejected on the difference images first; it needs the GAIN step.  `channels` (None
     or a Channels) with `row_solution` = (wl_a [S], wl_b [S]): the window pixels are also binned into wavelength
     channels, row y by lambda_y(u) = wl_a[y] + wl_b[y] u at bordered column coordinate u.  `variance` (None, True or a
-    Variances): variances come back with the spectra, the sky levels and the channels; it needs the GAIN step."""
+    Variances): variances come back with the spectra, the sky levels and the channels; it needs the GAIN step.  `optimal`
+    (None, True or an Optimal): the profile-weighted spectra and their variances come back too; it needs `variance`."""
 
     def __init__(self, row_windows, bg_cols=BG_COLS, steps=ALL, crrej=None, channels=None, row_solution=None,
-                 variance=None):
+                 variance=None, optimal=None):
         w = np.asarray(row_windows, dtype=np.int64)
         if w.ndim != 2 or w.shape[1] != 2 or not 2 <= w.shape[0] <= _lib.EXTRACT_PRODUCTS:
             raise ValueError("row_windows: (lo, hi) for each of the R read intervals and for the last read")
@@ -211,6 +254,9 @@ class Extraction(object):
         self.variance = Variances.coerce(variance)
         if self.variance is not None and not self.steps & GAIN:
             raise ValueError("variance needs the GAIN step: a variance is in electrons^2")
+        self.optimal = Optimal.coerce(optimal)
+        if self.optimal is not None and self.variance is None:
+            raise ValueError("optimal needs variance: the weights are formed from the variances")
         self.row_solution = None
         self.hull = None              # (u_lo, u_hi): the bordered columns the channels can touch
         if self.channels is not None:
@@ -222,17 +268,22 @@ class Extraction(object):
     def with_crrej(self, crrej):
         """The same plan with another `crrej`."""
         return Extraction(self.row_windows, self.bg_cols, self.steps, crrej, self.channels, self.row_solution,
-                          self.variance)
+                          self.variance, self.optimal)
 
     def with_channels(self, channels, row_solution=None):
         """The same plan with other `channels` (None: without); `row_solution` defaults to the plan's own."""
         return Extraction(self.row_windows, self.bg_cols, self.steps, self.crrej, channels,
-                          self.row_solution if row_solution is None else row_solution, self.variance)
+                          self.row_solution if row_solution is None else row_solution, self.variance, self.optimal)
 
     def with_variance(self, variance):
-        """The same plan with another `variance`."""
+        """The same plan with another `variance` (without one, also without `optimal`, which needs it)."""
         return Extraction(self.row_windows, self.bg_cols, self.steps, self.crrej, self.channels, self.row_solution,
-                          variance)
+                          variance, self.optimal if Variances.coerce(variance) is not None else None)
+
+    def with_optimal(self, optimal):
+        """The same plan with another `optimal`."""
+        return Extraction(self.row_windows, self.bg_cols, self.steps, self.crrej, self.channels, self.row_solution,
+                          self.variance, optimal)
 
     @property
     def mask_rows(self):
@@ -265,26 +316,38 @@ class ExtractionOptions(object):
     """Extraction planned per exposure: what `extraction=` takes where the star moves from exposure to exposure
     (Observation.frame_options, VisitRunner).  ExposureGenerator turns it into that exposure's Extraction (plan)."""
 
-    def __init__(self, margin=ROW_MARGIN, bg_cols=BG_COLS, steps=ALL, crrej=None, channels=None, variance=None):
+    def __init__(self, margin=ROW_MARGIN, bg_cols=BG_COLS, steps=ALL, crrej=None, channels=None, variance=None,
+                 optimal=None):
         self.margin, self.bg_cols, self.steps = int(margin), (int(bg_cols[0]), int(bg_cols[1])), int(steps)
         self.crrej = CosmicRejection.coerce(crrej)
         self.channels = Channels.coerce(channels)
         self.variance = Variances.coerce(variance)
+        self.optimal = Optimal.coerce(optimal)
+        if self.optimal is not None and self.variance is None:
+            raise ValueError("optimal needs variance: the weights are formed from the variances")
 
     def plan(self, grism, wl, x_ref, y_ref, scan_speed, read_times, sub_scale, S, channels=OWN):
         """This exposure's Extraction; `channels` (a Channels or None) replaces the options' own."""
         channels = self.channels if channels is OWN else Channels.coerce(channels)
         sol = None if channels is None else row_solution(grism, x_ref, y_ref, sub_scale, S)
         return Extraction(row_windows(grism, wl, x_ref, y_ref, scan_speed, read_times, sub_scale, S, self.margin),
-                          self.bg_cols, self.steps, self.crrej, channels, sol, self.variance)
+                          self.bg_cols, self.steps, self.crrej, channels, sol, self.variance, self.optimal)
 
 
 def for_exposure(extraction, grism, wl, x_ref, y_ref, scan_speed, read_times, sub_scale, S, crrej=None, channels=None,
-                 variance=None):
+                 variance=None, optimal=None):
     """`extraction=` of a frame -> that exposure's Extraction: None stays None, an Extraction is taken as it is, True is
     the default plan and an ExtractionOptions its own.  `crrej=` of the frame, when given, replaces the plan's; so does
     `channels=` (a Channels), with the row solution planned for this exposure, and so does `variance=` (True or a
-    Variances)."""
+    Variances) and `optimal=` (True or an Optimal; without variances on the plan it is an error)."""
+    if optimal is not None:
+        plan = for_exposure(extraction, grism, wl, x_ref, y_ref, scan_speed, read_times, sub_scale, S, crrej, channels,
+                            variance)
+        if plan is None:
+            if optimal is not False:
+                raise ValueError("optimal needs an extraction")
+            return None
+        return plan.with_optimal(optimal)
     if variance is not None:
         if extraction is None or extraction is False:
             if variance is not False:
@@ -397,7 +460,7 @@ def channel_weights(x_ref, edges, sub_scale, S):
 CHUNK_ROWS = 32            # rows of a chunk of a window (kExtractRows): partial sums are kept per chunk
 
 
-def algorithmic_bytes(plan, S, R, read_bytes=4, crrej=False, channels=False, variance=False):
+def algorithmic_bytes(plan, S, R, read_bytes=4, crrej=False, channels=False, variance=False, optimal=False):
     """Bytes the extraction's kernels must move for `plan` on a frame of side S with R non-zero reads of `read_bytes`
     a sample: per pixel of product j's window the reads P_{j+1}, P_j, P_0 (P_0 once for j = 0 and for the last read),
     four coefficient planes, dark_{j+1} and dark_j (float32 each; dark_0 = 0 is not stored), the pixel flat and the
@@ -410,7 +473,10 @@ def algorithmic_bytes(plan, S, R, read_bytes=4, crrej=False, channels=False, var
     planes when the flat is divided out, the row's wl_a / wl_b (2 float64 per row); the chunks' sums (2 C float64 per
     chunk) written and read once and channels [(R + 1) C] written.  `variance`: no plane is read for it -- plus the chunks'
     variance sums (a float64 per chunk and column; with `channels`, C float64 per chunk) written and read once and
-    spectra_var, sky_var [(R + 1)(S + 1)] and, with `channels`, channels_var [(R + 1) C] written."""
+    spectra_var, sky_var [(R + 1)(S + 1)] and, with `channels`, channels_var [(R + 1) C] written.  `optimal`: plus
+    k_extract_optimal's -- per window pixel the planes k_extract_rows reads (the flag word under `crrej` too) once more, the
+    chunks' sums (3 float64 per chunk and column) written and read once and optimal, optimal_var [2 (R + 1) S] written.
+    (The halo a tile re-reads, 1.5 times the tile, is not algorithmic.)"""
     total = 0
     hull = (plan.hull[1] - plan.hull[0]) if channels and plan.channels is not None else 0
     n_ch = plan.channels.n if hull or (channels and plan.channels is not None) else 0
@@ -437,6 +503,10 @@ def algorithmic_bytes(plan, S, R, read_bytes=4, crrej=False, channels=False, var
             total += rows * 16 + 2 * (chunks * 2 * n_ch * 8)
         if variance:
             total += 2 * (chunks * S * 8) + 2 * (chunks * n_ch * 8)
+        if optimal:
+            total += rows * S * (per_pixel + (2 if crrej else 0)) + 2 * (3 * chunks * S * 8)
+    if optimal:
+        total += 2 * (R + 1) * S * 8
     if variance:
         total += (R + 1) * (S + 1) * 8 + (R + 1) * n_ch * 8
     return total + (R + 1) * (S + 1) * 8 + (R + 1) * n_ch * 8
@@ -453,6 +523,7 @@ class Delivery(object):
         self.rejected = None      # n_rejected [R + 1] of the last wait (None: that slot extracts without rejection)
         self.channels = None      # channels [R + 1, C] of the last wait (None: that slot extracts without channels)
         self.variances = None     # (spectra_var, sky_var, channels_var or None) of the last wait (None: without variances)
+        self.optimal = None       # (optimal, optimal_var) of the last wait (None: that slot extracts without them)
 
     def upload(self, slot, desc):
         self.ctx.upload(slot, desc)
@@ -471,11 +542,12 @@ class Delivery(object):
         self.rejected = self.ctx.rejected(slot) if self.ctx.has_crrej(slot) else None
         self.channels = self.ctx.channels(slot) if self.ctx.has_channels(slot) else None
         self.variances = self.ctx.variances(slot) if self.ctx.has_variance(slot) else None
+        self.optimal = self.ctx.optimal(slot) if self.ctx.has_optimal(slot) else None
         return reads, spectra, sky
 
 
 def save_npz(path, spectra, sky, exposure_index, plans, x_ref, y_ref, read_times, exp_start, rejected=None, channels=None,
-             variances=None):
+             variances=None, optimal=None):
     """The file --spectra / --spectra-only write: spectra [n, R + 1, S], sky [n, R + 1], exposure_index [n], row_lo /
     row_hi [n, R + 1], bg_cols [2], x_ref / y_ref [n], read_times [R], exp_start [n].  With `rejected` [n, R + 1] (the
     exposures were extracted with cosmic-ray rejection) also n_rejected [n, R + 1] -- flags in each product's window,
@@ -483,7 +555,8 @@ def save_npz(path, spectra, sky, exposure_index, plans, x_ref, y_ref, read_times
     (the exposures were binned into wavelength channels) also channels, channel_edges_um [C + 1], channel_flat and the
     rows' wavelength solutions wl_a / wl_b [n, S].  With `variances` = (spectra_var [n, R + 1, S], sky_var [n, R + 1],
     channels_var [n, R + 1, C] or None) (the exposures were extracted with variances) also spectra_var, sky_var,
-    channels_var (with channels) and variance_read_noise."""
+    channels_var (with channels) and variance_read_noise.  With `optimal` = (optimal [n, R + 1, S], optimal_var
+    [n, R + 1, S]) (the exposures were extracted optimally too) also optimal, optimal_var and optimal_half_width."""
     n = len(exposure_index)
     more = {}
     if rejected is not None:
@@ -501,6 +574,9 @@ def save_npz(path, spectra, sky, exposure_index, plans, x_ref, y_ref, read_times
                     variance_read_noise=np.float64(plans[0].variance.read_noise))
         if variances[2] is not None:
             more["channels_var"] = np.asarray(variances[2], dtype=np.float64)
+    if optimal is not None:
+        more.update(optimal=np.asarray(optimal[0], dtype=np.float64), optimal_var=np.asarray(optimal[1], dtype=np.float64),
+                    optimal_half_width=np.int64(plans[0].optimal.half_width))
     np.savez(path, **more, spectra=np.asarray(spectra, dtype=np.float64), sky=np.asarray(sky, dtype=np.float64),
              exposure_index=np.asarray(exposure_index, dtype=np.int64),
              row_lo=np.array([p.row_lo for p in plans], dtype=np.int64).reshape(n, -1),

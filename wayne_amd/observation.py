@@ -68,6 +68,8 @@ class Observation(object):
         # flat-fielded wavelength channels: `spectra_result["channels"]` [n, R + 1, C] and the .npz's channels.
         # frame_options["variance"] (True or an extraction.Variances; CLI: --variances [RN]) delivers variances with
         # it: `spectra_result["spectra_var"]` / ["sky_var"] / ["channels_var"] and the .npz's keys of those names.
+        # frame_options["optimal"] (True or an extraction.Optimal; CLI: --optimal [H]) adds the optimal extraction on
+        # top of those variances: `spectra_result["optimal"]` / ["optimal_var"] and the .npz's keys of those names.
         self.frame_options = {"out_dtype": np.float32}
         self.spectra_out = None
         self.spectra_only = False
@@ -349,7 +351,7 @@ class Observation(object):
         from .exposure import FitsWriterPool
         from .pipeline import run_pipelined
         pool = FitsWriterPool() if write_fits_raw else None
-        got_spectra = []              # (index, spectra, sky, plan, x_ref, y_ref, n_rejected or None, channels or None) of every exposure, in delivery order; then its variances or None
+        got_spectra = []              # (index, spectra, sky, plan, x_ref, y_ref, n_rejected or None, channels or None) of every exposure, in delivery order; then its variances or None, then its (optimal, optimal_var) or None
 
         def prepare(i):
             gen = self._generate_exposure(self.exp_start_times[i], i + 1, write_fits=False, prepare_only=True)
@@ -361,8 +363,8 @@ class Observation(object):
                 reads, spectra, sky = reads
                 spectra, sky = np.array(spectra), np.array(sky)           # (copies: the pinned buffer is reused)
                 got_spectra.append((i, spectra, sky, gen.extraction_plan, gen.exp_info["x_ref"], gen.exp_info["y_ref"],
-                                    ctx.rejected, ctx.channels, ctx.variances))
-                frame = gen._fill_spectra(spectra, sky, ctx.rejected, ctx.channels, ctx.variances)
+                                    ctx.rejected, ctx.channels, ctx.variances, ctx.optimal))
+                frame = gen._fill_spectra(spectra, sky, ctx.rejected, ctx.channels, ctx.variances, ctx.optimal)
             if reads is not None:
                 frame = gen._fill_exposure(np.array(reads), gen._prepared[2])     # (a copy: the pinned buffer is reused)
             if pool is not None:
@@ -406,6 +408,9 @@ class Observation(object):
             self.spectra_result["sky_var"] = np.array([g[8][1] for g in got], dtype=np.float64)
             if all(g[8][2] is not None for g in got):
                 self.spectra_result["channels_var"] = np.array([g[8][2] for g in got], dtype=np.float64)
+        if got and all(g[9] is not None for g in got):        # extracted optimally too
+            self.spectra_result["optimal"] = np.array([g[9][0] for g in got], dtype=np.float64)
+            self.spectra_result["optimal_var"] = np.array([g[9][1] for g in got], dtype=np.float64)
         if not self.spectra_out:
             return None
         path = self.spectra_out
@@ -416,7 +421,8 @@ class Observation(object):
         with open(path, "wb") as f:
             _extraction.save_npz(f, r["spectra"], r["sky"], r["exposure_index"], r["plans"], r["x_ref"], r["y_ref"],
                                  r["read_times"], r["exp_start"], rejected=r.get("rejected"), channels=r.get("channels"),
-                                 variances=(r["spectra_var"], r["sky_var"], r.get("channels_var")) if "spectra_var" in r else None)
+                                 variances=(r["spectra_var"], r["sky_var"], r.get("channels_var")) if "spectra_var" in r else None,
+                                 optimal=(r["optimal"], r["optimal_var"]) if "optimal" in r else None)
         return path
 
     @staticmethod

@@ -2,7 +2,7 @@
 
     python -m wayne_amd.run_visit -p <parameter_file> [--calibration DIR] [--device N] [--max-exposures M] [--gpus G] [--resume]
                                   [--spectra OUT.npz | --spectra-only OUT.npz] [--reject-cosmics [K]]
-                                  [--channels LO:HI:N] [--no-channel-flat] [--variances [RN]]
+                                  [--channels LO:HI:N] [--no-channel-flat] [--variances [RN]] [--optimal [H]]
 
 Accepts the reference's parameter files (wayne/run_visit.py:1-9, example
 examples/hd209458b_12181_simulation_parameters.yml): sections `general`
@@ -38,7 +38,9 @@ examples/hd209458b_12181_simulation_parameters.yml): sections `general`
     solutions wl_a / wl_b [n, S].  `--variances [RN]` (with either): the device also sums every window pixel's variance
     -- Poisson on its own electrons plus the read noise RN of a difference of two reads (default 20 e-) through its own
     gain -- beside its flux; OUT.npz then also holds spectra_var [n, NSAMP, S], sky_var [n, NSAMP], with --channels
-    channels_var [n, NSAMP, N], and variance_read_noise;
+    channels_var [n, NSAMP, N], and variance_read_noise.  `--optimal [H]` (with --variances): the device also forms the
+    optimal (profile-weighted) spectra, each column's profile taken from the window's own light over 2H + 1 columns
+    (default H = 8, 1 .. 16); OUT.npz then also holds optimal, optimal_var [n, NSAMP, S] and optimal_half_width;
   * `--gpus G`: the process starts G rank processes itself (one per GPU of this node, before anything touches a
     GPU) and waits for them; under an external launcher (WORLD_SIZE / RANK set, one process per GPU) it is one
     rank.  Each rank generates its round-robin share of the exposures (observation.py:403-405 is the axis) on the
@@ -210,6 +212,10 @@ def run(argv=None):
                     help="with --spectra / --spectra-only: also deliver the variances of the spectra, the sky levels and "
                          "the channels, RN e- (default 20) the read noise of a difference of two reads; OUT.npz then also "
                          "holds spectra_var, sky_var, channels_var (with --channels) and variance_read_noise")
+    ap.add_argument("--optimal", nargs="?", type=int, const=8, default=None, metavar="H",
+                    help="with --variances: also deliver the optimal (profile-weighted) spectra and their variances, the "
+                         "profile of a column formed over 2H + 1 columns (default 8, 1 .. 16); OUT.npz then also holds "
+                         "optimal, optimal_var and optimal_half_width")
     args = ap.parse_args(argv)
     variance = None
     if args.variances is not None:
@@ -220,6 +226,15 @@ def run(argv=None):
             variance = Variances(read_noise=args.variances)
         except ValueError as e:
             raise SystemExit("--variances [RN] (e-, finite and >= 0): %s" % e)
+    optimal = None
+    if args.optimal is not None:
+        if variance is None:
+            raise SystemExit("--optimal needs --variances")
+        from .extraction import Optimal
+        try:
+            optimal = Optimal(half_width=args.optimal)
+        except ValueError as e:
+            raise SystemExit("--optimal [H] (columns, 1 .. 16): %s" % e)
     channels = None
     if args.no_channel_flat and args.channels is None:
         raise SystemExit("--no-channel-flat needs --channels")
@@ -297,6 +312,8 @@ def run(argv=None):
             obs.frame_options["channels"] = channels
         if variance is not None:
             obs.frame_options["variance"] = variance
+        if optimal is not None:
+            obs.frame_options["optimal"] = optimal
         obs.spectra_out = args.spectra or args.spectra_only
         obs.spectra_only = bool(args.spectra_only)
     os.makedirs(obs.outdir, exist_ok=True)

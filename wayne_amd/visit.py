@@ -94,10 +94,12 @@ class VisitRunner(object):
         device extracts each exposure's column spectra behind its reads and both are delivered --
         `on_spectra(i, spectra, sky)` gets views of the pinned buffer, and keep=True returns
         {index: (reads, spectra, sky)}.  When the extraction delivers variances, `self.spectra_var`, `self.sky_var` and
-        -- with channels -- `self.channels_var` are {index: array} of every exposure run (None otherwise)."""
+        -- with channels -- `self.channels_var` are {index: array} of every exposure run (None otherwise); when it
+        extracts optimally too, so are `self.optimal` and `self.optimal_var`."""
         eng = self.engine()
         results = {}
         self.spectra_var = self.sky_var = self.channels_var = None
+        self.optimal = self.optimal_var = None
         pool = FitsWriterPool() if self.out_dir is not None else None
 
         def prepare(i):
@@ -118,6 +120,10 @@ class VisitRunner(object):
                     self.spectra_var[i], self.sky_var[i] = ctx.variances[0], ctx.variances[1]
                     if self.channels_var is not None:
                         self.channels_var[i] = ctx.variances[2]
+                if ctx.optimal is not None:
+                    if self.optimal is None:
+                        self.optimal, self.optimal_var = {}, {}
+                    self.optimal[i], self.optimal_var[i] = ctx.optimal
                 if on_spectra is not None:
                     on_spectra(i, spectra, sky)
             if on_reads is not None:
@@ -144,7 +150,8 @@ class VisitRunner(object):
         extraction.Extraction; `self.rejected` [n, R + 1]: the flag counts of an extraction that rejects cosmic rays
         (None otherwise); `self.channels` [n, R + 1, C]: the channel fluxes of an extraction that bins into wavelength
         channels (None otherwise); `self.spectra_var` [n, R + 1, S], `self.sky_var` [n, R + 1] and -- with channels --
-        `self.channels_var` [n, R + 1, C]: the variances of an extraction that delivers them (None otherwise)."""
+        `self.channels_var` [n, R + 1, C]: the variances of an extraction that delivers them (None otherwise);
+        `self.optimal` and `self.optimal_var` [n, R + 1, S]: the optimal extraction's, when asked for (None otherwise)."""
         eng = self.engine()
         indices = list(indices)
         where = {i: n for n, i in enumerate(indices)}
@@ -155,6 +162,7 @@ class VisitRunner(object):
         counts = [None] * len(indices)
         binned = [None] * len(indices)
         varis = [None] * len(indices)
+        optis = [None] * len(indices)
         delivery = _extraction.Delivery(eng.ctx, reads=False)
 
         def prepare(i):
@@ -170,6 +178,7 @@ class VisitRunner(object):
             counts[where[i]] = delivery.rejected
             binned[where[i]] = delivery.channels
             varis[where[i]] = delivery.variances
+            optis[where[i]] = delivery.optimal
 
         run_pipelined(delivery, indices, prepare, finish, self.DEPTH, self.DEPTH)
         self.rejected = None if any(n is None for n in counts) or not counts else np.array(counts, dtype=np.uint32)
@@ -180,6 +189,10 @@ class VisitRunner(object):
             self.sky_var = np.array([v[1] for v in varis], dtype=np.float64)
             if not any(v[2] is None for v in varis):
                 self.channels_var = np.array([v[2] for v in varis], dtype=np.float64)
+        self.optimal = self.optimal_var = None
+        if optis and not any(o is None for o in optis):
+            self.optimal = np.array([o[0] for o in optis], dtype=np.float64)
+            self.optimal_var = np.array([o[1] for o in optis], dtype=np.float64)
         return spectra, sky
 
     def run_resident_spectra(self, n, on_spectra=None):
