@@ -20,6 +20,7 @@
 #ifndef WAYNE_HIP_H
 #define WAYNE_HIP_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -559,8 +560,8 @@ int wayne_exposure_variances(wayne_ctx *ctx, int slot, const double **spectra_va
  * Limits: the profile's own noise is not in 1 / W -- on a nearly unlit read interval the ensemble variance was 1.64 times
  * optimal_var; the read intervals are correlated through the reads they share, as for spectra_var; with read_noise = 0
  * a pixel whose model is <= 0 has V = 0, and its column then falls back to the box values.
- * Not covered: optimal wavelength-binned channels (weights on star-fixed columns applied to `optimal` serve those); a
- * profile from a PSF model or a polynomial fit along the dispersion; iterating the profile; rejecting on the optimal
+ * Optimal wavelength-binned channels and a profile supplied by the caller: below (wayne_exposure_set_optimal_channels,
+ * wayne_exposure_set_optimal_profile).  Not covered: a profile from a PSF model or a polynomial fit along the dispersion; iterating the profile; rejecting on the optimal
  * residuals; the direct image.
  */
 #define WAYNE_MAX_OPTIMAL_HALF_WIDTH 16
@@ -578,6 +579,69 @@ int wayne_exposure_set_optimal(wayne_ctx *ctx, int slot, const wayne_optimal_des
  * [(R+1)*S each], valid until the slot's spectra are fetched or the slot is uploaded again.  WAYNE_E_STATE before any
  * fetch or without wayne_exposure_set_optimal. */
 int wayne_exposure_optimal(wayne_ctx *ctx, int slot, const double **optimal, const double **optimal_var);
+/*
+ * Profile planes, and the optimal extraction with a profile the caller supplies (opt-in on top of
+ * wayne_exposure_set_optimal; without them nothing above changes.  Added within WAYNE_ABI_VERSION 7: new symbols only).
+ * The profile S1 / S0 above is formed from the exposure's own light, so its noise enters the weights: a pipeline that
+ * forms ONE profile per visit from several exposures and extracts every exposure with it has weights that do not depend
+ * on the exposure's own noise.  With --spectra-only the reads never leave the device, so the profile's raw material is
+ * formed there too.
+ * Layout of both (float64): the windows of all R + 1 products one behind the other, rows relative to the window --
+ *   element off_p + (y - lo_p) S + x,   off_p = sum_{p' < p} (hi_p' - lo_p') S.
+ * Delivery: planes[...] = S1(y,x) of the law above, the same left-to-right sum; zeros for p = R when WAYNE_X_LAST_READ is
+ * off (that window then counts with min(max(hi - lo, 0), S) rows).  It is S1 and not S1 / S0: the caller adds the planes of
+ * several exposures and normalises the sum -- a flux-weighted mean, and no division by a noisy S0.
+ * Supplied profile Pi: the law above with Pr := Pi(y,x); d, bt, q, rn, S0, SV0 and the box values are as above --
+ *   P = max(Pi, 0)     V = max(spectra_p[x] Pi + sky_p bt, 0) + rn^2 (q q)
+ *   U, W, G, ok(x), optimal_p and optimal_var_p as above (H enters through ok(x) alone; a column whose profile is 0 on
+ *   every row has W = 0 and keeps the box values to the bit).  The row sums are taken in the order of the law above.
+ * Limits: the profile is fixed on the detector -- a star that drifts by a fraction of a pixel between the profile's
+ * exposures and the extracted one, and a forward scan extracted with a reverse scan's profile, are weighted by a shifted
+ * profile (biased low where the profile is steep); a nearly unlit read interval has a profile of noise; the read intervals
+ * are correlated through the reads they share.
+ */
+/* After wayne_exposure_set_optimal, before run: every run of the slot also writes the profile planes (on = 0 clears; whatever
+ * clears the optimal extraction -- upload, set_extraction, set_variance, set_optimal -- clears it too).  WAYNE_E_STATE
+ * without wayne_exposure_set_optimal. */
+int wayne_exposure_deliver_profile(wayne_ctx *ctx, int slot, int on);
+/* After wayne_exposure_set_optimal, before run: extract with `profile` (copied before the call returns; NULL clears, back to
+ * the exposure's own profile; cleared by what clears the optimal extraction), laid out for windows of rows[0 .. R] rows.
+ * WAYNE_E_STATE without wayne_exposure_set_optimal; WAYNE_E_INVALID for a height outside 1 .. S (0 .. S for the last read).
+ * A run of a slot whose windows have other heights than rows[] returns WAYNE_E_INVALID and enqueues nothing; the slot stays
+ * usable (set another profile or clear it). */
+int wayne_exposure_set_optimal_profile(wayne_ctx *ctx, int slot, const double *profile, const int *rows);
+/* The same, for a caller that hands a slot the same profile again and again (a visit does, with every exposure it uploads
+ * there): `tag` != 0 identifies the CONTENT of `profile`.  The slot keeps its device copy across whatever clears the option,
+ * and a call with the tag, the heights and the length of the profile it holds copies nothing, does not wait for the slot's
+ * stream and does not read `profile`.  Equal tags are taken as equal content: a caller that reuses a tag for other values
+ * extracts with the old ones.  tag = 0: always copied (wayne_exposure_set_optimal_profile). */
+int wayne_exposure_set_optimal_profile_tagged(wayne_ctx *ctx, int slot, const double *profile, const int *rows, uint64_t tag);
+/* Profiles the two calls above have copied to the device since the context was created. */
+unsigned long long wayne_ctx_profile_uploads(const wayne_ctx *ctx);
+/* After wayne_exposure_set_channels AND wayne_exposure_set_optimal (and a supplied profile, if any), before run: the
+ * optimal channels (on = 0 clears; whatever clears the optimal extraction clears them, and so does set_channels).  With
+ * w_b and F exactly those of the channels' law, d, bt, P, V, q, rn of the optimal law (either profile source), W_p[x] the
+ * ascending chunk sum wayne_exposure_optimal's values were formed from and ok(x) its rule:
+ *   e  = ok(x) ? ((P d) / V) / W_p[x] : d           k = ok(x) ? ((P bt) / V) / W_p[x] : bt
+ *   ev = ok(x) ? ((P P) / V) / W_p[x]^2 : max(v, 0) + rn^2 q^2
+ *   channels_opt_p[b]     = sum_y sum_x w_b e / F          K_p[b] = sum_y sum_x w_b k / F
+ *   channels_opt_var_p[b] = sum_y sum_x w_b^2 ev / F^2 + K_p[b]^2 sky_var_p
+ * both (R+1)*C, behind optimal_var in the spectra's copy; zeros for p = R when WAYNE_X_LAST_READ is off.  With edges on
+ * whole columns, one solution for all rows and the flat off, channels_opt is `optimal` summed over a channel's columns and
+ * channels_opt_var sum 1 / W plus the sky level's share taken ONCE for the channel -- where summing optimal_var is wrong.
+ * With the exposure's own profile the profile's noise is common to a channel's columns and channels_opt_var is too small
+ * (measured: README); it is meant for a supplied profile.  WAYNE_E_STATE without channels or the optimal extraction. */
+int wayne_exposure_set_optimal_channels(wayne_ctx *ctx, int slot, int on);
+/* After wayne_exposure_wait_spectra / _download_spectra of such a slot: *channels_opt and *channels_opt_var [(R+1)*C each],
+ * valid as long as wayne_exposure_optimal's arrays.  WAYNE_E_STATE before any fetch or without the option. */
+int wayne_exposure_optimal_channels(wayne_ctx *ctx, int slot, const double **channels_opt, const double **channels_opt_var);
+/* After a run of a slot with profile delivery AND wayne_exposure_wait_spectra / _download_spectra of it (they settle the
+ * run): enqueue the copy of the planes into pinned host memory -- a copy of its own, not part of the spectra's (tens of MB
+ * on a full frame, wanted for a handful of exposures per visit).  Returns at once.  WAYNE_E_STATE otherwise. */
+int wayne_exposure_fetch_profile(wayne_ctx *ctx, int slot);
+/* Waits for wayne_exposure_fetch_profile's copy: *planes (valid until the next fetch_profile or upload of the slot) and
+ * *count, its doubles.  WAYNE_E_STATE without a fetch. */
+int wayne_exposure_profile(wayne_ctx *ctx, int slot, const double **planes, size_t *count);
 /* HIP-event time of the extraction's kernels (the channels', the variances' and the optimal extraction's included) while wayne_profile_enable is on, since
  * wayne_profile_reset: launches (one per extracted exposure) and total milliseconds.  wayne_profile_select's bit 8
  * selects it.  Synchronises. */

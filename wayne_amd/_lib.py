@@ -174,6 +174,14 @@ SYMBOLS = {
     "wayne_exposure_variances": (C.c_int, [_vp, C.c_int, C.POINTER(_dp), C.POINTER(_dp), C.POINTER(_dp)]),
     "wayne_exposure_set_optimal": (C.c_int, [_vp, C.c_int, C.POINTER(OptimalDesc)]),
     "wayne_exposure_optimal": (C.c_int, [_vp, C.c_int, C.POINTER(_dp), C.POINTER(_dp)]),
+    "wayne_exposure_deliver_profile": (C.c_int, [_vp, C.c_int, C.c_int]),
+    "wayne_exposure_set_optimal_profile": (C.c_int, [_vp, C.c_int, _dp, C.POINTER(C.c_int)]),
+    "wayne_exposure_set_optimal_profile_tagged": (C.c_int, [_vp, C.c_int, _dp, C.POINTER(C.c_int), C.c_uint64]),
+    "wayne_ctx_profile_uploads": (C.c_ulonglong, [_vp]),
+    "wayne_exposure_set_optimal_channels": (C.c_int, [_vp, C.c_int, C.c_int]),
+    "wayne_exposure_optimal_channels": (C.c_int, [_vp, C.c_int, C.POINTER(_dp), C.POINTER(_dp)]),
+    "wayne_exposure_fetch_profile": (C.c_int, [_vp, C.c_int]),
+    "wayne_exposure_profile": (C.c_int, [_vp, C.c_int, C.POINTER(_dp), C.POINTER(C.c_size_t)]),
     "wayne_extract_profile": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_double)]),
     "wayne_profile_enable": (C.c_int, [_vp, C.c_int]),
     "wayne_profile_select": (C.c_int, [_vp, C.c_uint]),
@@ -299,6 +307,8 @@ class Context(object):
         self._slot_chan = {}     # slot -> channels of its extraction (set_channels succeeded)
         self._slot_var = set()   # slots whose extraction delivers variances (set_variance succeeded)
         self._slot_opt = set()   # slots whose extraction delivers the optimal values too (set_optimal succeeded)
+        self._slot_optch = set() # slots whose extraction delivers the optimal channels (set_optimal_channels succeeded)
+        self._slot_prof = set()  # slots whose runs write the profile planes too (deliver_profile succeeded)
         _live_contexts.add(self)
         for name, value in _knob_defaults.items():
             self.set_knob(name, value)
@@ -423,6 +433,8 @@ class Context(object):
         self._slot_chan.pop(slot, None)
         self._slot_var.discard(slot)
         self._slot_opt.discard(slot)
+        self._slot_prof.discard(slot)
+        self._slot_optch.discard(slot)
         sources = getattr(desc, "_sources", None)
         if sources:
             self.set_sources(slot, sources)
@@ -470,6 +482,8 @@ class Context(object):
         self._slot_chan.pop(slot, None)
         self._slot_var.discard(slot)
         self._slot_opt.discard(slot)
+        self._slot_prof.discard(slot)
+        self._slot_optch.discard(slot)
         if extraction is None:
             self.check(self._L.wayne_exposure_set_extraction(self._h, int(slot), None))
             return
@@ -489,6 +503,8 @@ class Context(object):
         set_channels do not).  See wayne_exposure_set_variance."""
         self._slot_var.discard(slot)             # (a refusal leaves the slot extracting without variances)
         self._slot_opt.discard(slot)             # (the optimal extraction stands on them: set_optimal comes after)
+        self._slot_prof.discard(slot)
+        self._slot_optch.discard(slot)
         if variance is None or variance is False:
             self.check(self._L.wayne_exposure_set_variance(self._h, int(slot), None))
             return
@@ -520,6 +536,8 @@ class Context(object):
         half width in columns), True for its default or an int -- None clears; after set_variance, which clears it too
         (set_crrej and set_channels do not).  See wayne_exposure_set_optimal."""
         self._slot_opt.discard(slot)             # (a refusal leaves the slot extracting without it)
+        self._slot_prof.discard(slot)          # (the profile planes and a supplied profile go with it)
+        self._slot_optch.discard(slot)
         if optimal is None or optimal is False:
             self.check(self._L.wayne_exposure_set_optimal(self._h, int(slot), None))
             return
@@ -529,6 +547,12 @@ class Context(object):
             d = optimal.desc() if hasattr(optimal, "desc") else OptimalDesc(int(optimal))
         self.check(self._L.wayne_exposure_set_optimal(self._h, int(slot), C.byref(d)))
         self._slot_opt.add(slot)
+        if getattr(optimal, "profile", None) is not None:
+            self.set_optimal_profile(slot, optimal.profile)
+        if getattr(optimal, "deliver_profile", False):
+            self.deliver_profile(slot)
+        if getattr(optimal, "channels", False):
+            self.set_optimal_channels(slot)
 
     def has_optimal(self, slot):
         """Whether the slot's extraction delivers the optimal values (set_optimal succeeded since its last set_variance)."""
@@ -543,12 +567,87 @@ class Context(object):
         return (np.ctypeslib.as_array(po, shape=(R + 1, self.S)).copy(),
                 np.ctypeslib.as_array(pv, shape=(R + 1, self.S)).copy())
 
+    def set_optimal_profile(self, slot, profile):
+        """Extract the slot optimally with a supplied profile: an extraction.Profile (the planes, float64, and the window
+        heights they were made for) -- None goes back to the exposure's own profile; after set_optimal, which clears it
+        too.  The planes are copied.  A run of a slot whose windows have other heights is refused (E_INVALID).  See
+        wayne_exposure_set_optimal_profile."""
+        if profile is None:
+            self.check(self._L.wayne_exposure_set_optimal_profile(self._h, int(slot), None, None))
+            return
+        if isinstance(profile, dict):
+            raise ValueError("set_optimal_profile: one Profile, not {profile_key: Profile} (extraction.pick_profile chooses)")
+        planes = np.ascontiguousarray(profile.planes, dtype=np.float64)
+        rows = (C.c_int * len(profile.rows))(*[int(r) for r in profile.rows])
+        K, W, R, _ = self._slot_meta[slot]
+        if len(profile.rows) != R + 1 or planes.size != sum(profile.rows) * self.S:
+            raise ValueError("set_optimal_profile: the profile holds %d windows and %d values; the slot has %d windows of "
+                             "%d columns" % (len(profile.rows), planes.size, R + 1, self.S))
+        # (the Profile's tag names its content: a slot that already holds it copies nothing)
+        self.check(self._L.wayne_exposure_set_optimal_profile_tagged(self._h, int(slot), planes.ctypes.data_as(_dp), rows,
+                                                                     int(getattr(profile, "tag", 0))))
+
+    def set_optimal_channels(self, slot, on=True):
+        """The optimal channels beside the slot's channels and optimal values (on=False clears; after set_channels and
+        set_optimal -- and set_optimal_profile -- which clear them too).  See wayne_exposure_set_optimal_channels."""
+        self._slot_optch.discard(slot)
+        self.check(self._L.wayne_exposure_set_optimal_channels(self._h, int(slot), 1 if on else 0))
+        if on:
+            self._slot_optch.add(slot)
+
+    def has_optimal_channels(self, slot):
+        return slot in self._slot_optch
+
+    def optimal_channels(self, slot):
+        """(channels_opt [R + 1, C], channels_opt_var [R + 1, C]) -- float64 copies -- of the slot's last wait_spectra /
+        download_spectra."""
+        K, W, R, _ = self._slot_meta[slot]
+        pc, pv = _dp(), _dp()
+        self.check(self._L.wayne_exposure_optimal_channels(self._h, int(slot), C.byref(pc), C.byref(pv)))
+        n_ch = self._slot_chan[slot]
+        return (np.ctypeslib.as_array(pc, shape=(R + 1, n_ch)).copy(), np.ctypeslib.as_array(pv, shape=(R + 1, n_ch)).copy())
+
+    def profile_uploads(self):
+        """Profiles set_optimal_profile has copied to the device (a slot that already holds the same one copies nothing)."""
+        return int(self._L.wayne_ctx_profile_uploads(self._h))
+
+    def deliver_profile(self, slot, on=True):
+        """Every run of the slot also writes the profile planes S1 of its windows (on=False clears; after set_optimal,
+        which clears it too).  See wayne_exposure_deliver_profile."""
+        self._slot_prof.discard(slot)
+        self.check(self._L.wayne_exposure_deliver_profile(self._h, int(slot), 1 if on else 0))
+        if on:
+            self._slot_prof.add(slot)
+
+    def delivers_profile(self, slot):
+        """Whether the slot's runs write profile planes (deliver_profile succeeded since its last set_optimal)."""
+        return slot in self._slot_prof
+
+    def fetch_profile(self, slot):
+        """Enqueue the copy of the slot's profile planes into pinned host memory (returns at once); after the run's
+        wait_spectra / download_spectra."""
+        self.check(self._L.wayne_exposure_fetch_profile(self._h, int(slot)))
+
+    def profile_planes(self, slot):
+        """The planes fetch_profile asked for (it is called here if nobody has), blocking: a float64 copy [sum_p rows_p,
+        S], the windows of the R + 1 products one behind the other."""
+        pp, n = _dp(), C.c_size_t(0)
+        rc = self._L.wayne_exposure_profile(self._h, int(slot), C.byref(pp), C.byref(n))
+        if rc == E_STATE and slot in self._slot_prof:
+            self.fetch_profile(slot)
+            rc = self._L.wayne_exposure_profile(self._h, int(slot), C.byref(pp), C.byref(n))
+        self.check(rc)
+        if n.value == 0:
+            return np.zeros((0, self.S))
+        return np.ctypeslib.as_array(pp, shape=(n.value // self.S, self.S)).copy()
+
     def set_channels(self, slot, channels, row_solution=None):
         """Wavelength-binned channels of the slot's extraction: an extraction.Channels (edges in um, flat on / off) and
         the rows' wavelength solution (wl_a [S], wl_b [S]): lambda_y(u) = wl_a[y] + wl_b[y] u at bordered column
         coordinate u -- None clears; after set_extraction, which clears it too (set_crrej does not).  The arrays are
         copied.  See wayne_exposure_set_channels."""
         self._slot_chan.pop(slot, None)          # (a refusal leaves the slot extracting without channels)
+        self._slot_optch.discard(slot)           # (the optimal channels are the channels': set_optimal_channels comes after)
         if channels is None:
             self.check(self._L.wayne_exposure_set_channels(self._h, int(slot), None))
             return

@@ -16,6 +16,8 @@
 //   channels_desc_error  wayne_exposure_set_channels' argument check, and the column hull k_extract_bins walks
 //   variance_desc_error  wayne_exposure_set_variance's argument check
 //   optimal_desc_error   wayne_exposure_set_optimal's argument check
+//   profile_rows_error   wayne_exposure_set_optimal_profile's argument check, and the doubles of the profile;
+//                        profile_rows_match: whether a plan's windows have the heights a profile was made for
 //
 // Reference: the reach of the thrower bounds pyparallel_menu.c:87-108 as the device modes implement it; the trace is
 // grism.py:491-506, 779-803 (trace_coeffs, plan_consts.h); the frame offset exposure_generator.py:630-645.
@@ -472,6 +474,35 @@ inline const char* variance_desc_error(unsigned steps, double read_noise) {
 inline const char* optimal_desc_error(int half_width) {
   if (half_width < 1 || half_width > kOptMaxH) return "half_width must lie in 1 .. 16";
   return nullptr;
+}
+
+// Rows of product p's window in the profile planes' layout.  The last-read window of a plan that does not form it is
+// not validated by extract_desc_error: whatever it holds counts as 0 .. S rows (of zeros).
+inline int profile_window_rows(int S, int R, unsigned steps, const int* row_lo, const int* row_hi, int p) {
+  const long long h = (long long)row_hi[p] - (long long)row_lo[p];
+  if (p == R && !(steps & X_LAST_READ)) return (int)std::min<long long>(std::max<long long>(h, 0), S);
+  return (int)h;
+}
+
+// The window heights rows[0 .. R] a supplied profile was made for: each a possible height of a window inside the frame
+// (the last-read window may be empty: a plan without that product); *count: the doubles of the profile, sum_p rows[p] S.
+inline const char* profile_rows_error(int S, int R, const int* rows, size_t* count) {
+  if (S < 1 || S > kExtractMaxS) return "frame side outside 1 .. 1024";
+  if (R < 1 || R > kMaxReads) return "n_reads outside 1 .. 15";
+  if (!rows) return "null window heights";
+  size_t n = 0;
+  for (int p = 0; p <= R; ++p) {
+    if (rows[p] < (p == R ? 0 : 1) || rows[p] > S) return "a window height must lie in 1 .. S";
+    n += (size_t)rows[p] * (size_t)S;
+  }
+  if (count) *count = n;
+  return nullptr;
+}
+
+inline bool profile_rows_match(int S, int R, unsigned steps, const int* row_lo, const int* row_hi, const int* rows) {
+  for (int p = 0; p <= R; ++p)
+    if (profile_window_rows(S, R, steps, row_lo, row_hi, p) != rows[p]) return false;
+  return true;
 }
 
 // The mask rows of a valid extraction plan: [min_p row_lo[p], max_p row_hi[p]) over the products that are formed.

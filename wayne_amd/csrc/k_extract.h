@@ -93,6 +93,24 @@
 // workgroup per product) adds the chunks in ascending order, forms ok(x) from the same ascending sums S0 and SV0 and writes
 // optimal and optimal_var behind the variances.  No atomics.
 //
+// Profile planes and a supplied profile (wayne_exposure_deliver_profile, wayne_exposure_set_optimal_profile; off unless
+// asked for -- the kernels above are launched as before).  The profile S1 / S0 carries the exposure's own noise, and
+// neighbouring columns share 2H of their 2H + 1 profile columns: summed over the columns of a wavelength channel that noise
+// adds coherently (measured: 1.8 times the predicted variance of a 13-column sum).  A visit therefore forms ONE profile
+// from several exposures and extracts every exposure with it.  Both arrays hold the windows of all R + 1 products one
+// behind the other, rows relative to the window (ProfileArgs).  k_extract_profile<T, CR>, on the grid of k_extract_optimal
+// and in front of it: d into LDS in the same way, then S1(y, x) of every window pixel -- the same left-to-right sum -- to the
+// plane; S1 and not S1 / S0, so that planes of several exposures are added and the sum normalised (a flux-weighted mean, no
+// division by a noisy S0).  k_extract_optimal_fixed<T, CR>, in place of k_extract_optimal: the law above with Pr := the
+// supplied profile at the pixel -- no halo, no tile; a thread's rows, the waves and the chunks are added in the order of
+// k_extract_optimal into the same scratch, and k_extract_optimal_finish follows as it is (H enters through ok(x) alone).
+//
+// Optimal channels (wayne_exposure_set_optimal_channels; off unless asked for): the law and the kernels stand with them at
+// the end of this file.  k_extract_bins_opt<T, CR, FIXED> keeps three row buffers per wave (e / F, k / F, ev / F^2: 72 KB)
+// and W_p, S0 of the hull's columns (6 KB): 79.9 KB with a supplied profile, two workgroups per CU.  With the exposure's own
+// profile a wave also keeps d of its row with the halo (26 KB more: 106.5 KB, one workgroup per CU) and walks the row's
+// planes twice -- the variant whose variance is not to be trusted anyway (README), kept simple rather than fast.
+//
 // The file is compiled without FMA contraction (wayne_amd/build.py), so a pixel's chain rounds as the numpy statement
 // of it does; what differs from numpy is the order of the row sums alone.
 #pragma once
@@ -814,6 +832,297 @@ __global__ void __launch_bounds__(kExtractThreads) k_extract_optimal_finish(Extr
     out[x] = ok ? U / W : shS[x];
     out_var[x] = ok ? 1. / W + (GW * GW) * sky_var : shV[x];
   }
+}
+
+// ---- profile planes and the supplied profile (wayne_exposure_deliver_profile, wayne_exposure_set_optimal_profile) ----
+
+// Both lay a product's window out as [rows_p][S] float64, window-relative rows, the windows one behind the other:
+// element row_off[p] + (y - row_lo[p]) S + x, row_off[p] = sum_{p' < p} rows_{p'} S over ALL R + 1 windows.
+struct ProfileArgs {
+  size_t row_off[kExtractProducts];
+  double* planes;                    // k_extract_profile writes S1 here (null without delivery)
+  const double* fixed;               // k_extract_optimal_fixed reads its profile here (null without one)
+};
+
+constexpr int kProfOwn = kExtractRows * kOptW / kExtractThreads;          // staged values of a thread: 6
+static_assert(kExtractRows * kOptW % kExtractThreads == 0, "k_extract_profile: the tile and its halo are a whole number of entries per thread");
+
+// One workgroup per (64-column tile, chunk of the list of k_extract_rows): d of the chunk's rows x (64 + 2 kOptMaxH)
+// columns into LDS as k_extract_optimal forms it (0 outside the frame), then S1 of the thread's pixels -- the same
+// literal left-to-right sums -- to the plane.  Every pixel of a formed window is written; nothing else is.
+template <class T, bool CR>
+__global__ void __launch_bounds__(kExtractThreads) k_extract_profile(ExtractArgs a, OptimalArgs o, ProfileArgs f) {
+  int p = 0;
+  while (p < a.R && (int)blockIdx.y >= a.first_chunk[p + 1]) ++p;     // (wave-uniform: at most R steps)
+  const int chunk = (int)blockIdx.y - a.first_chunk[p];
+  const int lo = a.row_lo[p] + chunk * kExtractRows, hi = min(lo + kExtractRows, a.row_hi[p]);
+  const int tid = (int)threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int S = a.S, xt = (int)blockIdx.x * 64 - kOptMaxH;
+  const size_t SS = (size_t)S * S;
+  const T* reads = (const T*)a.reads;
+  const int r_hi = p < a.R ? p + 1 : a.R, r_lo = p < a.R ? p : 0;
+  const bool lin = (a.steps & X_LINEARISE) && a.lin[0];
+  const bool gain = (a.steps & X_GAIN) && a.pfl, sky = (a.steps & X_SKY) && a.sky;
+  const double sky_p = a.sky_out[p], scale = a.scale[p];
+  __shared__ double sd[kExtractRows][kOptW];
+#pragma unroll
+  for (int k = 0; k < kProfOwn; ++k) {
+    const int e = tid + k * kExtractThreads, ty = e / kOptW, c = e - ty * kOptW;
+    const int y = lo + ty, xs = xt + c;
+    double d = 0.;
+    if (y < hi && xs >= 0 && xs < S) {
+      const size_t pix = (size_t)y * S + xs;
+      const double v = extract_term<T, CR>(a, reads, SS, pix, p, r_hi, r_lo, lin, gain);
+      const double t = sky ? (double)a.sky[pix] : 0.;
+      d = v - sky_p * (scale * t);
+    }
+    sd[ty][c] = d;
+  }
+  __syncthreads();
+  const int x = xt + kOptMaxH + lane;
+  if (x < S) {
+    const int c0 = max(x - o.H, 0) - xt, c1 = min(x + o.H, S - 1) - xt;      // X(x), as LDS columns
+    for (int ty = wave; lo + ty < hi; ty += kExtractWaves) {
+      const double* row = sd[ty];
+      double S1 = 0.;
+      for (int c = c0; c <= c1; ++c) S1 += row[c];
+      f.planes[f.row_off[p] + (size_t)(lo + ty - a.row_lo[p]) * S + x] = S1;
+    }
+  }
+}
+
+// The law of k_extract_optimal with Pr := the supplied profile at the pixel: no halo and no LDS tile.  The grid and the
+// order of the row sums are k_extract_optimal's (a thread its rows wave, wave + 8, ... of the chunk, the waves in wave
+// order -> the same scratch), so k_extract_optimal_finish follows as it is; H enters there alone, through ok(x).
+template <class T, bool CR>
+__global__ void __launch_bounds__(kExtractThreads) k_extract_optimal_fixed(ExtractArgs a, OptimalArgs o, ProfileArgs f) {
+  int p = 0;
+  while (p < a.R && (int)blockIdx.y >= a.first_chunk[p + 1]) ++p;     // (wave-uniform: at most R steps)
+  const int chunk = (int)blockIdx.y - a.first_chunk[p];
+  const int lo = a.row_lo[p] + chunk * kExtractRows, hi = min(lo + kExtractRows, a.row_hi[p]);
+  const int wave = (int)threadIdx.x >> 6, lane = (int)threadIdx.x & 63;
+  const int S = a.S, x = (int)blockIdx.x * 64 + lane;
+  const size_t SS = (size_t)S * S;
+  const T* reads = (const T*)a.reads;
+  const int r_hi = p < a.R ? p + 1 : a.R, r_lo = p < a.R ? p : 0;
+  const bool lin = (a.steps & X_LINEARISE) && a.lin[0];
+  const bool gain = (a.steps & X_GAIN) && a.pfl, sky = (a.steps & X_SKY) && a.sky;
+  const double sky_p = a.sky_out[p], scale = a.scale[p];
+  double sU = 0., sW = 0., sG = 0.;
+  if (x < S) {
+    const double sp = a.spectra[(size_t)p * S + x];
+    const double* prof = f.fixed + f.row_off[p] + x;
+    for (int y = lo + wave; y < hi; y += kExtractWaves) {
+      const size_t pix = (size_t)y * S + x;
+      const double Pr = prof[(size_t)(y - a.row_lo[p]) * S];
+      double g;
+      const double v = extract_term<T, CR>(a, reads, SS, pix, p, r_hi, r_lo, lin, gain, &g);
+      const double t = sky ? (double)a.sky[pix] : 0.;
+      const double q = g / 2.35;
+      const double bt = scale * t;
+      const double d = v - sky_p * bt;
+      const double P = fmax(Pr, 0.);
+      const double V = fmax(sp * Pr + sky_p * bt, 0.) + a.vrn2 * (q * q);
+      sU += (P * d) / V;
+      sW += (P * P) / V;
+      sG += (P * bt) / V;
+    }
+  }
+  __shared__ double sh[3][kExtractWaves][64];
+  sh[0][wave][lane] = sU;
+  sh[1][wave][lane] = sW;
+  sh[2][wave][lane] = sG;
+  __syncthreads();
+  if (wave == 0 && x < S) {
+    const int NP = a.R + 1;
+    const size_t at = ((size_t)chunk * NP + p) * S + x, third = (size_t)a.n_chunks * NP * S;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      double t = sh[k][0][lane];
+      for (int w = 1; w < kExtractWaves; ++w) t += sh[k][w][lane];
+      o.part[k * third + at] = t;
+    }
+  }
+}
+
+// ---- optimal channels (wayne_exposure_set_optimal_channels) ----
+
+struct OptChanArgs {
+  double* part;                      // [n_chunks][kChanGroups][R+1][3][C]: a row group's E, K and EV
+  double* channels_opt;              // [(R+1)*C]
+  double* channels_opt_var;          // [(R+1)*C]
+};
+
+constexpr int kOptChanW = kChanMaxHull + 2 * kOptMaxH;               // a row of d with its halo: 416 columns
+static_assert(kExtractWaves * 3 * kChanMaxChannels <= kExtractWaves * 3 * kChanMaxHull,
+              "k_extract_bins_opt: the waves' sums of the widest channel plan must fit the row buffers they reuse");
+static_assert(kChanMaxHull <= kExtractThreads, "k_extract_bins_opt: one thread per column of the hull forms W_p and ok");
+
+// Behind k_extract_optimal_finish, shaped like k_extract_bins: one workgroup per (chunk of the list of k_extract_rows,
+// group of 8 rows of it), wave w takes row w of the group, lane = channel gathers in ascending x, the waves are added in
+// wave order.  First a thread per hull column forms W_p[x] from the optimal scratch -- the ascending chunk sum of
+// k_extract_optimal_finish -- and ok(x) by its rule (shW holds W where ok, else 0; shS0 the sum S0).  FIXED: Pr is the
+// supplied profile at the pixel.  Otherwise the wave first writes d of its row over the hull and kOptMaxH columns on either
+// side into LDS (0 outside the frame) and Pr = S1 / S0 is the literal left-to-right sum k_extract_optimal takes.  Then
+//   e = ok ? ((P d) / V) / W : d,   k = ok ? ((P bt) / V) / W : bt,   ev = ok ? ((P P) / V) / (W W) : max(v, 0) + rn^2 q^2
+// go to the wave's three row buffers as e / F, k / F and ev / (F F), and channel b adds w_b, w_b and w_b^2 times them.
+template <class T, bool CR, bool FIXED>
+__global__ void __launch_bounds__(kExtractThreads) k_extract_bins_opt(ExtractArgs a, ChannelArgs ch, OptimalArgs o, ProfileArgs f,
+                                                                      OptChanArgs oc) {
+  int p = 0;
+  while (p < a.R && (int)blockIdx.x >= a.first_chunk[p + 1]) ++p;
+  const int chunk = (int)blockIdx.x - a.first_chunk[p];
+  const int lo = a.row_lo[p] + chunk * kExtractRows, hi = min(lo + kExtractRows, a.row_hi[p]);
+  const int tid = (int)threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int S = a.S, C = ch.C, W = ch.u_hi - ch.u_lo, NP = a.R + 1;
+  const size_t SS = (size_t)S * S;
+  const T* reads = (const T*)a.reads;
+  const int r_hi = p < a.R ? p + 1 : a.R, r_lo = p < a.R ? p : 0;
+  const bool lin = (a.steps & X_LINEARISE) && a.lin[0];
+  const bool gain = (a.steps & X_GAIN) && a.pfl, sky = (a.steps & X_SKY) && a.sky;
+  const double sky_p = a.sky_out[p], scale = a.scale[p];
+  __shared__ double buf[kExtractWaves][3][kChanMaxHull];
+  __shared__ double shW[kChanMaxHull], shS0[kChanMaxHull];
+  __shared__ double bd[FIXED ? 1 : kExtractWaves][FIXED ? 1 : kOptChanW];
+  if (tid < W) {
+    const int x = ch.u_lo + tid;
+    const int x0 = max(x - o.H, 0), x1 = min(x + o.H, S - 1);
+    double S0 = 0., SV0 = 0.;
+    for (int c = x0; c <= x1; ++c) { S0 += a.spectra[(size_t)p * S + c]; SV0 += a.spectra_var[(size_t)p * S + c]; }
+    const int rows = a.row_hi[p] - a.row_lo[p];
+    const int chunks = (rows + kExtractRows - 1) / kExtractRows;
+    const size_t third = (size_t)a.n_chunks * NP * S;
+    double Ws = 0.;
+    for (int c = 0; c < chunks; ++c) Ws += o.part[third + ((size_t)c * NP + p) * S + x];      // ascending chunks
+    const bool ok = S0 > 0. && S0 * S0 > 9. * SV0 && Ws > 0.;
+    shW[tid] = ok ? Ws : 0.;
+    shS0[tid] = S0;
+  }
+  const int group = (int)blockIdx.y;
+  const int y = lo + wave + group * kExtractWaves;
+  const bool row = y < hi;                                   // (wave-uniform)
+  const int xd = ch.u_lo - kOptMaxH;                         // frame column of bd's column 0
+  if constexpr (!FIXED) {
+    if (row) {
+      for (int c = lane; c < W + 2 * kOptMaxH; c += 64) {
+        const int xs = xd + c;
+        double d = 0.;
+        if (xs >= 0 && xs < S) {
+          const size_t pix = (size_t)y * S + xs;
+          const double v = extract_term<T, CR>(a, reads, SS, pix, p, r_hi, r_lo, lin, gain);
+          const double t = sky ? (double)a.sky[pix] : 0.;
+          d = v - sky_p * (scale * t);
+        }
+        bd[wave][c] = d;
+      }
+    }
+  }
+  __syncthreads();
+  double* be = buf[wave][0];
+  double* bk = buf[wave][1];
+  double* bv = buf[wave][2];
+  double wa = 0., wb = 1.;
+  if (row) {
+    wa = ch.wl_a[y]; wb = ch.wl_b[y];
+    const bool y_in = y >= kBorder && y < S - kBorder;
+    for (int oo = lane; oo < W; oo += 64) {
+      const int x = ch.u_lo + oo;
+      const size_t pix = (size_t)y * S + x;
+      double g;
+      const double v = extract_term<T, CR>(a, reads, SS, pix, p, r_hi, r_lo, lin, gain, &g);
+      const double t = sky ? (double)a.sky[pix] : 0.;
+      const double F = chan_flat(ch, y, x, wa, wb, y_in, S);
+      const double q = g / 2.35;
+      const double bt = scale * t, rq = a.vrn2 * (q * q);
+      const double d = v - sky_p * bt;
+      const double Wx = shW[oo];
+      double e = d, k = bt, ev = fmax(v, 0.) + rq;
+      if (Wx > 0.) {                                         // ok(x)
+        double Pr;
+        if constexpr (FIXED) {
+          Pr = f.fixed[f.row_off[p] + (size_t)(y - a.row_lo[p]) * S + x];
+        } else {
+          const int c0 = max(x - o.H, 0) - xd, c1 = min(x + o.H, S - 1) - xd;      // X(x), as columns of bd
+          double S1 = 0.;
+          for (int c = c0; c <= c1; ++c) S1 += bd[wave][c];
+          Pr = S1 / shS0[oo];
+        }
+        const double P = fmax(Pr, 0.);
+        const double V = fmax(a.spectra[(size_t)p * S + x] * Pr + sky_p * bt, 0.) + rq;
+        e = ((P * d) / V) / Wx;
+        k = ((P * bt) / V) / Wx;
+        ev = ((P * P) / V) / (Wx * Wx);
+      }
+      be[oo] = e / F;
+      bk[oo] = k / F;
+      bv[oo] = ev / (F * F);
+    }
+  }
+  double e0[kChanPasses], e1[kChanPasses];
+#pragma unroll
+  for (int kk = 0; kk < kChanPasses; ++kk) {                 // (the edges only now: the row's chain needs the registers)
+    const int b = kk * 64 + lane;
+    e0[kk] = b < C ? ch.edges[b] : 0.;
+    e1[kk] = b < C ? ch.edges[b + 1] : 0.;
+  }
+  __syncthreads();
+  double E[kChanPasses], K[kChanPasses], EV[kChanPasses];
+#pragma unroll
+  for (int kk = 0; kk < kChanPasses; ++kk) {
+    E[kk] = 0.; K[kk] = 0.; EV[kk] = 0.;
+    if (row && kk * 64 + lane < C) {
+      const double ua0 = (e0[kk] - wa) / wb, ua1 = (e1[kk] - wa) / wb;
+      const int xs = (int)fmin(fmax(floor(ua0), (double)ch.u_lo), (double)ch.u_hi);
+      const int xe = (int)fmin(fmax(ceil(ua1), (double)ch.u_lo), (double)ch.u_hi);
+      for (int x = xs; x < xe; ++x) {
+        const double w = fmin(fmax(fmin((double)x + 1.0, ua1) - fmax((double)x, ua0), 0.), 1.);
+        E[kk] += w * be[x - ch.u_lo];
+        K[kk] += w * bk[x - ch.u_lo];
+        EV[kk] += (w * w) * bv[x - ch.u_lo];
+      }
+    }
+  }
+  __syncthreads();
+  // the waves' sums, added in wave order: the row buffers are free now (the barrier above)
+  double* red = &buf[0][0][0];                               // [kExtractWaves][3][C]
+#pragma unroll
+  for (int kk = 0; kk < kChanPasses; ++kk) {
+    const int b = kk * 64 + lane;
+    if (b < C) {
+      red[((size_t)wave * 3 + 0) * C + b] = E[kk];
+      red[((size_t)wave * 3 + 1) * C + b] = K[kk];
+      red[((size_t)wave * 3 + 2) * C + b] = EV[kk];
+    }
+  }
+  __syncthreads();
+  for (int i = tid; i < 3 * C; i += kExtractThreads) {
+    double t = red[i];
+    for (int w = 1; w < kExtractWaves; ++w) t += red[(size_t)w * 3 * C + i];
+    oc.part[(((size_t)chunk * kChanGroups + group) * NP + p) * 3 * C + i] = t;
+  }
+}
+
+// Behind k_extract_bins_opt: one workgroup per product adds the row groups in ascending order and writes
+// channels_opt_p[b] = E_p[b] and channels_opt_var_p[b] = EV_p[b] + K_p[b]^2 sky_var_p (zeros for a product not formed).
+__global__ void __launch_bounds__(kChanMaxChannels) k_extract_bins_opt_finish(ExtractArgs a, ChannelArgs ch, OptChanArgs oc) {
+  const int p = (int)blockIdx.x, b = (int)threadIdx.x, C = ch.C, NP = a.R + 1;
+  if (b >= C) return;
+  if (p == a.R && !(a.steps & X_LAST_READ)) {
+    oc.channels_opt[(size_t)p * C + b] = 0.;
+    oc.channels_opt_var[(size_t)p * C + b] = 0.;
+    return;
+  }
+  const int rows = a.row_hi[p] - a.row_lo[p];
+  const int chunks = (rows + kExtractRows - 1) / kExtractRows;
+  double E = 0., K = 0., EV = 0.;
+  for (int c = 0; c < chunks * kChanGroups; ++c) {           // ascending chunks, ascending groups of a chunk
+    const size_t at = ((size_t)c * NP + p) * 3 * C;
+    E += oc.part[at + b];
+    K += oc.part[at + C + b];
+    EV += oc.part[at + 2 * C + b];
+  }
+  oc.channels_opt[(size_t)p * C + b] = E;
+  oc.channels_opt_var[(size_t)p * C + b] = EV + (K * K) * a.sky_var[p];
 }
 
 }  // namespace wayne

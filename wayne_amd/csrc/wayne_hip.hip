@@ -246,6 +246,25 @@ struct Slot : SourceState {
   DevBuf opt_part;
   const double* opt_res = nullptr;
   std::vector<double> opt_host;
+  // profile planes of the optimal extraction (cleared by what clears it).  Delivery (wayne_exposure_deliver_profile):
+  // S1 of every window pixel [sum_p rows_p * S] and its pinned copy, fetched by a call of its own (`prof_fetched`: a copy
+  // is enqueued or done).  A supplied profile (wayne_exposure_set_optimal_profile): the device copy in the same layout and
+  // the window heights it was made for, checked against the plan's when the slot is run
+  bool prof_deliver = false, prof_valid = false, prof_fetched = false;   // (prof_valid: a run has written the planes)
+  DevBuf prof_planes;
+  PinnedBuf prof_pinned;
+  bool prof_fixed = false;
+  int prof_rows[kExtractProducts] = {0};
+  DevBuf prof_fix;
+  // optimal channels (wayne_exposure_set_optimal_channels; needs the optimal extraction AND channels; cleared by what
+  // clears either): the row groups' sums [chunks][4][R+1][3][C]; channels_opt and channels_opt_var [(R+1)*C each] ride
+  // behind optimal_var in ex_out
+  bool optch_on = false;
+  DevBuf optch_part;
+  bool prof_fix_valid = false;       // prof_fix holds the profile of prof_rows / prof_fix_n and the caller's tag prof_fix_hash (kept across clears)
+  size_t prof_fix_n = 0;
+  uint64_t prof_fix_hash = 0;
+  int prof_fix_R = 0;
   // staging arena of the descriptor's arrays: uploads are enqueued from here, so
   // wayne_exposure_upload returns without waiting for the slot's stream to drain
   StageArena stage;
@@ -364,6 +383,7 @@ struct wayne_ctx : CtxStreams {
   uint64_t prof_launches[kProfKernels] = {0};
   double prof_ms[kProfKernels] = {0};
   uint64_t electrons = 0;  // thrown through wayne_psf_apply (host-counted)
+  uint64_t profile_uploads = 0;   // profiles wayne_exposure_set_optimal_profile copied to the device (not those a slot already held)
   uint64_t reruns = 0;     // exposures run a second time because a bin lay beyond what the first launch sequence handles
   DevBuf counters;         // kCounterStripes u64 words, 128 B apart: electrons thrown by exposures (device-counted,
                            // count_electrons); word [1]: a spare for debug_fetch's own k_prep_sub launch
@@ -677,7 +697,10 @@ size_t variance_count(const wayne_ctx* c, const Slot& s) {
 size_t optimal_offset(const wayne_ctx* c, const Slot& s) {
   return variance_offset(c, s) + variance_count(c, s) * sizeof(double);
 }
-size_t optimal_count(const wayne_ctx* c, const Slot& s) { return (size_t)2 * (s.R + 1) * (size_t)c->S; }
+// (with the optimal channels: channels_opt and channels_opt_var [(R+1)*C each] behind optimal_var)
+size_t optimal_count(const wayne_ctx* c, const Slot& s) {
+  return (size_t)2 * (s.R + 1) * ((size_t)c->S + (s.optch_on ? (size_t)s.ch_C : 0));
+}
 
 template <bool CR, bool VAR>
 void launch_bins(int out, dim3 grid, dim3 block, hipStream_t st, const ExtractArgs& a, const ChannelArgs& ch) {
@@ -694,7 +717,7 @@ void launch_rows(int out, dim3 grid, dim3 block, hipStream_t st, const ExtractAr
 }
 
 // The channels of slot `s` (wayne_exposure_set_channels) behind k_extract_finish, from `a` as launch_extract filled it.
-int launch_channels(wayne_ctx* c, Slot& s, const ExtractArgs& a, int blocks, int out, bool cr) {
+ChannelArgs channel_args(const wayne_ctx* c, const Slot& s) {
   ChannelArgs ch{};
   ch.C = s.ch_C; ch.u_lo = s.ch_lo; ch.u_hi = s.ch_hi;
   ch.flat = (s.ch_flags & C_FLAT) && c->has_flat;
@@ -702,6 +725,39 @@ int launch_channels(wayne_ctx* c, Slot& s, const ExtractArgs& a, int blocks, int
   ch.flat_wmin = c->g.flat_wmin; ch.flat_wmax = c->g.flat_wmax;
   ch.edges = s.ch_edges.as<double>(); ch.wl_a = s.ch_wa.as<double>(); ch.wl_b = s.ch_wb.as<double>();
   for (int i = 0; i < 4; ++i) ch.cube[i] = c->has_flat ? c->flat[i].as<float>() : nullptr;
+  return ch;
+}
+
+template <bool CR, bool FIXED>
+void launch_bins_opt(int out, dim3 grid, dim3 block, hipStream_t st, const ExtractArgs& a, const ChannelArgs& ch, const OptimalArgs& o,
+                     const ProfileArgs& f, const OptChanArgs& oc) {
+  if (out == 1) hipLaunchKernelGGL((k_extract_bins_opt<double, CR, FIXED>), grid, block, 0, st, a, ch, o, f, oc);
+  else if (out == 2) hipLaunchKernelGGL((k_extract_bins_opt<uint16_t, CR, FIXED>), grid, block, 0, st, a, ch, o, f, oc);
+  else hipLaunchKernelGGL((k_extract_bins_opt<float, CR, FIXED>), grid, block, 0, st, a, ch, o, f, oc);
+}
+
+// The optimal channels of slot `s` (wayne_exposure_set_optimal_channels) behind k_extract_optimal_finish, from `a`, `o` and
+// `f` as launch_optimal filled them.
+template <bool CR>
+int launch_optimal_channels(wayne_ctx* c, Slot& s, const ExtractArgs& a, const OptimalArgs& o, const ProfileArgs& f, int blocks, int out) {
+  const ChannelArgs ch = channel_args(c, s);
+  OptChanArgs oc{};
+  oc.part = s.optch_part.as<double>();
+  oc.channels_opt = o.optimal_var + (size_t)(a.R + 1) * a.S;
+  oc.channels_opt_var = oc.channels_opt + (size_t)(a.R + 1) * ch.C;
+  const dim3 grid((unsigned)blocks, (unsigned)kChanGroups), block(kExtractThreads);
+  if (blocks > 0) {
+    if (s.prof_fixed) launch_bins_opt<CR, true>(out, grid, block, c->stream, a, ch, o, f, oc);
+    else launch_bins_opt<CR, false>(out, grid, block, c->stream, a, ch, o, f, oc);
+    HIP_TRY(c, hipGetLastError());
+  }
+  hipLaunchKernelGGL(k_extract_bins_opt_finish, dim3((unsigned)(a.R + 1)), dim3(kChanMaxChannels), 0, c->stream, a, ch, oc);
+  HIP_TRY(c, hipGetLastError());
+  return WAYNE_OK;
+}
+
+int launch_channels(wayne_ctx* c, Slot& s, const ExtractArgs& a, int blocks, int out, bool cr) {
+  ChannelArgs ch = channel_args(c, s);
   ch.part = s.ch_part.as<double>();
   ch.channels = (double*)((char*)s.ex_out.p + channels_offset(c, s));
   const bool var = s.var_on;
@@ -739,7 +795,32 @@ int launch_optimal(wayne_ctx* c, Slot& s, const ExtractArgs& a, dim3 grid, int o
   o.optimal = (double*)((char*)s.ex_out.p + optimal_offset(c, s));
   o.optimal_var = o.optimal + (size_t)(a.R + 1) * a.S;
   const dim3 block(kExtractThreads);
-  if (grid.y > 0) {
+  ProfileArgs f{};
+  if (s.prof_deliver || s.prof_fixed) {
+    size_t off = 0;
+    for (int p = 0; p <= a.R; ++p) { f.row_off[p] = off; off += (size_t)plan::profile_window_rows(a.S, a.R, a.steps, a.row_lo, a.row_hi, p) * a.S; }
+    f.planes = s.prof_deliver ? s.prof_planes.as<double>() : nullptr;
+    f.fixed = s.prof_fixed ? s.prof_fix.as<double>() : nullptr;
+  }
+  if (s.prof_deliver) {
+    // S1 of every window pixel; a product that is not formed (the last read, switched off) delivers zeros
+    if (!(a.steps & X_LAST_READ))
+      HIP_TRY(c, hipMemsetAsync(f.planes + f.row_off[a.R], 0, (size_t)plan::profile_window_rows(a.S, a.R, a.steps, a.row_lo, a.row_hi, a.R) * a.S * sizeof(double), c->stream));
+    if (grid.y > 0) {
+      if (out == 1) hipLaunchKernelGGL((k_extract_profile<double, CR>), grid, block, 0, c->stream, a, o, f);
+      else if (out == 2) hipLaunchKernelGGL((k_extract_profile<uint16_t, CR>), grid, block, 0, c->stream, a, o, f);
+      else hipLaunchKernelGGL((k_extract_profile<float, CR>), grid, block, 0, c->stream, a, o, f);
+      HIP_TRY(c, hipGetLastError());
+    }
+    s.prof_valid = true;
+    s.prof_fetched = false;          // (a copy fetched before this run holds the run before)
+  }
+  if (grid.y > 0 && s.prof_fixed) {
+    if (out == 1) hipLaunchKernelGGL((k_extract_optimal_fixed<double, CR>), grid, block, 0, c->stream, a, o, f);
+    else if (out == 2) hipLaunchKernelGGL((k_extract_optimal_fixed<uint16_t, CR>), grid, block, 0, c->stream, a, o, f);
+    else hipLaunchKernelGGL((k_extract_optimal_fixed<float, CR>), grid, block, 0, c->stream, a, o, f);
+    HIP_TRY(c, hipGetLastError());
+  } else if (grid.y > 0) {
     if (out == 1) hipLaunchKernelGGL((k_extract_optimal<double, CR>), grid, block, 0, c->stream, a, o);
     else if (out == 2) hipLaunchKernelGGL((k_extract_optimal<uint16_t, CR>), grid, block, 0, c->stream, a, o);
     else hipLaunchKernelGGL((k_extract_optimal<float, CR>), grid, block, 0, c->stream, a, o);
@@ -747,6 +828,13 @@ int launch_optimal(wayne_ctx* c, Slot& s, const ExtractArgs& a, dim3 grid, int o
   }
   hipLaunchKernelGGL(k_extract_optimal_finish, dim3((unsigned)(a.R + 1)), block, 0, c->stream, a, o);
   HIP_TRY(c, hipGetLastError());
+  if (s.optch_on) {
+    if (!(s.prof_deliver || s.prof_fixed)) {
+      size_t off = 0;
+      for (int p = 0; p <= a.R; ++p) { f.row_off[p] = off; off += (size_t)plan::profile_window_rows(a.S, a.R, a.steps, a.row_lo, a.row_hi, p) * a.S; }
+    }
+    return launch_optimal_channels<CR>(c, s, a, o, f, (int)grid.y, out);
+  }
   return WAYNE_OK;
 }
 
@@ -1306,6 +1394,7 @@ int wayne_exposure_upload(wayne_ctx* c, int slot, const wayne_exposure_desc* d) 
   s.var_on = false;          // ... and whose variances wait for wayne_exposure_set_variance
   s.var_res = nullptr;
   s.opt_on = false;          // ... and whose optimal extraction waits for wayne_exposure_set_optimal
+  s.prof_deliver = s.prof_fetched = s.prof_valid = s.prof_fixed = s.optch_on = false;   // (the profile planes and the optimal channels go with the optimal extraction)
   s.opt_res = nullptr;
   int rc;
   const size_t KW = (size_t)K * W;
@@ -1574,6 +1663,9 @@ int wayne_exposure_run_front(wayne_ctx* c, int slot) {
   if (slot < 0 || slot >= kSlots) return fail(c, WAYNE_E_INVALID, "run: slot");
   Slot& s = c->slots[slot];
   if (!s.uploaded) return fail(c, WAYNE_E_STATE, "run: slot not uploaded");
+  // a supplied profile is laid out for its own window heights: refused before anything is enqueued, the slot stays usable
+  if (s.extract_on && s.opt_on && s.prof_fixed && !plan::profile_rows_match(c->S, s.R, s.ex.steps, s.ex.row_lo, s.ex.row_hi, s.prof_rows))
+    return fail(c, WAYNE_E_INVALID, "run: the optimal profile was made for other window heights than the extraction's");
   (void)hipSetDevice(c->device);
   use_slot_stream(c, slot);
   const wayne_exposure_desc& d = s.d;
@@ -1745,6 +1837,8 @@ int wayne_exposure_status(wayne_ctx* c, int slot, int* status) {
 }
 
 unsigned long long wayne_ctx_reruns(const wayne_ctx* c) { return c ? (unsigned long long)c->reruns : 0ull; }
+
+unsigned long long wayne_ctx_profile_uploads(const wayne_ctx* c) { return c ? (unsigned long long)c->profile_uploads : 0ull; }
 
 int wayne_exposure_run_checked(wayne_ctx* c, int slot) {
   int rc = wayne_exposure_run(c, slot);
@@ -2074,6 +2168,7 @@ int wayne_exposure_set_extraction(wayne_ctx* c, int slot, const wayne_extract_de
   s.var_on = false;
   s.var_res = nullptr;
   s.opt_on = false;
+  s.prof_deliver = s.prof_fetched = s.prof_valid = s.prof_fixed = s.optch_on = false;   // (the profile planes and the optimal channels go with the optimal extraction)
   s.opt_res = nullptr;
   if (!x) return WAYNE_OK;
   int chunks = 0;
@@ -2120,6 +2215,7 @@ int wayne_exposure_set_channels(wayne_ctx* c, int slot, const wayne_channels_des
   Slot& s = c->slots[slot];
   if (!s.uploaded || !s.extract_on) return fail(c, WAYNE_E_STATE, "set_channels: no extraction set for the slot");
   s.chan_on = false;              // from here on a refusal leaves the slot extracting, without channels
+  s.optch_on = false;             // (the optimal channels are the channels': set_optimal_channels comes after this call)
   s.ch_res = nullptr;
   s.var_res = nullptr;
   s.opt_res = nullptr;
@@ -2159,6 +2255,7 @@ int wayne_exposure_set_variance(wayne_ctx* c, int slot, const wayne_variance_des
   s.var_on = false;               // from here on a refusal leaves the slot extracting, without variances
   s.var_res = nullptr;
   s.opt_on = false;               // (the optimal extraction stands on the variances: set_optimal comes after this call)
+  s.prof_deliver = s.prof_fetched = s.prof_valid = s.prof_fixed = s.optch_on = false;   // (the profile planes and the optimal channels go with the optimal extraction)
   s.opt_res = nullptr;
   s.ex_pinned_misc = nullptr;     // (a fetched block has the other layout)
   if (!v) return WAYNE_OK;
@@ -2182,6 +2279,7 @@ int wayne_exposure_set_optimal(wayne_ctx* c, int slot, const wayne_optimal_desc*
   Slot& s = c->slots[slot];
   if (!s.uploaded || !s.extract_on || !s.var_on) return fail(c, WAYNE_E_STATE, "set_optimal: no variances set for the slot");
   s.opt_on = false;               // from here on a refusal leaves the slot extracting with variances, without the optimal values
+  s.prof_deliver = s.prof_fetched = s.prof_valid = s.prof_fixed = s.optch_on = false;   // (the profile planes and the optimal channels go with the optimal extraction)
   s.opt_res = nullptr;
   s.ex_pinned_misc = nullptr;     // (a fetched block has the other length)
   if (!d) return WAYNE_OK;
@@ -2346,6 +2444,128 @@ int wayne_exposure_optimal(wayne_ctx* c, int slot, const double** optimal, const
   if (!s.opt_res) return fail(c, WAYNE_E_STATE, "optimal: wait_spectra or download_spectra first");
   *optimal = s.opt_res;
   *optimal_var = s.opt_res + (size_t)(s.R + 1) * c->S;
+  return WAYNE_OK;
+}
+
+int wayne_exposure_set_optimal_channels(wayne_ctx* c, int slot, int on) {
+  if (!c) return WAYNE_E_INVALID;
+  if (slot < 0 || slot >= kSlots) return fail(c, WAYNE_E_INVALID, "set_optimal_channels: slot");
+  Slot& s = c->slots[slot];
+  if (!s.uploaded || !s.extract_on || !s.var_on || !s.opt_on || !s.chan_on)
+    return fail(c, WAYNE_E_STATE, "set_optimal_channels: the slot needs channels and the optimal extraction");
+  s.optch_on = false;
+  s.opt_res = nullptr;
+  s.ex_pinned_misc = nullptr;     // (a fetched block has the other length)
+  if (!on) return WAYNE_OK;
+  (void)hipSetDevice(c->device);
+  const size_t NP = (size_t)s.R + 1, S = (size_t)c->S, C = (size_t)s.ch_C;
+  HIP_TRY(c, s.optch_part.reserve((size_t)s.ex_chunks * kChanGroups * NP * 3 * C * sizeof(double)));
+  HIP_TRY(c, s.ex_out.reserve(NP * (S + 1) * sizeof(double) + NP * sizeof(uint32_t) + 8 + NP * C * sizeof(double) +
+                              NP * (S + 1 + C) * sizeof(double) + 2 * NP * (S + C) * sizeof(double)));
+  s.optch_on = true;
+  return WAYNE_OK;
+}
+
+int wayne_exposure_optimal_channels(wayne_ctx* c, int slot, const double** channels_opt, const double** channels_opt_var) {
+  if (!c || !channels_opt || !channels_opt_var) return WAYNE_E_INVALID;
+  if (slot < 0 || slot >= kSlots) return fail(c, WAYNE_E_INVALID, "optimal_channels: slot");
+  Slot& s = c->slots[slot];
+  if (!s.uploaded || !s.extract_on || !s.var_on || !s.opt_on || !s.chan_on || !s.optch_on)
+    return fail(c, WAYNE_E_STATE, "optimal_channels: no optimal channels set for the slot");
+  if (!s.opt_res) return fail(c, WAYNE_E_STATE, "optimal_channels: wait_spectra or download_spectra first");
+  *channels_opt = s.opt_res + (size_t)2 * (s.R + 1) * c->S;
+  *channels_opt_var = *channels_opt + (size_t)(s.R + 1) * s.ch_C;
+  return WAYNE_OK;
+}
+
+// doubles of a slot's profile planes: every pixel of all R + 1 windows
+static size_t profile_count(const wayne_ctx* c, const Slot& s) {
+  size_t rows = 0;
+  for (int p = 0; p <= s.R; ++p) rows += (size_t)plan::profile_window_rows(c->S, s.R, s.ex.steps, s.ex.row_lo, s.ex.row_hi, p);
+  return rows * (size_t)c->S;
+}
+
+int wayne_exposure_deliver_profile(wayne_ctx* c, int slot, int on) {
+  if (!c) return WAYNE_E_INVALID;
+  if (slot < 0 || slot >= kSlots) return fail(c, WAYNE_E_INVALID, "deliver_profile: slot");
+  Slot& s = c->slots[slot];
+  if (!s.uploaded || !s.extract_on || !s.var_on || !s.opt_on)
+    return fail(c, WAYNE_E_STATE, "deliver_profile: no optimal extraction set for the slot");
+  s.prof_deliver = s.prof_fetched = s.prof_valid = false;
+  if (!on) return WAYNE_OK;
+  (void)hipSetDevice(c->device);
+  HIP_TRY(c, s.prof_planes.reserve(profile_count(c, s) * sizeof(double)));
+  s.prof_deliver = true;
+  return WAYNE_OK;
+}
+
+int wayne_exposure_set_optimal_profile(wayne_ctx* c, int slot, const double* profile, const int* rows) {
+  return wayne_exposure_set_optimal_profile_tagged(c, slot, profile, rows, 0);
+}
+
+int wayne_exposure_set_optimal_profile_tagged(wayne_ctx* c, int slot, const double* profile, const int* rows, uint64_t tag) {
+  if (!c) return WAYNE_E_INVALID;
+  if (slot < 0 || slot >= kSlots) return fail(c, WAYNE_E_INVALID, "set_optimal_profile: slot");
+  Slot& s = c->slots[slot];
+  if (!s.uploaded || !s.extract_on || !s.var_on || !s.opt_on)
+    return fail(c, WAYNE_E_STATE, "set_optimal_profile: no optimal extraction set for the slot");
+  s.prof_fixed = false;           // from here on a refusal leaves the slot with the exposure's own profile
+  if (!profile) return WAYNE_OK;
+  size_t n = 0;
+  if (const char* why = plan::profile_rows_error(c->S, s.R, rows, &n))
+    return fail(c, WAYNE_E_INVALID, std::string("set_optimal_profile: ") + why);
+  (void)hipSetDevice(c->device);
+  use_slot_stream(c, slot);
+  // A visit hands the same profile to a slot with every exposure it uploads there: the device copy outlives what clears
+  // the option, and a profile the CALLER identifies by the same non-zero tag, with the same heights and length, is not
+  // copied again -- no copy, no wait for the slot's stream, and the array is not looked at.
+  const uint64_t h = tag;
+  bool same = tag != 0 && s.prof_fix_valid && s.prof_fix_n == n && s.prof_fix_hash == h && s.prof_fix_R == s.R;
+  for (int p = 0; same && p <= s.R; ++p) same = s.prof_rows[p] == rows[p];
+  if (!same) {
+    s.prof_fix_valid = false;
+    HIP_TRY(c, s.prof_fix.reserve(n * sizeof(double)));
+    // (from the caller's memory: the call returns when the array has been read)
+    HIP_TRY(c, hipMemcpyAsync(s.prof_fix.p, profile, n * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    for (int p = 0; p <= s.R; ++p) s.prof_rows[p] = rows[p];
+    s.prof_fix_n = n; s.prof_fix_hash = h; s.prof_fix_R = s.R;
+    s.prof_fix_valid = true;
+    c->profile_uploads += 1;
+  }
+  s.prof_fixed = true;
+  return WAYNE_OK;
+}
+
+int wayne_exposure_fetch_profile(wayne_ctx* c, int slot) {
+  if (!c) return WAYNE_E_INVALID;
+  if (slot < 0 || slot >= kSlots) return fail(c, WAYNE_E_INVALID, "fetch_profile: slot");
+  Slot& s = c->slots[slot];
+  if (!s.uploaded || !s.extract_on || !s.var_on || !s.opt_on || !s.prof_deliver)
+    return fail(c, WAYNE_E_STATE, "fetch_profile: no profile delivery set for the slot");
+  if (!s.prof_valid || s.ran) return fail(c, WAYNE_E_STATE, "fetch_profile: run, then wait_spectra or download_spectra first");
+  (void)hipSetDevice(c->device);
+  use_slot_stream(c, slot);
+  const size_t bytes = profile_count(c, s) * sizeof(double);
+  s.prof_fetched = false;
+  if (!s.prof_pinned.reserve(std::max<size_t>(bytes, 8))) return fail(c, WAYNE_E_NOMEM, "fetch_profile: pinned host allocation failed");
+  HIP_TRY(c, hipMemcpyAsync(s.prof_pinned.p, s.prof_planes.p, bytes, hipMemcpyDeviceToHost, c->stream));
+  s.prof_fetched = true;
+  return WAYNE_OK;
+}
+
+int wayne_exposure_profile(wayne_ctx* c, int slot, const double** planes, size_t* count) {
+  if (!c || !planes || !count) return WAYNE_E_INVALID;
+  if (slot < 0 || slot >= kSlots) return fail(c, WAYNE_E_INVALID, "profile: slot");
+  Slot& s = c->slots[slot];
+  if (!s.uploaded || !s.extract_on || !s.var_on || !s.opt_on || !s.prof_deliver)
+    return fail(c, WAYNE_E_STATE, "profile: no profile delivery set for the slot");
+  if (!s.prof_fetched) return fail(c, WAYNE_E_STATE, "profile: fetch_profile first");
+  (void)hipSetDevice(c->device);
+  use_slot_stream(c, slot);
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  *planes = (const double*)s.prof_pinned.p;
+  *count = profile_count(c, s);
   return WAYNE_OK;
 }
 

@@ -186,15 +186,19 @@ class ExposureGenerator(object):
             self._fill_spectra(spectra, sky, eng.ctx.rejected(0) if desc._extraction.crrej is not None else None,
                                eng.ctx.channels(0) if desc._extraction.channels is not None else None,
                                eng.ctx.variances(0) if desc._extraction.variance is not None else None,
-                               eng.ctx.optimal(0) if desc._extraction.optimal is not None else None)
+                               eng.ctx.optimal(0) if desc._extraction.optimal is not None else None,
+                               eng.ctx.profile_planes(0) if eng.ctx.delivers_profile(0) else None,
+                               eng.ctx.optimal_channels(0) if eng.ctx.has_optimal_channels(0) else None)
         return frame
 
-    def _fill_spectra(self, spectra, sky, rejected=None, channels=None, variances=None, optimal=None):
+    def _fill_spectra(self, spectra, sky, rejected=None, channels=None, variances=None, optimal=None, profile_planes=None,
+                      channels_opt=None):
         """The device's extraction of this generator's exposure -> Exposure.spectra [R + 1, S] / Exposure.sky [R + 1]
         (and Exposure.extraction, the plan they were formed with; Exposure.rejected [R + 1] when it rejects cosmic
         rays; Exposure.channels [R + 1, C] when it bins into wavelength channels; Exposure.spectra_var / .sky_var /
         .channels_var -- the last None without channels -- when it delivers variances; Exposure.optimal / .optimal_var
-        when it extracts optimally too)."""
+        when it extracts optimally too; Exposure.profile_planes [sum of the window heights, S] when that extraction
+        delivers its profile planes)."""
         self.exposure.spectra, self.exposure.sky = spectra, sky
         self.exposure.extraction = self.extraction_plan
         if rejected is not None:
@@ -205,6 +209,10 @@ class ExposureGenerator(object):
             self.exposure.spectra_var, self.exposure.sky_var, self.exposure.channels_var = variances
         if optimal is not None:
             self.exposure.optimal, self.exposure.optimal_var = optimal
+        if profile_planes is not None:
+            self.exposure.profile_planes = profile_planes
+        if channels_opt is not None:               # Exposure.channels_opt / .channels_opt_var [R + 1, C]: the optimal channels
+            self.exposure.channels_opt, self.exposure.channels_opt_var = channels_opt
         return self.exposure
 
     def _fill_exposure(self, reads, start_time=None):
@@ -382,6 +390,8 @@ class ExposureGenerator(object):
         S = (1014 if self.SUBARRAY == 1024 else self.SUBARRAY) + 10
         self.extraction_plan = _extraction.for_exposure(extraction, self.grism, s_wl, x_ref, y_ref, scan_speed,
                                                         self.read_times, sub_scale, S, crrej, channels, variance, optimal)
+        # what exposures must share to share a profile of the optimal extraction (extraction.profile_key)
+        self.profile_key = None if self.extraction_plan is None else _extraction.profile_key(self.extraction_plan, scan_speed)
         self._read_dt = read_dt
         self._host_vectors = {"x_ref": s_x, "y_ref": s_y, "dur": s_dur, "seeds": s_rand_seeds, "read": sample_read}
         return _lib.make_desc(

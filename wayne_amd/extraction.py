@@ -46,9 +46,16 @@ wayne_optimal_desc).  A column without a 3-sigma source over its 2H + 1 columns 
 model variance (a data variance biased the flux by -0.09 %) and P is clamped at 0 but not renormalised (renormalising
 turned the margin rows' noise into flux: +0.16 %, +9.5 % on a nearly unlit interval).  Limits: the profile's own noise is
 not in optimal_var, which is too small on a nearly unlit interval (an ensemble showed 1.64 times it); the intervals'
-correlation through shared reads is as for spectra_var.  Not covered: optimal wavelength-binned channels
-(`channel_weights(...) @ optimal` serves star-fixed columns), a profile from a PSF model or a polynomial fit along the
+correlation through shared reads is as for spectra_var.  Not covered: a profile from a PSF model or a polynomial fit along the
 dispersion, iterating the profile, rejecting on the optimal residuals, the direct image.
+
+A profile formed once per visit: `Optimal(profile=..., deliver_profile=...)`.  The exposure's own profile carries its own
+noise, common to the 2H + 1 columns it is formed from, so it adds coherently over the columns of a channel.  With
+`deliver_profile` the planes S1 of every window pixel come back too (Exposure.profile_planes; fetched by a call of its
+own); ProfileSum adds those of several exposures and normalises them, and `profile=` (a Profile, or the {profile_key:
+Profile} of VisitRunner.build_profile) makes the weights come from that sum (the law: include/wayne_hip.h).  Limits: the
+profile is fixed on the detector (sub-pixel drift, forward against reverse scans), a nearly unlit interval has a profile
+of noise.
 
 Cosmic-ray rejection is opt-in (`crrej=` of Extraction / ExtractionOptions / the frames, CLI --reject-cosmics): on each
 read interval's difference image I a pixel at least 7 px inside the frame and in the plan's rows is flagged when it
@@ -61,6 +68,8 @@ stare256 at k = 4 .. 8, leaving 0.07-0.12 % of the hits' electrons.  `rejected` 
 flags in each product's window ((pixel, interval) pairs for the last-read product).  Not covered: hits on adjacent
 pixels of one interval (they shield each other), the 7-pixel frame margin, optimal extraction, the direct image.
 """
+import hashlib
+
 import numpy as np
 
 from . import _lib, tools
@@ -128,17 +137,112 @@ class Variances(object):
         return d
 
 
+class Profile(object):
+    """A profile for the optimal extraction of a visit's exposures (wayne_exposure_set_optimal_profile): `planes`
+    [sum_p rows_p, S] float64 -- the windows of the R + 1 products one behind the other, rows relative to the window -- and
+    `rows` [R + 1], the window heights they were made for.  An exposure whose windows have other heights is refused when it
+    is run.  `exposures`: how many exposures' planes were added up (0: not known)."""
+
+    def __init__(self, planes, rows, exposures=0):
+        rows = tuple(int(r) for r in rows)
+        planes = np.array(planes, dtype=np.float64, order="C")      # (a copy of its own, read-only: `tag` names its content)
+        if not 2 <= len(rows) <= _lib.EXTRACT_PRODUCTS or min(rows[:-1]) < 1 or rows[-1] < 0:
+            raise ValueError("Profile: rows holds the heights of the R read intervals' windows and of the last read's")
+        if planes.ndim != 2 or planes.shape[0] != sum(rows):
+            raise ValueError("Profile: planes must be [sum(rows), S]")
+        if not np.isfinite(planes).all():
+            raise ValueError("Profile: planes must be finite")
+        planes.setflags(write=False)
+        self.planes, self.rows, self.exposures = planes, rows, int(exposures)
+        # 64 bits of a cryptographic hash of heights and content, formed once: what a slot that already holds this
+        # profile recognises it by (wayne_exposure_set_optimal_profile_tagged), at no cost per exposure
+        h = hashlib.blake2b(np.asarray(rows, dtype=np.int64).tobytes(), digest_size=8)
+        h.update(planes)
+        self.tag = int.from_bytes(h.digest(), "little") or 1
+
+    def window(self, p):
+        """The profile of product p's window: a view [rows_p, S]."""
+        at = sum(self.rows[:p])
+        return self.planes[at:at + self.rows[p]]
+
+
+def window_heights(plan):
+    """The heights of a plan's R + 1 windows, as the profile planes lay them out (the last read's window counts whether
+    the plan forms that product or not: its rows are zeros then)."""
+    return tuple(int(hi) - int(lo) for lo, hi in plan.row_windows)
+
+
+def profile_key(plan, scan_speed):
+    """What exposures must share to share a profile: (the plan's window heights, the scan's direction +1 / -1 / 0)."""
+    speed = float(getattr(scan_speed, "value", scan_speed) or 0.0)
+    return window_heights(plan), int(np.sign(speed))
+
+
+class ProfileSum(object):
+    """Adds the delivered planes (S1) of several exposures with equal window heights and normalises the sum: a
+    flux-weighted mean profile, with no division by a noisy S0."""
+
+    def __init__(self):
+        self.rows, self.total, self.n = None, None, 0
+
+    def add(self, plan, planes):
+        rows = window_heights(plan)
+        planes = np.asarray(planes, dtype=np.float64)
+        if planes.ndim != 2 or planes.shape[0] != sum(rows):
+            raise ValueError("ProfileSum: planes must be [sum of the plan's window heights, S]")
+        if self.rows is None:
+            self.rows, self.total = rows, np.zeros_like(planes)
+        elif rows != self.rows or planes.shape != self.total.shape:
+            raise ValueError("ProfileSum: the exposure's window heights %s differ from %s" % (rows, self.rows))
+        self.total = self.total + planes
+        self.n += 1
+        return self
+
+    def profile(self):
+        """The Profile: every column of every window divided by its sum over the window's rows; a column whose sum is
+        not positive gets zeros (W = 0 there: the box values)."""
+        if self.rows is None:
+            raise ValueError("ProfileSum: nothing was added")
+        out = np.zeros_like(self.total)
+        at = 0
+        for r in self.rows:
+            w = self.total[at:at + r]
+            tot = w.sum(axis=0)
+            good = tot > 0.0
+            out[at:at + r][:, good] = w[:, good] / tot[good]
+            at += r
+        return Profile(out, self.rows, self.n)
+
+
 class Optimal(object):
     """Optimal (profile-weighted) extraction beside the box extraction (wayne_optimal_desc): `half_width`, the columns on
-    either side of a column whose light forms its profile (an integer in 1 .. 16).  It needs the variances."""
+    either side of a column whose light forms its profile (an integer in 1 .. 16).  It needs the variances.  `profile` (a
+    Profile): the weights come from it and not from the exposure's own light (half_width then enters through the
+    detection test alone); as {profile_key: Profile} (VisitRunner.build_profile) an ExtractionOptions picks each
+    exposure's by its window heights and scan direction.  `deliver_profile`: the exposure's own planes S1 come back too (Exposure.profile_planes; the raw
+    material of a ProfileSum).  `channels` (the plan must carry channels): the pixels' weighted terms are binned into the
+    plan's wavelength channels too -- channels_opt and channels_opt_var [R + 1, C] (wayne_exposure_set_optimal_channels);
+    meant for a supplied profile: with the exposure's own, channels_opt_var is too small (README)."""
 
-    def __init__(self, half_width=8):
+    def __init__(self, half_width=8, profile=None, deliver_profile=False, channels=False):
         if isinstance(half_width, bool) or int(half_width) != half_width:
             raise ValueError("Optimal: half_width must be an integer")
         half_width = int(half_width)
         if not 1 <= half_width <= _lib.MAX_OPTIMAL_HALF_WIDTH:
             raise ValueError("Optimal: half_width must lie in 1 .. %d" % _lib.MAX_OPTIMAL_HALF_WIDTH)
+        if isinstance(profile, dict):
+            if not all(isinstance(v, Profile) for v in profile.values()):
+                raise TypeError("Optimal: profile is None, an extraction.Profile or {profile_key: Profile}")
+        elif profile is not None and not isinstance(profile, Profile):
+            raise TypeError("Optimal: profile is None, an extraction.Profile or {profile_key: Profile}")
         self.half_width = half_width
+        self.profile = profile
+        self.deliver_profile = bool(deliver_profile)
+        self.channels = bool(channels)
+
+    def with_profile(self, profile, deliver_profile=False, channels=None):
+        """The same options with another `profile` and `deliver_profile` (and, if given, `channels`)."""
+        return Optimal(self.half_width, profile, deliver_profile, self.channels if channels is None else channels)
 
     @staticmethod
     def coerce(optimal):
@@ -257,6 +361,8 @@ class Extraction(object):
         self.optimal = Optimal.coerce(optimal)
         if self.optimal is not None and self.variance is None:
             raise ValueError("optimal needs variance: the weights are formed from the variances")
+        if self.optimal is not None and self.optimal.channels and self.channels is None:
+            raise ValueError("optimal channels need channels: they are binned by the channels' edges and row solution")
         self.row_solution = None
         self.hull = None              # (u_lo, u_hi): the bordered columns the channels can touch
         if self.channels is not None:
@@ -326,12 +432,27 @@ class ExtractionOptions(object):
         if self.optimal is not None and self.variance is None:
             raise ValueError("optimal needs variance: the weights are formed from the variances")
 
+    def with_optimal(self, optimal):
+        """The same options with another `optimal`."""
+        return ExtractionOptions(self.margin, self.bg_cols, self.steps, self.crrej, self.channels, self.variance, optimal)
+
     def plan(self, grism, wl, x_ref, y_ref, scan_speed, read_times, sub_scale, S, channels=OWN):
         """This exposure's Extraction; `channels` (a Channels or None) replaces the options' own."""
         channels = self.channels if channels is OWN else Channels.coerce(channels)
         sol = None if channels is None else row_solution(grism, x_ref, y_ref, sub_scale, S)
-        return Extraction(row_windows(grism, wl, x_ref, y_ref, scan_speed, read_times, sub_scale, S, self.margin),
+        plan = Extraction(row_windows(grism, wl, x_ref, y_ref, scan_speed, read_times, sub_scale, S, self.margin),
                           self.bg_cols, self.steps, self.crrej, channels, sol, self.variance, self.optimal)
+        return pick_profile(plan, scan_speed)
+
+
+def pick_profile(plan, scan_speed):
+    """`plan` with its exposure's own Profile where its Optimal carries {profile_key: Profile} (otherwise as it is)."""
+    if plan is None or plan.optimal is None or not isinstance(plan.optimal.profile, dict):
+        return plan
+    key = profile_key(plan, scan_speed)
+    if key not in plan.optimal.profile:
+        raise ValueError("optimal: no profile for window heights %s and scan direction %+d" % key)
+    return plan.with_optimal(plan.optimal.with_profile(plan.optimal.profile[key], plan.optimal.deliver_profile))
 
 
 def for_exposure(extraction, grism, wl, x_ref, y_ref, scan_speed, read_times, sub_scale, S, crrej=None, channels=None,
@@ -347,7 +468,7 @@ def for_exposure(extraction, grism, wl, x_ref, y_ref, scan_speed, read_times, su
             if optimal is not False:
                 raise ValueError("optimal needs an extraction")
             return None
-        return plan.with_optimal(optimal)
+        return pick_profile(plan.with_optimal(optimal), scan_speed)
     if variance is not None:
         if extraction is None or extraction is False:
             if variance is not False:
@@ -460,7 +581,8 @@ def channel_weights(x_ref, edges, sub_scale, S):
 CHUNK_ROWS = 32            # rows of a chunk of a window (kExtractRows): partial sums are kept per chunk
 
 
-def algorithmic_bytes(plan, S, R, read_bytes=4, crrej=False, channels=False, variance=False, optimal=False):
+def algorithmic_bytes(plan, S, R, read_bytes=4, crrej=False, channels=False, variance=False, optimal=False, profile=False,
+                      deliver_profile=False, optimal_channels=False):
     """Bytes the extraction's kernels must move for `plan` on a frame of side S with R non-zero reads of `read_bytes`
     a sample: per pixel of product j's window the reads P_{j+1}, P_j, P_0 (P_0 once for j = 0 and for the last read),
     four coefficient planes, dark_{j+1} and dark_j (float32 each; dark_0 = 0 is not stored), the pixel flat and the
@@ -476,7 +598,15 @@ def algorithmic_bytes(plan, S, R, read_bytes=4, crrej=False, channels=False, var
     spectra_var, sky_var [(R + 1)(S + 1)] and, with `channels`, channels_var [(R + 1) C] written.  `optimal`: plus
     k_extract_optimal's -- per window pixel the planes k_extract_rows reads (the flag word under `crrej` too) once more, the
     chunks' sums (3 float64 per chunk and column) written and read once and optimal, optimal_var [2 (R + 1) S] written.
-    (The halo a tile re-reads, 1.5 times the tile, is not algorithmic.)"""
+    (The halo a tile re-reads, 1.5 times the tile, is not algorithmic.)  `profile` (with `optimal`: a supplied
+    profile): plus one float64 of the profile read per window pixel -- k_extract_optimal_fixed re-reads no halo.
+    `deliver_profile` (with `optimal`): plus k_extract_profile's -- per window pixel the planes k_extract_rows reads (and the
+    flag word) once more and a float64 of S1 written, zeros for the window of a last read that is not formed.
+    `optimal_channels` (with `optimal` and `channels`): plus k_extract_bins_opt's -- the walk of the hull once more."""
+    if optimal_channels and not (optimal and channels and plan.channels is not None):
+        raise ValueError("algorithmic_bytes: optimal_channels belong to the optimal extraction and the channels")
+    if (profile or deliver_profile) and not optimal:
+        raise ValueError("algorithmic_bytes: profile and deliver_profile belong to the optimal extraction")
     total = 0
     hull = (plan.hull[1] - plan.hull[0]) if channels and plan.channels is not None else 0
     n_ch = plan.channels.n if hull or (channels and plan.channels is not None) else 0
@@ -486,6 +616,8 @@ def algorithmic_bytes(plan, S, R, read_bytes=4, crrej=False, channels=False, var
     steps = plan.steps
     for p, (lo, hi) in enumerate(plan.row_windows[:R + 1]):
         if p == R and not steps & LAST_READ:
+            if deliver_profile:
+                total += max(int(hi) - int(lo), 0) * S * 8
             continue
         first = p == 0 or p == R                    # L_{r-1} = L_0 = 0: one read and one dark plane fewer
         per_pixel = (2 if first else 3) * read_bytes
@@ -505,8 +637,19 @@ def algorithmic_bytes(plan, S, R, read_bytes=4, crrej=False, channels=False, var
             total += 2 * (chunks * S * 8) + 2 * (chunks * n_ch * 8)
         if optimal:
             total += rows * S * (per_pixel + (2 if crrej else 0)) + 2 * (3 * chunks * S * 8)
+        if profile:
+            total += rows * S * 8
+        if deliver_profile:
+            total += rows * S * (per_pixel + (2 if crrej else 0) + 8)
+        if optimal_channels:
+            # k_extract_bins' walk of the hull once more (with a supplied profile its float64 too), the columns' W from the
+            # optimal scratch per chunk, the row groups' three sums written and read once
+            total += rows * hull * (per_pixel + (2 if crrej else 0) + (16 if plan.channels.flat else 0) + (8 if profile else 0))
+            total += rows * 16 + chunks * hull * 8 + 2 * (chunks * 3 * n_ch * 8)
     if optimal:
         total += 2 * (R + 1) * S * 8
+    if optimal_channels:
+        total += 2 * (R + 1) * n_ch * 8
     if variance:
         total += (R + 1) * (S + 1) * 8 + (R + 1) * n_ch * 8
     return total + (R + 1) * (S + 1) * 8 + (R + 1) * n_ch * 8
@@ -524,6 +667,8 @@ class Delivery(object):
         self.channels = None      # channels [R + 1, C] of the last wait (None: that slot extracts without channels)
         self.variances = None     # (spectra_var, sky_var, channels_var or None) of the last wait (None: without variances)
         self.optimal = None       # (optimal, optimal_var) of the last wait (None: that slot extracts without them)
+        self.channels_opt = None  # (channels_opt, channels_opt_var) of the last wait (None: that slot does not form them)
+        self.profile_planes = None   # the planes S1 of the last wait (None: that slot does not deliver them)
 
     def upload(self, slot, desc):
         self.ctx.upload(slot, desc)
@@ -543,11 +688,14 @@ class Delivery(object):
         self.channels = self.ctx.channels(slot) if self.ctx.has_channels(slot) else None
         self.variances = self.ctx.variances(slot) if self.ctx.has_variance(slot) else None
         self.optimal = self.ctx.optimal(slot) if self.ctx.has_optimal(slot) else None
+        self.channels_opt = self.ctx.optimal_channels(slot) if self.ctx.has_optimal_channels(slot) else None
+        # (a copy of its own, behind the settled run: wanted for the handful of exposures that form a visit's profile)
+        self.profile_planes = self.ctx.profile_planes(slot) if self.ctx.delivers_profile(slot) else None
         return reads, spectra, sky
 
 
 def save_npz(path, spectra, sky, exposure_index, plans, x_ref, y_ref, read_times, exp_start, rejected=None, channels=None,
-             variances=None, optimal=None):
+             variances=None, optimal=None, optimal_profile_exposures=None, channels_opt=None):
     """The file --spectra / --spectra-only write: spectra [n, R + 1, S], sky [n, R + 1], exposure_index [n], row_lo /
     row_hi [n, R + 1], bg_cols [2], x_ref / y_ref [n], read_times [R], exp_start [n].  With `rejected` [n, R + 1] (the
     exposures were extracted with cosmic-ray rejection) also n_rejected [n, R + 1] -- flags in each product's window,
@@ -556,7 +704,9 @@ def save_npz(path, spectra, sky, exposure_index, plans, x_ref, y_ref, read_times
     rows' wavelength solutions wl_a / wl_b [n, S].  With `variances` = (spectra_var [n, R + 1, S], sky_var [n, R + 1],
     channels_var [n, R + 1, C] or None) (the exposures were extracted with variances) also spectra_var, sky_var,
     channels_var (with channels) and variance_read_noise.  With `optimal` = (optimal [n, R + 1, S], optimal_var
-    [n, R + 1, S]) (the exposures were extracted optimally too) also optimal, optimal_var and optimal_half_width."""
+    [n, R + 1, S]) (the exposures were extracted optimally too) also optimal, optimal_var and optimal_half_width; with
+    `optimal_profile_exposures` = N > 0 (their profiles were formed from the first N exposures of each group) also that;
+    with `channels_opt` = (channels_opt, channels_opt_var [n, R + 1, C]) (the optimal channels) also those two."""
     n = len(exposure_index)
     more = {}
     if rejected is not None:
@@ -577,6 +727,11 @@ def save_npz(path, spectra, sky, exposure_index, plans, x_ref, y_ref, read_times
     if optimal is not None:
         more.update(optimal=np.asarray(optimal[0], dtype=np.float64), optimal_var=np.asarray(optimal[1], dtype=np.float64),
                     optimal_half_width=np.int64(plans[0].optimal.half_width))
+        if optimal_profile_exposures:
+            more["optimal_profile_exposures"] = np.int64(optimal_profile_exposures)
+        if channels_opt is not None:
+            more.update(channels_opt=np.asarray(channels_opt[0], dtype=np.float64),
+                        channels_opt_var=np.asarray(channels_opt[1], dtype=np.float64))
     np.savez(path, **more, spectra=np.asarray(spectra, dtype=np.float64), sky=np.asarray(sky, dtype=np.float64),
              exposure_index=np.asarray(exposure_index, dtype=np.int64),
              row_lo=np.array([p.row_lo for p in plans], dtype=np.int64).reshape(n, -1),

@@ -73,6 +73,12 @@ class Observation(object):
         self.frame_options = {"out_dtype": np.float32}
         self.spectra_out = None
         self.spectra_only = False
+        # N > 0 (CLI: --optimal-profile N; needs frame_options["optimal"]): run_observation first forms the visit's
+        # profiles from the first N exposures of each group (_build_optimal_profiles) and extracts every exposure with
+        # its group's; `optimal_profiles` {extraction.profile_key: Profile} is what it formed, and the .npz also holds
+        # optimal_profile_exposures.
+        self.optimal_profile_exposures = 0
+        self.optimal_profiles = None
         self.spectra_result = None
         self.contaminants = []       # field stars on every exposure (setup_contaminants)
         self.charge_traps = None     # per-pixel charge trapping (setup_charge_traps)
@@ -363,8 +369,9 @@ class Observation(object):
                 reads, spectra, sky = reads
                 spectra, sky = np.array(spectra), np.array(sky)           # (copies: the pinned buffer is reused)
                 got_spectra.append((i, spectra, sky, gen.extraction_plan, gen.exp_info["x_ref"], gen.exp_info["y_ref"],
-                                    ctx.rejected, ctx.channels, ctx.variances, ctx.optimal))
-                frame = gen._fill_spectra(spectra, sky, ctx.rejected, ctx.channels, ctx.variances, ctx.optimal)
+                                    ctx.rejected, ctx.channels, ctx.variances, ctx.optimal, ctx.channels_opt))
+                frame = gen._fill_spectra(spectra, sky, ctx.rejected, ctx.channels, ctx.variances, ctx.optimal,
+                                          ctx.profile_planes, ctx.channels_opt)
             if reads is not None:
                 frame = gen._fill_exposure(np.array(reads), gen._prepared[2])     # (a copy: the pinned buffer is reused)
             if pool is not None:
@@ -373,6 +380,8 @@ class Observation(object):
             else:
                 frames[i + 1] = frame
 
+        if extraction is not None and self.optimal_profile_exposures:
+            self._build_optimal_profiles(mine, eng.ctx)
         try:
             # up to 3 exposures in flight on 4 context slots in rotation (even / odd slots run on different HIP streams)
             ctx = eng.ctx
@@ -386,6 +395,49 @@ class Observation(object):
         if extraction is not None:
             self._keep_spectra(got_spectra, rank, world)
         return frames
+
+    def _build_optimal_profiles(self, mine, ctx):
+        """The first pass of `optimal_profile_exposures` = N: the first N exposures of each group among `mine` -- a group
+        is what extraction.profile_key tells apart, window heights and scan direction, so a visit whose windows change
+        height as the star drifts over a row boundary has several -- are synthesised with their profile planes delivered
+        (the reads never leave the device), each group's planes are added up and normalised, and
+        frame_options["optimal"] then carries {key: Profile}: every exposure of the visit proper is extracted with its
+        group's.  Every exposure's host half runs once more for it (its plan tells its group).  With several ranks each
+        forms its profiles from its own share."""
+        from . import extraction as _extraction
+        from .pipeline import run_pipelined
+        optimal = _extraction.Optimal.coerce(self.frame_options.get("optimal"))
+        if optimal is None:
+            raise ValueError("optimal_profile_exposures needs frame_options['optimal']")
+        n = int(self.optimal_profile_exposures)
+        kept = dict(self.frame_options)
+        seen, first = {}, []
+        self.frame_options = dict(kept, optimal=optimal.with_profile(None))
+        try:
+            for i in mine:
+                gen = self._generate_exposure(self.exp_start_times[i], i + 1, write_fits=False, prepare_only=True)
+                key = gen.profile_key
+                if seen.get(key, 0) < n:
+                    seen[key] = seen.get(key, 0) + 1
+                    first.append((i, key))
+            keys = dict(first)
+            sums = {}
+            # (the optimal channels of these exposures would be thrown away: off)
+            self.frame_options = dict(kept, optimal=optimal.with_profile(None, deliver_profile=True, channels=False))
+            delivery = _extraction.Delivery(ctx, reads=False)
+
+            def prepare(i):
+                gen = self._generate_exposure(self.exp_start_times[i], i + 1, write_fits=False, prepare_only=True)
+                return gen._prepared[1], gen
+
+            def finish(i, gen, got):
+                sums.setdefault(keys[i], _extraction.ProfileSum()).add(gen.extraction_plan, delivery.profile_planes)
+
+            run_pipelined(delivery, [i for i, _ in first], prepare, finish, depth=3, n_slots=4)
+        finally:
+            self.frame_options = kept
+        self.optimal_profiles = {key: acc.profile() for key, acc in sums.items()}
+        self.frame_options = dict(kept, optimal=optimal.with_profile(self.optimal_profiles, optimal.deliver_profile))
 
     def _keep_spectra(self, got, rank, world):
         """What the exposures' extraction delivered -> `spectra_result` (the arrays of extraction.save_npz), written to
@@ -411,6 +463,9 @@ class Observation(object):
         if got and all(g[9] is not None for g in got):        # extracted optimally too
             self.spectra_result["optimal"] = np.array([g[9][0] for g in got], dtype=np.float64)
             self.spectra_result["optimal_var"] = np.array([g[9][1] for g in got], dtype=np.float64)
+        if got and all(g[10] is not None for g in got):       # the optimal channels
+            self.spectra_result["channels_opt"] = np.array([g[10][0] for g in got], dtype=np.float64)
+            self.spectra_result["channels_opt_var"] = np.array([g[10][1] for g in got], dtype=np.float64)
         if not self.spectra_out:
             return None
         path = self.spectra_out
@@ -422,7 +477,9 @@ class Observation(object):
             _extraction.save_npz(f, r["spectra"], r["sky"], r["exposure_index"], r["plans"], r["x_ref"], r["y_ref"],
                                  r["read_times"], r["exp_start"], rejected=r.get("rejected"), channels=r.get("channels"),
                                  variances=(r["spectra_var"], r["sky_var"], r.get("channels_var")) if "spectra_var" in r else None,
-                                 optimal=(r["optimal"], r["optimal_var"]) if "optimal" in r else None)
+                                 optimal=(r["optimal"], r["optimal_var"]) if "optimal" in r else None,
+                                 optimal_profile_exposures=self.optimal_profile_exposures if "optimal" in r else None,
+                                 channels_opt=(r["channels_opt"], r["channels_opt_var"]) if "channels_opt" in r else None)
         return path
 
     @staticmethod

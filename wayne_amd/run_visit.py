@@ -2,7 +2,7 @@
 
     python -m wayne_amd.run_visit -p <parameter_file> [--calibration DIR] [--device N] [--max-exposures M] [--gpus G] [--resume]
                                   [--spectra OUT.npz | --spectra-only OUT.npz] [--reject-cosmics [K]]
-                                  [--channels LO:HI:N] [--no-channel-flat] [--variances [RN]] [--optimal [H]]
+                                  [--channels LO:HI:N] [--no-channel-flat] [--variances [RN]] [--optimal [H]] [--optimal-profile N] [--optimal-channels]
 
 Accepts the reference's parameter files (wayne/run_visit.py:1-9, example
 examples/hd209458b_12181_simulation_parameters.yml): sections `general`
@@ -41,6 +41,8 @@ examples/hd209458b_12181_simulation_parameters.yml): sections `general`
     channels_var [n, NSAMP, N], and variance_read_noise.  `--optimal [H]` (with --variances): the device also forms the
     optimal (profile-weighted) spectra, each column's profile taken from the window's own light over 2H + 1 columns
     (default H = 8, 1 .. 16); OUT.npz then also holds optimal, optimal_var [n, NSAMP, S] and optimal_half_width;
+    `--optimal-profile N` (with --optimal): the profiles are formed once, from the first N exposures of each group, and
+    OUT.npz also holds optimal_profile_exposures;
   * `--gpus G`: the process starts G rank processes itself (one per GPU of this node, before anything touches a
     GPU) and waits for them; under an external launcher (WORLD_SIZE / RANK set, one process per GPU) it is one
     rank.  Each rank generates its round-robin share of the exposures (observation.py:403-405 is the axis) on the
@@ -216,6 +218,13 @@ def run(argv=None):
                     help="with --variances: also deliver the optimal (profile-weighted) spectra and their variances, the "
                          "profile of a column formed over 2H + 1 columns (default 8, 1 .. 16); OUT.npz then also holds "
                          "optimal, optimal_var and optimal_half_width")
+    ap.add_argument("--optimal-profile", type=int, default=None, metavar="N",
+                    help="with --optimal: a first pass over the first N exposures of each group (window heights and scan "
+                         "direction) forms one profile per group on the device, and every exposure is then extracted with "
+                         "its group's profile instead of its own; OUT.npz then also holds optimal_profile_exposures")
+    ap.add_argument("--optimal-channels", action="store_true",
+                    help="with --optimal and --channels: also bin the optimal extraction's weighted pixels into the channels; "
+                         "OUT.npz then also holds channels_opt and channels_opt_var (meant for --optimal-profile)")
     args = ap.parse_args(argv)
     variance = None
     if args.variances is not None:
@@ -235,6 +244,16 @@ def run(argv=None):
             optimal = Optimal(half_width=args.optimal)
         except ValueError as e:
             raise SystemExit("--optimal [H] (columns, 1 .. 16): %s" % e)
+    if args.optimal_channels:
+        if optimal is None or args.channels is None:
+            raise SystemExit("--optimal-channels needs --optimal and --channels")
+        from .extraction import Optimal
+        optimal = Optimal(optimal.half_width, channels=True)
+    if args.optimal_profile is not None:
+        if optimal is None:
+            raise SystemExit("--optimal-profile needs --optimal")
+        if args.optimal_profile < 1:
+            raise SystemExit("--optimal-profile N: at least 1 exposure")
     channels = None
     if args.no_channel_flat and args.channels is None:
         raise SystemExit("--no-channel-flat needs --channels")
@@ -314,6 +333,7 @@ def run(argv=None):
             obs.frame_options["variance"] = variance
         if optimal is not None:
             obs.frame_options["optimal"] = optimal
+            obs.optimal_profile_exposures = args.optimal_profile or 0
         obs.spectra_out = args.spectra or args.spectra_only
         obs.spectra_only = bool(args.spectra_only)
     os.makedirs(obs.outdir, exist_ok=True)

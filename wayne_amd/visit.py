@@ -95,11 +95,14 @@ class VisitRunner(object):
         `on_spectra(i, spectra, sky)` gets views of the pinned buffer, and keep=True returns
         {index: (reads, spectra, sky)}.  When the extraction delivers variances, `self.spectra_var`, `self.sky_var` and
         -- with channels -- `self.channels_var` are {index: array} of every exposure run (None otherwise); when it
-        extracts optimally too, so are `self.optimal` and `self.optimal_var`."""
+        extracts optimally too, so are `self.optimal` and `self.optimal_var`, and `self.profile_planes` when it delivers
+        its profile planes."""
         eng = self.engine()
         results = {}
         self.spectra_var = self.sky_var = self.channels_var = None
         self.optimal = self.optimal_var = None
+        self.profile_planes = None
+        self.channels_opt = self.channels_opt_var = None      # {index: [R + 1, C]} when the optimal channels are formed
         pool = FitsWriterPool() if self.out_dir is not None else None
 
         def prepare(i):
@@ -124,6 +127,14 @@ class VisitRunner(object):
                     if self.optimal is None:
                         self.optimal, self.optimal_var = {}, {}
                     self.optimal[i], self.optimal_var[i] = ctx.optimal
+                if ctx.channels_opt is not None:
+                    if self.channels_opt is None:
+                        self.channels_opt, self.channels_opt_var = {}, {}
+                    self.channels_opt[i], self.channels_opt_var[i] = ctx.channels_opt
+                if ctx.profile_planes is not None:
+                    if self.profile_planes is None:
+                        self.profile_planes = {}
+                    self.profile_planes[i] = ctx.profile_planes
                 if on_spectra is not None:
                     on_spectra(i, spectra, sky)
             if on_reads is not None:
@@ -151,7 +162,9 @@ class VisitRunner(object):
         (None otherwise); `self.channels` [n, R + 1, C]: the channel fluxes of an extraction that bins into wavelength
         channels (None otherwise); `self.spectra_var` [n, R + 1, S], `self.sky_var` [n, R + 1] and -- with channels --
         `self.channels_var` [n, R + 1, C]: the variances of an extraction that delivers them (None otherwise);
-        `self.optimal` and `self.optimal_var` [n, R + 1, S]: the optimal extraction's, when asked for (None otherwise)."""
+        `self.optimal` and `self.optimal_var` [n, R + 1, S]: the optimal extraction's, when asked for (None otherwise);
+        `self.profile_planes` [n] arrays [sum of the exposure's window heights, S]: its profile planes, when the optimal
+        extraction delivers them (None otherwise)."""
         eng = self.engine()
         indices = list(indices)
         where = {i: n for n, i in enumerate(indices)}
@@ -163,6 +176,9 @@ class VisitRunner(object):
         binned = [None] * len(indices)
         varis = [None] * len(indices)
         optis = [None] * len(indices)
+        planes = [None] * len(indices)
+        keys = [None] * len(indices)
+        optch = [None] * len(indices)
         delivery = _extraction.Delivery(eng.ctx, reads=False)
 
         def prepare(i):
@@ -179,6 +195,9 @@ class VisitRunner(object):
             binned[where[i]] = delivery.channels
             varis[where[i]] = delivery.variances
             optis[where[i]] = delivery.optimal
+            planes[where[i]] = delivery.profile_planes
+            keys[where[i]] = gen.profile_key
+            optch[where[i]] = delivery.channels_opt
 
         run_pipelined(delivery, indices, prepare, finish, self.DEPTH, self.DEPTH)
         self.rejected = None if any(n is None for n in counts) or not counts else np.array(counts, dtype=np.uint32)
@@ -193,7 +212,28 @@ class VisitRunner(object):
         if optis and not any(o is None for o in optis):
             self.optimal = np.array([o[0] for o in optis], dtype=np.float64)
             self.optimal_var = np.array([o[1] for o in optis], dtype=np.float64)
+        self.profile_planes = planes if planes and not any(a is None for a in planes) else None
+        self.profile_keys = keys          # [n] extraction.profile_key of each exposure
+        self.channels_opt = self.channels_opt_var = None      # [n, R + 1, C]: the optimal channels, when asked for
+        if optch and not any(o is None for o in optch):
+            self.channels_opt = np.array([o[0] for o in optch], dtype=np.float64)
+            self.channels_opt_var = np.array([o[1] for o in optch], dtype=np.float64)
         return spectra, sky
+
+    def build_profile(self, indices, extraction):
+        """The visit's profiles for the optimal extraction: the exposures `indices` are run with `extraction` (an
+        ExtractionOptions or Extraction with variances and optimal) and their profile planes delivered, added up and
+        normalised -> {(window heights [R + 1], scan direction +1 / -1 / 0): extraction.Profile}, one per distinct key
+        (forward and reverse scans illuminate the rows in opposite order; exposures whose windows differ in height cannot
+        share planes)."""
+        indices = list(indices)
+        if getattr(extraction, "optimal", None) is None:
+            raise ValueError("build_profile: the extraction must carry optimal=")
+        self.run_spectra(indices, extraction=extraction.with_optimal(extraction.optimal.with_profile(None, deliver_profile=True, channels=False)))
+        sums = {}
+        for key, plan, planes in zip(self.profile_keys, self.plans, self.profile_planes):
+            sums.setdefault(key, _extraction.ProfileSum()).add(plan, planes)
+        return {key: acc.profile() for key, acc in sums.items()}
 
     def run_resident_spectra(self, n, on_spectra=None):
         """run_resident with only the spectra delivered: the descriptors AND their extraction are already in slots
