@@ -97,7 +97,7 @@ int wayne_ctx_synchronize(wayne_ctx *ctx);
  * other entry point looks at the environment, so editing it from another thread cannot change what a live context
  * launches.  Afterwards only this call changes a knob (value < 0: back to the library's own choice).  Names:
  * tile_ints, batch, thin, no_acc_box, lane_reach, throw_wgs, keep_narrow, no_fuse, fork_narrow, streams,
- * upload_timing, narrow_compact, lane_tight_tile, ramp_reads (timing builds only).  None changes a frame (integer
+ * upload_timing, narrow_compact, lane_tight_tile, fuse_thrower, prep_wl_per_run, ramp_reads (timing builds only).  None changes a frame (integer
  * accumulation commutes); they change launch shapes.  WAYNE_E_INVALID for an unknown name. */
 int wayne_ctx_set_knob(wayne_ctx *ctx, const char *name, long long value);
 int wayne_ctx_get_knob(const wayne_ctx *ctx, const char *name, long long *value);
@@ -249,7 +249,10 @@ int wayne_exposure_run_checked(wayne_ctx *ctx, int slot);
  * wayne_exposure_download / _wait / _run_checked / _debug_fetch and wayne_ctx_synchronize -- looks at the word itself
  * and runs such an exposure a second time with the general sequence; only a caller that waits on wayne_ctx_stream
  * with its own HIP calls bypasses that and must look here.  wayne_ctx_reruns: how many such second runs the context
- * has made (their electrons are counted twice in wayne_profile.electrons). */
+ * has made (their electrons are counted twice in wayne_profile.electrons).  The word is that of the LAST run enqueued
+ * on the slot: the library numbers a slot's runs and a flag raised by an earlier run does not show (nothing on the
+ * device clears the block between runs, and no kernel runs in front of an exposure's k_prep_sub: the per-wavelength
+ * arrays are worked out by wayne_exposure_upload / _set_sources and kept while the grid and the grism stay the same). */
 int wayne_exposure_status(wayne_ctx *ctx, int slot, int *status);
 unsigned long long wayne_ctx_reruns(const wayne_ctx *ctx);
 /* Copy the NSAMP reads (read 0 = zero read) of `slot` to the host:

@@ -70,6 +70,7 @@ def setup(name):
     runner = wvisit.VisitRunner(v, 0, out_dtype=np.float32)
     eng = runner.engine()
     eng.ctx.set_knob("streams", 1)
+    eng.ctx.set_knob("fuse_thrower", 0)                    # k_lane as a launch of its own (not inside k_thrower)
     for slot in range(4):
         eng.ctx.upload(slot, runner.descriptor(slot, eng))
     eng.ctx.synchronize()

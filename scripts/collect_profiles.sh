@@ -10,6 +10,8 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$R/gpurun_out/prof_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
+# k_lane and k_narrow as launches of their own (the default is one grid for both, k_thrower): per-kernel times and counters
+export WAYNE_FUSE_THROWER=0
 B="python3 $R/bench.py --full --no-cpu-baseline --no-extra-pass"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_split -o t -- $B --steps 30 --warmup 3 > $OUT/bench_under_rocprof.json 2> $OUT/trace_split.log
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_electron -o t -- $B --steps 30 --warmup 3 --thrower electron > $OUT/bench_under_rocprof_thrower_electron.json 2> $OUT/trace_electron.log

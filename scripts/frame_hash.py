@@ -3,6 +3,8 @@
 showing that two builds of the library produce the SAME frames bit for bit.
 
     WAYNE_HIP_LIB=ab/A.so python scripts/frame_hash.py cfg4 3;  WAYNE_HIP_LIB=ab/B.so python scripts/frame_hash.py cfg4 3
+
+A third argument `exact` takes the frames with exact_samplers=True (the library's exact-math kernels).
 """
 import hashlib
 import os
@@ -18,13 +20,14 @@ from wayne_amd import _lib  # noqa: E402
 
 name = sys.argv[1] if len(sys.argv) > 1 else "cfg4"
 n = int(sys.argv[2]) if len(sys.argv) > 2 else 3
+exact = "exact" in sys.argv[3:]
 v = helpers.make_visit(name, n_exposures=n)
 for mode, label in ((_lib.RNG_SPLIT, "split"), (_lib.RNG_PHILOX, "philox")):
     h = hashlib.sha256()
     for i in range(n):
         pg = helpers.product_generator(v, i)
-        reads = np.stack([r[0] for r in pg.scanning_frame(rng_mode=mode, **v.frame_kwargs(i)).reads]) if v.scan_speed else \
-            np.stack([r[0] for r in pg.staring_frame(rng_mode=mode, **{k: x for k, x in v.frame_kwargs(i).items()
+        reads = np.stack([r[0] for r in pg.scanning_frame(rng_mode=mode, exact_samplers=exact, **v.frame_kwargs(i)).reads]) if v.scan_speed else \
+            np.stack([r[0] for r in pg.staring_frame(rng_mode=mode, exact_samplers=exact, **{k: x for k, x in v.frame_kwargs(i).items()
                                                                         if k not in ("scan_speed", "sample_rate", "ssv_generator")}).reads])
         h.update(reads.tobytes())
-    print("%s %s %d exposures %s" % (name, label, n, h.hexdigest()[:32]), flush=True)
+    print("%s %s%s %d exposures %s" % (name, label, " exact" if exact else "", n, h.hexdigest()[:32]), flush=True)

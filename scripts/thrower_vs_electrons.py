@@ -24,6 +24,7 @@ for E in (0.0625e9, 0.125e9, 0.25e9, 0.5e9, 1e9, 1.5e9, 2e9):
     v = synthetic.Visit("cfg4", det, gr, cal, n_exposures=1, E=E)
     eng = engine.get_engine(0, gr, det, cal, v.NSAMP, v.SAMPSEQ, v.SUBARRAY)
     ctx = eng.ctx
+    ctx.set_knob("fuse_thrower", 0)                        # k_lane and k_narrow as launches of their own (not k_thrower)
     eg = ExposureGenerator(det, gr, v.NSAMP, v.SAMPSEQ, v.SUBARRAY, calibration=cal, seed=v.seed)
     ctx.upload(0, eg.build_descriptor(eng, out_dtype=np.float32, **v.frame_kwargs(0)))
     ctx.run(0)

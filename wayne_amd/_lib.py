@@ -263,7 +263,8 @@ def i32(a):
 
 
 KNOBS = ("tile_ints", "batch", "thin", "no_acc_box", "lane_reach", "throw_wgs", "keep_narrow", "no_fuse", "fork_narrow",
-         "streams", "upload_timing", "ramp_reads", "narrow_compact", "lane_tight_tile")
+         "streams", "upload_timing", "ramp_reads", "narrow_compact", "lane_tight_tile",
+         "fuse_thrower", "prep_wl_per_run")
 _live_contexts = weakref.WeakSet()
 _knob_defaults = {}
 

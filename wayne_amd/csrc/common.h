@@ -24,7 +24,7 @@ constexpr double kPi = 3.14159265358979323846;
 // (GrismDev, kBorder and the routing / launch-shape constants the host planner shares: plan_consts.h)
 
 // Per sub-sample record written by k_prep_sub and read by k_throw.
-constexpr int kTrStride = 8;   // doubles per sub-sample in the trace-coefficient array (k_prep_wl): 6 coefficients, 1 / m_wl, pad
+// (kTrStride, the doubles per sub-sample of the trace-coefficient array: plan_consts.h)
 
 struct SubInfo {
   uint32_t electrons;      // E_k

@@ -6,6 +6,8 @@
 // spectrum estimates that survived wayne_ctx_set_grism, commit d35fc47), behind a boundary only a GPU box could reach.
 //
 //   SpectrumEstimate     per-bin factors that depend on (grism, wavelengths, stellar flux) alone, cached on their content
+//   WlCache              when the per-wavelength arrays a source holds on the device (k_prep_wl) are still the ones of an upload
+//   trace_table          the trace coefficients of the K sub-samples, as k_prep_sub reads them
 //   estimate_thrown      expected electrons per k_lane / k_narrow chunk -> launch order, batches, what k_throw is sized for
 //   accumulator_boxes    per read interval: where the thrower's electrons can land (k_ramp loads accumulators only there)
 //   plan_psf_apply       the host half of wayne_psf_apply: count reduction, N = (int)(counts ratio), routing, clip rectangle
@@ -49,6 +51,40 @@ inline bool sens_table_ok(const double* swl, const double* sval, int n) {
     if (i > 0 && swl[i] < swl[i - 1]) return false;
   }
   return true;
+}
+
+// The per-wavelength arrays of a source (ratio, sigl, sigh, sens, dlam: k_prep_wl) are worked out when its wavelength grid
+// is uploaded, not per run.  They stay valid for that slot and source while the NEXT upload brings the same grid -- same
+// W, the same bytes (a NaN compares equal to itself, -0 differs from +0: whatever the kernel would read is what is
+// compared) -- under the same grism generation: the context counts wayne_ctx_set_grism and wayne_ctx_set_calibration
+// calls, so arrays worked out with an earlier grism never serve a later one.  A visit re-uploading one grid pays a
+// compare of W doubles and launches nothing.
+struct WlCache {
+  std::vector<double> wl;      // the grid the device arrays were worked out for
+  unsigned long long gen = 0;  // ... and the grism generation
+  bool valid = false;
+  bool holds(int W, const double* wl_um, unsigned long long generation) const {
+    return valid && W >= 0 && gen == generation && wl.size() == (size_t)W &&
+           (W == 0 || std::memcmp(wl.data(), wl_um, (size_t)W * sizeof(double)) == 0);
+  }
+  void adopt(int W, const double* wl_um, unsigned long long generation) {
+    wl.assign(wl_um, wl_um + (W > 0 ? W : 0));
+    gen = generation;
+    valid = true;
+  }
+  void drop() { valid = false; }
+};
+
+// Trace coefficients of the K sub-samples as k_prep_sub and k_lane_fused read them: kTrStride doubles each -- the six of
+// trace_coeffs, 1 / m_wl (bin_position_bound) and a pad.  The same function in the same arithmetic as the device's
+// (+ - x / and sqrt, no contraction: both sides are built with -ffp-contract=off), so the same bits.
+inline void trace_table(const GrismDev& g, int K, const double* x_ref, const double* y_ref, double* tr) {
+  for (int k = 0; k < K; ++k) {
+    double* t = tr + (size_t)kTrStride * k;
+    trace_coeffs(g, x_ref[k], y_ref[k], t);
+    t[6] = 1. / t[4];
+    t[7] = 0.;
+  }
 }
 
 struct SpectrumEstimate {

@@ -82,15 +82,24 @@ __device__ __forceinline__ float upper_tail(float t) {
   return (t > kTailCut) ? 0.f : (0.5f * u) * M::exp_(p);
 }
 
+// THE LARGE LDS ARRAYS of k_narrow and k_lane are views into ONE buffer of kThrowerLds ints that the kernel declares
+// and hands to the body: k_lane's tile, or k_narrow's tile, s_q, s_pool and s_cond.  k_thrower (end of this file) holds
+// workgroups of both kinds in one grid and a kernel's LDS is what its largest path declares: with an array set per
+// body the two would add up (76 KB: two workgroups per CU instead of four).
+constexpr int kLaneTile = 9216;         // ints of LDS (36 KB): 512 bins span ~20 px of the trace, + 2 x margin, by 2 x margin + a few rows
+constexpr int kNarrowLds = kNarrowTile + kPoolRows * kNarrowThreads + 2 * kNarrowThreads;
+constexpr int kThrowerLds = kNarrowLds > kLaneTile ? kNarrowLds : kLaneTile;     // 9728 ints (38 KB)
+
+// `lds`: kNarrowLds ints; `by`: the workgroup's rank among the narrow workgroups of its sub-sample (blockIdx.y of k_narrow)
 template <int FLUSH, bool FAST, bool COMPACT>
-__global__ __launch_bounds__(kNarrowThreads) void k_narrow(ThrowArgs a) {
+__device__ __forceinline__ void narrow_body(const ThrowArgs& a, int* const lds, const unsigned by) {
   typedef typename std::conditional<FAST, FastMath, ExactMath<float> >::type M;
-  __shared__ int tile[kNarrowTile];
+  int* const tile = lds;                                // [kNarrowTile]
   // per lane: the running sums of a pooling bin's residual row masses q_b(t) - qbar(t), t = 0..13; any other bin's CONDITIONAL row
   // probabilities in visiting order (see below)
-  __shared__ float s_q[kPoolRows][kNarrowThreads];
-  __shared__ int s_pool[kNarrowThreads];                // [group][column of the group's window]: pooled column counts
-  __shared__ float s_cond[kNarrowThreads];              // [group][i]: conditional probability of the i-th row visited by a pooled chain
+  float (*const s_q)[kNarrowThreads] = reinterpret_cast<float (*)[kNarrowThreads]>(lds + kNarrowTile);   // [kPoolRows][kNarrowThreads]
+  int* const s_pool = lds + kNarrowTile + kPoolRows * kNarrowThreads;      // [group][column of the group's window]: pooled column counts
+  float* const s_cond = reinterpret_cast<float*>(s_pool + kNarrowThreads); // [group][i]: conditional probability of the i-th row visited by a pooled chain
   __shared__ int s_box[4];
   __shared__ float s_fc[10];                            // stirling_tail(0..9), indexed per lane in the rejection sampler
   // COMPACT: X0 and J0 of the 32 groups; the live chains by the highest set bit of their start count
@@ -101,8 +110,8 @@ __global__ __launch_bounds__(kNarrowThreads) void k_narrow(ThrowArgs a) {
   const int tid = threadIdx.x;
   // (the workgroup's chunk by a scalar load of the argument word that holds its byte; the bin's count, position and
   // sigma asked for together, whether or not the count turns out positive: see k_lane)
-  const uint32_t order_word = reinterpret_cast<const uint32_t*>(a.chunk_order)[blockIdx.y >> 2];
-  const int w = (int)((order_word >> (8 * (blockIdx.y & 3))) & 0xFFu) * kNarrowThreads + tid;
+  const uint32_t order_word = reinterpret_cast<const uint32_t*>(a.chunk_order)[by >> 2];
+  const int w = (int)((order_word >> (8 * (by & 3))) & 0xFFu) * kNarrowThreads + tid;
   const SubInfo si = a.sub[k];
   int n0 = 0;                                                  // narrow electrons of the bin's multinomial
   double xd = 0., yd = 0., sgd = 1.;
@@ -392,6 +401,12 @@ __global__ __launch_bounds__(kNarrowThreads) void k_narrow(ThrowArgs a) {
   }
 }
 
+template <int FLUSH, bool FAST, bool COMPACT>
+__global__ __launch_bounds__(kNarrowThreads) void k_narrow(ThrowArgs a) {
+  __shared__ int lds[kNarrowLds];
+  narrow_body<FLUSH, FAST, COMPACT>(a, lds, blockIdx.y);
+}
+
 // ---------------------------------------------------------------------------
 // k_lane : a bin's one-by-one electrons, thrown by the bin's own lane
 // ---------------------------------------------------------------------------
@@ -437,7 +452,7 @@ constexpr float kLaneR16 = 4.63f;
 constexpr float kLaneR34 = 6.9f;        // reach of the refined radius (6.87 sigma): the tile rule with lane_tight_tile = 0
 constexpr int kLaneMargin = 30;
 constexpr int kLaneReachMax = 48;       // largest margin of a test-free tile (sigma_h up to 6.8 px)
-constexpr int kLaneTile = 9216;         // ints of LDS (36 KB): 512 bins span ~20 px of the trace, + 2 x margin, by 2 x margin + a few rows
+// (kLaneTile = 9216 ints of LDS: above, with the kernels' common buffer)
 
 // BATCHES.  A finely sampled scan (the reference's default 10 ms sampling: K = 2233 sub-samples of ~2.5 electrons
 // per bin) launches K x chunks workgroups of ~1300 electrons each.  A workgroup can take `kb` consecutive sub-samples
@@ -459,9 +474,9 @@ constexpr int kLaneTile = 9216;         // ints of LDS (36 KB): 512 bins span ~2
 // and read back here, the six K x W arrays of intermediates were ~900 MB of traffic per exposure and the two kernels
 // spent two thirds of their wave-cycles waiting on them.  Only the counts are still stored (for
 // wayne_exposure_debug_fetch); positions are worked out again by a k_prep_sub launch if a caller asks for them.
+// `tile`: kLaneTile ints of LDS; `by`: the workgroup's rank among the lane workgroups of its sub-samples (blockIdx.y of k_lane)
 template <int FLUSH, bool THIN, bool BATCH, bool FUSED>
-__device__ __forceinline__ void lane_body(const ThrowArgs& a, const PrepArgs& p, const CosmicArgs& ca) {
-  __shared__ int tile[kLaneTile];
+__device__ __forceinline__ void lane_body(const ThrowArgs& a, const PrepArgs& p, const CosmicArgs& ca, int* const tile, const unsigned by) {
   __shared__ SubInfo s_sub[FUSED ? kLaneBatchMax : 1];
   __shared__ uint32_t s_hits;
   __shared__ unsigned short s_list[THIN ? kLaneListCap : 1];
@@ -473,8 +488,8 @@ __device__ __forceinline__ void lane_body(const ThrowArgs& a, const PrepArgs& p,
   const int tid = threadIdx.x;
   // (the chunk of this workgroup from the kernel arguments by a scalar load of the word that holds its byte: indexed as
   // a byte array it is a vector load from the argument segment, a memory latency in front of every other load here)
-  const uint32_t order_word = reinterpret_cast<const uint32_t*>(a.lane_order)[blockIdx.y >> 2];
-  const int w = (int)((order_word >> (8 * (blockIdx.y & 3))) & 0xFFu) * kLaneThreads + tid;
+  const uint32_t order_word = reinterpret_cast<const uint32_t*>(a.lane_order)[by >> 2];
+  const int w = (int)((order_word >> (8 * (by & 3))) & 0xFFu) * kLaneThreads + tid;
   const bool inw = w < a.W;
   // One sub-sample per workgroup (the rule: BATCH = false): everything the bin needs is asked for at once -- its
   // sigmas, its count, position and wide count -- instead of count first, then (if positive) the rest, then all of it
@@ -617,8 +632,8 @@ __device__ __forceinline__ void lane_body(const ThrowArgs& a, const PrepArgs& p,
       const BinPlan b = plan_bin(p, k, w, f_wl, f_flux, f_sens, f_dlam, f_ratio, f_sigl, p.tr + kTrStride * (size_t)k, p.x_ref[k],
                                  p.y_ref[k], p.dur_ms[k], p.depth ? p.depth[kw] : 0.);
       p.counts[kw] = (int32_t)b.count;
-      if (b.overflow) atomicOr(p.status, 1);
-      if (b.narrow > 0u || b.rest > 0u) atomicOr(p.status, 2);   // a bin for k_narrow / k_throw after all: the host runs the exposure again
+      if (b.overflow) raise_status(p, 1);
+      if (b.narrow > 0u || b.rest > 0u) raise_status(p, 2);   // a bin for k_narrow / k_throw after all: the host runs the exposure again
       n = (int)b.lane;
       f_electrons += b.lane;
       if (n > 0) { bl = bin_local(b.xs, b.ys); nw = min(max(b.nwide, 0), n); }
@@ -830,12 +845,39 @@ __device__ __forceinline__ void lane_body(const ThrowArgs& a, const PrepArgs& p,
 
 template <int FLUSH, bool THIN, bool BATCH>
 __global__ __launch_bounds__(kLaneThreads) void k_lane(ThrowArgs a) {
-  lane_body<FLUSH, THIN, BATCH, false>(a, PrepArgs{}, CosmicArgs{});
+  __shared__ int tile[kLaneTile];
+  lane_body<FLUSH, THIN, BATCH, false>(a, PrepArgs{}, CosmicArgs{}, tile, blockIdx.y);
 }
 // (two workgroups per CU: 128 VGPRs)
 template <int FLUSH>
 __global__ __launch_bounds__(kLaneThreads) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_lane_fused(ThrowArgs a, PrepArgs p, CosmicArgs ca) {
-  lane_body<FLUSH, true, true, true>(a, p, ca);
+  __shared__ int tile[kLaneTile];
+  lane_body<FLUSH, true, true, true>(a, p, ca, tile, blockIdx.y);
+}
+
+// ---------------------------------------------------------------------------
+// k_thrower : k_lane<FLUSH, false, false> and k_narrow<FLUSH, true, true> in ONE grid
+// ---------------------------------------------------------------------------
+// The two kernels depend on k_prep_sub alone, not on each other (both only add into the accumulators), and share their
+// decomposition: one workgroup of 512 lanes per (sub-sample, chunk of 512 bins).  Launched one after the other, each
+// pays its own fill, prologue of dependent loads and drain -- the last workgroups of k_lane run on a nearly empty chip
+// while k_narrow waits behind the kernel boundary.  Here the grid is (K, lane_chunks + narrow chunks): a workgroup with
+// blockIdx.y < lane_chunks is k_lane's of rank blockIdx.y (lane_order), any other is k_narrow's of rank
+// blockIdx.y - lane_chunks (chunk_order).  Lane workgroups come first in the grid, so that where the hardware hands
+// workgroups out in grid order the narrow ones fill the slots k_lane's drain leaves idle (measured against the narrow
+// ones first: 213.8 against 221.6 us, profiles/three_launches.json) -- a speed hint only: no
+// workgroup waits for, or reads anything of, another, and the frames are the same in any dispatch order (integer adds
+// into the accumulators commute).  The role is uniform over the workgroup, so every barrier of either body stands under
+// a workgroup-uniform condition as before.  Production pair only (one sub-sample per workgroup, no THIN list, fast
+// samplers, compacted chains: knob fuse_thrower); every other combination launches the two kernels.
+// (pinned to 8 waves per SIMD -- four workgroups per CU, what the LDS allows and what either kernel has on its own:
+// left alone the allocator keeps 102 scalar registers live across the two bodies, which is 7)
+template <int FLUSH>
+__global__ __launch_bounds__(kLaneThreads) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_thrower(ThrowArgs a, int lane_chunks) {
+  static_assert(kLaneThreads == kNarrowThreads, "k_thrower: one workgroup shape for both roles");
+  __shared__ int lds[kThrowerLds];
+  if ((int)blockIdx.y < lane_chunks) lane_body<FLUSH, false, false, false>(a, PrepArgs{}, CosmicArgs{}, lds, blockIdx.y);
+  else narrow_body<FLUSH, true, true>(a, lds, blockIdx.y - (unsigned)lane_chunks);
 }
 
 }  // namespace wayne

@@ -5,27 +5,19 @@
 namespace wayne {
 
 // ---------------------------------------------------------------------------
-// k_prep_wl : A8 + the wavelength-only part of A9
+// k_prep_wl : A8 + the wavelength-only part of A9 (at upload, not per run)
 // ---------------------------------------------------------------------------
 // (trace_coeffs: plan_consts.h -- the host's accumulator boxes use the same function)
 
-// (also: thread k computes the trace coefficients of sub-sample k -- six numbers that every workgroup of k_prep_sub
-// needs before it can start; computed there by one thread with the other 511 waiting at a barrier they were ~2 us of
-// serial fp64 latency per workgroup)
-__global__ void k_prep_wl(GrismDev g, int W, const double* __restrict__ wl, WlArrays o, uint32_t* misc, int K,
-                          const double* __restrict__ x_ref, const double* __restrict__ y_ref, double* __restrict__ tr) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  // the exposure's status words (total electrons, overflow flag) start from zero: cleared here, by the
-  // first kernel of the exposure, instead of by a separate fill in front of it (misc = NULL: a contaminant's
-  // k_prep_wl, which runs after the target's)
-  if (misc && i < 16) misc[i] = 0u;
-  if (i < K) {
-    double* t = tr + kTrStride * (size_t)i;
-    trace_coeffs(g, x_ref[i], y_ref[i], t);
-    t[6] = 1. / t[4];     // (for bin_position_bound)
-    t[7] = 0.;
-  }
-  if (i >= W) return;
+// What the kernel writes per wavelength (ratio, sigl, sigh, sens, dlam) depends on the wavelength grid and the grism
+// tables alone -- the same for every exposure of a visit -- so it is NOT part of an exposure's run: k_prep_wl is
+// launched when a source's grid is uploaded and its arrays are kept while the grid and the grism stay what they were
+// (plan::WlCache, host_plan.h).  The other two things an exposure needs in front of k_prep_sub come from the host: the
+// trace coefficients of the K sub-samples (plan::trace_table, the same trace_coeffs in the same arithmetic, shipped
+// with the descriptor's arrays) and a status block that needs no clearing (raise_status below).
+// k_prep_wl_run is the launch as it was, per run (knob prep_wl_per_run; also the run after the grism changed under an
+// uploaded slot): the arrays, the trace coefficients worked out by thread k for sub-sample k, the status block cleared.
+__device__ __forceinline__ void prep_wl_bin(const GrismDev& g, int W, const double* __restrict__ wl, const WlArrays& o, int i) {
   const double x = wl[i];
   o.ratio[i] = poly3(g.p_ratio, x);
   o.sigl[i] = poly3(g.p_sigl, x);
@@ -81,6 +73,23 @@ __global__ void k_prep_wl(GrismDev g, int W, const double* __restrict__ wl, WlAr
   }
   o.dlam[i] = left + right;
 }
+__global__ void k_prep_wl(GrismDev g, int W, const double* __restrict__ wl, WlArrays o) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < W) prep_wl_bin(g, W, wl, o, i);
+}
+__global__ void k_prep_wl_run(GrismDev g, int W, const double* __restrict__ wl, WlArrays o, uint32_t* misc, int K,
+                              const double* __restrict__ x_ref, const double* __restrict__ y_ref, double* __restrict__ tr) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  // (misc = NULL: a contaminant's launch, which runs after the target's)
+  if (misc && i < 16) misc[i] = 0u;
+  if (i < K) {
+    double* t = tr + kTrStride * (size_t)i;
+    trace_coeffs(g, x_ref[i], y_ref[i], t);
+    t[6] = 1. / t[4];     // (for bin_position_bound)
+    t[7] = 0.;
+  }
+  if (i < W) prep_wl_bin(g, W, wl, o, i);
+}
 
 // ---------------------------------------------------------------------------
 // k_prep_sub : one workgroup per sub-sample
@@ -117,12 +126,19 @@ struct PrepArgs {
   double* ypos;              // [K*W]
   SubInfo* sub;              // [K]
   unsigned long long* total_electrons;  // += E_k
-  int* status;               // set non-zero on overflow
+  uint32_t* status;          // two words, raised to `run` by raise_status: [0] overflow, [1] a bin beyond the launch sequence
+  uint32_t run;              // the number of this run of the slot (>= 1, counted by the host)
   uint32_t* chunk_total;     // [K * n_chunks] electrons (for k_throw) per chunk of kPrepThreads bins
   double* chunk_box;         // [K * n_chunks * 4] xmin, xmax, ymin, ymax of the chunk's populated bins
   int fix_inline;            // split mode without a k_throw launch: chunk 0 writes SubInfo, k_prep_fix is not launched
   int no_narrow;             // k_narrow is not launched either (the host expects no bin with split_min narrow electrons)
 };
+
+// The status words of a slot are never cleared on the device: the host numbers the runs of a slot, a kernel raises a
+// flag with atomicMax(word, run number), and the host takes a flag as set when its word EQUALS the number of the run it
+// is looking at -- a word left behind by an earlier run is smaller.  (bit: 1 overflow, 2 beyond the launch sequence --
+// the bits wayne_exposure_status reports)
+__device__ __forceinline__ void raise_status(const PrepArgs& a, int bit) { atomicMax(a.status + (bit >> 1), a.run); }
 
 // The device-side electron count (wayne_profile_get) is kept in kCounterStripes words a cache line apart, a workgroup adding
 // to the stripe of its index: atomics on ONE address complete one after the other (8 ns apiece) and the 1152 workgroups of
@@ -449,11 +465,11 @@ __global__ __launch_bounds__(kPrepThreads) void k_prep_sub(PrepArgs a, CosmicArg
       c = b.rest;                                            // c: electrons left for k_throw
       // launched without k_throw (the host expected no bin beyond a lane's reach) and here is one after all:
       // tell the host, which runs the exposure again with k_throw (wayne_hip.hip, check_status)
-      if (a.fix_inline && c > 0u) atomicOr(a.status, 2);
-      if (a.no_narrow && b.narrow > 0u) atomicOr(a.status, 2);     // ... or without k_narrow, and here is a bin for it
+      if (a.fix_inline && c > 0u) raise_status(a, 2);
+      if (a.no_narrow && b.narrow > 0u) raise_status(a, 2);     // ... or without k_narrow, and here is a bin for it
     }
   }
-  if (overflow) atomicOr(a.status, 1);
+  if (overflow) raise_status(a, 1);
   // electrons handed to k_lane / k_narrow: one atomic per workgroup (DPP row sums per wave -- six rounds of 64-bit
   // shuffles through the LDS crossbar at the end of a wave that has nothing to hide them behind were 1.8 us of the
   // launch --, then LDS)
@@ -489,7 +505,7 @@ __global__ __launch_bounds__(kPrepThreads) void k_prep_sub(PrepArgs a, CosmicArg
       if (i < wave) wave_off += t;
       chunk_total += t;
     }
-    if (chunk_total > 0xFFFFFFFFull) atomicOr(a.status, 1);
+    if (chunk_total > 0xFFFFFFFFull) raise_status(a, 1);
     if (w < W) a.prefix[(size_t)k * (W + 1) + w] = (uint32_t)(wave_off + incl - c);   // chunk-local for now
     if (tid == 0) {
       for (int i = 1; i < NW; ++i) {
@@ -540,7 +556,7 @@ __global__ __launch_bounds__(kPrepThreads) void k_prep_fix(PrepArgs a, int n_chu
   __syncthreads();
   for (int w = tid; w < W; w += kPrepThreads) a.prefix[(size_t)k * (W + 1) + w] += s_off[w / kPrepThreads];
   if (tid == 0) {
-    if (s_over) atomicOr(a.status, 1);
+    if (s_over) raise_status(a, 1);
     double xmin = 1e300, xmax = -1e300, ymin = 1e300, ymax = -1e300;
     for (int i = 0; i < n_chunks; ++i) {
       const size_t ci = (size_t)k * n_chunks + i;

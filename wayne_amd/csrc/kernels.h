@@ -1,7 +1,8 @@
 // HIP kernels (gfx950) of the WFC3-IR exposure-synthesis path, one header per stage:
 //
 //   k_lightcurve.h  k_lightcurve   transit depths depth[K][W] from z[K], rp[W], limb darkening
-//   k_prep.h        k_prep_wl      per-wavelength arrays: PSF polynomials, sensitivity LUT, bin widths   (A8, A9)
+//   k_prep.h        k_prep_wl      per-wavelength arrays: PSF polynomials, sensitivity LUT, bin widths   (A8, A9) -- when a
+//                                  source's grid is uploaded, not per run (k_prep_wl_run: the per-run form, knob prep_wl_per_run)
 //                   k_prep_sub     per sub-sample: trace, bin positions, expected counts, Poisson/round,
 //                                  sigma split, routing of the bins, prefix, electron count and clip rectangle
 //                                  per sub-sample; cosmic-ray hits per read interval          (A6, A7, A9, A10, A13, cosmic_rays.py)
@@ -10,6 +11,7 @@
 //   k_narrow.h      k_narrow       narrow PSF component as one multinomial per bin
 //                   k_lane         a bin's one-by-one electrons (wide component, thin bins) thrown by its own lane
 //                   k_lane_fused   thin exposures: k_lane planning its bins itself (plan_bin of k_prep.h), no k_prep_sub
+//                   k_thrower      k_lane and k_narrow of the production pair as ONE grid (knob fuse_thrower)
 //   k_ramp.h        k_ramp         fused up-the-ramp kernel: sky, gain, cumulative, dark, non-linearity,
 //                                  clip, reference pixels, zero read, read noise                          (A13-A15)
 //   k_extract.h     k_extract_rows / k_extract_finish   opt-in: column spectra per read interval from the reads

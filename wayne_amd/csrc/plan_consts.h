@@ -58,6 +58,8 @@ constexpr unsigned C_FLAT = 1u << 0, C_ALL = C_FLAT;   // wayne_channels_desc.fl
 // optimal extraction (k_extract_optimal; validated by plan::optimal_desc_error)
 constexpr int kOptMaxH = 16;                      // WAYNE_MAX_OPTIMAL_HALF_WIDTH: the halo of a 64-column tile on either side
 
+constexpr int kTrStride = 8;   // doubles per sub-sample in the trace-coefficient array: 6 coefficients, 1 / m_wl, pad
+
 WAYNE_HD void trace_coeffs(const GrismDev& g, double x_ref, double y_ref, double* o) {
   // o = {m_t, c_t, m_w, c_w, m_wl, c_wl}
     // wavelength_calibration_coeffs (grism.py:779-803)

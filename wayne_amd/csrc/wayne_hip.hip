@@ -146,7 +146,8 @@ struct SourceState {
   uint32_t seed = 0;          // visit seed of the source's thrower-side streams (wayne_source_seed)
   DevBuf wl, flux, xref, yref;   // target: views into the slot's `stage`; contaminant: views into src_stage
   DevBuf ratio, sigl, sigh, sens, dlam;
-  DevBuf counts, nwide, nsplit, nlane, prefix, xpos, ypos, sub, chunk_total, chunk_box, tr;
+  DevBuf counts, nwide, nsplit, nlane, prefix, xpos, ypos, sub, chunk_total, chunk_box;
+  DevBuf tr;                  // trace coefficients of the K sub-samples (plan::trace_table): a view into the arena of xref / yref
   int kb = 1;             // sub-samples a workgroup of k_lane takes (k_lane, "BATCHES")
   bool thin = false;      // few electrons per (workgroup, sub-sample): k_lane flushes from its first-touch list
   double max_narrow = 0.;   // host estimate: most narrow electrons expected in a bin of the longest sub-sample
@@ -154,7 +155,8 @@ struct SourceState {
   double est_thrown = 0.;   // host estimate of the electrons k_throw handles in the longest sub-sample
   unsigned char chunk_order[kMaxChunks] = {0};   // chunks of kNarrowThreads bins, most electrons first (ThrowArgs::chunk_order)
   unsigned char lane_order[kMaxChunks] = {0};    // chunks of kLaneThreads bins, most electrons first
-  StageArena src_stage;   // a contaminant's own inputs (wl, flux, offset positions)
+  StageArena src_stage;   // a contaminant's own inputs (wl, flux, offset positions, trace coefficients)
+  plan::WlCache wl_cache;   // what ratio .. dlam on the device were worked out for (k_prep_wl at upload; host_plan.h)
 };
 
 constexpr int kMaxSources = WAYNE_MAX_SOURCES;   // contaminants per exposure
@@ -167,6 +169,11 @@ struct Slot : SourceState {
   bool acc_init = false;
   bool force_throw = false;   // the last run met a bin beyond a lane's reach: run with k_throw (set by look_at_status)
   bool ran = false;           // a whole run was enqueued whose status word nobody has looked at yet (settle)
+  // The runs of the slot are numbered (from 1; counted on by wayne_exposure_run_front): a kernel raises a status word to
+  // the number of its run and nothing clears the block on the device (k_prep.h, raise_status).  A copy of the block is
+  // read against the number that was current when the copy was ENQUEUED: run_no for a read that waits for the stream,
+  // pinned_run / ex_pinned_run for the copies fetch_async / fetch_spectra_async enqueue.
+  uint32_t run_no = 0, pinned_run = 0, ex_pinned_run = 0;
   wayne_exposure_desc d{};  // host copy (pointers are NOT valid after upload)
   int K = 0, R = 0;
   bool has_depth = false, has_replay_seed = false, has_lc = false, has_lc_hidden = false;
@@ -175,12 +182,18 @@ struct Slot : SourceState {
   SourceState extra[kMaxSources];
   uint32_t extra_tag[kMaxSources] = {0};
   SourceState& source(int i) { return i == 0 ? *this : extra[i - 1]; }
-  DevBuf acc, out, misc;  // misc: [0] total electrons (u64), [1] status (int)
+  DevBuf acc, out, misc;  // misc: the slot's status block (Misc)
   DevBuf seg;             // cosmic-ray segments (CosmicArgs::seg): zeroed when allocated, k_ramp clears what it reads
   bool use_box = false;   // acc_box is valid: k_ramp loads the accumulators of a read only inside it (and where `seg` says)
   int acc_box[16][4] = {{0}};
   PinnedBuf pinned;       // pinned host copy of `out` (fetch_async / wait), followed by a copy of `misc`
-  struct Misc { unsigned long long electrons; int status; int pad; };   // the layout of `misc`, declared here only
+  // the layout of `misc`, declared here only: [8] the last run that overflowed, [12] the last run that met a bin beyond
+  // its launch sequence (PrepArgs::status points at these two; the first word is spare)
+  struct Misc {
+    unsigned long long spare;
+    uint32_t over_run, beyond_run;
+    int bits(uint32_t run) const { return (run && over_run == run ? 1 : 0) | (run && beyond_run == run ? 2 : 0); }   // as wayne_exposure_status reports them
+  };
   Misc* pinned_misc = nullptr;   // inside `pinned`: a copy into pageable memory would block the caller
   // sky alias tables of this exposure (k_ramp): their arena, the view of the device copy, the lam_max they were built for
   StageArena sky_stage;
@@ -301,6 +314,8 @@ struct Knobs {
   long long streams = -1;        // 1: every slot on one stream
   long long upload_timing = -1;  // 1: wayne_ctx_destroy prints the host time of wayne_exposure_upload by part
   long long narrow_compact = -1; // 0: k_narrow's pooled row chains stay on their groups' lanes (default: compacted across the workgroup)
+  long long prep_wl_per_run = -1; // 1: k_prep_wl_run in front of every run (arrays, trace coefficients, status clear), as before the upload-time cache
+  long long fuse_thrower = -1;   // 0: k_lane and k_narrow of the production pair as two launches (default: one grid, k_thrower)
   long long lane_tight_tile = -1; // 0: k_lane sizes its test-free tiles for the refined radius, 6.9 sigma (default: kLaneR16, the 16-bit radius)
   long long ramp_reads = -1;     // TIMING BUILDS (-DWAYNE_TIMING_KNOBS) only: k_ramp works through the first n reads
 };
@@ -314,8 +329,10 @@ const KnobName kKnobNames[] = {
     {"upload_timing", "WAYNE_UPLOAD_TIMING", &Knobs::upload_timing}, {"ramp_reads", "WAYNE_RAMP_READS", &Knobs::ramp_reads},
     {"narrow_compact", "WAYNE_NARROW_COMPACT", &Knobs::narrow_compact},
     {"lane_tight_tile", "WAYNE_LANE_TIGHT_TILE", &Knobs::lane_tight_tile},
+    {"fuse_thrower", "WAYNE_FUSE_THROWER", &Knobs::fuse_thrower},
+    {"prep_wl_per_run", "WAYNE_PREP_WL_PER_RUN", &Knobs::prep_wl_per_run},
 };
-constexpr size_t kMiscBytes = 64;   // status block of a slot: [0] electrons (u64), [8] status (int); k_prep_wl clears all of it
+constexpr size_t kMiscBytes = 64;   // status block of a slot (Slot::Misc), zeroed when the context is created
 
 constexpr size_t kCounterBytes = (size_t)kCounterStripes * kCounterStride * sizeof(unsigned long long);
 
@@ -354,6 +371,7 @@ struct wayne_ctx : CtxStreams {
   std::string err;
   // grism
   bool have_grism = false;
+  unsigned long long grism_gen = 1;      // counts wayne_ctx_set_grism / wayne_ctx_set_calibration: what a source's per-wavelength arrays were worked out under (plan::WlCache)
   GrismDev g{};
   DevBuf sens_wl, sens_val;
   // what the upload keeps per spectrum (host_plan.h): per-bin count rates through this grism's sensitivity, the wide
@@ -411,7 +429,6 @@ int reserve_source(wayne_ctx* c, SourceState& ss, int K, int W) {
   HIP_TRY(c, ss.xpos.reserve(KW * sizeof(double)));
   HIP_TRY(c, ss.ypos.reserve(KW * sizeof(double)));
   HIP_TRY(c, ss.sub.reserve((size_t)K * sizeof(SubInfo)));
-  HIP_TRY(c, ss.tr.reserve((size_t)K * kTrStride * sizeof(double)));
   HIP_TRY(c, ss.chunk_total.reserve(K * n_chunks * sizeof(uint32_t)));
   HIP_TRY(c, ss.chunk_box.reserve(K * n_chunks * 4 * sizeof(double)));
   return WAYNE_OK;
@@ -506,6 +523,22 @@ using plan::build_sky_alias;
 template <class T>
 int upload_staged(wayne_ctx* c, Slot& s, DevBuf& b, const T* src, size_t n) {
   if (!s.stage.put(b, src, n * sizeof(T))) return fail(c, WAYNE_E_NOMEM, "upload: staging arena too small");
+  return WAYNE_OK;
+}
+
+// The per-wavelength arrays of a source whose grid `wl_um` (W doubles, already on its way into ss.wl on the slot's stream)
+// has just been uploaded: kept if they are the ones of this grid under this grism (plan::WlCache), else worked out now,
+// on the slot's stream -- no run of the slot launches k_prep_wl.
+int prepare_wl_arrays(wayne_ctx* c, SourceState& ss, int W, const double* wl_um) {
+  if (ss.wl_cache.holds(W, wl_um, c->grism_gen)) return WAYNE_OK;
+  ss.wl_cache.drop();
+  WlArrays wa{ss.ratio.as<double>(), ss.sigl.as<double>(), ss.sigh.as<double>(), ss.sens.as<double>(), ss.dlam.as<double>()};
+  {
+    ProfScope ps(c, PK_PREP_WL);
+    hipLaunchKernelGGL(k_prep_wl, dim3((W + 255) / 256), dim3(256), 0, c->stream, c->g, W, ss.wl.as<double>(), wa);
+    HIP_TRY(c, hipGetLastError());
+  }
+  ss.wl_cache.adopt(W, wl_um, c->grism_gen);
   return WAYNE_OK;
 }
 
@@ -629,6 +662,21 @@ int launch_lane(wayne_ctx* c, const ThrowArgs& a, bool thin, const PrepArgs* fus
   return WAYNE_OK;
 }
 
+
+// k_lane<FLUSH, false, false> and k_narrow<FLUSH, true, true> of one source as ONE grid (k_thrower): used when both
+// kernels would be launched on the same stream in their production form -- one sub-sample per workgroup, no THIN list,
+// fast samplers, compacted chains -- and knob fuse_thrower is not 0.  Any other combination launches the two kernels.
+bool fuse_thrower(const wayne_ctx* c, const ThrowArgs& a, bool thin, bool exact) {
+  return c->knobs.fuse_thrower != 0 && a.kb == 1 && !thin && !exact && c->knobs.narrow_compact != 0;
+}
+template <int FLUSH>
+int launch_thrower(wayne_ctx* c, const ThrowArgs& a) {
+  const int lane_chunks = (a.W + kLaneThreads - 1) / kLaneThreads, narrow_chunks = (a.W + kNarrowThreads - 1) / kNarrowThreads;
+  const dim3 grid((unsigned)a.K, (unsigned)(lane_chunks + narrow_chunks));
+  hipLaunchKernelGGL((k_thrower<FLUSH>), grid, dim3(kLaneThreads), 0, c->stream, a, lane_chunks);
+  HIP_TRY(c, hipGetLastError());
+  return WAYNE_OK;
+}
 
 // k_ramp_trap<reads' type, production / exact math, sky sampler, gaussian-noise stage, every switch on>
 typedef void (*RampTrapKernel)(RampArgs, TrapArgs);
@@ -1020,15 +1068,19 @@ static int read_status(wayne_ctx* c, const Slot& s, Slot::Misc* m) {
 // lanes' reach in an exposure launched without k_throw: if the caller names what to run `again` (wayne_exposure_run,
 // or wayne_exposure_run_front between the two halves), that is enqueued, now with k_throw, and *reran set -- the caller
 // then fetches what it needs a second time and looks again, without `again`.  The one place that re-runs an exposure.
+// `run`: the slot's run number when the copy was enqueued (0: the current one -- a read from the device, which waits for
+// the stream, or settle's copy, taken with every stream idle).
 static int look_at_status(wayne_ctx* c, int slot, const Slot::Misc* host_copy, int (*again)(wayne_ctx*, int) = nullptr,
-                          bool* reran = nullptr) {
+                          bool* reran = nullptr, uint32_t run = 0) {
   Slot& s = c->slots[slot];
   Slot::Misc m{};
   if (host_copy) m = *host_copy;
   else if (int rc = read_status(c, s, &m)) return rc;
-  s.ran = false;                           // looked at
-  if (m.status & 1) return fail(c, WAYNE_E_OVERFLOW, "exposure: a sub-sample holds >= 2^32 electrons (or a bin >= 2^31)");
-  if (!(m.status & 2) || !again) return WAYNE_OK;
+  const uint32_t looked = run ? run : s.run_no;
+  if (looked == s.run_no) s.ran = false;   // looked at (a copy that an earlier run left says nothing about the last one: settle still looks)
+  const int status = m.bits(looked);
+  if (status & 1) return fail(c, WAYNE_E_OVERFLOW, "exposure: a sub-sample holds >= 2^32 electrons (or a bin >= 2^31)");
+  if (!(status & 2) || !again) return WAYNE_OK;
   s.force_throw = true;
   c->reruns += 1;
   *reran = true;
@@ -1236,13 +1288,21 @@ int wayne_psf_apply_ex(wayne_ctx* c, const int32_t* counts, int size, const doub
       rc = (rng_mode == WAYNE_RNG_REPLAY) ? launch_throw<0, 0>(c, a, lds_ints) : launch_throw<1, 0>(c, a, lds_ints);
       if (rc) return rc;
     }
-    if (any_lane) {
+    const bool exact = (flags & WAYNE_F_EXACT_SAMPLERS) != 0;
+    if (any_lane && any_split && fuse_thrower(c, a, false, exact)) {
+      // (one grid for both: PK_THROW and PK_LANE span it, PK_NARROW records nothing)
+      ProfScope ps_throw(c, PK_THROW);
       ProfScope ps(c, PK_LANE);
-      if ((rc = launch_lane<0>(c, a, false))) return rc;
-    }
-    if (any_split) {
-      ProfScope ps(c, PK_NARROW);
-      if ((rc = launch_narrow<0>(c, a, (flags & WAYNE_F_EXACT_SAMPLERS) != 0))) return rc;
+      if ((rc = launch_thrower<0>(c, a))) return rc;
+    } else {
+      if (any_lane) {
+        ProfScope ps(c, PK_LANE);
+        if ((rc = launch_lane<0>(c, a, false))) return rc;
+      }
+      if (any_split) {
+        ProfScope ps(c, PK_NARROW);
+        if ((rc = launch_narrow<0>(c, a, exact))) return rc;
+      }
     }
     c->electrons += (uint64_t)total;
   }
@@ -1281,6 +1341,7 @@ int wayne_ctx_set_grism(wayne_ctx* c, const wayne_grism_desc* g) {
   d.sens_wl = c->sens_wl.as<double>();
   d.sens_val = c->sens_val.as<double>();
   c->have_grism = true;
+  c->grism_gen += 1;       // per-wavelength arrays worked out under the previous grism serve no later upload (plan::WlCache)
   // (... which also forgets what the upload kept per spectrum: it was worked out with the previous grism)
   c->est.set_grism(d, g->sens_wl_um, g->sens_val, g->n_sens);
   for (plan::SpectrumEstimate& e : c->src_est) e.set_grism(d, g->sens_wl_um, g->sens_val, g->n_sens);
@@ -1344,6 +1405,7 @@ int wayne_ctx_set_calibration(wayne_ctx* c, const wayne_calibration* k) {
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   c->subarray = sub; c->N = N; c->S = S; c->cal_R = k->n_reads;
   c->have_cal = true;
+  c->grism_gen += 1;       // (every slot is uploaded afresh: so are its per-wavelength arrays)
   for (Slot& s : c->slots) { s.uploaded = false; s.acc_init = false; }
   return WAYNE_OK;
 }
@@ -1400,7 +1462,8 @@ int wayne_exposure_upload(wayne_ctx* c, int slot, const wayne_exposure_desc* d) 
   const size_t KW = (size_t)K * W;
   {
     // staging arena: every array of the descriptor, 64-byte aligned
-    size_t need = 2 * align64((size_t)W * 8) + 3 * align64((size_t)K * 8) + 2 * align64((size_t)K * 4) + align64((size_t)R * 8) + 1024;
+    size_t need = 2 * align64((size_t)W * 8) + 3 * align64((size_t)K * 8) + 2 * align64((size_t)K * 4) + align64((size_t)R * 8) +
+                  align64((size_t)K * kTrStride * 8) + 1024;
     if (d->lc_z) need += 2 * align64((size_t)K * 8) + align64((size_t)W * 8);
     if (d->depth) need += align64(KW * 8);
     // (waits if the previous upload of this slot is still reading the arena)
@@ -1425,6 +1488,12 @@ int wayne_exposure_upload(wayne_ctx* c, int slot, const wayne_exposure_desc* d) 
   if ((rc = upload_staged(c, s, s.xref, d->x_ref, (size_t)K))) return rc;
   if ((rc = upload_staged(c, s, s.yref, d->y_ref, (size_t)K))) return rc;
   if ((rc = upload_staged(c, s, s.dur, d->dur_ms, (size_t)K))) return rc;
+  {
+    // the trace coefficients of the K sub-samples, worked out here (they were k_prep_wl's, per run)
+    double* tr = (double*)s.stage.place(s.tr, (size_t)K * kTrStride * sizeof(double));
+    if (!tr) return fail(c, WAYNE_E_NOMEM, "upload: staging arena too small");
+    plan::trace_table(c->g, K, d->x_ref, d->y_ref, tr);
+  }
   s.has_replay_seed = d->replay_seed != nullptr;
   if (s.has_replay_seed && (rc = upload_staged(c, s, s.rseed, d->replay_seed, (size_t)K))) return rc;
   if ((rc = upload_staged(c, s, s.sread, d->sample_read, (size_t)K))) return rc;
@@ -1433,6 +1502,7 @@ int wayne_exposure_upload(wayne_ctx* c, int slot, const wayne_exposure_desc* d) 
   if ((size_t)(W + kPrepThreads - 1) / kPrepThreads > (size_t)kMaxPrepChunks || W > 32768)
     return fail(c, WAYNE_E_INVALID, "upload: more than 32768 wavelength bins");
   if ((rc = reserve_source(c, s, K, W))) return rc;
+  if ((rc = prepare_wl_arrays(c, s, W, d->wl_um))) return rc;
   s.misc.view((char*)c->status_all.p + (size_t)slot * kMiscBytes);
   s.ran = false;
   const size_t SS = (size_t)c->S * c->S;
@@ -1488,12 +1558,17 @@ static int front_source(wayne_ctx* c, int slot, Slot& s, SourceState& ss, int sr
   const int W = ss.W, K = s.K, R = s.R, N = c->N, S = c->S;
   WlArrays wa{ss.ratio.as<double>(), ss.sigl.as<double>(), ss.sigh.as<double>(), ss.sens.as<double>(),
               ss.dlam.as<double>()};
-  {
+  // Nothing runs in front of k_prep_sub: the per-wavelength arrays are the upload's (prepare_wl_arrays), the trace
+  // coefficients came with the descriptor's arrays and the status block needs no clearing.  The launch as it was, per
+  // run: knob prep_wl_per_run -- and the run after the grism changed under an uploaded slot, whose arrays and
+  // coefficients are the old grism's (from then on they are this grism's, for the same grid).
+  if (c->knobs.prep_wl_per_run > 0 || ss.wl_cache.gen != c->grism_gen) {
     ProfScope ps(c, PK_PREP_WL);
-    hipLaunchKernelGGL(k_prep_wl, dim3((std::max(W, K) + 255) / 256), dim3(256), 0, c->stream, c->g, W,
+    hipLaunchKernelGGL(k_prep_wl_run, dim3((std::max(W, K) + 255) / 256), dim3(256), 0, c->stream, c->g, W,
                        ss.wl.as<double>(), wa, src == 0 ? s.misc.as<uint32_t>() : nullptr, K, ss.xref.as<double>(), ss.yref.as<double>(),
                        ss.tr.as<double>());
     HIP_TRY(c, hipGetLastError());
+    if (ss.wl_cache.valid) ss.wl_cache.gen = c->grism_gen;
   }
   // margin of a thrower workgroup's tile around its slice of the trace: 5 sigma_h, so that practically no electron
   // takes the in-loop global-atomic path (see k_lane)
@@ -1536,7 +1611,8 @@ static int front_source(wayne_ctx* c, int slot, Slot& s, SourceState& ss, int sr
     a.prefix = ss.prefix.as<uint32_t>(); a.xpos = ss.xpos.as<double>(); a.ypos = ss.ypos.as<double>();
     a.sub = ss.sub.as<SubInfo>();
     a.total_electrons = c->counters.as<unsigned long long>();
-    a.status = (int*)(s.misc.as<char>() + 8);
+    a.status = (uint32_t*)(s.misc.as<char>() + 8);
+    a.run = s.run_no;
     const int n_chunks = (W + kPrepThreads - 1) / kPrepThreads;
     a.chunk_total = ss.chunk_total.as<uint32_t>();
     a.chunk_box = ss.chunk_box.as<double>();
@@ -1622,6 +1698,9 @@ static int front_source(wayne_ctx* c, int slot, Slot& s, SourceState& ss, int sr
     if ((d.flags & WAYNE_F_ADD_FLAT) && !c->has_flat) return fail(c, WAYNE_E_STATE, "run: add_flat without a flat cube");
     const int si_ = slot % c->n_streams;
     const bool fork = d.rng_mode == WAYNE_RNG_SPLIT && c->fork_narrow && !skip_narrow;
+    // k_lane and k_narrow as one grid (k_thrower): both would follow each other on this stream in their production form
+    const bool one_grid = d.rng_mode == WAYNE_RNG_SPLIT && !skip_narrow && !fork && !fused &&
+                          fuse_thrower(c, a, ss.thin, (d.flags & WAYNE_F_EXACT_SAMPLERS) != 0);
     hipStream_t main_stream = c->stream;
     {
       // (with the fork, the PK_THROW interval spans all thrower kernels; PK_NARROW / PK_LANE are those kernels' own)
@@ -1644,12 +1723,14 @@ static int front_source(wayne_ctx* c, int slot, Slot& s, SourceState& ss, int sr
                : (d.rng_mode == WAYNE_RNG_REPLAY) ? launch_throw<0, 1>(c, a, lds_ints) : launch_throw<1, 1>(c, a, lds_ints);
       if (rc) return rc;
       if (d.rng_mode == WAYNE_RNG_SPLIT) {
+        // (one grid: the PK_THROW and PK_LANE intervals span the combined launch, PK_NARROW records nothing)
         ProfScope ps(c, PK_LANE);
-        if ((rc = fused ? launch_lane<1>(c, a, true, &prep_args, &cosmic_args) : launch_lane<1>(c, a, ss.thin))) return rc;
+        if ((rc = one_grid ? launch_thrower<1>(c, a)
+                  : fused  ? launch_lane<1>(c, a, true, &prep_args, &cosmic_args) : launch_lane<1>(c, a, ss.thin))) return rc;
       }
       if (fork) HIP_TRY(c, hipStreamWaitEvent(main_stream, c->ev_join[si_], 0));
     }
-    if (!fork && d.rng_mode == WAYNE_RNG_SPLIT && !skip_narrow) {
+    if (!fork && !one_grid && d.rng_mode == WAYNE_RNG_SPLIT && !skip_narrow) {
       ProfScope ps(c, PK_NARROW);
       int rc = launch_narrow<1>(c, a, (d.flags & WAYNE_F_EXACT_SAMPLERS) != 0);
       if (rc) return rc;
@@ -1707,6 +1788,12 @@ int wayne_exposure_run_front(wayne_ctx* c, int slot) {
     HIP_TRY(c, hipGetLastError());
   }
 
+  // the number of this run (Slot::run_no); after 2^32 - 1 runs the block is cleared once, on the stream, and the count starts over
+  if (s.run_no == 0xFFFFFFFFu) {
+    HIP_TRY(c, hipMemsetAsync(s.misc.p, 0, kMiscBytes, c->stream));
+    s.run_no = 0;
+  }
+  s.run_no += 1;
   for (int i = 0; i <= s.n_extra; ++i) {
     int rc = front_source(c, slot, s, s.source(i), i);
     if (rc) return rc;
@@ -1832,7 +1919,7 @@ int wayne_exposure_status(wayne_ctx* c, int slot, int* status) {
   Slot::Misc m{};
   int rc = read_status(c, s, &m);
   if (rc) return rc;
-  *status = m.status;
+  *status = m.bits(s.run_no);
   return WAYNE_OK;
 }
 
@@ -1887,6 +1974,7 @@ int wayne_exposure_fetch_async(wayne_ctx* c, int slot) {
   }
   HIP_TRY(c, hipMemcpyAsync(s.pinned.p, s.out.p, bytes, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipMemcpyAsync(s.pinned_misc, s.misc.p, sizeof(Slot::Misc), hipMemcpyDeviceToHost, c->stream));
+  s.pinned_run = s.run_no;
   return WAYNE_OK;
 }
 
@@ -1900,13 +1988,13 @@ int wayne_exposure_wait(wayne_ctx* c, int slot, void** host_reads) {
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   *host_reads = s.pinned.p;
   bool reran = false;                        // (the status word came with the reads)
-  int rc = look_at_status(c, slot, s.pinned_misc, wayne_exposure_run, &reran);
+  int rc = look_at_status(c, slot, s.pinned_misc, wayne_exposure_run, &reran, s.pinned_run);
   if (rc || !reran) return rc;
   if ((rc = wayne_exposure_fetch_async(c, slot))) return rc;     // a bin beyond the lanes' reach: once more, with k_throw
   // (spectra fetched beside the reads are those of the first run: fetched again too, with the second run's status word)
   if (s.extract_on && s.ex_pinned_misc && (rc = wayne_exposure_fetch_spectra_async(c, slot))) return rc;
   HIP_TRY(c, hipStreamSynchronize(c->stream));
-  return look_at_status(c, slot, s.pinned_misc);
+  return look_at_status(c, slot, s.pinned_misc, nullptr, nullptr, s.pinned_run);
 }
 
 void* wayne_exposure_device_reads(wayne_ctx* c, int slot) {
@@ -2054,15 +2142,19 @@ int wayne_exposure_set_sources(wayne_ctx* c, int slot, const wayne_source_desc* 
     SourceState& e = s.extra[i];
     const int W = q.n_wl;
     StageArena& st = e.src_stage;
-    int rc = st.begin(c, 2 * align64((size_t)W * 8) + 2 * align64((size_t)K * 8) + 256, "set_sources: pinned staging allocation failed");
+    int rc = st.begin(c, 2 * align64((size_t)W * 8) + 2 * align64((size_t)K * 8) + align64((size_t)K * kTrStride * 8) + 256,
+                      "set_sources: pinned staging allocation failed");
     if (rc) return rc;
     const bool fits = st.put(e.wl, q.wl_um, (size_t)W * 8) && st.put(e.flux, q.flux, (size_t)W * 8);
     double* xs = (double*)st.place(e.xref, (size_t)K * 8);
     double* ys = (double*)st.place(e.yref, (size_t)K * 8);
-    if (!fits || !xs || !ys) return fail(c, WAYNE_E_NOMEM, "set_sources: staging arena too small");
+    double* tr = (double*)st.place(e.tr, (size_t)K * kTrStride * sizeof(double));
+    if (!fits || !xs || !ys || !tr) return fail(c, WAYNE_E_NOMEM, "set_sources: staging arena too small");
     for (int k = 0; k < K; ++k) { xs[k] = x0[k] + q.dx; ys[k] = y0[k] + q.dy; }
+    plan::trace_table(c->g, K, xs, ys, tr);
     if ((rc = st.commit(c, c->stream))) return rc;
     if ((rc = reserve_source(c, e, K, W))) return rc;
+    if ((rc = prepare_wl_arrays(c, e, W, q.wl_um))) return rc;
     e.W = W;
     e.seed = wayne_source_seed(s.d.seed, q.tag);
     e.fused_last = false;
@@ -2321,6 +2413,7 @@ int wayne_exposure_fetch_spectra_async(wayne_ctx* c, int slot) {
   // (120 KB behind the slot's kernels on its own stream: nothing here for the other stream to keep out of phase with)
   HIP_TRY(c, hipMemcpyAsync(s.ex_pinned.p, s.ex_out.p, bytes, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipMemcpyAsync(s.ex_pinned_misc, s.misc.p, sizeof(Slot::Misc), hipMemcpyDeviceToHost, c->stream));
+  s.ex_pinned_run = s.run_no;
   return WAYNE_OK;
 }
 
@@ -2341,11 +2434,11 @@ int wayne_exposure_wait_spectra(wayne_ctx* c, int slot, double** spectra, double
   s.var_res = s.var_on ? (const double*)(s.ex_pinned.p + variance_offset(c, s)) : nullptr;
   s.opt_res = s.opt_on ? (const double*)(s.ex_pinned.p + optimal_offset(c, s)) : nullptr;
   bool reran = false;                        // (the status word came with the spectra)
-  int rc = look_at_status(c, slot, s.ex_pinned_misc, wayne_exposure_run, &reran);
+  int rc = look_at_status(c, slot, s.ex_pinned_misc, wayne_exposure_run, &reran, s.ex_pinned_run);
   if (rc || !reran) return rc;
   if ((rc = wayne_exposure_fetch_spectra_async(c, slot))) return rc;     // a bin beyond the lanes' reach: once more, with k_throw
   HIP_TRY(c, hipStreamSynchronize(c->stream));
-  return look_at_status(c, slot, s.ex_pinned_misc);
+  return look_at_status(c, slot, s.ex_pinned_misc, nullptr, nullptr, s.ex_pinned_run);
 }
 
 int wayne_exposure_download_spectra(wayne_ctx* c, int slot, double* spectra, double* sky) {
