@@ -371,6 +371,52 @@ typedef struct wayne_trap_desc {
  * not uploaded.  The back half then launches k_ramp_trap<...> (wayne_exposure_ramp_variant names it). */
 int wayne_exposure_set_traps(wayne_ctx *ctx, int slot, const wayne_trap_desc *t);
 
+/* ---- a carried trap history: each pixel's trap state from exposure to exposure ----
+ * (opt-in; without these calls every launch and every byte stay as they are.  Added within WAYNE_ABI_VERSION 7: new
+ * symbols and a new struct only.)
+ *
+ * A context owns one trap state: [S*S][2] float32 in bordered coordinates, [pixel][0] slow and [pixel][1] fast.  A slot
+ * with traps AND a history descriptor does not look at its start table: for every light-sensitive pixel and population p
+ *     E_p <- state[pixel][p]
+ *     E_p <- the exact step of E_p over gap_s seconds at rate (lit ? f_bar : 0)      (gap_s = 0 leaves E_p as it is)
+ *     E_p <- min(E_p + fill[p], N_p)
+ *     ... the read intervals as wayne_exposure_set_traps describes them, E_p(zero read) = the value above ...
+ *     state[pixel][p] <- E_p after the last read, rounded to float32
+ * (f_bar: the pixel's mean rate of THIS exposure, as above; float32 arithmetic in the production chain, float64 in the
+ * others).  Reference pixels are neither read nor written.  The back half launches k_ramp_hist<...> with
+ * k_ramp_trap's template list (wayne_exposure_ramp_variant names it).  The state belongs to the back half:
+ * wayne_exposure_run_front does not touch it.
+ *
+ * Order: exposures run in the order of their wayne_exposure_run / _run_back calls, whatever their slots -- each
+ * k_ramp_hist waits for the one enqueued before it (an event between the two streams); the front kernels of an exposure
+ * still overlap the previous exposure.
+ * Every run advances the state: wayne_exposure_run twice on such a slot steps the traps through the exposure twice.  For
+ * the same reason the library never runs such an exposure a second time by itself: its slot is launched with the general
+ * kernel sequence from the start (as a slot whose first run met a bin beyond the lanes' reach is on its second), so
+ * status bit 1 is never raised.  The cost is the k_throw launch that finds nothing to do (~8 us) on configurations that
+ * otherwise go without it.
+ */
+typedef struct wayne_trap_history_desc {
+  double gap_s;            /* seconds since the previous exposure's last read, finite and >= 0 */
+  int lit;                 /* != 0: the pixel collected at f_bar during the gap (staring); 0: a dark gap (a scan, an orbit's gap) */
+  double fill[2];          /* added after the gap, in [0, n_traps[p]] (an orbit's start); the sum is clipped to n_traps[p] */
+} wayne_trap_history_desc;
+
+/* The trap state.  reset: every pixel := (initial[0], initial[1]), finite and >= 0 (allocated on first use).  upload /
+ * download: the whole state, [S*S*2] float32.  Rare calls: each brings every stream to rest before and after.
+ * WAYNE_E_STATE without calibration (S is not known), and for download before any reset or upload.  A calibration of
+ * another frame size discards the state. */
+int wayne_ctx_trap_state_reset(wayne_ctx *ctx, const double initial[2]);
+int wayne_ctx_trap_state_upload(wayne_ctx *ctx, const float *state);
+int wayne_ctx_trap_state_download(wayne_ctx *ctx, float *state);
+
+/* After wayne_exposure_set_traps, before run: the slot's exposure carries the state (h = NULL clears; upload and
+ * set_traps clear too).  WAYNE_E_INVALID (the slot stays usable, without a history: a plain k_ramp_trap exposure) on a
+ * non-finite or negative gap or a fill outside [0, n_traps]; WAYNE_E_STATE without traps on the slot, before any
+ * wayne_ctx_trap_state_reset / _upload, or between wayne_exposure_run_front and _run_back (the front half chooses the
+ * launch sequence). */
+int wayne_exposure_set_trap_history(wayne_ctx *ctx, int slot, const wayne_trap_history_desc *h);
+
 /* ---- device-side spectral extraction (no reference counterpart) ---------- */
 
 /*

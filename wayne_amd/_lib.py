@@ -94,6 +94,10 @@ class TrapDesc(C.Structure):
                 ("n_rate", C.c_int), ("rate_lo", C.c_double), ("rate_hi", C.c_double), ("start", _dp * 2)]
 
 
+class TrapHistoryDesc(C.Structure):
+    _fields_ = [("gap_s", C.c_double), ("lit", C.c_int), ("fill", C.c_double * 2)]
+
+
 class ExtractDesc(C.Structure):
     _fields_ = [("steps", C.c_uint32), ("row_lo", C.c_int * EXTRACT_PRODUCTS), ("row_hi", C.c_int * EXTRACT_PRODUCTS),
                 ("bg_col_lo", C.c_int), ("bg_col_hi", C.c_int)]
@@ -160,6 +164,10 @@ SYMBOLS = {
     "wayne_exposure_set_sources": (C.c_int, [_vp, C.c_int, C.POINTER(SourceDesc), C.c_int]),
     "wayne_source_seed": (C.c_uint32, [C.c_uint32, C.c_uint32]),
     "wayne_exposure_set_traps": (C.c_int, [_vp, C.c_int, C.POINTER(TrapDesc)]),
+    "wayne_ctx_trap_state_reset": (C.c_int, [_vp, _dp]),
+    "wayne_ctx_trap_state_upload": (C.c_int, [_vp, _vp]),
+    "wayne_ctx_trap_state_download": (C.c_int, [_vp, _vp]),
+    "wayne_exposure_set_trap_history": (C.c_int, [_vp, C.c_int, C.POINTER(TrapHistoryDesc)]),
     "wayne_exposure_debug_fetch_source": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp]),
     "wayne_exposure_set_extraction": (C.c_int, [_vp, C.c_int, C.POINTER(ExtractDesc)]),
     "wayne_exposure_fetch_spectra_async": (C.c_int, [_vp, C.c_int]),
@@ -426,7 +434,7 @@ class Context(object):
 
     def upload(self, slot, desc):
         """Stage the descriptor in `slot`; contaminants and charge traps it carries (make_desc(sources=..., traps=...))
-        are set with it."""
+        are set with it, and with traps.CarriedTraps their history (set_trap_history)."""
         self.check(self._L.wayne_exposure_upload(self._h, int(slot), C.byref(desc)))
         self._slot_meta[slot] = (desc.n_samples, desc.n_wl, desc.n_reads, out_dtype_of(desc.flags))
         self._slot_src[slot] = ()
@@ -442,6 +450,8 @@ class Context(object):
         traps = getattr(desc, "_traps", None)
         if traps is not None:
             self.set_traps(slot, traps)
+            if getattr(traps, "gap_s", None) is not None:      # traps.CarriedTraps: the history rides with the traps
+                self.set_trap_history(slot, traps)
         extraction = getattr(desc, "_extraction", None)
         if extraction is not None:
             self.set_extraction(slot, extraction)
@@ -725,6 +735,40 @@ class Context(object):
         rows = [np.ascontiguousarray(table[0]), np.ascontiguousarray(table[1])]
         t.start[0], t.start[1] = ptr(rows[0], C.c_double), ptr(rows[1], C.c_double)
         self.check(self._L.wayne_exposure_set_traps(self._h, int(slot), C.byref(t)))
+
+    def set_trap_history(self, slot, history):
+        """A carried history of the slot's trapped exposure: an object with gap_s, lit and fill [2] (traps.CarriedTraps) --
+        None clears; after set_traps, which clears it too.  The exposure then starts from the context's trap state and
+        leaves its own behind.  See wayne_exposure_set_trap_history."""
+        if history is None:
+            self.check(self._L.wayne_exposure_set_trap_history(self._h, int(slot), None))
+            return
+        h = TrapHistoryDesc()
+        h.gap_s, h.lit = float(history.gap_s), int(bool(history.lit))
+        h.fill[:] = [float(v) for v in history.fill]
+        self.check(self._L.wayne_exposure_set_trap_history(self._h, int(slot), C.byref(h)))
+
+    def trap_state_reset(self, initial):
+        """Every pixel of the context's trap state := initial (slow, fast).  See wayne_ctx_trap_state_reset."""
+        v = (C.c_double * 2)(float(initial[0]), float(initial[1]))
+        self.check(self._L.wayne_ctx_trap_state_reset(self._h, v))
+
+    def trap_state_upload(self, state):
+        """The context's trap state from a [S, S, 2] float32 array (bordered coordinates; [..., 0] slow, [..., 1] fast)."""
+        if not getattr(self, "S", 0):
+            raise WayneError(E_STATE, "trap_state_upload: set the calibration first")
+        state = np.ascontiguousarray(state, dtype=np.float32)
+        if state.shape != (self.S, self.S, 2):
+            raise ValueError("trap state: expected shape (%d, %d, 2), got %s" % (self.S, self.S, state.shape))
+        self.check(self._L.wayne_ctx_trap_state_upload(self._h, state.ctypes.data_as(C.c_void_p)))
+
+    def trap_state_download(self):
+        """The context's trap state, [S, S, 2] float32."""
+        if not getattr(self, "S", 0):
+            raise WayneError(E_STATE, "trap_state_download: set the calibration first")
+        out = np.empty((self.S, self.S, 2), dtype=np.float32)
+        self.check(self._L.wayne_ctx_trap_state_download(self._h, out.ctypes.data_as(C.c_void_p)))
+        return out
 
     def set_sources(self, slot, sources):
         """Contaminating field stars of the slot's uploaded exposure: a sequence of objects with tag, wl, flux, dx, dy

@@ -60,6 +60,22 @@ struct TrapArgs {
   float dt[16], inv_dt[16];  // read_dt[r] and 1 / read_dt[r]
 };
 
+// A carried history (wayne_exposure_set_trap_history; k_ramp_hist only): E_p at the zero read is not the table's but the
+// context's trap state, state[pixel] = (slow, fast) in bordered coordinates, as the previous exposure left it -- stepped
+// over the gap since that exposure's last read (at the pixel's mean rate f_bar if the gap is lit, in the dark otherwise),
+// then raised by fill_p and clipped to N_p (an orbit's start; fill = 0 elsewhere).  What the traps hold after the last
+// read is written back.  Reference pixels are neither read nor written.
+struct TrapHistArgs {
+  float2* state;             // [S*S]
+  double gap_s;
+  float gap_f;
+  int lit;
+  double fill[2];
+  float fill_f[2];
+  double n[2];               // capacity N_p
+  float n_f[2];
+};
+
 // 1 - e^{-x} for x >= 0 without the cancellation of 1 - exp(-x) at small x (slow traps at sky rates: x ~ 2e-4 a read).
 // float32: a fifth-order Taylor polynomial below 1/8 (relative error < x^5 / 720 <= 5e-8), the hardware exp above
 // (absolute error ~6e-8, relative <= 5e-7 there).  float64: expm1.
@@ -361,8 +377,12 @@ __device__ __forceinline__ void sky_counts(const RampArgs& a, uint32_t p, int ti
 // compiled in or out: its stream would otherwise hold four registers of a kernel that lives at the 64-VGPR limit
 // TRAP: charge trapping (TrapArgs; k_ramp_trap only): the pixel's mean rate in a pre-pass over its live accumulators,
 // one interpolation of the start table, then per read and population the exact step of the trap occupancy
-template <class OutT, bool FAST, int SKY, bool NOISE, bool ALLON, bool TRAP = false>
-__device__ __forceinline__ void ramp_body(const RampArgs& a, const TrapArgs& tr = TrapArgs{}) {
+// HIST: a carried history (TrapHistArgs; k_ramp_hist only, on top of TRAP): the zero read's occupancy comes from the
+// context's trap state instead of the table, and the occupancy after the last read goes back into it
+template <class OutT, bool FAST, int SKY, bool NOISE, bool ALLON, bool TRAP = false, bool HIST = false>
+__device__ __forceinline__ void ramp_body(const RampArgs& a, const TrapArgs& tr = TrapArgs{},
+                                          const TrapHistArgs& th = TrapHistArgs{}) {
+  static_assert(TRAP || !HIST, "a carried history needs the traps");
   constexpr bool ALIAS = SKY != 0;
   // OutT fixes the store; the arithmetic follows ArithT.  uint16 reads (WAYNE_F_OUT_U16) are the float32 reads of the
   // same instantiation, quantised in st_out: every choice below that float32 reads make, they make
@@ -568,8 +588,13 @@ __device__ __forceinline__ void ramp_body(const RampArgs& a, const TrapArgs& tr 
   // pixels are not trapped (their reads are set to zero below).
   float te_s = 0.f, te_f = 0.f, te_0 = 0.f;              // production chain: slow, fast, their sum at the zero read
   double td_s = 0., td_f = 0.;                           // generic loop
+  // (HIST) the trap state: one 8-byte load and one 8-byte store per light-sensitive pixel, the kernel's buffer addressing
+  const __amdgpu_buffer_rsrc_t rs_state =
+      __builtin_amdgcn_make_buffer_rsrc((void*)th.state, 0, HIST ? (int)(SS * sizeof(float2)) : 0, 0x00020000);
   if constexpr (TRAP) {
     if (interior) {
+      v2u st_bits = {0u, 0u};
+      if constexpr (HIST) st_bits = __builtin_amdgcn_raw_buffer_load_b64(rs_state, off8, 0, 0);   // (in flight over the pre-pass)
       long long qs = 0;
       for (int r = 0; r < a.R; ++r)
         if (acc_live(r)) qs += ld_acc(r);
@@ -577,16 +602,37 @@ __device__ __forceinline__ void ramp_body(const RampArgs& a, const TrapArgs& tr 
       if constexpr (PROD) {
         const float e_acc = fmaf((float)(int)(qs >> 32), 16.0f, (float)(uint32_t)qs * 3.725290298461914e-09f);
         const float fbar = fmaf(sky_px, tr.sum_bg_f, e_acc) * tr.inv_sum_dt_f;
-        te_s = trap_start<float>(tr.start_f, tr, 0, fbar);
-        te_f = trap_start<float>(tr.start_f, tr, 1, fbar);
+        if constexpr (HIST) {
+          const float f_gap = th.lit ? fbar : 0.f;
+          te_s = trap_step<float>(__uint_as_float(st_bits.x), f_gap, th.gap_f, tr.eta_f[0], tr.eta_n_f[0], tr.inv_tau_f[0]);
+          te_f = trap_step<float>(__uint_as_float(st_bits.y), f_gap, th.gap_f, tr.eta_f[1], tr.eta_n_f[1], tr.inv_tau_f[1]);
+          te_s = fminf(te_s + th.fill_f[0], th.n_f[0]);
+          te_f = fminf(te_f + th.fill_f[1], th.n_f[1]);
+        } else {
+          te_s = trap_start<float>(tr.start_f, tr, 0, fbar);
+          te_f = trap_start<float>(tr.start_f, tr, 1, fbar);
+        }
         te_0 = te_s + te_f;
       } else {
         const double fbar = ((double)qs * kInvQ + (double)sky_px * tr.sum_bg) / tr.sum_dt;
-        td_s = trap_start<double>(tr.start_d, tr, 0, fbar);
-        td_f = trap_start<double>(tr.start_d, tr, 1, fbar);
+        if constexpr (HIST) {
+          const double f_gap = th.lit ? fbar : 0.;
+          td_s = trap_step<double>((double)__uint_as_float(st_bits.x), f_gap, th.gap_s, tr.eta[0], tr.eta_n[0], tr.inv_tau[0]);
+          td_f = trap_step<double>((double)__uint_as_float(st_bits.y), f_gap, th.gap_s, tr.eta[1], tr.eta_n[1], tr.inv_tau[1]);
+          td_s = fmin(td_s + th.fill[0], th.n[0]);
+          td_f = fmin(td_f + th.fill[1], th.n[1]);
+        } else {
+          td_s = trap_start<double>(tr.start_d, tr, 0, fbar);
+          td_f = trap_start<double>(tr.start_d, tr, 1, fbar);
+        }
       }
     }
   }
+  // (HIST) what the traps hold after the last read, back into the state
+  auto st_state = [&](float es, float ef) {
+    if (interior)
+      __builtin_amdgcn_raw_buffer_store_b64(v2u{__float_as_uint(es), __float_as_uint(ef)}, rs_state, off8, 0, 0);
+  };
 
   // software-pipelined ramp: the planes of read r+1 are requested before the
   // (VALU-heavy) work on read r so that HBM latency hides behind it.  The dark planes and the reads are
@@ -713,6 +759,7 @@ __device__ __forceinline__ void ramp_body(const RampArgs& a, const TrapArgs& tr 
         if (r + 1 < a.R) step(r + 1, qB, dsB, deB, qA, dsA, deA);
       }
     }
+    if constexpr (HIST) st_state(te_s, te_f);
     return;
   }
   for (int r = 0; r < a.R; ++r) {
@@ -797,6 +844,7 @@ __device__ __forceinline__ void ramp_body(const RampArgs& a, const TrapArgs& tr 
     if (rdn) v = v + kReadNoise * (double)zr;   // add_read_noise (detector.py:193-198)
     st_out(r + 1, (ArithT)v);
   }
+  if constexpr (HIST) st_state((float)td_s, (float)td_f);
 }
 
 // The production-math variants with a table-driven sky fit 64 registers -- 8 waves per SIMD, which is what hides the
@@ -817,6 +865,17 @@ __global__ __launch_bounds__(kRampThreads) void k_ramp_wide(RampArgs a) {
 template <class OutT, bool FAST, int SKY, bool NOISE, bool ALLON>
 __global__ __launch_bounds__(kRampThreads) void k_ramp_trap(RampArgs a, TrapArgs t) {
   ramp_body<OutT, FAST, SKY, NOISE, ALLON, true>(a, t);
+}
+// With charge traps and a carried history (wayne_exposure_set_trap_history): k_ramp_trap's template list again.
+template <class OutT, bool FAST, int SKY, bool NOISE, bool ALLON>
+__global__ __launch_bounds__(kRampThreads) void k_ramp_hist(RampArgs a, TrapArgs t, TrapHistArgs h) {
+  ramp_body<OutT, FAST, SKY, NOISE, ALLON, true, true>(a, t, h);
+}
+
+// Every pixel of the trap state := (initial_s, initial_f) (wayne_ctx_trap_state_reset)
+__global__ __launch_bounds__(256) void k_trap_state_fill(float2* state, int n, float initial_s, float initial_f) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) state[i] = make_float2(initial_s, initial_f);
 }
 
 }  // namespace wayne

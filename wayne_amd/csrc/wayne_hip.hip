@@ -213,6 +213,11 @@ struct Slot : SourceState {
   int trap_G = 0;
   StageArena trap_stage;
   DevBuf trap_d, trap_f;             // views of the float64 / float32 tables
+  // a carried history on top of the traps (wayne_exposure_set_trap_history; cleared by upload and set_traps): the
+  // exposure starts from the context's trap state and leaves its own behind (k_ramp_hist)
+  bool hist_on = false;
+  double hist_gap = 0., hist_fill[2] = {0., 0.};
+  int hist_lit = 0;
   // spectral extraction of this exposure (wayne_exposure_set_extraction; cleared by upload): the plan, the partial sums
   // [2][chunks][R+1][S], the result -- spectra [(R+1)*S] then sky [R+1] -- and its pinned host copy, followed by a
   // copy of `misc` (fetch_spectra_async / wait_spectra)
@@ -351,7 +356,14 @@ struct CtxStreams {
   // then both copy and share the PCIe link: 640 exposures/s -- instead of one copying while the other computes (810).
   hipEvent_t ev_kdone[kStreams] = {nullptr, nullptr};
   bool kdone_valid[kStreams] = {false, false};
+  // Carried trap state (wayne_exposure_set_trap_history): exposures alternate over the streams and each k_ramp_hist reads
+  // the state its predecessor wrote.  One event, recorded behind every k_ramp_hist launch and waited for in front of the
+  // next one: the ramp kernels form a chain, the front kernels (prep, thrower) still overlap the previous exposure.
+  // Created with the state (trap_state_reset / _upload).
+  hipEvent_t ev_trap_chain = nullptr;
+  bool trap_chain_valid = false;
   ~CtxStreams() {
+    if (ev_trap_chain) (void)hipEventDestroy(ev_trap_chain);
     for (int i = 0; i < kStreams; ++i) {
       if (streams[i]) (void)hipStreamDestroy(streams[i]);
       if (side[i]) (void)hipStreamDestroy(side[i]);
@@ -402,6 +414,8 @@ struct wayne_ctx : CtxStreams {
   double prof_ms[kProfKernels] = {0};
   uint64_t electrons = 0;  // thrown through wayne_psf_apply (host-counted)
   uint64_t profile_uploads = 0;   // profiles wayne_exposure_set_optimal_profile copied to the device (not those a slot already held)
+  DevBuf trap_state;       // [S*S][2] float32, (slow, fast) per bordered pixel: what k_ramp_hist carries from exposure to exposure
+  bool trap_state_valid = false;   // reset or uploaded for this calibration's S
   uint64_t reruns = 0;     // exposures run a second time because a bin lay beyond what the first launch sequence handles
   DevBuf counters;         // kCounterStripes u64 words, 128 B apart: electrons thrown by exposures (device-counted,
                            // count_electrons); word [1]: a spare for debug_fetch's own k_prep_sub launch
@@ -693,9 +707,26 @@ RampTrapKernel pick_ramp_trap(int out, bool exact, int sky, bool noise, bool all
                   : (exact ? trap_sky<float, false>(sky, noise) : trap_sky<float, true>(sky, noise));
 }
 
+// k_ramp_hist<...>: k_ramp_trap's list again, for a slot with a carried history
+typedef void (*RampHistKernel)(RampArgs, TrapArgs, TrapHistArgs);
+template <class OutT, bool FAST, int SKY>
+RampHistKernel hist_noise(bool noise) { return noise ? k_ramp_hist<OutT, FAST, SKY, true, false> : k_ramp_hist<OutT, FAST, SKY, false, false>; }
+template <class OutT, bool FAST>
+RampHistKernel hist_sky(int sky, bool noise) {
+  return sky == 1 ? hist_noise<OutT, FAST, 1>(noise) : sky == 2 ? hist_noise<OutT, FAST, 2>(noise) : hist_noise<OutT, FAST, 0>(noise);
+}
+RampHistKernel pick_ramp_hist(int out, bool exact, int sky, bool noise, bool allon) {
+  if (allon) return out == 2 ? k_ramp_hist<uint16_t, true, 1, false, true> : k_ramp_hist<float, true, 1, false, true>;
+  return out == 1 ? (exact ? hist_sky<double, false>(sky, noise) : hist_sky<double, true>(sky, noise))
+       : out == 2 ? (exact ? hist_sky<uint16_t, false>(sky, noise) : hist_sky<uint16_t, true>(sky, noise))
+                  : (exact ? hist_sky<float, false>(sky, noise) : hist_sky<float, true>(sky, noise));
+}
+
 // The k_ramp instantiation the back half of slot `s` launches, and (if asked) its name as the kernel trace prints it.
-// A slot with charge traps launches k_ramp_trap instead: *trap (when given) is then set, else left null.
-void (*select_ramp(const wayne_ctx* c, const Slot& s, std::string* name, RampTrapKernel* trap = nullptr))(RampArgs) {
+// A slot with charge traps launches k_ramp_trap instead: *trap (when given) is then set, else left null; one with a
+// carried history on top of them k_ramp_hist: *hist likewise.
+void (*select_ramp(const wayne_ctx* c, const Slot& s, std::string* name, RampTrapKernel* trap = nullptr,
+                   RampHistKernel* hist = nullptr))(RampArgs) {
   const wayne_exposure_desc& d = s.d;
   const int out = out_kind(d.flags);
   const bool f64 = out == 1, exact = (d.flags & WAYNE_F_EXACT_SAMPLERS) != 0;
@@ -707,13 +738,15 @@ void (*select_ramp(const wayne_ctx* c, const Slot& s, std::string* name, RampTra
   const uint32_t all_on = WAYNE_F_ADD_DARK | WAYNE_F_ADD_NON_LINEAR | WAYNE_F_CLIP_DET_LIMITS | WAYNE_F_ADD_READ_NOISE;
   const bool allon = !f64 && !exact && sky_mode == 1 && !noise && (d.flags & all_on) == all_on && c->has_dark && c->has_lin;
   if (allon) kern = out == 2 ? k_ramp<uint16_t, true, 1, false, true> : k_ramp<float, true, 1, false, true>;
-  if (trap) *trap = s.traps_on ? pick_ramp_trap(out, exact, sky_mode, noise, allon) : nullptr;
+  const bool with_hist = s.traps_on && s.hist_on;
+  if (trap) *trap = s.traps_on && !with_hist ? pick_ramp_trap(out, exact, sky_mode, noise, allon) : nullptr;
+  if (hist) *hist = with_hist ? pick_ramp_hist(out, exact, sky_mode, noise, allon) : nullptr;
   if (name) {
     const bool pinned = !exact && sky_mode != 0 && !noise;      // ramp_kernel(): k_ramp where it fits 64 registers, else k_ramp_wide
     char buf[96];
     if (s.traps_on)
-      std::snprintf(buf, sizeof buf, "k_ramp_trap<%s, %s, %d, %s, %s>", out_name, exact ? "false" : "true",
-                    sky_mode, noise ? "true" : "false", allon ? "true" : "false");
+      std::snprintf(buf, sizeof buf, "%s<%s, %s, %d, %s, %s>", with_hist ? "k_ramp_hist" : "k_ramp_trap", out_name,
+                    exact ? "false" : "true", sky_mode, noise ? "true" : "false", allon ? "true" : "false");
     else
       std::snprintf(buf, sizeof buf, "%s<%s, %s, %d, %s%s>", pinned ? "k_ramp" : "k_ramp_wide", out_name,
                     exact ? "false" : "true", sky_mode, noise ? "true" : "false", pinned ? (allon ? ", true" : ", false") : "");
@@ -1360,6 +1393,7 @@ int wayne_ctx_set_calibration(wayne_ctx* c, const wayne_calibration* k) {
   const int N = side_of(sub), S = N + 2 * kBorder;
   const size_t NN = (size_t)N * N, SS = (size_t)S * S;
   int rc;
+  if (c->have_cal && S != c->S) c->trap_state_valid = false;   // a trap state belongs to its frame size
   c->has_flat = k->flat[0] && k->flat[1] && k->flat[2] && k->flat[3];
   if (c->has_flat)
     for (int i = 0; i < 4; ++i)
@@ -1447,6 +1481,7 @@ int wayne_exposure_upload(wayne_ctx* c, int slot, const wayne_exposure_desc* d) 
   s.fused_last = false;      // (last_prep points into buffers this call may re-allocate)
   s.n_extra = 0;             // a new exposure has no contaminants until wayne_exposure_set_sources says so
   s.traps_on = false;        // ... and no charge traps until wayne_exposure_set_traps says so
+  s.hist_on = false;         // ... nor a carried history (wayne_exposure_set_trap_history)
   s.extract_on = false;      // ... and no spectral extraction until wayne_exposure_set_extraction says so
   s.ex_pinned_misc = nullptr;
   s.crrej_on = false;        // ... whose cosmic-ray rejection waits for wayne_exposure_set_crrej
@@ -1575,6 +1610,10 @@ static int front_source(wayne_ctx* c, int slot, Slot& s, SourceState& ss, int sr
   bool skip_narrow = false;
   bool lane_unlimited = false;   // split mode without a k_throw launch: the lanes take every bin (up to kLaneReach)
   bool fused = false;            // ... and no k_prep_sub either: k_lane<.., FUSED> plans its bins itself
+  // A slot with a carried trap history takes the general sequence from the start, like a slot that is being re-run:
+  // its exposure must never be run a second time (later exposures may have consumed the state it left), so status bit 1
+  // must not be raised.  The cost: the k_throw launch that finds nothing to do.
+  const bool force_throw = s.force_throw || (s.traps_on && s.hist_on);
   const int margin = d.thrower_margin > 0 ? d.thrower_margin : 30;
   PrepArgs prep_args{};
   CosmicArgs cosmic_args{};
@@ -1605,7 +1644,7 @@ static int front_source(wayne_ctx* c, int slot, Slot& s, SourceState& ss, int sr
     // (knob `lane_reach`: a test knob that lowers the lanes' reach so that the re-run path can be exercised)
     int reach = kLaneReach;
     if (c->knobs.lane_reach >= 0) reach = (int)std::min<long long>(std::max<long long>(c->knobs.lane_reach, 1), kLaneReach);
-    lane_unlimited = d.rng_mode == WAYNE_RNG_SPLIT && ss.est_thrown <= 0. && d.thrower_splits <= 0 && !s.force_throw &&
+    lane_unlimited = d.rng_mode == WAYNE_RNG_SPLIT && ss.est_thrown <= 0. && d.thrower_splits <= 0 && !force_throw &&
                      c->knobs.throw_wgs < 0;
     a.lane_max = lane_unlimited ? reach : kLaneMax;
     a.prefix = ss.prefix.as<uint32_t>(); a.xpos = ss.xpos.as<double>(); a.ypos = ss.ypos.as<double>();
@@ -1662,7 +1701,7 @@ static int front_source(wayne_ctx* c, int slot, Slot& s, SourceState& ss, int sr
         splits = (int)std::min(4096., std::ceil(lanes / kThrowThreads));
         // split mode with no bin expected beyond a lane's cap: k_throw finds nothing to do (any stray bin is
         // handled by the one workgroup per sub-sample launched here)
-        if (d.rng_mode == WAYNE_RNG_SPLIT && ss.est_thrown <= 0. && !s.force_throw) splits = -1;
+        if (d.rng_mode == WAYNE_RNG_SPLIT && ss.est_thrown <= 0. && !force_throw) splits = -1;
         // a lane takes several units when the launch would exceed ~24 workgroups per CU: then ~12 per CU
         // (each lane a handful of units) is the measured optimum (scripts/sweep_throw.py)
         const int cap = std::max(1, (3072 + K - 1) / K);
@@ -1846,11 +1885,14 @@ int wayne_exposure_run_back(wayne_ctx* c, int slot) {
   a.seg = s.seg.as<uint32_t>();
   const int threads = kRampThreads;
   const unsigned blocks = (unsigned)(((size_t)S * S + threads - 1) / threads);
+  if (s.traps_on && s.hist_on && (!c->trap_state_valid || !c->ev_trap_chain))
+    return fail(c, WAYNE_E_STATE, "run: a trap history without a trap state (wayne_ctx_trap_state_reset / _upload first)");
   {
     ProfScope ps(c, PK_RAMP, true);
     RampTrapKernel trap = nullptr;
-    void (*kern)(RampArgs) = select_ramp(c, s, nullptr, &trap);
-    if (trap) {
+    RampHistKernel hist = nullptr;
+    void (*kern)(RampArgs) = select_ramp(c, s, nullptr, &trap, &hist);
+    if (trap || hist) {
       // charge traps (wayne_exposure_set_traps): the model, the per-read intervals and the staged start tables
       TrapArgs t{};
       t.G = s.trap_G;
@@ -1873,7 +1915,22 @@ int wayne_exposure_run_back(wayne_ctx* c, int slot) {
       }
       t.inv_sum_dt_f = (float)(1.0 / t.sum_dt);
       t.sum_bg_f = (float)t.sum_bg;
-      if (ps.on) hipExtLaunchKernelGGL(trap, dim3(blocks), dim3(threads), 0, c->stream, ps.rec.a, ps.rec.b, 0, a, t);
+      if (hist) {
+        // a carried history: the state's read-after-write chain over the two streams (CtxStreams::ev_trap_chain)
+        TrapHistArgs h{};
+        h.state = c->trap_state.as<float2>();
+        h.gap_s = s.hist_gap; h.gap_f = (float)s.hist_gap;
+        h.lit = s.hist_lit;
+        for (int p = 0; p < 2; ++p) {
+          h.fill[p] = s.hist_fill[p]; h.fill_f[p] = (float)s.hist_fill[p];
+          h.n[p] = s.trap_n[p]; h.n_f[p] = (float)s.trap_n[p];
+        }
+        if (c->trap_chain_valid) HIP_TRY(c, hipStreamWaitEvent(c->stream, c->ev_trap_chain, 0));
+        if (ps.on) hipExtLaunchKernelGGL(hist, dim3(blocks), dim3(threads), 0, c->stream, ps.rec.a, ps.rec.b, 0, a, t, h);
+        else hipLaunchKernelGGL(hist, dim3(blocks), dim3(threads), 0, c->stream, a, t, h);
+        HIP_TRY(c, hipEventRecord(c->ev_trap_chain, c->stream));
+        c->trap_chain_valid = true;
+      } else if (ps.on) hipExtLaunchKernelGGL(trap, dim3(blocks), dim3(threads), 0, c->stream, ps.rec.a, ps.rec.b, 0, a, t);
       else hipLaunchKernelGGL(trap, dim3(blocks), dim3(threads), 0, c->stream, a, t);
     } else {
       if (ps.on) hipExtLaunchKernelGGL(kern, dim3(blocks), dim3(threads), 0, c->stream, ps.rec.a, ps.rec.b, 0, a);
@@ -2194,6 +2251,7 @@ int wayne_exposure_set_traps(wayne_ctx* c, int slot, const wayne_trap_desc* t) {
   Slot& s = c->slots[slot];
   if (!s.uploaded) return fail(c, WAYNE_E_STATE, "set_traps: slot not uploaded");
   s.traps_on = false;             // from here on a refusal leaves the slot usable, without traps
+  s.hist_on = false;              // (a history belongs to the traps it was set after)
   if (!t) return WAYNE_OK;
   if (s.d.rng_mode == WAYNE_RNG_REPLAY)
     return fail(c, WAYNE_E_INVALID, "set_traps: replay mode reproduces the reference, which has no charge traps");
@@ -2239,6 +2297,81 @@ int wayne_exposure_set_traps(wayne_ctx* c, int slot, const wayne_trap_desc* t) {
   s.trap_hi = t->rate_hi;
   s.trap_G = G;
   s.traps_on = true;
+  return WAYNE_OK;
+}
+
+// The context's trap state.  The three calls below are rare (a visit's start and end): every stream is brought to rest
+// before and after, so no exposure is in flight while the state changes and the chain starts afresh.
+static int trap_state_ready(wayne_ctx* c, const char* who) {
+  if (!c->have_cal) return fail(c, WAYNE_E_STATE, std::string(who) + ": set the calibration first (the frame size is not known)");
+  (void)hipSetDevice(c->device);
+  int rc = sync_all(c);
+  if (rc) return rc;
+  c->stream = c->streams[0];
+  c->trap_chain_valid = false;
+  return WAYNE_OK;
+}
+static int trap_state_alloc(wayne_ctx* c) {
+  if (!c->ev_trap_chain) HIP_TRY(c, hipEventCreateWithFlags(&c->ev_trap_chain, hipEventDisableTiming));
+  c->trap_state_valid = false;
+  HIP_TRY(c, c->trap_state.reserve((size_t)c->S * c->S * sizeof(float2)));
+  return WAYNE_OK;
+}
+
+int wayne_ctx_trap_state_reset(wayne_ctx* c, const double initial[2]) {
+  if (!c || !initial) return WAYNE_E_INVALID;
+  if (!std::isfinite(initial[0]) || !std::isfinite(initial[1]) || initial[0] < 0. || initial[1] < 0.)
+    return fail(c, WAYNE_E_INVALID, "trap_state_reset: the initial occupancies must be finite and >= 0");
+  int rc = trap_state_ready(c, "trap_state_reset");
+  if (rc || (rc = trap_state_alloc(c))) return rc;
+  const int n = c->S * c->S;
+  hipLaunchKernelGGL(k_trap_state_fill, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, c->trap_state.as<float2>(),
+                     n, (float)initial[0], (float)initial[1]);
+  HIP_TRY(c, hipGetLastError());
+  if ((rc = sync_all(c))) return rc;
+  c->trap_state_valid = true;
+  return WAYNE_OK;
+}
+
+int wayne_ctx_trap_state_upload(wayne_ctx* c, const float* state) {
+  if (!c || !state) return WAYNE_E_INVALID;
+  int rc = trap_state_ready(c, "trap_state_upload");
+  if (rc || (rc = trap_state_alloc(c))) return rc;
+  HIP_TRY(c, hipMemcpy(c->trap_state.p, state, (size_t)c->S * c->S * sizeof(float2), hipMemcpyHostToDevice));
+  if ((rc = sync_all(c))) return rc;
+  c->trap_state_valid = true;
+  return WAYNE_OK;
+}
+
+int wayne_ctx_trap_state_download(wayne_ctx* c, float* state) {
+  if (!c || !state) return WAYNE_E_INVALID;
+  if (c->have_cal && !c->trap_state_valid) return fail(c, WAYNE_E_STATE, "trap_state_download: no trap state (reset or upload first)");
+  int rc = trap_state_ready(c, "trap_state_download");
+  if (rc) return rc;
+  HIP_TRY(c, hipMemcpy(state, c->trap_state.p, (size_t)c->S * c->S * sizeof(float2), hipMemcpyDeviceToHost));
+  return sync_all(c);
+}
+
+int wayne_exposure_set_trap_history(wayne_ctx* c, int slot, const wayne_trap_history_desc* h) {
+  if (!c) return WAYNE_E_INVALID;
+  if (slot < 0 || slot >= kSlots) return fail(c, WAYNE_E_INVALID, "set_trap_history: slot");
+  Slot& s = c->slots[slot];
+  if (!s.uploaded) return fail(c, WAYNE_E_STATE, "set_trap_history: slot not uploaded");
+  s.hist_on = false;              // from here on a refusal leaves the slot usable, without a history
+  if (!h) return WAYNE_OK;
+  if (!s.traps_on) return fail(c, WAYNE_E_STATE, "set_trap_history: wayne_exposure_set_traps first");
+  // (the front half picks the launch sequence that can never ask for a second run: it has to know about the history)
+  if (s.front_done) return fail(c, WAYNE_E_STATE, "set_trap_history: not between wayne_exposure_run_front and _run_back");
+  if (!c->trap_state_valid) return fail(c, WAYNE_E_STATE, "set_trap_history: no trap state (wayne_ctx_trap_state_reset / _upload first)");
+  if (!std::isfinite(h->gap_s) || !(h->gap_s >= 0.)) return fail(c, WAYNE_E_INVALID, "set_trap_history: gap_s must be finite and >= 0");
+  for (int p = 0; p < 2; ++p)
+    if (!std::isfinite(h->fill[p]) || !(h->fill[p] >= 0. && h->fill[p] <= s.trap_n[p]))
+      return fail(c, WAYNE_E_INVALID, "set_trap_history: fill must lie in [0, n_traps]");
+  s.hist_gap = h->gap_s;
+  s.hist_lit = h->lit ? 1 : 0;
+  s.hist_fill[0] = h->fill[0];
+  s.hist_fill[1] = h->fill[1];
+  s.hist_on = true;
   return WAYNE_OK;
 }
 

@@ -83,6 +83,10 @@ class Observation(object):
         self.contaminants = []       # field stars on every exposure (setup_contaminants)
         self.charge_traps = None     # per-pixel charge trapping (setup_charge_traps)
         self._trap_tables = None
+        self.trap_history = "planned"     # "carried": the device carries each pixel's trap state through the visit
+        self.trap_initial_state = None    # [S, S, 2] float32 the carried state starts from (None: the model's `initial`)
+        self.trap_state = None            # carried mode: the state after the visit's last exposure (run_observation)
+        self._trap_plan = None
 
     # -- setup_* (observation.py:46-291) ----------------------------------------
     def setup_observation(self, x_ref, y_ref, spatial_scan=False, scan_speed=False):
@@ -98,20 +102,49 @@ class Observation(object):
             raise ValueError("at most %d contaminants" % MAX_CONTAMINANTS)
         self.contaminants = contaminants
 
-    def setup_charge_traps(self, traps):
+    def setup_charge_traps(self, traps, history=None, initial_state=None):
         """Per-pixel charge trapping, the ramp effect (traps.ChargeTraps; traps.ChargeTraps.from_config builds it from the
-        YAML's `charge_traps:` section); None: none.  Exposure i gets its start tables from the visit plan
-        (ChargeTraps.start_tables: the visit's history at each pixel's own mean rate), so exposures stay independent."""
-        from .traps import ChargeTraps
+        YAML's `charge_traps:` section); None: none.  `history` (None: the model's own setting, `traps.history`):
+        "planned" -- exposure i gets its start tables from the visit plan (ChargeTraps.start_tables: the visit's history
+        at each pixel's own mean rate), so exposures stay independent; "carried" -- the device carries each pixel's trap
+        state from exposure to exposure (ChargeTraps.history_plan; run_observation then runs the visit in order on one
+        rank and keeps the final state in `trap_state`).  `initial_state`: carried mode only, a [S, S, 2] float32 array
+        (bordered frame; [..., 0] slow, [..., 1] fast) the visit starts from in place of the model's `initial` --
+        persistence from an earlier visit, or the `trap_state` saved from one."""
+        from .traps import ChargeTraps, HISTORIES
         if traps is not None and not isinstance(traps, ChargeTraps):
             raise TypeError("setup_charge_traps: expected traps.ChargeTraps or None")
-        self.charge_traps = traps
+        if history is None:
+            history = traps.history if traps is not None else "planned"
+        if history not in HISTORIES:
+            raise ValueError("setup_charge_traps: history must be planned or carried, got %r" % (history,))
+        if initial_state is not None:
+            if traps is None or history != "carried":
+                raise ValueError("setup_charge_traps: initial_state needs history='carried'")
+            initial_state = np.ascontiguousarray(initial_state, dtype=np.float32)
+            if initial_state.ndim != 3 or initial_state.shape[0] != initial_state.shape[1] or initial_state.shape[2] != 2:
+                raise ValueError("setup_charge_traps: initial_state has shape (S, S, 2), got %s" % (initial_state.shape,))
+        self.charge_traps = traps.with_history(history) if traps is not None else None     # (its cards name the mode)
+        self.trap_history = history if traps is not None else "planned"
+        self.trap_initial_state = initial_state
+        self.trap_state = None
         self._trap_tables = None
+        self._trap_plan = None
+
+    @property
+    def traps_carried(self):
+        return self.charge_traps is not None and self.trap_history == "carried"
 
     def exposure_traps(self, index):
-        """Exposure `index`'s charge traps (traps.ExposureTraps), or None without them."""
+        """Exposure `index`'s charge traps (traps.ExposureTraps; traps.CarriedTraps in carried mode), or None without
+        them."""
         if self.charge_traps is None:
             return None
+        if self.traps_carried:
+            if self._trap_plan is None:
+                exptime = self.detector.exptime(self.NSAMP, self.SUBARRAY, self.SAMPSEQ)
+                self._trap_plan = self.charge_traps.history_plan(self.visit_plan, exptime, staring=not self.spatial_scan)
+            return self.charge_traps.carried(self._trap_plan, index)
         from .traps import ExposureTraps
         if self._trap_tables is None:
             exptime = self.detector.exptime(self.NSAMP, self.SUBARRAY, self.SAMPSEQ)
@@ -174,6 +207,7 @@ class Observation(object):
             self.exp_start_times = self.visit_plan["exp_times"] / (24. * 60.) + self.start_JD
             self.visit_plan["exp_start_times"] = self.exp_start_times
         self._trap_tables = None
+        self._trap_plan = None
 
     def setup_reductions(self, add_dark=True, add_flat=True, add_gain_variations=True, add_non_linear=True,
                          add_initial_bias=True):
@@ -319,6 +353,15 @@ class Observation(object):
             raise ValueError("spectra_out / spectra_only need frame_options['extraction']")
         if extraction is not None and resume:
             raise ValueError("spectra are not delivered by a resumed visit: the exposures it skips have none")
+        if self.traps_carried:
+            # every exposure starts from the state its predecessor left on ONE device: the visit runs whole and in order
+            if world > 1:
+                raise ValueError("charge_traps history: carried -- the visit cannot be sharded (world > 1)")
+            if resume:
+                raise ValueError("charge_traps history: carried -- resume=True would skip exposures the state depends on")
+            if self.optimal_profile_exposures:
+                raise ValueError("charge_traps history: carried -- optimal_profile_exposures runs exposures in a first "
+                                 "pass, which would advance the trap state")
         if self.spectra_only:
             write_fits_raw = False
         else:
@@ -382,6 +425,12 @@ class Observation(object):
 
         if extraction is not None and self.optimal_profile_exposures:
             self._build_optimal_profiles(mine, eng.ctx)
+        if self.traps_carried:
+            if self.trap_initial_state is not None:
+                eng.ctx.trap_state_upload(self.trap_initial_state)
+            else:
+                eng.ctx.trap_state_reset(self.charge_traps.array("initial"))
+            self.trap_state = None
         try:
             # up to 3 exposures in flight on 4 context slots in rotation (even / odd slots run on different HIP streams)
             ctx = eng.ctx
@@ -392,6 +441,8 @@ class Observation(object):
         finally:
             if pool is not None:
                 pool.close()
+        if self.traps_carried:
+            self.trap_state = eng.ctx.trap_state_download()
         if extraction is not None:
             self._keep_spectra(got_spectra, rank, world)
         return frames

@@ -23,7 +23,8 @@ examples/hd209458b_12181_simulation_parameters.yml): sections `general`
     `temperature` or a PHOENIX `spectrum_file`; at most 8.  First order only, not in the direct image, constant;
   * an optional top-level `charge_traps:` section turns on per-pixel charge trapping, the ramp effect
     (wayne_amd/traps.py): `slow` / `fast` mappings of n_traps, efficiency, lifetime_s, initial, orbit_fill; `{}` = the
-    defaults, an omitted key its default;
+    defaults, an omitted key its default; `history: carried` carries each pixel's trap state from exposure to exposure
+    on the device (default `planned`) -- one rank only, no --resume;
   * `--spectra OUT.npz`: the device extracts every exposure's column spectra behind its reads (wayne_amd/extraction.py)
     and they are written to OUT.npz beside the _raw files: spectra [n, NSAMP, S], sky [n, NSAMP], exposure_index, row_lo,
     row_hi, bg_cols, x_ref, y_ref, read_times, exp_start.  `--spectra-only OUT.npz`: the same file, no _raw files, and
@@ -176,6 +177,18 @@ def build_observation(cfg, base_dir=".", calibration=None, device=0):
     return obs
 
 
+def carried_history(parameter_file):
+    """Does the visit's YAML ask for a carried trap history (`charge_traps: {history: carried}`)?  Read before anything
+    is started; a file that does not parse says no here and is reported where the visit is built."""
+    try:
+        with open(parameter_file) as f:
+            cfg = yaml.safe_load(f)
+    except (OSError, yaml.YAMLError):
+        return False
+    section = cfg.get("charge_traps") if isinstance(cfg, dict) else None
+    return isinstance(section, dict) and section.get("history") == "carried"
+
+
 def run(argv=None):
     ap = argparse.ArgumentParser(prog="wayne", description=__doc__.split("\n")[0])
     ap.add_argument("-p", "--parameter_file", required=True)
@@ -276,6 +289,13 @@ def run(argv=None):
     if args.gpus < 1 or args.ranks_per_gpu < 1:
         raise SystemExit("--gpus and --ranks-per-gpu must be at least 1")
     n_ranks = args.gpus * args.ranks_per_gpu
+    if (n_ranks > 1 or args.resume or int(os.environ.get("WORLD_SIZE", "1")) > 1) and carried_history(args.parameter_file):
+        # a carried trap history chains every exposure to its predecessor on one device: refused here, before any rank
+        # process is started
+        what = "--gpus > 1" if args.gpus > 1 else "--ranks-per-gpu > 1" if args.ranks_per_gpu > 1 else \
+               "--resume" if args.resume else "several ranks (WORLD_SIZE > 1)"
+        raise SystemExit("charge_traps history: carried cannot be combined with %s: every exposure starts from the trap "
+                         "state its predecessor left on one device" % what)
     given = list(sys.argv[1:] if argv is None else argv)
     if n_ranks > 1 and "WORLD_SIZE" not in os.environ and any(a == "--device" or a.startswith("--device=") for a in given):
         # forwarded to every rank it would put them all on one GPU: each rank takes its device from LOCAL_RANK

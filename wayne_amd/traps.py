@@ -20,8 +20,18 @@ eta = 0.008407, tau = 281.463 s; Zhou et al. 2017 and its public RECTE code), qu
 hand -- check them against it before relying on them.  Nothing but the defaults depends on these numbers.
 Known artefacts: cosmic-ray charge counts in f_bar (a hit pixel's history looks brighter, by an electron or two); the
 history ignores the transit and the visit-trend scale (<= 2 % of f_bar); the direct image neither traps nor enters the
-history.  Not modelled: a sequential history carrying each pixel's state from one exposure to the next, persistence
-from earlier visits, replay mode.
+history.
+
+Carried history (`history: carried`, opt-in): the device keeps each pixel's state (slow, fast) from one exposure to the
+next instead (k_ramp_hist; wayne_exposure_set_trap_history).  An exposure starts from what the previous one left, stepped
+over the gap between them and raised by `orbit_fill` at an orbit's start (`ChargeTraps.history_plan`: the schedule of
+`start_tables`), and leaves its own state behind.  The history is then the charge each pixel really collected -- the
+transit, the visit trend, every sky draw, and a cosmic ray in the pixel it hit -- and a state from an earlier visit can
+be handed in (Observation.setup_charge_traps(initial_state=...)).  Exposures are no longer independent: no sharding over
+ranks and no --resume in that mode.
+
+Not modelled: replay mode; in the gaps of a carried history the rate is the exposure's own mean rate (staring) or zero
+(a scan), as in the planned one.
 """
 import math
 import struct
@@ -38,6 +48,7 @@ GRID = 1024                  # points of a start table (wayne_trap_desc.n_rate)
 MAX_GRID = 4096              # WAYNE_MAX_TRAP_RATES
 RATE_LO, RATE_HI = 1e-2, 1e6
 SECONDS_PER_DAY = 86400.0
+HISTORIES = ("planned", "carried")
 
 
 class ChargeTrapConfigError(ValueError):
@@ -77,9 +88,13 @@ def interpolate(table, f, rate_lo, rate_hi):
 class ChargeTraps(object):
     """The model's parameters.  `slow` / `fast`: mappings with n_traps, efficiency, lifetime_s, initial (occupancy at the
     visit's first exposure) and orbit_fill (added at every later orbit's start, clipped to n_traps); a key left out takes
-    its default.  `grid`, `rate_lo`, `rate_hi`: the start tables' grid."""
+    its default.  `grid`, `rate_lo`, `rate_hi`: the start tables' grid.  `history`: "planned" (start tables; exposures
+    stay independent) or "carried" (the device carries each pixel's state from exposure to exposure: `history_plan`)."""
 
-    def __init__(self, slow=None, fast=None, grid=GRID, rate_lo=RATE_LO, rate_hi=RATE_HI):
+    def __init__(self, slow=None, fast=None, grid=GRID, rate_lo=RATE_LO, rate_hi=RATE_HI, history="planned"):
+        if history not in HISTORIES:
+            raise ChargeTrapConfigError("charge_traps.history: expected planned or carried, got %r" % (history,))
+        self.history = history
         self.params = {}
         for name, given in (("slow", slow), ("fast", fast)):
             given = {} if given is None else given
@@ -130,10 +145,18 @@ class ChargeTraps(object):
             section = {}
         if not isinstance(section, dict):
             raise ChargeTrapConfigError("`charge_traps` must be a mapping with optional `slow` and `fast` entries")
-        unknown = sorted(set(section) - set(POPULATIONS))
+        unknown = sorted(set(section) - set(POPULATIONS) - {"history"})
         if unknown:
-            raise ChargeTrapConfigError("charge_traps: unknown key(s) %s (expected slow, fast)" % ", ".join(map(str, unknown)))
-        return cls(slow=section.get("slow"), fast=section.get("fast"))
+            raise ChargeTrapConfigError("charge_traps: unknown key(s) %s (expected slow, fast, history)" % ", ".join(map(str, unknown)))
+        history = section.get("history")
+        return cls(slow=section.get("slow"), fast=section.get("fast"), history="planned" if history is None else history)
+
+    def with_history(self, history):
+        """This model with another `history` setting (itself if it has that one already)."""
+        if history == self.history:
+            return self
+        return ChargeTraps(slow=self.params["slow"], fast=self.params["fast"], grid=self.grid, rate_lo=self.rate_lo,
+                           rate_hi=self.rate_hi, history=history)
 
     def __repr__(self):
         return "ChargeTraps(slow=%r, fast=%r)" % (self.params["slow"], self.params["fast"])
@@ -166,12 +189,15 @@ class ChargeTraps(object):
         out += [("CTGRID", self.grid, "trap start tables: points of the rate grid"),
                 ("CTRATELO", self.rate_lo, "trap start tables: lowest non-zero rate (e-/s)"),
                 ("CTRATEHI", self.rate_hi, "trap start tables: highest rate (e-/s)")]
+        if self.history == "carried":
+            out += [("CTHIST", "CARRIED", "trap state carried from exposure to exposure")]
         return out
 
     def digest_bytes(self):
         """What identifies the model in a descriptor digest (visit.descriptor_digest)."""
         vals = [self.params[n][k] for n in POPULATIONS for k in KEYS] + [self.rate_lo, self.rate_hi]
-        return b"charge_traps" + struct.pack("<i", self.grid) + np.array(vals, dtype=np.float64).tobytes()
+        tail = b"history=carried" if self.history == "carried" else b""
+        return b"charge_traps" + struct.pack("<i", self.grid) + np.array(vals, dtype=np.float64).tobytes() + tail
 
     # -- start tables -----------------------------------------------------------------------------------------------
     def rates(self):
@@ -219,6 +245,29 @@ class ChargeTraps(object):
     def interpolate(self, table, f):
         return interpolate(table, f, self.rate_lo, self.rate_hi)
 
+    def history_plan(self, visit_plan, exptime_s, staring, n_exposures=None):
+        """What each exposure of a carried history hands the device beside the state (CarriedTraps), on the schedule of
+        `start_tables`: a dict of gap_s [n_exp] (seconds since the previous exposure's last read), lit [n_exp] (bool: the
+        pixel kept collecting at its mean rate during the gap) and fill [n_exp, 2] (added after the gap, clipped to
+        n_traps).  Exposure 0: no gap, no fill (the state has been reset to `initial`); the same orbit: gap =
+        max(t[k+1] - t[k] - exptime_s, 0), dark for a scan and lit for staring; an orbit's start: a dark gap, then
+        `orbit_fill`."""
+        t = np.asarray(visit_plan["exp_start_times"], dtype=np.float64)
+        n = len(t) if n_exposures is None else int(n_exposures)
+        starts = set(int(i) for i in visit_plan.get("orbit_start_index", [0]))
+        gap, lit, fill = np.zeros(n), np.zeros(n, dtype=bool), np.zeros((n, 2))
+        for k in range(1, n):
+            gap[k] = max((t[k] - t[k - 1]) * SECONDS_PER_DAY - float(exptime_s), 0.0)
+            if k in starts:
+                fill[k] = self.array("orbit_fill")
+            else:
+                lit[k] = bool(staring)
+        return {"gap_s": gap, "lit": lit, "fill": fill}
+
+    def carried(self, plan, index):
+        """Exposure `index` of a `history_plan` -> CarriedTraps."""
+        return CarriedTraps(self, plan["gap_s"][index], plan["lit"][index], plan["fill"][index])
+
 
 class ExposureTraps(object):
     """The model with one exposure's start tables [2, G]: what an exposure descriptor carries to the device
@@ -237,8 +286,25 @@ class ExposureTraps(object):
         return self.traps.digest_bytes() + self.table.tobytes()
 
 
+class CarriedTraps(ExposureTraps):
+    """The model with one exposure's share of a carried history, accepted wherever ExposureTraps is: the exposure starts
+    from the context's trap state -- stepped over `gap_s` seconds (lit: at the pixel's mean rate; else dark), then raised
+    by `fill` [2] and clipped to n_traps -- and leaves its own state behind (Context.upload ->
+    wayne_exposure_set_trap_history).  Its start table is the flat one and is not looked at."""
+
+    __slots__ = ("gap_s", "lit", "fill")
+
+    def __init__(self, traps, gap_s=0.0, lit=False, fill=(0.0, 0.0)):
+        ExposureTraps.__init__(self, traps)
+        self.gap_s, self.lit = float(gap_s), bool(lit)
+        self.fill = np.array(fill, dtype=np.float64).reshape(2)
+
+    def digest_bytes(self):
+        return (self.traps.digest_bytes() + b"carried" + struct.pack("<d?", self.gap_s, self.lit) + self.fill.tobytes())
+
+
 def for_exposure(charge_traps):
-    """ChargeTraps (flat table at `initial`) or ExposureTraps -> ExposureTraps; None -> None."""
+    """ChargeTraps (flat table at `initial`) or ExposureTraps / CarriedTraps -> itself; None -> None."""
     if charge_traps is None or isinstance(charge_traps, ExposureTraps):
         return charge_traps
     if isinstance(charge_traps, ChargeTraps):
