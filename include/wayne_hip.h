@@ -696,6 +696,49 @@ int wayne_exposure_profile(wayne_ctx *ctx, int slot, const double **planes, size
  * selects it.  Synchronises. */
 int wayne_extract_profile(wayne_ctx *ctx, uint64_t *launches, double *ms);
 
+/* ---- device-side FITS words (no reference counterpart) ------------------- */
+
+/*
+ * The reads of an exposure as the data sections of its HST-style file, formed on the device (k_fits_words) and fetched
+ * into pinned host memory, from which a file is written without a pass over the samples on the host.  For the slot's
+ * reads P_0 .. P_R (each S*S samples of type T, bordered) the payload is (R + 1) * stride bytes:
+ *
+ *   payload[f*stride + i*B ...]                       = words(P_{R-f} flat [i])   f = 0 .. R: the last read first, the
+ *                                                                                  order of the file's SCI images
+ *   payload[f*stride + plane_bytes .. (f + 1)*stride) = 0                          the HDU's padding
+ *   words(v):  float32 reads: the 8 bytes of (double)v, most significant first (BITPIX -64)
+ *              float64 reads: the 8 bytes of v, most significant first          (BITPIX -64)
+ *              uint16 reads : the 2 bytes of v ^ 0x8000, most significant first (BITPIX 16 with BZERO 32768)
+ *   B = 8, 8, 2;  plane_bytes = S*S*B;  stride = plane_bytes rounded up to a multiple of 2880 (a multiple of 64)
+ *
+ * so plane f is one contiguous piece of a file: a data section with its padding.  The bit patterns of NaN reads are not
+ * specified (the reads are clipped and finite).  Opt-in: without wayne_exposure_set_fits every launch and every byte stay
+ * as they are.  Added within WAYNE_ABI_VERSION 7: new symbols only.
+ */
+
+/* The layout for bordered side S, R reads behind the zero read and the sample type of descriptor flags `out_flags`
+ * (WAYNE_F_OUT_F64, WAYNE_F_OUT_U16 or neither; other bits are ignored): *plane_bytes, *stride, *bitpix (-64 or 16).
+ * Any output pointer may be NULL.  Pure host arithmetic, callable without a device.  WAYNE_E_INVALID for S < 2, an odd
+ * S, R < 1 or both type flags. */
+int wayne_fits_layout(int S, int R, uint32_t out_flags, size_t *plane_bytes, size_t *stride, int *bitpix);
+/* After wayne_exposure_upload, before run: the back half of every run of the slot also forms the payload, behind the
+ * ramp kernel and the extraction's launches on the slot's stream (on = 0 clears).  wayne_exposure_upload clears it, so a
+ * caller that never calls this gets today's exposure and today's launches.  WAYNE_E_STATE on a slot that is not uploaded. */
+int wayne_exposure_set_fits(wayne_ctx *ctx, int slot, int on);
+/* Pinned-host delivery of the payload, shaped like wayne_exposure_fetch_async / _wait: fetch enqueues the copy into a
+ * pinned mirror of its own behind the slot's kernels and returns at once; wait blocks until the slot's work is done and
+ * returns the mirror, (R + 1) * stride bytes, valid until the next fetch_fits_async or upload of the slot.  The status word rides behind
+ * the payload: an exposure that met a bin beyond its launch sequence's reach is run a second time and fetched again
+ * (spectra fetched beside it too), as wayne_exposure_wait does.  The reads themselves need not be fetched.
+ * WAYNE_E_STATE on a slot without wayne_exposure_set_fits. */
+int wayne_exposure_fetch_fits_async(wayne_ctx *ctx, int slot);
+int wayne_exposure_wait_fits(wayne_ctx *ctx, int slot, void **host_payload);
+/* The payload into the caller's (pageable) memory, (R + 1) * stride bytes.  Synchronises; for tests. */
+int wayne_exposure_download_fits(wayne_ctx *ctx, int slot, void *out_payload);
+/* HIP-event time of k_fits_words while wayne_profile_enable is on, since wayne_profile_reset: launches and total
+ * milliseconds.  wayne_profile_select's bit 9 selects it.  Synchronises. */
+int wayne_fits_profile(wayne_ctx *ctx, uint64_t *launches, double *ms);
+
 /* ---- measurement ------------------------------------------------------- */
 
 #define WAYNE_PROF_KERNELS 8

@@ -191,6 +191,13 @@ SYMBOLS = {
     "wayne_exposure_fetch_profile": (C.c_int, [_vp, C.c_int]),
     "wayne_exposure_profile": (C.c_int, [_vp, C.c_int, C.POINTER(_dp), C.POINTER(C.c_size_t)]),
     "wayne_extract_profile": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_double)]),
+    "wayne_fits_layout": (C.c_int, [C.c_int, C.c_int, C.c_uint32, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t),
+                                    C.POINTER(C.c_int)]),
+    "wayne_exposure_set_fits": (C.c_int, [_vp, C.c_int, C.c_int]),
+    "wayne_exposure_fetch_fits_async": (C.c_int, [_vp, C.c_int]),
+    "wayne_exposure_wait_fits": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_void_p)]),
+    "wayne_exposure_download_fits": (C.c_int, [_vp, C.c_int, _vp]),
+    "wayne_fits_profile": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_double)]),
     "wayne_profile_enable": (C.c_int, [_vp, C.c_int]),
     "wayne_profile_select": (C.c_int, [_vp, C.c_uint]),
     "wayne_profile_reset": (C.c_int, [_vp]),
@@ -318,6 +325,7 @@ class Context(object):
         self._slot_opt = set()   # slots whose extraction delivers the optimal values too (set_optimal succeeded)
         self._slot_optch = set() # slots whose extraction delivers the optimal channels (set_optimal_channels succeeded)
         self._slot_prof = set()  # slots whose runs write the profile planes too (deliver_profile succeeded)
+        self._slot_fits = {}     # slot -> (plane_bytes, stride, bitpix) of its FITS payload (set_fits succeeded)
         _live_contexts.add(self)
         for name, value in _knob_defaults.items():
             self.set_knob(name, value)
@@ -444,6 +452,7 @@ class Context(object):
         self._slot_opt.discard(slot)
         self._slot_prof.discard(slot)
         self._slot_optch.discard(slot)
+        self._slot_fits.pop(slot, None)
         sources = getattr(desc, "_sources", None)
         if sources:
             self.set_sources(slot, sources)
@@ -455,6 +464,54 @@ class Context(object):
         extraction = getattr(desc, "_extraction", None)
         if extraction is not None:
             self.set_extraction(slot, extraction)
+        if getattr(desc, "_device_fits", False):
+            self.set_fits(slot)
+
+    # -- device-side FITS words ----------------------------------------------------
+    def set_fits(self, slot, on=True):
+        """Every run of the slot also forms its reads' FITS words on the device (on=False clears; after upload, which
+        clears it too).  See wayne_exposure_set_fits."""
+        self._slot_fits.pop(slot, None)
+        self.check(self._L.wayne_exposure_set_fits(self._h, int(slot), 1 if on else 0))
+        if on:
+            K, W, R, dtype = self._slot_meta[slot]
+            self._slot_fits[slot] = fits_layout(self.S, R, dtype)
+
+    def has_fits(self, slot):
+        """Whether the slot's runs form FITS words (set_fits succeeded since its last upload)."""
+        return slot in self._slot_fits
+
+    def fits_layout_of(self, slot):
+        """(plane_bytes, stride, bitpix) of the slot's payload (fits_layout); KeyError without set_fits."""
+        return self._slot_fits[slot]
+
+    def fetch_fits_async(self, slot):
+        """Enqueue the copy of the slot's FITS words into their pinned host mirror (returns at once)."""
+        self.check(self._L.wayne_exposure_fetch_fits_async(self._h, int(slot)))
+
+    def wait_fits(self, slot):
+        """Block until the slot's work is done -> its payload, (R + 1) * stride bytes, as a uint8 numpy VIEW of the pinned
+        mirror (valid until the slot's next fetch_fits_async or upload)."""
+        p = C.c_void_p()
+        self.check(self._L.wayne_exposure_wait_fits(self._h, int(slot), C.byref(p)))
+        K, W, R, _ = self._slot_meta[slot]
+        n = (R + 1) * self._slot_fits[slot][1]
+        return np.frombuffer((C.c_ubyte * n).from_address(p.value), dtype=np.uint8)
+
+    def download_fits(self, slot):
+        """The slot's payload, blocking; a uint8 array of the caller's own."""
+        K, W, R, _ = self._slot_meta[slot]
+        if slot not in self._slot_fits:
+            raise WayneError(E_STATE, "download_fits: no FITS words set for the slot")
+        out = np.empty((R + 1) * self._slot_fits[slot][1], dtype=np.uint8)
+        self.check(self._L.wayne_exposure_download_fits(self._h, int(slot), ptr(out)))
+        return out
+
+    def fits_profile(self):
+        """{"launches", "ms"} of k_fits_words by HIP events (profile_enable; since profile_reset)."""
+        n, ms = C.c_uint64(0), C.c_double(0.0)
+        self.check(self._L.wayne_fits_profile(self._h, C.byref(n), C.byref(ms)))
+        return {"launches": int(n.value), "ms": float(ms.value)}
 
     def set_crrej(self, slot, crrej):
         """Cosmic-ray rejection of the slot's extraction: an extraction.CosmicRejection (k, read_noise) -- None clears;
@@ -886,7 +943,7 @@ class Context(object):
         if names is None:
             mask = 0xFFFFFFFF
         else:
-            order = list(self.profile_get().keys())[:PROF_KERNELS] + ["k_extract"]
+            order = list(self.profile_get().keys())[:PROF_KERNELS] + ["k_extract", "k_fits_words"]
             mask = 0
             for n in names:
                 mask |= 1 << order.index(n)
@@ -909,12 +966,13 @@ def make_desc(seed, exposure_index, flags, sub_scale, wl_um, flux, depth, x_ref,
               sample_read, read_dt_s, replay_seed=None, rng_mode=RNG_PHILOX, threads_compat=1,
               sky_ct_s=0.0, cosmic_rate=-1.0, scale_factor=1.0, noise_mean=0.0, noise_std=0.0,
               thrower_margin=0, thrower_splits=0, lc_z=None, lc_hidden=None, lc_rp=None, lc_ld=None, sources=None,
-              traps=None, extraction=None):
+              traps=None, extraction=None, device_fits=False):
     """The exposure descriptor.  `sources`: contaminating field stars (sources.Contaminant), carried beside the C struct
     and set by Context.upload (wayne_exposure_set_sources); None or [] = the target alone.  `traps`: charge traps
     (traps.ExposureTraps, or a traps.ChargeTraps whose table is flat at `initial`), set by Context.upload
     (wayne_exposure_set_traps); None = no trapping.  `extraction`: the spectral extraction of the exposure
-    (extraction.Extraction), set by Context.upload (wayne_exposure_set_extraction); None = reads only."""
+    (extraction.Extraction), set by Context.upload (wayne_exposure_set_extraction); None = reads only.  `device_fits`: the reads' FITS words are formed on the device too,
+    set by Context.upload (wayne_exposure_set_fits)."""
     d = ExposureDesc()
     keep = []
 
@@ -966,6 +1024,7 @@ def make_desc(seed, exposure_index, flags, sub_scale, wl_um, flux, depth, x_ref,
         traps = _traps.for_exposure(traps)
     d._traps = traps
     d._extraction = extraction
+    d._device_fits = bool(device_fits)
     return d
 
 
@@ -979,6 +1038,17 @@ def philox4x32(ctr, key):
     out = np.empty(4, dtype=np.uint32)
     load().wayne_philox4x32(ptr(ctr), ptr(key), ptr(out))
     return out
+
+
+def fits_layout(S, R, dtype):
+    """(plane_bytes, stride, bitpix) of the FITS payload of R + 1 reads of bordered side S and sample type `dtype`
+    (float32, float64 or uint16; or a descriptor's flag word): see wayne_fits_layout.  Needs no device."""
+    flags = int(dtype) if isinstance(dtype, (int, np.integer)) else OUT_FLAGS[np.dtype(dtype)]
+    pb, stride, bitpix = C.c_size_t(0), C.c_size_t(0), C.c_int(0)
+    rc = load().wayne_fits_layout(int(S), int(R), flags, C.byref(pb), C.byref(stride), C.byref(bitpix))
+    if rc != OK:
+        raise WayneError(rc, "fits_layout: no layout for S = %d, R = %d, flags %#x" % (S, R, flags))
+    return int(pb.value), int(stride.value), int(bitpix.value)
 
 
 def source_seed(seed, tag):

@@ -17,6 +17,8 @@
 //   k_extract.h     k_extract_rows / k_extract_finish   opt-in: column spectra per read interval from the reads
 //                                  just written (linearise, dark, gain, row sums, sky level), no reference counterpart
 //                   k_extract_crmask                    opt-in on top of it: the cosmic-ray flag plane of the difference images
+//   k_fits.h        k_fits_words   opt-in: the reads as the big-endian data sections of their FITS file, in file order,
+//                                  padding included (a streaming byte reversal), no reference counterpart
 //
 // "A<n>" are the row ids of SURVEY.md section 8(a); reference file:line
 // citations are next to each formula.
@@ -28,3 +30,4 @@
 #include "k_narrow.h"
 #include "k_ramp.h"
 #include "k_extract.h"
+#include "k_fits.h"

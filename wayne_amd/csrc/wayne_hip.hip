@@ -37,8 +37,8 @@ int fail(wayne_ctx* c, int code, const std::string& msg);   // (keeps `msg` as t
 inline size_t align64(size_t n) { return (n + 63) & ~(size_t)63; }
 
 enum ProfKernel { PK_PREP_WL = 0, PK_PREP_SUB, PK_THROW, PK_COSMIC, PK_RAMP, PK_LIGHTCURVE, PK_NARROW, PK_LANE,
-                  PK_EXTRACT };   // (PK_EXTRACT lies beyond wayne_profile's arrays, which the ABI fixes: wayne_extract_profile reports it)
-constexpr int kProfKernels = WAYNE_PROF_KERNELS + 1;
+                  PK_EXTRACT, PK_FITS };   // (PK_EXTRACT and PK_FITS lie beyond wayne_profile's arrays, which the ABI fixes: wayne_extract_profile / wayne_fits_profile report them)
+constexpr int kProfKernels = WAYNE_PROF_KERNELS + 2;
 const char* const kProfNames[WAYNE_PROF_KERNELS] = {"k_prep_wl", "k_prep_sub",   "k_throw",  "k_cosmic",   /* (cosmic rays ride in k_prep_sub: slot kept for the ABI) */
                                                     "k_ramp",    "k_lightcurve", "k_narrow", "k_lane"};
 
@@ -283,6 +283,15 @@ struct Slot : SourceState {
   size_t prof_fix_n = 0;
   uint64_t prof_fix_hash = 0;
   int prof_fix_R = 0;
+  // FITS words of this exposure (wayne_exposure_set_fits; cleared by upload): the payload [(R+1)][fits_stride] bytes that
+  // k_fits_words writes behind the ramp kernel and the extraction, and its pinned mirror followed by a copy of `misc`
+  // (fetch_fits_async / wait_fits; fits_pinned_run: the run the copy was enqueued behind)
+  bool fits_on = false;
+  size_t fits_plane_bytes = 0, fits_stride = 0;
+  DevBuf fits_dev;
+  PinnedBuf fits_pinned;
+  Misc* fits_pinned_misc = nullptr;
+  uint32_t fits_pinned_run = 0;
   // staging arena of the descriptor's arrays: uploads are enqueued from here, so
   // wayne_exposure_upload returns without waiting for the slot's stream to drain
   StageArena stage;
@@ -992,6 +1001,39 @@ int launch_extract(wayne_ctx* c, Slot& s) {
   return s.chan_on ? launch_channels(c, s, a, a.first_chunk[products], out, false) : WAYNE_OK;
 }
 
+// The layout of a slot's FITS payload (wayne_fits_layout): false for a side or a flag word it is not defined for.
+bool fits_layout(int S, int R, uint32_t flags, size_t* plane_bytes, size_t* stride, int* bitpix) {
+  if (S < 2 || (S & 1) || R < 1 || ((flags & WAYNE_F_OUT_F64) && (flags & WAYNE_F_OUT_U16))) return false;
+  const size_t B = (flags & WAYNE_F_OUT_U16) ? 2 : 8;
+  const size_t pb = (size_t)S * S * B;
+  if (plane_bytes) *plane_bytes = pb;
+  if (stride) *stride = (pb + kFitsBlock - 1) / kFitsBlock * kFitsBlock;
+  if (bitpix) *bitpix = (flags & WAYNE_F_OUT_U16) ? 16 : -64;
+  return true;
+}
+
+// The FITS words of slot `s` (wayne_exposure_set_fits) behind its ramp kernel -- and behind the extraction's launches,
+// which so stay where they are without the option, directly behind the kernel whose reads they take: one launch,
+// grid (units of a plane, capped; R + 1 planes).
+int launch_fits(wayne_ctx* c, Slot& s) {
+  FitsArgs a{};
+  a.reads = s.out.p;
+  a.payload = s.fits_dev.as<unsigned char>();
+  a.planes = s.R + 1;
+  a.n = (unsigned)((size_t)c->S * c->S);
+  a.stride = s.fits_stride;
+  const int out = out_kind(s.d.flags);
+  const size_t units = s.fits_stride / (out == 2 ? 16 : 32);
+  const size_t cap = std::max<size_t>(1, (size_t)kFitsMaxBlocks / (size_t)a.planes);
+  const dim3 grid((unsigned)std::min(cap, (units + kFitsThreads - 1) / kFitsThreads), (unsigned)a.planes), block(kFitsThreads);
+  ProfScope ps(c, PK_FITS);
+  if (out == 1) hipLaunchKernelGGL((k_fits_words<double>), grid, block, 0, c->stream, a);
+  else if (out == 2) hipLaunchKernelGGL((k_fits_words<unsigned short>), grid, block, 0, c->stream, a);
+  else hipLaunchKernelGGL((k_fits_words<float>), grid, block, 0, c->stream, a);
+  HIP_TRY(c, hipGetLastError());
+  return WAYNE_OK;
+}
+
 }  // namespace
 
 namespace {
@@ -1493,6 +1535,8 @@ int wayne_exposure_upload(wayne_ctx* c, int slot, const wayne_exposure_desc* d) 
   s.opt_on = false;          // ... and whose optimal extraction waits for wayne_exposure_set_optimal
   s.prof_deliver = s.prof_fetched = s.prof_valid = s.prof_fixed = s.optch_on = false;   // (the profile planes and the optimal channels go with the optimal extraction)
   s.opt_res = nullptr;
+  s.fits_on = false;         // ... and no FITS words until wayne_exposure_set_fits says so
+  s.fits_pinned_misc = nullptr;
   int rc;
   const size_t KW = (size_t)K * W;
   {
@@ -1940,6 +1984,8 @@ int wayne_exposure_run_back(wayne_ctx* c, int slot) {
   }
   if (s.extract_on)
     if (int rc = launch_extract(c, s)) return rc;   // the spectra of the reads just written, behind them on the stream
+  if (s.fits_on)
+    if (int rc = launch_fits(c, s)) return rc;      // ... and their FITS words
   s.acc_dirty = false;
 #ifdef WAYNE_TIMING_KNOBS
   if (ramp_reads_cut) s.acc_dirty = true;     // the next front half starts from cleared accumulators
@@ -2050,6 +2096,7 @@ int wayne_exposure_wait(wayne_ctx* c, int slot, void** host_reads) {
   if ((rc = wayne_exposure_fetch_async(c, slot))) return rc;     // a bin beyond the lanes' reach: once more, with k_throw
   // (spectra fetched beside the reads are those of the first run: fetched again too, with the second run's status word)
   if (s.extract_on && s.ex_pinned_misc && (rc = wayne_exposure_fetch_spectra_async(c, slot))) return rc;
+  if (s.fits_on && s.fits_pinned_misc && (rc = wayne_exposure_fetch_fits_async(c, slot))) return rc;   // (... and FITS words likewise)
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   return look_at_status(c, slot, s.pinned_misc, nullptr, nullptr, s.pinned_run);
 }
@@ -2816,6 +2863,105 @@ int wayne_extract_profile(wayne_ctx* c, uint64_t* launches, double* ms) {
   if (rc) return rc;
   if (launches) *launches = c->prof_launches[PK_EXTRACT];
   if (ms) *ms = c->prof_ms[PK_EXTRACT];
+  return WAYNE_OK;
+}
+
+// ---------------------------------------------------------------------------
+// device-side FITS words
+// ---------------------------------------------------------------------------
+int wayne_fits_layout(int S, int R, uint32_t out_flags, size_t* plane_bytes, size_t* stride, int* bitpix) {
+  return fits_layout(S, R, out_flags, plane_bytes, stride, bitpix) ? WAYNE_OK : WAYNE_E_INVALID;
+}
+
+int wayne_exposure_set_fits(wayne_ctx* c, int slot, int on) {
+  if (!c) return WAYNE_E_INVALID;
+  if (slot < 0 || slot >= kSlots) return fail(c, WAYNE_E_INVALID, "set_fits: slot");
+  Slot& s = c->slots[slot];
+  if (!s.uploaded) return fail(c, WAYNE_E_STATE, "set_fits: slot not uploaded");
+  s.fits_on = false;           // from here on a refusal leaves the slot usable, without FITS words
+  s.fits_pinned_misc = nullptr;
+  if (!on) return WAYNE_OK;
+  size_t pb = 0, stride = 0;
+  if (!fits_layout(c->S, s.R, s.d.flags, &pb, &stride, nullptr)) return fail(c, WAYNE_E_INVALID, "set_fits: no layout for this side");
+  (void)hipSetDevice(c->device);
+  HIP_TRY(c, s.fits_dev.reserve((size_t)(s.R + 1) * stride));
+  s.fits_plane_bytes = pb;
+  s.fits_stride = stride;
+  s.fits_on = true;
+  return WAYNE_OK;
+}
+
+int wayne_exposure_fetch_fits_async(wayne_ctx* c, int slot) {
+  if (!c) return WAYNE_E_INVALID;
+  if (slot < 0 || slot >= kSlots) return fail(c, WAYNE_E_INVALID, "fetch_fits_async: slot");
+  Slot& s = c->slots[slot];
+  if (!s.uploaded) return fail(c, WAYNE_E_STATE, "fetch_fits_async: slot not uploaded");
+  if (!s.fits_on) return fail(c, WAYNE_E_STATE, "fetch_fits_async: no FITS words set for the slot");
+  (void)hipSetDevice(c->device);
+  use_slot_stream(c, slot);
+  const size_t bytes = (size_t)(s.R + 1) * s.fits_stride, tail = align64(bytes);
+  s.fits_pinned_misc = nullptr;
+  if (!s.fits_pinned.reserve(tail + 64)) return fail(c, WAYNE_E_NOMEM, "fetch_fits_async: pinned host allocation failed");
+  s.fits_pinned_misc = (Slot::Misc*)(s.fits_pinned.p + tail);
+  // (the exposure on the other stream waits for this one's kernels, not for its copy: as wayne_exposure_fetch_async --
+  // which has made the record already when this run's reads were fetched in front of the payload)
+  if (c->n_streams == 2 && c->ev_kdone[slot % 2] && !(s.pinned_misc && s.pinned_run == s.run_no)) {
+    HIP_TRY(c, hipEventRecord(c->ev_kdone[slot % 2], c->stream));
+    c->kdone_valid[slot % 2] = true;
+  }
+  HIP_TRY(c, hipMemcpyAsync(s.fits_pinned.p, s.fits_dev.p, bytes, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(s.fits_pinned_misc, s.misc.p, sizeof(Slot::Misc), hipMemcpyDeviceToHost, c->stream));
+  s.fits_pinned_run = s.run_no;
+  return WAYNE_OK;
+}
+
+int wayne_exposure_wait_fits(wayne_ctx* c, int slot, void** host_payload) {
+  if (!c || !host_payload) return WAYNE_E_INVALID;
+  if (slot < 0 || slot >= kSlots) return fail(c, WAYNE_E_INVALID, "wait_fits: slot");
+  Slot& s = c->slots[slot];
+  if (!s.uploaded) return fail(c, WAYNE_E_STATE, "wait_fits: slot not uploaded");
+  if (!s.fits_on) return fail(c, WAYNE_E_STATE, "wait_fits: no FITS words set for the slot");
+  if (!s.fits_pinned.p || !s.fits_pinned_misc) return fail(c, WAYNE_E_STATE, "wait_fits: fetch_fits_async first");
+  (void)hipSetDevice(c->device);
+  use_slot_stream(c, slot);
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  *host_payload = s.fits_pinned.p;
+  const uint32_t first_run = s.fits_pinned_run;
+  bool reran = false;                        // (the status word came with the payload)
+  int rc = look_at_status(c, slot, s.fits_pinned_misc, wayne_exposure_run, &reran, s.fits_pinned_run);
+  if (rc || !reran) return rc;
+  if ((rc = wayne_exposure_fetch_fits_async(c, slot))) return rc;     // a bin beyond the lanes' reach: once more, with k_throw
+  // (reads and spectra fetched beside the payload are those of the first run: fetched again too)
+  if (s.pinned_misc && s.pinned_run == first_run && (rc = wayne_exposure_fetch_async(c, slot))) return rc;
+  if (s.extract_on && s.ex_pinned_misc && (rc = wayne_exposure_fetch_spectra_async(c, slot))) return rc;
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  *host_payload = s.fits_pinned.p;
+  return look_at_status(c, slot, s.fits_pinned_misc, nullptr, nullptr, s.fits_pinned_run);
+}
+
+int wayne_exposure_download_fits(wayne_ctx* c, int slot, void* out_payload) {
+  if (!c || !out_payload) return WAYNE_E_INVALID;
+  if (slot < 0 || slot >= kSlots) return fail(c, WAYNE_E_INVALID, "download_fits: slot");
+  Slot& s = c->slots[slot];
+  if (!s.uploaded) return fail(c, WAYNE_E_STATE, "download_fits: slot not uploaded");
+  if (!s.fits_on) return fail(c, WAYNE_E_STATE, "download_fits: no FITS words set for the slot");
+  (void)hipSetDevice(c->device);
+  use_slot_stream(c, slot);
+  const size_t bytes = (size_t)(s.R + 1) * s.fits_stride;
+  HIP_TRY(c, hipMemcpyAsync(out_payload, s.fits_dev.p, bytes, hipMemcpyDeviceToHost, c->stream));
+  bool reran = false;
+  int rc = look_at_status(c, slot, nullptr, wayne_exposure_run, &reran);
+  if (rc || !reran) return rc;
+  HIP_TRY(c, hipMemcpyAsync(out_payload, s.fits_dev.p, bytes, hipMemcpyDeviceToHost, c->stream));
+  return look_at_status(c, slot, nullptr);
+}
+
+int wayne_fits_profile(wayne_ctx* c, uint64_t* launches, double* ms) {
+  if (!c) return WAYNE_E_INVALID;
+  int rc = collect_profile(c);
+  if (rc) return rc;
+  if (launches) *launches = c->prof_launches[PK_FITS];
+  if (ms) *ms = c->prof_ms[PK_FITS];
   return WAYNE_OK;
 }
 

@@ -30,9 +30,25 @@ class Exposure(object):
         self.NSAMP = self.exp_info.get("NSAMP")
         self.SAMPSEQ = self.exp_info.get("SAMPSEQ")
         self.reads = []   # [(array (S, S), header dict)], read 0 first
+        self.stored = []  # [(piece, header dict, shape, type code)], read 0 first: reads held as their FITS words (add_stored_read)
 
     def add_read(self, data, read_info=None):
         self.reads.append((data, self.generate_read_header(read_info) if read_info is not None else {}))
+
+    def add_stored_read(self, piece, read_info, shape, code):
+        """A read that is held as the FITS words of its image instead of an array: `piece` is a bytes-like object with
+        the HDU's data section AND its padding to the 2880-byte block (the device forms it: _lib.Context.wait_fits),
+        `shape` the image's (S, S) and `code` its type, "f8" (BITPIX -64) or "u2" (BITPIX 16, BZERO 32768).
+        generate_fits writes the piece untouched between the header blocks it renders for an array read.  An exposure
+        holds its reads one way or the other: every read of a file is added here, read 0 first, or none is."""
+        if code not in ("f8", "u2"):
+            raise ValueError("stored read: type code %r (f8 or u2)" % (code,))
+        shape = tuple(int(n) for n in shape)
+        nbytes = shape[0] * shape[1] * (8 if code == "f8" else 2)
+        if len(piece) != nbytes + (-nbytes) % fitsio.BLOCK:
+            raise ValueError("stored read: %d bytes for a %s image of %s (%d with its padding)"
+                             % (len(piece), code, shape, nbytes + (-nbytes) % fitsio.BLOCK))
+        self.stored.append((piece, self.generate_read_header(read_info) if read_info is not None else {}, shape, code))
 
     def generate_read_header(self, read_info):
         """SAMPTIME / DELTATIM / CRPIX1 of a read (exposure.py:412-429)."""
@@ -148,6 +164,21 @@ class Exposure(object):
             cards += traps.cards()
         return fitsio.Header(cards)
 
+    @staticmethod
+    def _sci_cards(samp, i, hdr):
+        """(cards, cache key) of the SCI image of read `samp`, the i-th image of the file."""
+        sampt, delt, crpix = float(hdr.get("SAMPTIME", 0.0)), float(hdr.get("DELTATIM", 0.0)), hdr.get("CRPIX1", 0)
+        cards = [("SAMPNUM", samp, ""), ("SAMPTIME", sampt, "s"), ("DELTATIM", delt, "s"), ("CRPIX1", crpix, ""),
+                 ("EXTVER", i + 1, ""), ("BUNIT", "COUNTS", "")]
+        return cards, (samp, sampt, delt, type(crpix), crpix, i + 1)
+
+    @classmethod
+    def _sci_header_block(cls, samp, i, hdr, shape, code):
+        """The (memoised) header block of that image for a data section of `shape` and type `code` ("f8" or "u2")."""
+        cards, key = cls._sci_cards(samp, i, hdr)
+        return fitsio.cached_header_block(("SCI", shape) + key + (("u2",) if code == "u2" else ()),
+                                          cards, data_shape=shape, dtype_code=code, name="SCI")
+
     def generate_fits(self, out_dir="", filename=None, ldcoeffs=None):
         """Write the HST-style file (exposure.py:133-214): primary header, then for each
         read in REVERSE time order a float64 SCI image (an unsigned 16-bit one when every read is uint16) with SAMPNUM / SAMPTIME / DELTATIM /
@@ -161,6 +192,19 @@ class Exposure(object):
         # os.writev -- what is left under the interpreter lock per file is the primary header's ~100 (memoised) cards.
         # Byte for byte the file fitsio.write([HDU, ...]) produces (tests/test_visit_driver.py).
         primary = fitsio._image_hdu_parts(None, self.generate_science_header(ldcoeffs=ldcoeffs).cards, primary=True)[0]
+        if self.stored:
+            # reads held as their FITS words: the same header blocks, each piece (data section + padding) as it is
+            if self.reads:
+                raise ValueError("an exposure holds its reads as arrays or as stored words, not both")
+            n = len(self.stored)
+            pieces = [primary]
+            for i, (piece, hdr, shape, code) in enumerate(reversed(self.stored)):
+                pieces.append(self._sci_header_block(n - 1 - i, i, hdr, shape, code))
+                pieces.append(piece)
+                for ext in ("ERR", "DQ", "SAMP", "TIME"):
+                    pieces.append(fitsio.cached_header_block((ext, i + 1), [("EXTVER", i + 1, "")], name=ext))
+            fitsio.write_pieces(path, pieces)
+            return path
         n = len(self.reads)
         arrs = [np.asarray(d) for d, _ in self.reads]
         same = n > 0 and all(a.shape == arrs[0].shape and a.ndim == 2 for a in arrs)
@@ -181,19 +225,14 @@ class Exposure(object):
             pad = b"\x00" * ((-cube[0].nbytes) % fitsio.BLOCK)
         for i, (data, hdr) in enumerate(reversed(self.reads)):
             samp = n - 1 - i
-            sampt, delt, crpix = float(hdr.get("SAMPTIME", 0.0)), float(hdr.get("DELTATIM", 0.0)), hdr.get("CRPIX1", 0)
-            cards = [("SAMPNUM", samp, ""), ("SAMPTIME", sampt, "s"), ("DELTATIM", delt, "s"), ("CRPIX1", crpix, ""),
-                     ("EXTVER", i + 1, ""), ("BUNIT", "COUNTS", "")]
             if same:
-                shape = arrs[samp].shape
-                pieces.append(fitsio.cached_header_block(("SCI", shape, samp, sampt, delt, type(crpix), crpix, i + 1) +
-                                                         (("u2",) if u16 else ()),
-                                                         cards, data_shape=shape, dtype_code=code, name="SCI"))
+                pieces.append(self._sci_header_block(samp, i, hdr, arrs[samp].shape, code))
                 pieces.append(memoryview(cube[samp].reshape(-1)).cast("B"))
                 if pad:
                     pieces.append(pad)
             else:
-                pieces += fitsio._image_hdu_parts(np.asarray(data, dtype=np.float64), cards, primary=False, name="SCI")
+                pieces += fitsio._image_hdu_parts(np.asarray(data, dtype=np.float64), self._sci_cards(samp, i, hdr)[0],
+                                                  primary=False, name="SCI")
             for ext in ("ERR", "DQ", "SAMP", "TIME"):
                 pieces.append(fitsio.cached_header_block((ext, i + 1), [("EXTVER", i + 1, "")], name=ext))
         fitsio.write_pieces(path, pieces)   # (replaces an existing file, as the reference's remove + writeto does: exposure.py:211-213)
@@ -221,23 +260,34 @@ class FitsWriterPool(object):
         for t in self._threads:
             t.start()
 
+    @property
+    def n_threads(self):
+        """Writer threads of the pool: files that can be under a writer at a time."""
+        return len(self._threads)
+
     def _work(self):
         while True:
             item = self._q.get()
             if item is None:
                 self._q.task_done()
                 return
-            exposure, out_dir, filename = item
+            exposure, out_dir, filename, done = item
             try:
                 exposure.generate_fits(out_dir, filename)
             except Exception as e:      # surfaced by close()
                 self._errors.append(e)
             finally:
-                self._q.task_done()
+                try:
+                    if done is not None:
+                        done()
+                finally:
+                    self._q.task_done()
 
-    def submit(self, exposure, out_dir, filename):
-        """`exposure.reads` must own their data (not views of a buffer that will be reused)."""
-        self._q.put((exposure, out_dir, filename))
+    def submit(self, exposure, out_dir, filename, done=None):
+        """`exposure.reads` must own their data (not views of a buffer that will be reused) -- unless `done` is given:
+        it is called, on the writer's thread, when the file is out or the write has failed, and the caller keeps the
+        buffer untouched until then (fits_delivery.FitsDelivery)."""
+        self._q.put((exposure, out_dir, filename, done))
 
     def close(self):
         for _ in self._threads:

@@ -230,6 +230,24 @@ class ExposureGenerator(object):
             self.exp_info["sim_time"] = time.time() - start_time
         return self.exposure
 
+    def _fill_stored(self, payload, layout, start_time=None):
+        """The FITS words of this generator's descriptor (device_fits: _lib.Context.wait_fits and its layout) -> its
+        Exposure, holding every read as a stored piece -- views of `payload`, nothing copied: the payload must stay
+        untouched until the file is written."""
+        from . import fits_delivery
+        R = len(self.read_times)
+        S = (1014 if self.SUBARRAY == 1024 else self.SUBARRAY) + 10
+        code = "u2" if layout[2] == 16 else "f8"
+        pieces = fits_delivery.stored_pieces(payload, layout, R + 1)      # plane f holds read R - f
+        self.exposure.add_stored_read(pieces[R], {"cumulative_exp_time": 0.0, "read_exp_time": 0.0, "CRPIX1": 0}, (S, S), code)
+        for r in range(R):
+            self.exposure.add_stored_read(pieces[R - 1 - r], {"cumulative_exp_time": float(self.read_times[r]),
+                                                              "read_exp_time": float(self._read_dt[r]), "CRPIX1": 0}, (S, S), code)
+        assert len(self.exposure.stored) == self.NSAMP
+        if start_time is not None:
+            self.exp_info["sim_time"] = time.time() - start_time
+        return self.exposure
+
     def _host_half(self, x_ref, y_ref, x_jitter, y_jitter, wl, stellar_flux, planet_signal,
                    scan_speed, sample_rate, sample_mid_points=None, sample_durations=None,
                    read_index=None, ssv_generator=None, noise_mean=False, noise_std=False,
@@ -239,7 +257,7 @@ class ExposureGenerator(object):
                    add_initial_bias=True, progress_bar=None, threads=2,
                    rng_mode=_lib.RNG_SPLIT, out_dtype=np.float32, reference_quirks=False,
                    exact_samplers=False, contaminants=None, charge_traps=None, extraction=None,
-                       crrej=None, channels=None, variance=None, optimal=None):
+                       crrej=None, channels=None, variance=None, optimal=None, device_fits=False):
         """scanning_frame's arguments -> (engine, descriptor, start time): the mode's engine (cached after its first
         use) and build_descriptor.  No GPU call once the engine exists."""
         start_time = time.time()
@@ -250,7 +268,8 @@ class ExposureGenerator(object):
             sample_mid_points, sample_durations, read_index, ssv_generator, noise_mean, noise_std, add_dark,
             add_flat, cosmic_rate, sky_background, scale_factor, add_gain_variations, add_non_linear,
             clip_values_det_limits, add_read_noise, add_stellar_noise, add_initial_bias, progress_bar, threads,
-            rng_mode, out_dtype, reference_quirks, exact_samplers, contaminants, charge_traps, extraction, crrej, channels, variance, optimal)
+            rng_mode, out_dtype, reference_quirks, exact_samplers, contaminants, charge_traps, extraction, crrej, channels, variance, optimal,
+            device_fits=device_fits)
         return eng, desc, start_time
 
     def prepare(self, *args, staring=False, **kw):
@@ -272,11 +291,13 @@ class ExposureGenerator(object):
                          add_initial_bias=True, progress_bar=None, threads=2,
                          rng_mode=_lib.RNG_SPLIT, out_dtype=np.float32, reference_quirks=False,
                          exact_samplers=False, contaminants=None, charge_traps=None, extraction=None,
-                       crrej=None, channels=None, variance=None, optimal=None):
+                       crrej=None, channels=None, variance=None, optimal=None, device_fits=False):
         """The host half of scanning_frame: sample timing, scan positions, SSV,
         jitter / seed draws, spectrum crop (exposure_generator.py:247-334) ->
         one wayne_exposure_desc for the device.  Pure host code (`eng` may be
-        None when no GPU is involved, e.g. when sharding a visit on the CPU)."""
+        None when no GPU is involved, e.g. when sharding a visit on the CPU).
+        `device_fits`: Context.upload also asks the device for the reads' FITS words (wayne_exposure_set_fits), the way
+        it applies `extraction`; nothing the device computes for the reads changes."""
         out_dtype = np.dtype(out_dtype)
         if out_dtype not in _lib.OUT_FLAGS:
             raise ValueError("out_dtype must be float32, float64 or uint16, not %s" % out_dtype)
@@ -402,7 +423,7 @@ class ExposureGenerator(object):
             scale_factor=1.0 if scale_factor is None else float(scale_factor),
             noise_mean=float(noise_mean) if noise_mean else 0.0,
             noise_std=float(noise_std) if noise_std else 0.0, sources=contaminants, traps=charge_traps,
-            extraction=self.extraction_plan, **lc)
+            extraction=self.extraction_plan, device_fits=device_fits, **lc)
 
     def direct_image(self, x_ref, y_ref):
         """The unscaled 2-D gaussian direct image used to calibrate x_ref / y_ref

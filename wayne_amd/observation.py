@@ -70,7 +70,11 @@ class Observation(object):
         # it: `spectra_result["spectra_var"]` / ["sky_var"] / ["channels_var"] and the .npz's keys of those names.
         # frame_options["optimal"] (True or an extraction.Optimal; CLI: --optimal [H]) adds the optimal extraction on
         # top of those variances: `spectra_result["optimal"]` / ["optimal_var"] and the .npz's keys of those names.
+        # frame_options["device_fits"] (True; CLI: --device-fits): the device forms the data sections of the _raw files and
+        # run_observation writes every file straight from its slot's pinned mirror (fits_delivery) -- the same files,
+        # without the host's pass over the samples.  The direct image stays on the host path; not with `spectra_only`.
         self.frame_options = {"out_dtype": np.float32}
+        self._fits_active = False    # run_observation's main loop is delivering FITS words (see _generate_exposure)
         self.spectra_out = None
         self.spectra_only = False
         # N > 0 (CLI: --optimal-profile N; needs frame_options["optimal"]): run_observation first forms the visit's
@@ -353,6 +357,9 @@ class Observation(object):
             raise ValueError("spectra_out / spectra_only need frame_options['extraction']")
         if extraction is not None and resume:
             raise ValueError("spectra are not delivered by a resumed visit: the exposures it skips have none")
+        device_fits = bool(self.frame_options.get("device_fits", False))
+        if device_fits and self.spectra_only:
+            raise ValueError("device_fits forms the data sections of the raw files; spectra_only writes none")
         if self.traps_carried:
             # every exposure starts from the state its predecessor left on ONE device: the visit runs whole and in order
             if world > 1:
@@ -400,7 +407,8 @@ class Observation(object):
         from .exposure import FitsWriterPool
         from .pipeline import run_pipelined
         pool = FitsWriterPool() if write_fits_raw else None
-        got_spectra = []              # (index, spectra, sky, plan, x_ref, y_ref, n_rejected or None, channels or None) of every exposure, in delivery order; then its variances or None, then its (optimal, optimal_var) or None
+        fits = device_fits and pool is not None       # (no raw files: nothing to form on the device)
+        got_spectra = []            # (index, spectra, sky, plan, x_ref, y_ref, n_rejected or None, channels or None) of every exposure, in delivery order; then its variances or None, then its (optimal, optimal_var) or None
 
         def prepare(i):
             gen = self._generate_exposure(self.exp_start_times[i], i + 1, write_fits=False, prepare_only=True)
@@ -408,6 +416,13 @@ class Observation(object):
 
         def finish(i, gen, reads):
             frame = None
+            payload = None
+            if fits:
+                # the file's data sections instead of the reads, which stay on the device
+                if extraction is not None:
+                    payload, reads = reads[0], (None,) + tuple(reads[1:])
+                else:
+                    payload, reads = reads, None
             if extraction is not None:
                 reads, spectra, sky = reads
                 spectra, sky = np.array(spectra), np.array(sky)           # (copies: the pinned buffer is reused)
@@ -417,7 +432,12 @@ class Observation(object):
                                           ctx.profile_planes, ctx.channels_opt)
             if reads is not None:
                 frame = gen._fill_exposure(np.array(reads), gen._prepared[2])     # (a copy: the pinned buffer is reused)
-            if pool is not None:
+            if payload is not None:
+                # (views of the pinned mirror, no copy: the slot is not uploaded again until the writer has released it)
+                frame = gen._fill_stored(payload, ctx.layout, gen._prepared[2])
+                pool.submit(frame, self.outdir, "{:04d}_raw.fits".format(i + 1), done=ctx.lease())
+                frames[i + 1] = None
+            elif pool is not None:
                 pool.submit(frame, self.outdir, "{:04d}_raw.fits".format(i + 1))
                 frames[i + 1] = None          # on disk; do not keep 64 MB per exposure alive
             else:
@@ -434,11 +454,19 @@ class Observation(object):
         try:
             # up to 3 exposures in flight on 4 context slots in rotation (even / odd slots run on different HIP streams)
             ctx = eng.ctx
+            n_slots = 4
             if extraction is not None:
                 from .extraction import Delivery
-                ctx = Delivery(eng.ctx, reads=not self.spectra_only)
-            run_pipelined(ctx, mine, prepare, finish, depth=3, n_slots=4)
+                ctx = Delivery(eng.ctx, reads=not self.spectra_only and not fits)
+            if fits:
+                # ... on more slots than that: a slot's pinned mirror belongs to its file until a writer has it out
+                from .fits_delivery import FitsDelivery, slots_for
+                ctx = FitsDelivery(eng.ctx, extraction=ctx if extraction is not None else None)
+                n_slots = slots_for(4, pool.n_threads)
+                self._fits_active = True
+            run_pipelined(ctx, mine, prepare, finish, depth=3, n_slots=n_slots)
         finally:
+            self._fits_active = False
             if pool is not None:
                 pool.close()
         if self.traps_carried:
@@ -561,6 +589,9 @@ class Observation(object):
                       add_read_noise=self.add_read_noise, add_stellar_noise=self.add_stellar_noise,
                       add_initial_bias=self.add_initial_bias, threads=self.threads)
         common.update(self.frame_options)
+        # (device_fits belongs to run_observation's file-writing loop: only its descriptors ask for the FITS words)
+        if common.pop("device_fits", False) and prepare_only and self._fits_active:
+            common["device_fits"] = True
         if self.contaminants:
             common["contaminants"] = self.contaminants
         if self.charge_traps is not None:

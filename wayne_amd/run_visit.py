@@ -3,6 +3,7 @@
     python -m wayne_amd.run_visit -p <parameter_file> [--calibration DIR] [--device N] [--max-exposures M] [--gpus G] [--resume]
                                   [--spectra OUT.npz | --spectra-only OUT.npz] [--reject-cosmics [K]]
                                   [--channels LO:HI:N] [--no-channel-flat] [--variances [RN]] [--optimal [H]] [--optimal-profile N] [--optimal-channels]
+                                  [--float64-reads | --uint16-reads] [--device-fits]
 
 Accepts the reference's parameter files (wayne/run_visit.py:1-9, example
 examples/hd209458b_12181_simulation_parameters.yml): sections `general`
@@ -44,6 +45,10 @@ examples/hd209458b_12181_simulation_parameters.yml): sections `general`
     (default H = 8, 1 .. 16); OUT.npz then also holds optimal, optimal_var [n, NSAMP, S] and optimal_half_width;
     `--optimal-profile N` (with --optimal): the profiles are formed once, from the first N exposures of each group, and
     OUT.npz also holds optimal_profile_exposures;
+  * `--device-fits`: the device forms the data sections of the _raw files (big-endian words in file order, padding
+    included) and every file is written straight from the pinned memory they are copied into: the same files, byte for
+    byte, without the host's pass over the samples (wayne_amd/fits_delivery.py).  With every other option but
+    --spectra-only (which writes no _raw files); the direct image stays on the host path;
   * `--gpus G`: the process starts G rank processes itself (one per GPU of this node, before anything touches a
     GPU) and waits for them; under an external launcher (WORLD_SIZE / RANK set, one process per GPU) it is one
     rank.  Each rank generates its round-robin share of the exposures (observation.py:403-405 is the axis) on the
@@ -207,6 +212,9 @@ def run(argv=None):
     reads.add_argument("--uint16-reads", action="store_true",
                        help="16-bit unsigned reads, the ADC's sample type: the float32 read rounded and saturated to "
                             "0 .. 65535 on the device; the _raw files are then BITPIX 16 / BZERO 32768, a quarter the size")
+    ap.add_argument("--device-fits", action="store_true",
+                    help="form the data sections of the _raw files on the device and write every file straight from pinned "
+                         "memory: the same files, without the host's pass over the samples (not with --spectra-only)")
     spectra = ap.add_mutually_exclusive_group()
     spectra.add_argument("--spectra", metavar="OUT.npz", default=None,
                          help="extract every exposure's column spectra on the device and write them to OUT.npz beside "
@@ -284,6 +292,9 @@ def run(argv=None):
             raise SystemExit("--reject-cosmics needs --spectra or --spectra-only")
         if not (np.isfinite(args.reject_cosmics) and args.reject_cosmics > 0):
             raise SystemExit("--reject-cosmics: K must be finite and > 0")
+    if args.device_fits and args.spectra_only:
+        # (the API's refusal, Observation.run_observation's ValueError, raised before any rank process is started)
+        raise ValueError("--device-fits forms the data sections of the _raw files; --spectra-only writes none")
     if args.resume and (args.spectra or args.spectra_only):
         raise SystemExit("--spectra / --spectra-only cannot be combined with --resume (a skipped exposure has no spectra)")
     if args.gpus < 1 or args.ranks_per_gpu < 1:
@@ -342,6 +353,8 @@ def run(argv=None):
         obs.frame_options["out_dtype"] = np.float64
     if args.uint16_reads:
         obs.frame_options["out_dtype"] = np.uint16
+    if args.device_fits:
+        obs.frame_options["device_fits"] = True
     if args.spectra or args.spectra_only:
         obs.frame_options["extraction"] = True
         if args.reject_cosmics is not None:

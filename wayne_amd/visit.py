@@ -15,6 +15,7 @@ from . import engine as _engine
 from . import extraction as _extraction
 from .exposure import FitsWriterPool
 from .exposure_generator import ExposureGenerator
+from .fits_delivery import FitsDelivery, slots_for
 from .pipeline import run_pipelined
 
 
@@ -50,13 +51,16 @@ class VisitRunner(object):
     # keeps the streams balanced; scripts/probe_pipeline.py: 2 -> 826 /s, 3 -> 646, 4 -> 809 for resident descriptors)
     DEPTH = 4
 
-    def __init__(self, visit, device=0, out_dir=None, out_dtype=np.float32, frame_overrides=None, device_lc=False):
+    def __init__(self, visit, device=0, out_dir=None, out_dtype=np.float32, frame_overrides=None, device_lc=False,
+                 device_fits=False):
         """`device_lc`: hand the device the K + W + 4 numbers of the light-curve model (visit.device_depths)
-        instead of a K x W transit-depth matrix computed on the host."""
+        instead of a K x W transit-depth matrix computed on the host.  `device_fits`: the device forms the files' data
+        sections and `run` writes each file straight from the slot's pinned mirror (fits_delivery): the same files."""
         self.visit, self.device, self.out_dir = visit, device, out_dir
         self.out_dtype = out_dtype
         self.frame_overrides = frame_overrides or {}
         self.device_lc = device_lc
+        self.device_fits = bool(device_fits)
         self.rng_mode = 2            # WAYNE_RNG_SPLIT
         self._eng = None
 
@@ -104,18 +108,29 @@ class VisitRunner(object):
         self.profile_planes = None
         self.channels_opt = self.channels_opt_var = None      # {index: [R + 1, C]} when the optimal channels are formed
         pool = FitsWriterPool() if self.out_dir is not None else None
+        # device_fits: the files' data sections come from the device and each file is written from its slot's pinned
+        # mirror; the reads themselves are fetched only for a caller that asked for them
+        fits = self.device_fits and pool is not None
+        want_reads = keep or on_reads is not None
 
         def prepare(i):
             gen = self.generator(i)
             kw = self.frame_kwargs(i)
             if extraction is not None:
                 kw["extraction"] = extraction
+            if fits:
+                kw["device_fits"] = True
             return gen.build_descriptor(eng, out_dtype=self.out_dtype, rng_mode=self.rng_mode, **kw), gen
 
         def finish(i, gen, got):
-            reads = got
-            if extraction is not None:
+            reads = payload = got
+            if fits:
+                reads = ctx.reads_view
+                if extraction is not None:
+                    payload, spectra, sky = got
+            elif extraction is not None:
                 reads, spectra, sky = got
+            if extraction is not None:
                 if ctx.variances is not None:
                     if self.spectra_var is None:
                         self.spectra_var, self.sky_var = {}, {}
@@ -141,14 +156,24 @@ class VisitRunner(object):
                 on_reads(i, reads)
             if keep:
                 results[i] = reads.copy() if extraction is None else (reads.copy(), spectra.copy(), sky.copy())
-            if pool is not None:
+            if fits:
+                os.makedirs(self.out_dir, exist_ok=True)
+                # (no copy: the slot is not uploaded again until the writer has released it -- FitsDelivery.lease)
+                pool.submit(gen._fill_stored(payload, ctx.layout), self.out_dir, gen.exp_info["filename"], done=ctx.lease())
+            elif pool is not None:
                 os.makedirs(self.out_dir, exist_ok=True)
                 # (a copy: the pinned buffer is reused by the next exposure)
                 pool.submit(gen._fill_exposure(reads.copy()), self.out_dir, gen.exp_info["filename"])
 
-        ctx = eng.ctx if extraction is None else _extraction.Delivery(eng.ctx, reads=True)
+        n_slots = self.DEPTH
+        if fits:
+            inner = None if extraction is None else _extraction.Delivery(eng.ctx, reads=want_reads)
+            ctx = FitsDelivery(eng.ctx, extraction=inner, reads=want_reads)
+            n_slots = slots_for(self.DEPTH, pool.n_threads)
+        else:
+            ctx = eng.ctx if extraction is None else _extraction.Delivery(eng.ctx, reads=True)
         try:
-            run_pipelined(ctx, indices, prepare, finish, self.DEPTH, self.DEPTH)
+            run_pipelined(ctx, indices, prepare, finish, self.DEPTH, n_slots)
         finally:
             if pool is not None:
                 pool.close()
