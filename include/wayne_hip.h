@@ -465,6 +465,16 @@ int wayne_exposure_fetch_spectra_async(wayne_ctx *ctx, int slot);
 int wayne_exposure_wait_spectra(wayne_ctx *ctx, int slot, double **spectra, double **sky);
 /* The blocking form: spectra [(R+1)*S] and sky [R+1] into the caller's arrays.  Synchronises. */
 int wayne_exposure_download_spectra(wayne_ctx *ctx, int slot, double *spectra, double *sky);
+/* The spectra block -- what one copy brings to pinned memory, and where the accessors below point into it -- holds, one
+ * behind the other, float64 unless noted:
+ *   spectra [(R+1)*S], sky [R+1]
+ *   with rejection       n_rejected [R+1] (uint32); whatever follows begins on the next multiple of 8 bytes
+ *   with channels        channels [(R+1)*C]
+ *   with variances       spectra_var [(R+1)*S], sky_var [R+1] and, with channels, channels_var [(R+1)*C]
+ *   with set_optimal     optimal [(R+1)*S], optimal_var [(R+1)*S] and, with the optimal channels, channels_opt and
+ *                        channels_opt_var [(R+1)*C each]
+ * Every setter of the extraction's options changes the layout: what was fetched before it is gone (WAYNE_E_STATE from
+ * the accessors until the next wait_spectra / download_spectra). */
 /*
  * Cosmic-ray rejection on the extraction's difference images (opt-in; without it nothing above changes).  I_r and g are
  * the extraction law's.  For read interval j = 0 .. R-1 let I = I_{j+1}.  A pixel (y, x) is TESTED iff 7 <= y < S-7,

@@ -20,6 +20,7 @@ import extraction_law as law
 import fixed_profile_law as fpl
 import helpers
 import optimal_law
+import spectra_layout_law as sll
 from wayne_amd import _lib, engine, extraction, run_visit
 from wayne_amd.visit import VisitRunner
 
@@ -710,3 +711,75 @@ def test_optimal_channels_with_steps_off_and_short_windows():
     ctx.run(0)
     ctx.download_spectra(0)
     assert ctx.optimal_channels(0)[0].tobytes() == got.tobytes() and ctx.profile_planes(0).any()
+
+
+# ---- the spectra block: one layout, whichever way the options were set (plan::spectra_layout) ----
+
+PRODUCTS = ("spectra", "sky", "n_rejected", "channels", "spectra_var", "sky_var", "channels_var", "optimal", "optimal_var",
+            "channels_opt", "channels_opt_var")
+
+
+def every_product(ctx, slot, spectra, sky):
+    sv, kv, cv = ctx.variances(slot)
+    op, ov = ctx.optimal(slot)
+    co, cov = ctx.optimal_channels(slot)
+    return dict(zip(PRODUCTS, (spectra.copy(), sky.copy(), ctx.rejected(slot), ctx.channels(slot), sv, kv, cv, op, ov, co, cov)))
+
+
+def pinned_addresses(ctx, slot, spectra, sky):
+    """{product: address} in the slot's pinned copy: wait_spectra's views and what the accessors return behind it."""
+    L, h = ctx._L, ctx._h
+    p = {name: (C.POINTER(C.c_uint32)() if name == "n_rejected" else _lib._dp()) for name in PRODUCTS[2:]}
+    ref = {name: C.byref(ptr) for name, ptr in p.items()}
+    at = {"spectra": spectra.ctypes.data, "sky": sky.ctypes.data}
+    assert L.wayne_exposure_rejected(h, slot, ref["n_rejected"]) == 0
+    assert L.wayne_exposure_channels(h, slot, ref["channels"]) == 0
+    assert L.wayne_exposure_variances(h, slot, ref["spectra_var"], ref["sky_var"], ref["channels_var"]) == 0
+    assert L.wayne_exposure_optimal(h, slot, ref["optimal"], ref["optimal_var"]) == 0
+    assert L.wayne_exposure_optimal_channels(h, slot, ref["channels_opt"], ref["channels_opt_var"]) == 0
+    at.update({name: C.cast(ptr, C.c_void_p).value or 0 for name, ptr in p.items()})
+    return at
+
+
+def test_every_product_lies_where_the_layout_says():
+    """tiny_g102: S = 74, R = 2 -- three 4-byte counts, so the channels behind them need padding.  Slot 0 gets every
+    option with its upload; slot 1 is uploaded plain and gets them through the context, the variances first and the
+    rejection last, switched off and on again.  Same bytes in every product, by either way of fetching, and in the pinned
+    copy every product where tests/spectra_layout_law.py puts it."""
+    v = visit("tiny_g102")
+    ctx = engine_of(v).ctx
+    S, R = planes_of(v).S, v.NSAMP - 1
+    assert (S, R) == (74, 2)
+    ch = extraction.Channels.linear(*WIDE[v.grism.name], 5)
+    over = dict(cosmic_rate=busy_rate(v), stellar_flux=np.asarray(v.stellar_flux) * BRIGHTER["tiny_g102"])
+    opts = extraction.ExtractionOptions(margin=40, crrej=True, channels=ch, variance=extraction.Variances(RN),
+                                        optimal=extraction.Optimal(1, channels=True))
+    desc, gen = descriptor(v, 0, opts, **over)
+    plan = gen.extraction_plan
+    plain, _ = descriptor(v, 0, extraction.ExtractionOptions(margin=40), **over)
+    ctx.upload(0, desc)
+    ctx.upload(1, plain)
+    ctx.set_variance(1, plan.variance)
+    ctx.set_optimal(1, extraction.Optimal(1))
+    ctx.set_channels(1, plan.channels, plan.row_solution)
+    ctx.set_crrej(1, plan.crrej)
+    ctx.set_optimal_channels(1)
+    ctx.set_crrej(1, None)
+    ctx.set_crrej(1, plan.crrej)
+    for slot in (0, 1):
+        assert ctx.has_crrej(slot) and ctx.has_channels(slot) and ctx.has_variance(slot) and ctx.has_optimal(slot) and ctx.has_optimal_channels(slot)
+        ctx.run(slot)
+    down = [every_product(ctx, slot, *ctx.download_spectra(slot)) for slot in (0, 1)]
+    want, total = sll.layout(S, R, crrej=True, C=5, variance=True, optimal=True, optimal_channels=True)
+    assert want["channels"] == want["n_rejected"] + 3 * 4 + 4 and sorted(want) == sorted(PRODUCTS)
+    for slot in (0, 1):
+        ctx.fetch_spectra_async(slot)
+        spectra, sky = ctx.wait_spectra(slot)
+        at = pinned_addresses(ctx, slot, spectra, sky)
+        assert {name: at[name] - at["spectra"] for name in PRODUCTS} == want, slot
+        pinned = every_product(ctx, slot, spectra, sky)
+        for name in PRODUCTS:
+            assert pinned[name].tobytes() == down[slot][name].tobytes() == down[0][name].tobytes(), (slot, name)
+    got = down[0]
+    assert got["n_rejected"].sum() > 0 and got["n_rejected"].dtype == np.uint32
+    assert all(got[name].any() for name in PRODUCTS) and got["channels_opt"].shape == (R + 1, 5)

@@ -541,6 +541,60 @@ inline bool profile_rows_match(int S, int R, unsigned steps, const int* row_lo, 
   return true;
 }
 
+// Where the windows begin in the profile planes: row_off[p] = sum_{p' < p} rows_{p'} S doubles over ALL R + 1 windows
+// (row_off may be null).  Returns the doubles of all of them.
+inline size_t profile_offsets(int S, int R, unsigned steps, const int* row_lo, const int* row_hi, size_t* row_off) {
+  size_t off = 0;
+  for (int p = 0; p <= R; ++p) {
+    if (row_off) row_off[p] = off;
+    off += (size_t)profile_window_rows(S, R, steps, row_lo, row_hi, p) * (size_t)S;
+  }
+  return off;
+}
+
+// The layout of a slot's spectra block, on the device and in every host copy of it (include/wayne_hip.h): the byte
+// offset of every region, kNoRegion for one that is off, and the block's length.  Float64 unless noted:
+//   spectra [(R+1)*S], sky [R+1];  with rejection n_rejected [R+1] (uint32);  with channels, channels [(R+1)*C];
+//   with variances spectra_var [(R+1)*S], sky_var [R+1] and, with channels, channels_var [(R+1)*C];
+//   with the optimal extraction optimal, optimal_var [(R+1)*S each] and, with the optimal channels, channels_opt,
+//   channels_opt_var [(R+1)*C each]
+// one behind the other in this order, each beginning on a multiple of 8 bytes.
+constexpr size_t kNoRegion = ~(size_t)0;
+struct SpectraLayout {
+  size_t spectra = 0, sky = kNoRegion, n_rejected = kNoRegion, channels = kNoRegion;
+  size_t spectra_var = kNoRegion, sky_var = kNoRegion, channels_var = kNoRegion;
+  size_t optimal = kNoRegion, optimal_var = kNoRegion, channels_opt = kNoRegion, channels_opt_var = kNoRegion;
+  size_t bytes = 0;
+};
+
+// C = 0: no channels.  The optimal products stand on the variances, the optimal channels on those and the channels:
+// a switch whose footing is off counts as off.
+inline SpectraLayout spectra_layout(int S, int R, bool crrej, int C, bool variance, bool optimal, bool optimal_channels) {
+  const size_t NP = (size_t)R + 1, cols = NP * (size_t)S * sizeof(double), chans = NP * (size_t)C * sizeof(double);
+  SpectraLayout l;
+  auto take = [&l](size_t n) {
+    const size_t at = (l.bytes + 7) & ~(size_t)7;
+    l.bytes = at + n;
+    return at;
+  };
+  l.spectra = take(cols);
+  l.sky = take(NP * sizeof(double));
+  if (crrej) l.n_rejected = take(NP * sizeof(uint32_t));
+  if (C > 0) l.channels = take(chans);
+  if (!variance) return l;
+  l.spectra_var = take(cols);
+  l.sky_var = take(NP * sizeof(double));
+  if (C > 0) l.channels_var = take(chans);
+  if (!optimal) return l;
+  l.optimal = take(cols);
+  l.optimal_var = take(cols);
+  if (optimal_channels && C > 0) {
+    l.channels_opt = take(chans);
+    l.channels_opt_var = take(chans);
+  }
+  return l;
+}
+
 // The mask rows of a valid extraction plan: [min_p row_lo[p], max_p row_hi[p]) over the products that are formed.
 inline void crrej_mask_rows(int R, unsigned steps, const int* row_lo, const int* row_hi, int* lo, int* hi) {
   const int n = (steps & X_LAST_READ) ? R + 1 : R;

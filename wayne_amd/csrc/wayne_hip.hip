@@ -14,6 +14,7 @@
 #include <map>
 #include <new>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "kernels.h"
@@ -219,51 +220,42 @@ struct Slot : SourceState {
   double hist_gap = 0., hist_fill[2] = {0., 0.};
   int hist_lit = 0;
   // spectral extraction of this exposure (wayne_exposure_set_extraction; cleared by upload): the plan, the partial sums
-  // [2][chunks][R+1][S], the result -- spectra [(R+1)*S] then sky [R+1] -- and its pinned host copy, followed by a
-  // copy of `misc` (fetch_spectra_async / wait_spectra)
+  // [2][chunks][R+1][S], and the result: the spectra block `ex_out`, laid out by `lay` (plan::spectra_layout; kept by
+  // ex_relayout, which every setter below calls), with its pinned host copy followed by a copy of `misc`
+  // (fetch_spectra_async / wait_spectra).  `ex_base`: the block as the last wait_spectra (in ex_pinned) or
+  // download_spectra (in ex_host, which holds nothing in front of n_rejected) brought it back; null before any
   bool extract_on = false;
   wayne_extract_desc ex{};
   int ex_chunks = 0;
   DevBuf ex_part, ex_out;
+  plan::SpectraLayout lay;
   PinnedBuf ex_pinned;
   Misc* ex_pinned_misc = nullptr;
+  const char* ex_base = nullptr;
+  std::vector<double> ex_host;
   // cosmic-ray rejection of the extraction (wayne_exposure_set_crrej; cleared by upload and set_extraction): the flag
-  // plane [S*S] uint16, the chunks' flag counts [chunks][R+1][S], and n_rejected [R+1] behind sky in ex_out.  `ex_rej`:
-  // the counts the last wait_spectra / download_spectra brought back (null before any)
+  // plane [S*S] uint16 and the chunks' flag counts [chunks][R+1][S]
   bool crrej_on = false;
   double cr_k = 0., cr_rn = 0.;
   int cr_lo = 0, cr_hi = 0;          // the mask rows
   DevBuf cr_mask, ex_part_n;
-  const uint32_t* ex_rej = nullptr;
-  std::vector<uint32_t> ex_rej_host;
   // wavelength-binned channels of the extraction (wayne_exposure_set_channels; cleared by upload and set_extraction, not
-  // by set_crrej): edges [C+1], wl_a [S], wl_b [S] in an arena of their own, the row groups' sums [chunks][4][R+1][2][C], and
-  // channels [(R+1)*C] behind sky / n_rejected in ex_out, 8-byte aligned.  `ch_res`: what the last wait_spectra /
-  // download_spectra brought back (null before any)
+  // by set_crrej): edges [C+1], wl_a [S], wl_b [S] in an arena of their own and the row groups' sums [chunks][4][R+1][2][C]
   bool chan_on = false;
   int ch_C = 0, ch_lo = 0, ch_hi = 0;
   uint32_t ch_flags = 0;
   StageArena ch_stage;
   DevBuf ch_edges, ch_wa, ch_wb, ch_part;
-  const double* ch_res = nullptr;
-  std::vector<double> ch_host;
   // variances of the extraction (wayne_exposure_set_variance; cleared by upload and set_extraction, not by set_crrej or
-  // set_channels): the chunks' sums [chunks][R+1][S] and, with channels, the row groups' [chunks][4][R+1][C]; the result --
-  // spectra_var [(R+1)*S], sky_var [R+1] and, with channels, channels_var [(R+1)*C] -- behind everything else in ex_out,
-  // 8-byte aligned.  `var_res`: that block as the last wait_spectra / download_spectra brought it back (null before any)
+  // set_channels): the chunks' sums [chunks][R+1][S] and, with channels, the row groups' [chunks][4][R+1][C]
   bool var_on = false;
   double var_rn = 0.;
   DevBuf ex_part_v, ch_part_v;
-  const double* var_res = nullptr;
-  std::vector<double> var_host;
   // optimal extraction on top of the variances (wayne_exposure_set_optimal; cleared by what clears the variances): the
-  // chunks' sums [3][chunks][R+1][S]; the result -- optimal [(R+1)*S], optimal_var [(R+1)*S] -- behind the variances in
-  // ex_out.  `opt_res`: that block as the last wait_spectra / download_spectra brought it back (null before any)
+  // chunks' sums [3][chunks][R+1][S]
   bool opt_on = false;
   int opt_H = 0;
   DevBuf opt_part;
-  const double* opt_res = nullptr;
-  std::vector<double> opt_host;
   // profile planes of the optimal extraction (cleared by what clears it).  Delivery (wayne_exposure_deliver_profile):
   // S1 of every window pixel [sum_p rows_p * S] and its pinned copy, fetched by a call of its own (`prof_fetched`: a copy
   // is enqueued or done).  A supplied profile (wayne_exposure_set_optimal_profile): the device copy in the same layout and
@@ -275,8 +267,7 @@ struct Slot : SourceState {
   int prof_rows[kExtractProducts] = {0};
   DevBuf prof_fix;
   // optimal channels (wayne_exposure_set_optimal_channels; needs the optimal extraction AND channels; cleared by what
-  // clears either): the row groups' sums [chunks][4][R+1][3][C]; channels_opt and channels_opt_var [(R+1)*C each] ride
-  // behind optimal_var in ex_out
+  // clears either): the row groups' sums [chunks][4][R+1][3][C]
   bool optch_on = false;
   DevBuf optch_part;
   bool prof_fix_valid = false;       // prof_fix holds the profile of prof_rows / prof_fix_n and the caller's tag prof_fix_hash (kept across clears)
@@ -767,44 +758,18 @@ void (*select_ramp(const wayne_ctx* c, const Slot& s, std::string* name, RampTra
 static_assert(WAYNE_MAX_CHANNELS == kChanMaxChannels && WAYNE_MAX_CHANNEL_HULL == kChanMaxHull && WAYNE_C_FLAT == C_FLAT,
               "include/wayne_hip.h and plan_consts.h must agree on the channels' caps and flag");
 
-// Where channels [(R+1)*C] begin in a slot's spectra block: behind spectra, sky and (with rejection) n_rejected, on the
-// next multiple of 8 bytes.
-size_t channels_offset(const wayne_ctx* c, const Slot& s) {
-  const size_t b = (size_t)(s.R + 1) * ((size_t)c->S + 1) * sizeof(double) + (s.crrej_on ? (size_t)(s.R + 1) * sizeof(uint32_t) : 0);
-  return (b + 7) & ~(size_t)7;
+// The kernels of an exposure's reads are templates on the reads' type and on a few switches.  with_reads calls f with a
+// tag of the type for out_kind(flags), with_flag with std::true_type / std::false_type: the branches are written here only.
+template <class T> struct Reads { using type = T; };
+template <class F> void with_reads(int out, F&& f) {
+  if (out == 1) f(Reads<double>{});
+  else if (out == 2) f(Reads<uint16_t>{});
+  else f(Reads<float>{});
 }
+template <class F> auto with_flag(bool on, F&& f) { return on ? f(std::true_type{}) : f(std::false_type{}); }
 
-// Where the variances begin in a slot's spectra block: behind everything else (the channels, if any), on a multiple of
-// 8 bytes; and their doubles: spectra_var [(R+1)*S], sky_var [R+1], with channels channels_var [(R+1)*C].
-size_t variance_offset(const wayne_ctx* c, const Slot& s) {
-  return channels_offset(c, s) + (s.chan_on ? (size_t)(s.R + 1) * s.ch_C * sizeof(double) : 0);
-}
-size_t variance_count(const wayne_ctx* c, const Slot& s) {
-  return (size_t)(s.R + 1) * ((size_t)c->S + 1 + (s.chan_on ? (size_t)s.ch_C : 0));
-}
-
-// Where optimal and optimal_var [(R+1)*S each] begin in a slot's spectra block: behind the variances.
-size_t optimal_offset(const wayne_ctx* c, const Slot& s) {
-  return variance_offset(c, s) + variance_count(c, s) * sizeof(double);
-}
-// (with the optimal channels: channels_opt and channels_opt_var [(R+1)*C each] behind optimal_var)
-size_t optimal_count(const wayne_ctx* c, const Slot& s) {
-  return (size_t)2 * (s.R + 1) * ((size_t)c->S + (s.optch_on ? (size_t)s.ch_C : 0));
-}
-
-template <bool CR, bool VAR>
-void launch_bins(int out, dim3 grid, dim3 block, hipStream_t st, const ExtractArgs& a, const ChannelArgs& ch) {
-  if (out == 1) hipLaunchKernelGGL((k_extract_bins<double, CR, VAR>), grid, block, 0, st, a, ch);
-  else if (out == 2) hipLaunchKernelGGL((k_extract_bins<uint16_t, CR, VAR>), grid, block, 0, st, a, ch);
-  else hipLaunchKernelGGL((k_extract_bins<float, CR, VAR>), grid, block, 0, st, a, ch);
-}
-
-template <bool CR, bool VAR>
-void launch_rows(int out, dim3 grid, dim3 block, hipStream_t st, const ExtractArgs& a) {
-  if (out == 1) hipLaunchKernelGGL((k_extract_rows<double, CR, VAR>), grid, block, 0, st, a);
-  else if (out == 2) hipLaunchKernelGGL((k_extract_rows<uint16_t, CR, VAR>), grid, block, 0, st, a);
-  else hipLaunchKernelGGL((k_extract_rows<float, CR, VAR>), grid, block, 0, st, a);
-}
+// A region of slot `s`'s spectra block on the device (s.lay: plan::spectra_layout).
+double* ex_region(const Slot& s, size_t offset) { return (double*)((char*)s.ex_out.p + offset); }
 
 // The channels of slot `s` (wayne_exposure_set_channels) behind k_extract_finish, from `a` as launch_extract filled it.
 ChannelArgs channel_args(const wayne_ctx* c, const Slot& s) {
@@ -818,14 +783,6 @@ ChannelArgs channel_args(const wayne_ctx* c, const Slot& s) {
   return ch;
 }
 
-template <bool CR, bool FIXED>
-void launch_bins_opt(int out, dim3 grid, dim3 block, hipStream_t st, const ExtractArgs& a, const ChannelArgs& ch, const OptimalArgs& o,
-                     const ProfileArgs& f, const OptChanArgs& oc) {
-  if (out == 1) hipLaunchKernelGGL((k_extract_bins_opt<double, CR, FIXED>), grid, block, 0, st, a, ch, o, f, oc);
-  else if (out == 2) hipLaunchKernelGGL((k_extract_bins_opt<uint16_t, CR, FIXED>), grid, block, 0, st, a, ch, o, f, oc);
-  else hipLaunchKernelGGL((k_extract_bins_opt<float, CR, FIXED>), grid, block, 0, st, a, ch, o, f, oc);
-}
-
 // The optimal channels of slot `s` (wayne_exposure_set_optimal_channels) behind k_extract_optimal_finish, from `a`, `o` and
 // `f` as launch_optimal filled them.
 template <bool CR>
@@ -833,12 +790,16 @@ int launch_optimal_channels(wayne_ctx* c, Slot& s, const ExtractArgs& a, const O
   const ChannelArgs ch = channel_args(c, s);
   OptChanArgs oc{};
   oc.part = s.optch_part.as<double>();
-  oc.channels_opt = o.optimal_var + (size_t)(a.R + 1) * a.S;
-  oc.channels_opt_var = oc.channels_opt + (size_t)(a.R + 1) * ch.C;
+  oc.channels_opt = ex_region(s, s.lay.channels_opt);
+  oc.channels_opt_var = ex_region(s, s.lay.channels_opt_var);
   const dim3 grid((unsigned)blocks, (unsigned)kChanGroups), block(kExtractThreads);
   if (blocks > 0) {
-    if (s.prof_fixed) launch_bins_opt<CR, true>(out, grid, block, c->stream, a, ch, o, f, oc);
-    else launch_bins_opt<CR, false>(out, grid, block, c->stream, a, ch, o, f, oc);
+    with_reads(out, [&](auto t) {
+      with_flag(s.prof_fixed, [&](auto fixed) {
+        hipLaunchKernelGGL((k_extract_bins_opt<typename decltype(t)::type, CR, decltype(fixed)::value>), grid, block, 0, c->stream,
+                           a, ch, o, f, oc);
+      });
+    });
     HIP_TRY(c, hipGetLastError());
   }
   hipLaunchKernelGGL(k_extract_bins_opt_finish, dim3((unsigned)(a.R + 1)), dim3(kChanMaxChannels), 0, c->stream, a, ch, oc);
@@ -846,29 +807,23 @@ int launch_optimal_channels(wayne_ctx* c, Slot& s, const ExtractArgs& a, const O
   return WAYNE_OK;
 }
 
-int launch_channels(wayne_ctx* c, Slot& s, const ExtractArgs& a, int blocks, int out, bool cr) {
+template <bool CR, bool VAR>
+int launch_channels(wayne_ctx* c, Slot& s, const ExtractArgs& a, int blocks, int out) {
   ChannelArgs ch = channel_args(c, s);
   ch.part = s.ch_part.as<double>();
-  ch.channels = (double*)((char*)s.ex_out.p + channels_offset(c, s));
-  const bool var = s.var_on;
-  if (var) {
+  ch.channels = ex_region(s, s.lay.channels);
+  if (VAR) {
     ch.part_v = s.ch_part_v.as<double>();
-    ch.channels_var = a.sky_var + (a.R + 1);
+    ch.channels_var = ex_region(s, s.lay.channels_var);
   }
   const dim3 grid((unsigned)blocks, (unsigned)kChanGroups), block(kExtractThreads);
   if (blocks > 0) {
-    if (cr) {
-      if (var) launch_bins<true, true>(out, grid, block, c->stream, a, ch);
-      else launch_bins<true, false>(out, grid, block, c->stream, a, ch);
-    } else {
-      if (var) launch_bins<false, true>(out, grid, block, c->stream, a, ch);
-      else launch_bins<false, false>(out, grid, block, c->stream, a, ch);
-    }
+    with_reads(out, [&](auto t) {
+      hipLaunchKernelGGL((k_extract_bins<typename decltype(t)::type, CR, VAR>), grid, block, 0, c->stream, a, ch);
+    });
     HIP_TRY(c, hipGetLastError());
   }
-  const dim3 products_grid((unsigned)(a.R + 1)), channels_block(kChanMaxChannels);
-  if (var) hipLaunchKernelGGL(k_extract_bins_finish<true>, products_grid, channels_block, 0, c->stream, a, ch);
-  else hipLaunchKernelGGL(k_extract_bins_finish<false>, products_grid, channels_block, 0, c->stream, a, ch);
+  hipLaunchKernelGGL(k_extract_bins_finish<VAR>, dim3((unsigned)(a.R + 1)), dim3(kChanMaxChannels), 0, c->stream, a, ch);
   HIP_TRY(c, hipGetLastError());
   return WAYNE_OK;
 }
@@ -882,50 +837,60 @@ int launch_optimal(wayne_ctx* c, Slot& s, const ExtractArgs& a, dim3 grid, int o
   OptimalArgs o{};
   o.H = s.opt_H;
   o.part = s.opt_part.as<double>();
-  o.optimal = (double*)((char*)s.ex_out.p + optimal_offset(c, s));
-  o.optimal_var = o.optimal + (size_t)(a.R + 1) * a.S;
+  o.optimal = ex_region(s, s.lay.optimal);
+  o.optimal_var = ex_region(s, s.lay.optimal_var);
   const dim3 block(kExtractThreads);
   ProfileArgs f{};
-  if (s.prof_deliver || s.prof_fixed) {
-    size_t off = 0;
-    for (int p = 0; p <= a.R; ++p) { f.row_off[p] = off; off += (size_t)plan::profile_window_rows(a.S, a.R, a.steps, a.row_lo, a.row_hi, p) * a.S; }
-    f.planes = s.prof_deliver ? s.prof_planes.as<double>() : nullptr;
-    f.fixed = s.prof_fixed ? s.prof_fix.as<double>() : nullptr;
-  }
+  const size_t planes_n = plan::profile_offsets(a.S, a.R, a.steps, a.row_lo, a.row_hi, f.row_off);
+  f.planes = s.prof_deliver ? s.prof_planes.as<double>() : nullptr;
+  f.fixed = s.prof_fixed ? s.prof_fix.as<double>() : nullptr;
   if (s.prof_deliver) {
     // S1 of every window pixel; a product that is not formed (the last read, switched off) delivers zeros
     if (!(a.steps & X_LAST_READ))
-      HIP_TRY(c, hipMemsetAsync(f.planes + f.row_off[a.R], 0, (size_t)plan::profile_window_rows(a.S, a.R, a.steps, a.row_lo, a.row_hi, a.R) * a.S * sizeof(double), c->stream));
+      HIP_TRY(c, hipMemsetAsync(f.planes + f.row_off[a.R], 0, (planes_n - f.row_off[a.R]) * sizeof(double), c->stream));
     if (grid.y > 0) {
-      if (out == 1) hipLaunchKernelGGL((k_extract_profile<double, CR>), grid, block, 0, c->stream, a, o, f);
-      else if (out == 2) hipLaunchKernelGGL((k_extract_profile<uint16_t, CR>), grid, block, 0, c->stream, a, o, f);
-      else hipLaunchKernelGGL((k_extract_profile<float, CR>), grid, block, 0, c->stream, a, o, f);
+      with_reads(out, [&](auto t) {
+        hipLaunchKernelGGL((k_extract_profile<typename decltype(t)::type, CR>), grid, block, 0, c->stream, a, o, f);
+      });
       HIP_TRY(c, hipGetLastError());
     }
     s.prof_valid = true;
     s.prof_fetched = false;          // (a copy fetched before this run holds the run before)
   }
-  if (grid.y > 0 && s.prof_fixed) {
-    if (out == 1) hipLaunchKernelGGL((k_extract_optimal_fixed<double, CR>), grid, block, 0, c->stream, a, o, f);
-    else if (out == 2) hipLaunchKernelGGL((k_extract_optimal_fixed<uint16_t, CR>), grid, block, 0, c->stream, a, o, f);
-    else hipLaunchKernelGGL((k_extract_optimal_fixed<float, CR>), grid, block, 0, c->stream, a, o, f);
-    HIP_TRY(c, hipGetLastError());
-  } else if (grid.y > 0) {
-    if (out == 1) hipLaunchKernelGGL((k_extract_optimal<double, CR>), grid, block, 0, c->stream, a, o);
-    else if (out == 2) hipLaunchKernelGGL((k_extract_optimal<uint16_t, CR>), grid, block, 0, c->stream, a, o);
-    else hipLaunchKernelGGL((k_extract_optimal<float, CR>), grid, block, 0, c->stream, a, o);
+  if (grid.y > 0) {
+    with_reads(out, [&](auto t) {
+      using T = typename decltype(t)::type;
+      if (s.prof_fixed) hipLaunchKernelGGL((k_extract_optimal_fixed<T, CR>), grid, block, 0, c->stream, a, o, f);
+      else hipLaunchKernelGGL((k_extract_optimal<T, CR>), grid, block, 0, c->stream, a, o);
+    });
     HIP_TRY(c, hipGetLastError());
   }
   hipLaunchKernelGGL(k_extract_optimal_finish, dim3((unsigned)(a.R + 1)), block, 0, c->stream, a, o);
   HIP_TRY(c, hipGetLastError());
-  if (s.optch_on) {
-    if (!(s.prof_deliver || s.prof_fixed)) {
-      size_t off = 0;
-      for (int p = 0; p <= a.R; ++p) { f.row_off[p] = off; off += (size_t)plan::profile_window_rows(a.S, a.R, a.steps, a.row_lo, a.row_hi, p) * a.S; }
-    }
-    return launch_optimal_channels<CR>(c, s, a, o, f, (int)grid.y, out);
+  return s.optch_on ? launch_optimal_channels<CR>(c, s, a, o, f, (int)grid.y, out) : WAYNE_OK;
+}
+
+// The launches of launch_extract, which filled `a`: with rejection the flag plane first, then the row sums of every
+// product, the chunks added up, and behind them the optimal extraction and the channels.
+template <bool CR, bool VAR>
+int launch_extract_as(wayne_ctx* c, Slot& s, const ExtractArgs& a, int products, int out) {
+  const dim3 grid((unsigned)((a.S + 63) / 64), (unsigned)a.first_chunk[products]);
+  const dim3 block(kExtractThreads);
+  if (CR) {
+    // tiles of the mask rows
+    const dim3 tiles((unsigned)((a.S + kCrTileCols - 1) / kCrTileCols), (unsigned)((a.m_hi - a.m_lo + kCrTileRows - 1) / kCrTileRows));
+    with_reads(out, [&](auto t) { hipLaunchKernelGGL((k_extract_crmask<typename decltype(t)::type>), tiles, block, 0, c->stream, a); });
+    HIP_TRY(c, hipGetLastError());
   }
-  return WAYNE_OK;
+  with_reads(out, [&](auto t) {
+    hipLaunchKernelGGL((k_extract_rows<typename decltype(t)::type, CR, VAR>), grid, block, 0, c->stream, a);
+  });
+  HIP_TRY(c, hipGetLastError());
+  hipLaunchKernelGGL((k_extract_finish<CR, VAR>), dim3((unsigned)(a.R + 1)), block, 0, c->stream, a);
+  HIP_TRY(c, hipGetLastError());
+  if (s.opt_on)
+    if (int rc = launch_optimal<CR>(c, s, a, grid, out)) return rc;
+  return s.chan_on ? launch_channels<CR, VAR>(c, s, a, a.first_chunk[products], out) : WAYNE_OK;
 }
 
 // The extraction of slot `s` (wayne_exposure_set_extraction) behind its ramp kernel: the row sums of every product, then
@@ -947,58 +912,33 @@ int launch_extract(wayne_ctx* c, Slot& s) {
   for (int i = 0; i < 4; ++i) a.lin[i] = c->has_lin ? c->lin[i].as<float>() : nullptr;
   a.dark = c->has_dark ? c->dark_sci.as<float>() : nullptr;
   a.part = s.ex_part.as<double>();
-  a.spectra = s.ex_out.as<double>();
-  a.sky_out = s.ex_out.as<double>() + (size_t)(R + 1) * S;
-  const bool cr = s.crrej_on;
-  if (cr) {
+  a.spectra = ex_region(s, s.lay.spectra);
+  a.sky_out = ex_region(s, s.lay.sky);
+  if (s.crrej_on) {
     a.mask = s.cr_mask.as<uint16_t>();
     a.part_n = s.ex_part_n.as<unsigned>();
-    a.n_rej = (unsigned*)(a.sky_out + (R + 1));
+    a.n_rej = (unsigned*)ex_region(s, s.lay.n_rejected);
     a.m_lo = s.cr_lo; a.m_hi = s.cr_hi;
     a.k2 = s.cr_k * s.cr_k; a.rn2 = s.cr_rn * s.cr_rn;
   }
-  const bool var = s.var_on;
-  if (var) {
+  if (s.var_on) {
     a.vrn2 = s.var_rn * s.var_rn;
     a.part_v = s.ex_part_v.as<double>();
-    a.spectra_var = (double*)((char*)s.ex_out.p + variance_offset(c, s));
-    a.sky_var = a.spectra_var + (size_t)(R + 1) * S;
+    a.spectra_var = ex_region(s, s.lay.spectra_var);
+    a.sky_var = ex_region(s, s.lay.sky_var);
   }
   const int products = (a.steps & X_LAST_READ) ? R + 1 : R;
   for (int p = 0; p <= kExtractProducts; ++p) a.first_chunk[p] = 0;
   for (int p = 0; p < products; ++p)
     a.first_chunk[p + 1] = a.first_chunk[p] + (a.row_hi[p] - a.row_lo[p] + kExtractRows - 1) / kExtractRows;
   for (int p = products; p < kExtractProducts; ++p) a.first_chunk[p + 1] = a.first_chunk[p];
-  const dim3 grid((unsigned)((S + 63) / 64), (unsigned)a.first_chunk[products]);
   ProfScope ps(c, PK_EXTRACT);
   const int out = out_kind(s.d.flags);
-  const dim3 block(kExtractThreads), products_grid((unsigned)(R + 1));
-  if (cr) {
-    // the flag plane first: tiles of the mask rows
-    const dim3 tiles((unsigned)((S + kCrTileCols - 1) / kCrTileCols), (unsigned)((a.m_hi - a.m_lo + kCrTileRows - 1) / kCrTileRows));
-    if (out == 1) hipLaunchKernelGGL((k_extract_crmask<double>), tiles, block, 0, c->stream, a);
-    else if (out == 2) hipLaunchKernelGGL((k_extract_crmask<uint16_t>), tiles, block, 0, c->stream, a);
-    else hipLaunchKernelGGL((k_extract_crmask<float>), tiles, block, 0, c->stream, a);
-    HIP_TRY(c, hipGetLastError());
-    if (var) launch_rows<true, true>(out, grid, block, c->stream, a);
-    else launch_rows<true, false>(out, grid, block, c->stream, a);
-    HIP_TRY(c, hipGetLastError());
-    if (var) hipLaunchKernelGGL((k_extract_finish<true, true>), products_grid, block, 0, c->stream, a);
-    else hipLaunchKernelGGL((k_extract_finish<true, false>), products_grid, block, 0, c->stream, a);
-    HIP_TRY(c, hipGetLastError());
-    if (s.opt_on)
-      if (int rc = launch_optimal<true>(c, s, a, grid, out)) return rc;
-    return s.chan_on ? launch_channels(c, s, a, a.first_chunk[products], out, true) : WAYNE_OK;
-  }
-  if (var) launch_rows<false, true>(out, grid, block, c->stream, a);
-  else launch_rows<false, false>(out, grid, block, c->stream, a);
-  HIP_TRY(c, hipGetLastError());
-  if (var) hipLaunchKernelGGL((k_extract_finish<false, true>), products_grid, block, 0, c->stream, a);
-  else hipLaunchKernelGGL((k_extract_finish<false, false>), products_grid, block, 0, c->stream, a);
-  HIP_TRY(c, hipGetLastError());
-  if (s.opt_on)
-    if (int rc = launch_optimal<false>(c, s, a, grid, out)) return rc;
-  return s.chan_on ? launch_channels(c, s, a, a.first_chunk[products], out, false) : WAYNE_OK;
+  return with_flag(s.crrej_on, [&](auto cr) {
+    return with_flag(s.var_on, [&](auto var) {
+      return launch_extract_as<decltype(cr)::value, decltype(var)::value>(c, s, a, products, out);
+    });
+  });
 }
 
 // The layout of a slot's FITS payload (wayne_fits_layout): false for a side or a flag word it is not defined for.
@@ -1027,12 +967,53 @@ int launch_fits(wayne_ctx* c, Slot& s) {
   const size_t cap = std::max<size_t>(1, (size_t)kFitsMaxBlocks / (size_t)a.planes);
   const dim3 grid((unsigned)std::min(cap, (units + kFitsThreads - 1) / kFitsThreads), (unsigned)a.planes), block(kFitsThreads);
   ProfScope ps(c, PK_FITS);
-  if (out == 1) hipLaunchKernelGGL((k_fits_words<double>), grid, block, 0, c->stream, a);
-  else if (out == 2) hipLaunchKernelGGL((k_fits_words<unsigned short>), grid, block, 0, c->stream, a);
-  else hipLaunchKernelGGL((k_fits_words<float>), grid, block, 0, c->stream, a);
+  with_reads(out, [&](auto t) { hipLaunchKernelGGL((k_fits_words<typename decltype(t)::type>), grid, block, 0, c->stream, a); });
   HIP_TRY(c, hipGetLastError());
   return WAYNE_OK;
 }
+
+// No extraction on slot `s` (upload, set_extraction): every switch of it off, nothing fetched.  The profile planes and
+// the optimal channels go with the optimal extraction wherever that is cleared.
+void ex_clear(Slot& s) {
+  s.extract_on = s.crrej_on = s.chan_on = s.var_on = s.opt_on = s.optch_on = false;
+  s.prof_deliver = s.prof_fetched = s.prof_valid = s.prof_fixed = false;
+  s.ex_pinned_misc = nullptr;
+  s.ex_base = nullptr;
+}
+
+// What every setter of the extraction calls once it has changed its switch: the spectra block's layout follows the
+// switches, the device block has room for it, and what was fetched -- it has another layout -- is gone.  Nothing of the
+// block is kept: the next run writes all of it.  The room always includes the rejection's counts, so that set_crrej,
+// before or after the other setters, never moves the block: DevBuf::reserve frees and allocates when it grows.  Without
+// room the slot is left without extraction (the block is gone).
+int ex_relayout(wayne_ctx* c, Slot& s) {
+  const int C = s.chan_on ? s.ch_C : 0;
+  s.lay = plan::spectra_layout(c->S, s.R, s.crrej_on, C, s.var_on, s.opt_on, s.optch_on);
+  s.ex_pinned_misc = nullptr;
+  s.ex_base = nullptr;
+  (void)hipSetDevice(c->device);
+  const hipError_t e = s.ex_out.reserve(plan::spectra_layout(c->S, s.R, true, C, s.var_on, s.opt_on, s.optch_on).bytes);
+  if (e != hipSuccess) s.extract_on = false;
+  HIP_TRY(c, e);
+  return WAYNE_OK;
+}
+
+// What the extraction's entry points may ask of a slot beyond an upload, and the head they share: the context, the slot
+// number and the switches `need` names, refused as `who`: `missing`.  *sp: the slot.
+enum : unsigned { EX_ON = 1, EX_CRREJ = 2, EX_CHAN = 4, EX_VAR = 8, EX_OPT = 16, EX_OPTCH = 32, EX_PROF = 64 };
+int ex_gate(wayne_ctx* c, int slot, const char* who, unsigned need, const char* missing, Slot** sp) {
+  if (!c) return WAYNE_E_INVALID;
+  if (slot < 0 || slot >= kSlots) return fail(c, WAYNE_E_INVALID, std::string(who) + ": slot");
+  Slot& s = c->slots[slot];
+  const unsigned have = (s.extract_on ? EX_ON : 0) | (s.crrej_on ? EX_CRREJ : 0) | (s.chan_on ? EX_CHAN : 0) | (s.var_on ? EX_VAR : 0) |
+                        (s.opt_on ? EX_OPT : 0) | (s.optch_on ? EX_OPTCH : 0) | (s.prof_deliver ? EX_PROF : 0);
+  if (!s.uploaded || (need & ~have)) return fail(c, WAYNE_E_STATE, std::string(who) + ": " + missing);
+  *sp = &s;
+  return WAYNE_OK;
+}
+constexpr const char* kNoExtraction = "no extraction set for the slot";
+constexpr const char* kNoOptimal = "no optimal extraction set for the slot";
+constexpr const char* kFetchFirst = "wait_spectra or download_spectra first";
 
 }  // namespace
 
@@ -1524,17 +1505,7 @@ int wayne_exposure_upload(wayne_ctx* c, int slot, const wayne_exposure_desc* d) 
   s.n_extra = 0;             // a new exposure has no contaminants until wayne_exposure_set_sources says so
   s.traps_on = false;        // ... and no charge traps until wayne_exposure_set_traps says so
   s.hist_on = false;         // ... nor a carried history (wayne_exposure_set_trap_history)
-  s.extract_on = false;      // ... and no spectral extraction until wayne_exposure_set_extraction says so
-  s.ex_pinned_misc = nullptr;
-  s.crrej_on = false;        // ... whose cosmic-ray rejection waits for wayne_exposure_set_crrej
-  s.ex_rej = nullptr;
-  s.chan_on = false;         // ... and whose channels wait for wayne_exposure_set_channels
-  s.ch_res = nullptr;
-  s.var_on = false;          // ... and whose variances wait for wayne_exposure_set_variance
-  s.var_res = nullptr;
-  s.opt_on = false;          // ... and whose optimal extraction waits for wayne_exposure_set_optimal
-  s.prof_deliver = s.prof_fetched = s.prof_valid = s.prof_fixed = s.optch_on = false;   // (the profile planes and the optimal channels go with the optimal extraction)
-  s.opt_res = nullptr;
+  ex_clear(s);               // ... and no spectral extraction, nor any option of it, until wayne_exposure_set_extraction says so
   s.fits_on = false;         // ... and no FITS words until wayne_exposure_set_fits says so
   s.fits_pinned_misc = nullptr;
   int rc;
@@ -2427,46 +2398,28 @@ int wayne_exposure_set_trap_history(wayne_ctx* c, int slot, const wayne_trap_his
 // ---------------------------------------------------------------------------
 
 int wayne_exposure_set_extraction(wayne_ctx* c, int slot, const wayne_extract_desc* x) {
-  if (!c) return WAYNE_E_INVALID;
-  if (slot < 0 || slot >= kSlots) return fail(c, WAYNE_E_INVALID, "set_extraction: slot");
-  Slot& s = c->slots[slot];
-  if (!s.uploaded) return fail(c, WAYNE_E_STATE, "set_extraction: slot not uploaded");
-  s.extract_on = false;           // from here on a refusal leaves the slot usable, without extraction
-  s.ex_pinned_misc = nullptr;
-  s.crrej_on = false;
-  s.ex_rej = nullptr;
-  s.chan_on = false;
-  s.ch_res = nullptr;
-  s.var_on = false;
-  s.var_res = nullptr;
-  s.opt_on = false;
-  s.prof_deliver = s.prof_fetched = s.prof_valid = s.prof_fixed = s.optch_on = false;   // (the profile planes and the optimal channels go with the optimal extraction)
-  s.opt_res = nullptr;
+  Slot* sp;
+  if (int rc = ex_gate(c, slot, "set_extraction", 0, "slot not uploaded", &sp)) return rc;
+  Slot& s = *sp;
+  ex_clear(s);                    // from here on a refusal leaves the slot usable, without extraction
   if (!x) return WAYNE_OK;
   int chunks = 0;
   if (const char* why = plan::extract_desc_error(c->S, s.R, x->steps, x->row_lo, x->row_hi, x->bg_col_lo, x->bg_col_hi, &chunks))
     return fail(c, WAYNE_E_INVALID, std::string("set_extraction: ") + why);
   (void)hipSetDevice(c->device);
-  const size_t NP = (size_t)s.R + 1, S = (size_t)c->S;
-  HIP_TRY(c, s.ex_part.reserve((size_t)2 * chunks * NP * S * sizeof(double)));
-  HIP_TRY(c, s.ex_out.reserve(NP * (S + 1) * sizeof(double) + NP * sizeof(uint32_t)));   // (room for set_crrej's counts)
+  HIP_TRY(c, s.ex_part.reserve((size_t)2 * chunks * ((size_t)s.R + 1) * c->S * sizeof(double)));
   s.ex = *x;
   s.ex_chunks = chunks;
   s.extract_on = true;
-  return WAYNE_OK;
+  return ex_relayout(c, s);
 }
 
 int wayne_exposure_set_crrej(wayne_ctx* c, int slot, const wayne_crrej_desc* r) {
-  if (!c) return WAYNE_E_INVALID;
-  if (slot < 0 || slot >= kSlots) return fail(c, WAYNE_E_INVALID, "set_crrej: slot");
-  Slot& s = c->slots[slot];
-  if (!s.uploaded || !s.extract_on) return fail(c, WAYNE_E_STATE, "set_crrej: no extraction set for the slot");
+  Slot* sp;
+  if (int rc = ex_gate(c, slot, "set_crrej", EX_ON, kNoExtraction, &sp)) return rc;
+  Slot& s = *sp;
   s.crrej_on = false;             // from here on a refusal leaves the slot extracting, without rejection
-  s.ex_rej = nullptr;
-  s.ch_res = nullptr;
-  s.var_res = nullptr;
-  s.opt_res = nullptr;
-  s.ex_pinned_misc = nullptr;     // (a fetched block has the other layout)
+  if (int rc = ex_relayout(c, s)) return rc;
   if (!r) return WAYNE_OK;
   if (const char* why = plan::crrej_desc_error(s.ex.steps, r->k, r->read_noise_e))
     return fail(c, WAYNE_E_INVALID, std::string("set_crrej: ") + why);
@@ -2478,20 +2431,16 @@ int wayne_exposure_set_crrej(wayne_ctx* c, int slot, const wayne_crrej_desc* r) 
   s.cr_k = r->k;
   s.cr_rn = r->read_noise_e;
   s.crrej_on = true;
-  return WAYNE_OK;
+  return ex_relayout(c, s);
 }
 
 int wayne_exposure_set_channels(wayne_ctx* c, int slot, const wayne_channels_desc* d) {
-  if (!c) return WAYNE_E_INVALID;
-  if (slot < 0 || slot >= kSlots) return fail(c, WAYNE_E_INVALID, "set_channels: slot");
-  Slot& s = c->slots[slot];
-  if (!s.uploaded || !s.extract_on) return fail(c, WAYNE_E_STATE, "set_channels: no extraction set for the slot");
+  Slot* sp;
+  if (int rc = ex_gate(c, slot, "set_channels", EX_ON, kNoExtraction, &sp)) return rc;
+  Slot& s = *sp;
   s.chan_on = false;              // from here on a refusal leaves the slot extracting, without channels
   s.optch_on = false;             // (the optimal channels are the channels': set_optimal_channels comes after this call)
-  s.ch_res = nullptr;
-  s.var_res = nullptr;
-  s.opt_res = nullptr;
-  s.ex_pinned_misc = nullptr;     // (a fetched block has the other layout)
+  if (int rc = ex_relayout(c, s)) return rc;
   if (!d) return WAYNE_OK;
   int u_lo = 0, u_hi = 0;
   if (const char* why = plan::channels_desc_error(c->S, s.R, s.ex.steps, s.ex.row_lo, s.ex.row_hi, d->n_channels, d->edges_um,
@@ -2501,11 +2450,7 @@ int wayne_exposure_set_channels(wayne_ctx* c, int slot, const wayne_channels_des
   use_slot_stream(c, slot);
   const size_t NP = (size_t)s.R + 1, S = (size_t)c->S, C = (size_t)d->n_channels;
   HIP_TRY(c, s.ch_part.reserve((size_t)s.ex_chunks * kChanGroups * NP * 2 * C * sizeof(double)));
-  // the spectra block grows by the channels, 8-byte aligned behind sky and (set_crrej may come before or after) the counts;
-  // nothing of it is kept: the next run writes all of it
-  // (and by the variances, when set_variance came first: they lie behind the channels and take on channels_var)
-  HIP_TRY(c, s.ex_out.reserve(NP * (S + 1) * sizeof(double) + NP * sizeof(uint32_t) + 8 + NP * C * sizeof(double) +
-                              (s.var_on ? NP * (S + 1 + C) * sizeof(double) : 0) + (s.opt_on ? 2 * NP * S * sizeof(double) : 0)));
+  // (set_variance may have come first: the variances take on channels_var)
   if (s.var_on) HIP_TRY(c, s.ch_part_v.reserve((size_t)s.ex_chunks * kChanGroups * NP * C * sizeof(double)));
   if (int rc = s.ch_stage.begin(c, 3 * 64 + (2 * S + C + 1) * sizeof(double), "set_channels: pinned host allocation failed")) return rc;
   if (!s.ch_stage.put(s.ch_edges, d->edges_um, (C + 1) * sizeof(double)) || !s.ch_stage.put(s.ch_wa, d->wl_a, S * sizeof(double)) ||
@@ -2516,20 +2461,17 @@ int wayne_exposure_set_channels(wayne_ctx* c, int slot, const wayne_channels_des
   s.ch_lo = u_lo; s.ch_hi = u_hi;
   s.ch_flags = d->flags;
   s.chan_on = true;
-  return WAYNE_OK;
+  return ex_relayout(c, s);
 }
 
 int wayne_exposure_set_variance(wayne_ctx* c, int slot, const wayne_variance_desc* v) {
-  if (!c) return WAYNE_E_INVALID;
-  if (slot < 0 || slot >= kSlots) return fail(c, WAYNE_E_INVALID, "set_variance: slot");
-  Slot& s = c->slots[slot];
-  if (!s.uploaded || !s.extract_on) return fail(c, WAYNE_E_STATE, "set_variance: no extraction set for the slot");
+  Slot* sp;
+  if (int rc = ex_gate(c, slot, "set_variance", EX_ON, kNoExtraction, &sp)) return rc;
+  Slot& s = *sp;
   s.var_on = false;               // from here on a refusal leaves the slot extracting, without variances
-  s.var_res = nullptr;
   s.opt_on = false;               // (the optimal extraction stands on the variances: set_optimal comes after this call)
   s.prof_deliver = s.prof_fetched = s.prof_valid = s.prof_fixed = s.optch_on = false;   // (the profile planes and the optimal channels go with the optimal extraction)
-  s.opt_res = nullptr;
-  s.ex_pinned_misc = nullptr;     // (a fetched block has the other layout)
+  if (int rc = ex_relayout(c, s)) return rc;
   if (!v) return WAYNE_OK;
   if (const char* why = plan::variance_desc_error(s.ex.steps, v->read_noise))
     return fail(c, WAYNE_E_INVALID, std::string("set_variance: ") + why);
@@ -2537,56 +2479,36 @@ int wayne_exposure_set_variance(wayne_ctx* c, int slot, const wayne_variance_des
   const size_t NP = (size_t)s.R + 1, S = (size_t)c->S, C = s.chan_on ? (size_t)s.ch_C : 0;
   HIP_TRY(c, s.ex_part_v.reserve((size_t)s.ex_chunks * NP * S * sizeof(double)));
   if (s.chan_on) HIP_TRY(c, s.ch_part_v.reserve((size_t)s.ex_chunks * kChanGroups * NP * C * sizeof(double)));
-  // the spectra block grows by the variances, behind the counts' room and the channels; nothing of it is kept
-  HIP_TRY(c, s.ex_out.reserve(NP * (S + 1) * sizeof(double) + NP * sizeof(uint32_t) + 8 + NP * C * sizeof(double) +
-                              NP * (S + 1 + C) * sizeof(double)));
   s.var_rn = v->read_noise;
   s.var_on = true;
-  return WAYNE_OK;
+  return ex_relayout(c, s);
 }
 
 int wayne_exposure_set_optimal(wayne_ctx* c, int slot, const wayne_optimal_desc* d) {
-  if (!c) return WAYNE_E_INVALID;
-  if (slot < 0 || slot >= kSlots) return fail(c, WAYNE_E_INVALID, "set_optimal: slot");
-  Slot& s = c->slots[slot];
-  if (!s.uploaded || !s.extract_on || !s.var_on) return fail(c, WAYNE_E_STATE, "set_optimal: no variances set for the slot");
+  Slot* sp;
+  if (int rc = ex_gate(c, slot, "set_optimal", EX_ON | EX_VAR, "no variances set for the slot", &sp)) return rc;
+  Slot& s = *sp;
   s.opt_on = false;               // from here on a refusal leaves the slot extracting with variances, without the optimal values
   s.prof_deliver = s.prof_fetched = s.prof_valid = s.prof_fixed = s.optch_on = false;   // (the profile planes and the optimal channels go with the optimal extraction)
-  s.opt_res = nullptr;
-  s.ex_pinned_misc = nullptr;     // (a fetched block has the other length)
+  if (int rc = ex_relayout(c, s)) return rc;
   if (!d) return WAYNE_OK;
   if (const char* why = plan::optimal_desc_error(d->half_width))
     return fail(c, WAYNE_E_INVALID, std::string("set_optimal: ") + why);
   (void)hipSetDevice(c->device);
-  const size_t NP = (size_t)s.R + 1, S = (size_t)c->S, C = s.chan_on ? (size_t)s.ch_C : 0;
-  HIP_TRY(c, s.opt_part.reserve((size_t)3 * s.ex_chunks * NP * S * sizeof(double)));
-  // the spectra block grows by optimal and optimal_var, behind the variances; nothing of it is kept
-  HIP_TRY(c, s.ex_out.reserve(NP * (S + 1) * sizeof(double) + NP * sizeof(uint32_t) + 8 + NP * C * sizeof(double) +
-                              NP * (S + 1 + C) * sizeof(double) + 2 * NP * S * sizeof(double)));
+  HIP_TRY(c, s.opt_part.reserve((size_t)3 * s.ex_chunks * ((size_t)s.R + 1) * c->S * sizeof(double)));
   s.opt_H = d->half_width;
   s.opt_on = true;
-  return WAYNE_OK;
-}
-
-// bytes of a slot's spectra block: spectra [(R+1)*S], then sky [R+1]; with rejection, n_rejected [R+1] (uint32) behind
-// them; with channels, channels [(R+1)*C] behind those on the next multiple of 8 bytes; with variances, those behind
-// everything else -- but for optimal and optimal_var, which lie behind the variances
-static size_t spectra_bytes(const wayne_ctx* c, const Slot& s) {
-  if (s.opt_on) return optimal_offset(c, s) + optimal_count(c, s) * sizeof(double);
-  if (s.var_on) return variance_offset(c, s) + variance_count(c, s) * sizeof(double);
-  if (s.chan_on) return channels_offset(c, s) + (size_t)(s.R + 1) * s.ch_C * sizeof(double);
-  return (size_t)(s.R + 1) * ((size_t)c->S + 1) * sizeof(double) + (s.crrej_on ? (size_t)(s.R + 1) * sizeof(uint32_t) : 0);
+  return ex_relayout(c, s);
 }
 
 int wayne_exposure_fetch_spectra_async(wayne_ctx* c, int slot) {
-  if (!c) return WAYNE_E_INVALID;
-  if (slot < 0 || slot >= kSlots) return fail(c, WAYNE_E_INVALID, "fetch_spectra_async: slot");
-  Slot& s = c->slots[slot];
-  if (!s.uploaded) return fail(c, WAYNE_E_STATE, "fetch_spectra_async: slot not uploaded");
+  Slot* sp;
+  if (int rc = ex_gate(c, slot, "fetch_spectra_async", 0, "slot not uploaded", &sp)) return rc;
+  Slot& s = *sp;
   if (!s.extract_on) return fail(c, WAYNE_E_STATE, "fetch_spectra_async: no extraction set for the slot");
   (void)hipSetDevice(c->device);
   use_slot_stream(c, slot);
-  const size_t bytes = spectra_bytes(c, s), tail = align64(bytes);
+  const size_t bytes = s.lay.bytes, tail = align64(bytes);
   s.ex_pinned_misc = nullptr;
   if (!s.ex_pinned.reserve(tail + 64)) return fail(c, WAYNE_E_NOMEM, "fetch_spectra_async: pinned host allocation failed");
   s.ex_pinned_misc = (Slot::Misc*)(s.ex_pinned.p + tail);
@@ -2598,21 +2520,18 @@ int wayne_exposure_fetch_spectra_async(wayne_ctx* c, int slot) {
 }
 
 int wayne_exposure_wait_spectra(wayne_ctx* c, int slot, double** spectra, double** sky) {
-  if (!c || !spectra || !sky) return WAYNE_E_INVALID;
-  if (slot < 0 || slot >= kSlots) return fail(c, WAYNE_E_INVALID, "wait_spectra: slot");
-  Slot& s = c->slots[slot];
-  if (!s.uploaded) return fail(c, WAYNE_E_STATE, "wait_spectra: slot not uploaded");
+  if (!spectra || !sky) return WAYNE_E_INVALID;
+  Slot* sp;
+  if (int rc = ex_gate(c, slot, "wait_spectra", 0, "slot not uploaded", &sp)) return rc;
+  Slot& s = *sp;
   if (!s.extract_on) return fail(c, WAYNE_E_STATE, "wait_spectra: no extraction set for the slot");
   if (!s.ex_pinned.p || !s.ex_pinned_misc) return fail(c, WAYNE_E_STATE, "wait_spectra: fetch_spectra_async first");
   (void)hipSetDevice(c->device);
   use_slot_stream(c, slot);
   HIP_TRY(c, hipStreamSynchronize(c->stream));
-  *spectra = (double*)s.ex_pinned.p;
-  *sky = (double*)s.ex_pinned.p + (size_t)(s.R + 1) * c->S;
-  s.ex_rej = s.crrej_on ? (const uint32_t*)(*sky + (s.R + 1)) : nullptr;
-  s.ch_res = s.chan_on ? (const double*)(s.ex_pinned.p + channels_offset(c, s)) : nullptr;
-  s.var_res = s.var_on ? (const double*)(s.ex_pinned.p + variance_offset(c, s)) : nullptr;
-  s.opt_res = s.opt_on ? (const double*)(s.ex_pinned.p + optimal_offset(c, s)) : nullptr;
+  s.ex_base = s.ex_pinned.p;
+  *spectra = (double*)(s.ex_pinned.p + s.lay.spectra);
+  *sky = (double*)(s.ex_pinned.p + s.lay.sky);
   bool reran = false;                        // (the status word came with the spectra)
   int rc = look_at_status(c, slot, s.ex_pinned_misc, wayne_exposure_run, &reran, s.ex_pinned_run);
   if (rc || !reran) return rc;
@@ -2622,51 +2541,27 @@ int wayne_exposure_wait_spectra(wayne_ctx* c, int slot, double** spectra, double
 }
 
 int wayne_exposure_download_spectra(wayne_ctx* c, int slot, double* spectra, double* sky) {
-  if (!c || !spectra || !sky) return WAYNE_E_INVALID;
-  if (slot < 0 || slot >= kSlots) return fail(c, WAYNE_E_INVALID, "download_spectra: slot");
-  Slot& s = c->slots[slot];
-  if (!s.uploaded) return fail(c, WAYNE_E_STATE, "download_spectra: slot not uploaded");
+  if (!spectra || !sky) return WAYNE_E_INVALID;
+  Slot* sp;
+  if (int rc = ex_gate(c, slot, "download_spectra", 0, "slot not uploaded", &sp)) return rc;
+  Slot& s = *sp;
   if (!s.extract_on) return fail(c, WAYNE_E_STATE, "download_spectra: no extraction set for the slot");
   (void)hipSetDevice(c->device);
   use_slot_stream(c, slot);
-  const size_t n = (size_t)(s.R + 1) * c->S;
+  // spectra and sky go straight to the caller's arrays; what lies behind them comes, in one copy, to its own offset of
+  // ex_host, for the accessors below
+  const plan::SpectraLayout& l = s.lay;
+  const size_t head = l.sky + ((size_t)s.R + 1) * sizeof(double);
+  s.ex_host.resize((l.bytes + 7) / 8);
+  char* const host = (char*)s.ex_host.data();
+  s.ex_base = host;
   auto copy = [&]() -> int {
-    HIP_TRY(c, hipMemcpyAsync(spectra, s.ex_out.p, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(sky, s.ex_out.as<double>() + n, (size_t)(s.R + 1) * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    if (s.crrej_on)
-      HIP_TRY(c, hipMemcpyAsync(s.ex_rej_host.data(), s.ex_out.as<double>() + n + (s.R + 1), (size_t)(s.R + 1) * sizeof(uint32_t),
-                                hipMemcpyDeviceToHost, c->stream));
-    if (s.chan_on)
-      HIP_TRY(c, hipMemcpyAsync(s.ch_host.data(), (const char*)s.ex_out.p + channels_offset(c, s), s.ch_host.size() * sizeof(double),
-                                hipMemcpyDeviceToHost, c->stream));
-    if (s.var_on)
-      HIP_TRY(c, hipMemcpyAsync(s.var_host.data(), (const char*)s.ex_out.p + variance_offset(c, s), s.var_host.size() * sizeof(double),
-                                hipMemcpyDeviceToHost, c->stream));
-    if (s.opt_on)
-      HIP_TRY(c, hipMemcpyAsync(s.opt_host.data(), (const char*)s.ex_out.p + optimal_offset(c, s), s.opt_host.size() * sizeof(double),
-                                hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(spectra, (const char*)s.ex_out.p + l.spectra, l.sky - l.spectra, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(sky, (const char*)s.ex_out.p + l.sky, head - l.sky, hipMemcpyDeviceToHost, c->stream));
+    if (l.bytes > head)
+      HIP_TRY(c, hipMemcpyAsync(host + head, (const char*)s.ex_out.p + head, l.bytes - head, hipMemcpyDeviceToHost, c->stream));
     return WAYNE_OK;
   };
-  s.opt_res = nullptr;
-  if (s.opt_on) {
-    s.opt_host.assign(optimal_count(c, s), 0.);
-    s.opt_res = s.opt_host.data();
-  }
-  s.var_res = nullptr;
-  if (s.var_on) {
-    s.var_host.assign(variance_count(c, s), 0.);
-    s.var_res = s.var_host.data();
-  }
-  s.ch_res = nullptr;
-  if (s.chan_on) {
-    s.ch_host.assign((size_t)(s.R + 1) * s.ch_C, 0.);
-    s.ch_res = s.ch_host.data();
-  }
-  s.ex_rej = nullptr;
-  if (s.crrej_on) {
-    s.ex_rej_host.assign((size_t)s.R + 1, 0u);
-    s.ex_rej = s.ex_rej_host.data();
-  }
   int rc = copy();
   if (rc) return rc;
   bool reran = false;
@@ -2676,94 +2571,84 @@ int wayne_exposure_download_spectra(wayne_ctx* c, int slot, double* spectra, dou
   return look_at_status(c, slot, nullptr);
 }
 
+// A region of the block the slot's last wait_spectra / download_spectra brought back (null: the region is off).
+static const double* ex_fetched(const Slot& s, size_t offset) {
+  return offset == plan::kNoRegion ? nullptr : (const double*)(s.ex_base + offset);
+}
+
 int wayne_exposure_rejected(wayne_ctx* c, int slot, const uint32_t** n_rejected) {
-  if (!c || !n_rejected) return WAYNE_E_INVALID;
-  if (slot < 0 || slot >= kSlots) return fail(c, WAYNE_E_INVALID, "rejected: slot");
-  Slot& s = c->slots[slot];
-  if (!s.uploaded || !s.extract_on || !s.crrej_on) return fail(c, WAYNE_E_STATE, "rejected: no rejection set for the slot");
-  if (!s.ex_rej) return fail(c, WAYNE_E_STATE, "rejected: wait_spectra or download_spectra first");
-  *n_rejected = s.ex_rej;
+  if (!n_rejected) return WAYNE_E_INVALID;
+  Slot* s;
+  if (int rc = ex_gate(c, slot, "rejected", EX_ON | EX_CRREJ, "no rejection set for the slot", &s)) return rc;
+  if (!s->ex_base) return fail(c, WAYNE_E_STATE, std::string("rejected: ") + kFetchFirst);
+  *n_rejected = (const uint32_t*)ex_fetched(*s, s->lay.n_rejected);
   return WAYNE_OK;
 }
 
 int wayne_exposure_channels(wayne_ctx* c, int slot, const double** channels) {
-  if (!c || !channels) return WAYNE_E_INVALID;
-  if (slot < 0 || slot >= kSlots) return fail(c, WAYNE_E_INVALID, "channels: slot");
-  Slot& s = c->slots[slot];
-  if (!s.uploaded || !s.extract_on || !s.chan_on) return fail(c, WAYNE_E_STATE, "channels: no channels set for the slot");
-  if (!s.ch_res) return fail(c, WAYNE_E_STATE, "channels: wait_spectra or download_spectra first");
-  *channels = s.ch_res;
+  if (!channels) return WAYNE_E_INVALID;
+  Slot* s;
+  if (int rc = ex_gate(c, slot, "channels", EX_ON | EX_CHAN, "no channels set for the slot", &s)) return rc;
+  if (!s->ex_base) return fail(c, WAYNE_E_STATE, std::string("channels: ") + kFetchFirst);
+  *channels = ex_fetched(*s, s->lay.channels);
   return WAYNE_OK;
 }
 
 int wayne_exposure_variances(wayne_ctx* c, int slot, const double** spectra_var, const double** sky_var, const double** channels_var) {
-  if (!c || !spectra_var || !sky_var || !channels_var) return WAYNE_E_INVALID;
-  if (slot < 0 || slot >= kSlots) return fail(c, WAYNE_E_INVALID, "variances: slot");
-  Slot& s = c->slots[slot];
-  if (!s.uploaded || !s.extract_on || !s.var_on) return fail(c, WAYNE_E_STATE, "variances: no variances set for the slot");
-  if (!s.var_res) return fail(c, WAYNE_E_STATE, "variances: wait_spectra or download_spectra first");
-  *spectra_var = s.var_res;
-  *sky_var = s.var_res + (size_t)(s.R + 1) * c->S;
-  *channels_var = s.chan_on ? *sky_var + (s.R + 1) : nullptr;
+  if (!spectra_var || !sky_var || !channels_var) return WAYNE_E_INVALID;
+  Slot* s;
+  if (int rc = ex_gate(c, slot, "variances", EX_ON | EX_VAR, "no variances set for the slot", &s)) return rc;
+  if (!s->ex_base) return fail(c, WAYNE_E_STATE, std::string("variances: ") + kFetchFirst);
+  *spectra_var = ex_fetched(*s, s->lay.spectra_var);
+  *sky_var = ex_fetched(*s, s->lay.sky_var);
+  *channels_var = ex_fetched(*s, s->lay.channels_var);
   return WAYNE_OK;
 }
 
 int wayne_exposure_optimal(wayne_ctx* c, int slot, const double** optimal, const double** optimal_var) {
-  if (!c || !optimal || !optimal_var) return WAYNE_E_INVALID;
-  if (slot < 0 || slot >= kSlots) return fail(c, WAYNE_E_INVALID, "optimal: slot");
-  Slot& s = c->slots[slot];
-  if (!s.uploaded || !s.extract_on || !s.var_on || !s.opt_on)
-    return fail(c, WAYNE_E_STATE, "optimal: no optimal extraction set for the slot");
-  if (!s.opt_res) return fail(c, WAYNE_E_STATE, "optimal: wait_spectra or download_spectra first");
-  *optimal = s.opt_res;
-  *optimal_var = s.opt_res + (size_t)(s.R + 1) * c->S;
+  if (!optimal || !optimal_var) return WAYNE_E_INVALID;
+  Slot* s;
+  if (int rc = ex_gate(c, slot, "optimal", EX_ON | EX_VAR | EX_OPT, kNoOptimal, &s)) return rc;
+  if (!s->ex_base) return fail(c, WAYNE_E_STATE, std::string("optimal: ") + kFetchFirst);
+  *optimal = ex_fetched(*s, s->lay.optimal);
+  *optimal_var = ex_fetched(*s, s->lay.optimal_var);
   return WAYNE_OK;
 }
 
 int wayne_exposure_set_optimal_channels(wayne_ctx* c, int slot, int on) {
-  if (!c) return WAYNE_E_INVALID;
-  if (slot < 0 || slot >= kSlots) return fail(c, WAYNE_E_INVALID, "set_optimal_channels: slot");
-  Slot& s = c->slots[slot];
-  if (!s.uploaded || !s.extract_on || !s.var_on || !s.opt_on || !s.chan_on)
-    return fail(c, WAYNE_E_STATE, "set_optimal_channels: the slot needs channels and the optimal extraction");
+  Slot* sp;
+  if (int rc = ex_gate(c, slot, "set_optimal_channels", EX_ON | EX_VAR | EX_OPT | EX_CHAN, "the slot needs channels and the optimal extraction", &sp))
+    return rc;
+  Slot& s = *sp;
   s.optch_on = false;
-  s.opt_res = nullptr;
-  s.ex_pinned_misc = nullptr;     // (a fetched block has the other length)
+  if (int rc = ex_relayout(c, s)) return rc;
   if (!on) return WAYNE_OK;
   (void)hipSetDevice(c->device);
-  const size_t NP = (size_t)s.R + 1, S = (size_t)c->S, C = (size_t)s.ch_C;
-  HIP_TRY(c, s.optch_part.reserve((size_t)s.ex_chunks * kChanGroups * NP * 3 * C * sizeof(double)));
-  HIP_TRY(c, s.ex_out.reserve(NP * (S + 1) * sizeof(double) + NP * sizeof(uint32_t) + 8 + NP * C * sizeof(double) +
-                              NP * (S + 1 + C) * sizeof(double) + 2 * NP * (S + C) * sizeof(double)));
+  HIP_TRY(c, s.optch_part.reserve((size_t)s.ex_chunks * kChanGroups * ((size_t)s.R + 1) * 3 * s.ch_C * sizeof(double)));
   s.optch_on = true;
-  return WAYNE_OK;
+  return ex_relayout(c, s);
 }
 
 int wayne_exposure_optimal_channels(wayne_ctx* c, int slot, const double** channels_opt, const double** channels_opt_var) {
-  if (!c || !channels_opt || !channels_opt_var) return WAYNE_E_INVALID;
-  if (slot < 0 || slot >= kSlots) return fail(c, WAYNE_E_INVALID, "optimal_channels: slot");
-  Slot& s = c->slots[slot];
-  if (!s.uploaded || !s.extract_on || !s.var_on || !s.opt_on || !s.chan_on || !s.optch_on)
-    return fail(c, WAYNE_E_STATE, "optimal_channels: no optimal channels set for the slot");
-  if (!s.opt_res) return fail(c, WAYNE_E_STATE, "optimal_channels: wait_spectra or download_spectra first");
-  *channels_opt = s.opt_res + (size_t)2 * (s.R + 1) * c->S;
-  *channels_opt_var = *channels_opt + (size_t)(s.R + 1) * s.ch_C;
+  if (!channels_opt || !channels_opt_var) return WAYNE_E_INVALID;
+  Slot* s;
+  if (int rc = ex_gate(c, slot, "optimal_channels", EX_ON | EX_VAR | EX_OPT | EX_CHAN | EX_OPTCH, "no optimal channels set for the slot", &s))
+    return rc;
+  if (!s->ex_base) return fail(c, WAYNE_E_STATE, std::string("optimal_channels: ") + kFetchFirst);
+  *channels_opt = ex_fetched(*s, s->lay.channels_opt);
+  *channels_opt_var = ex_fetched(*s, s->lay.channels_opt_var);
   return WAYNE_OK;
 }
 
 // doubles of a slot's profile planes: every pixel of all R + 1 windows
 static size_t profile_count(const wayne_ctx* c, const Slot& s) {
-  size_t rows = 0;
-  for (int p = 0; p <= s.R; ++p) rows += (size_t)plan::profile_window_rows(c->S, s.R, s.ex.steps, s.ex.row_lo, s.ex.row_hi, p);
-  return rows * (size_t)c->S;
+  return plan::profile_offsets(c->S, s.R, s.ex.steps, s.ex.row_lo, s.ex.row_hi, nullptr);
 }
 
 int wayne_exposure_deliver_profile(wayne_ctx* c, int slot, int on) {
-  if (!c) return WAYNE_E_INVALID;
-  if (slot < 0 || slot >= kSlots) return fail(c, WAYNE_E_INVALID, "deliver_profile: slot");
-  Slot& s = c->slots[slot];
-  if (!s.uploaded || !s.extract_on || !s.var_on || !s.opt_on)
-    return fail(c, WAYNE_E_STATE, "deliver_profile: no optimal extraction set for the slot");
+  Slot* sp;
+  if (int rc = ex_gate(c, slot, "deliver_profile", EX_ON | EX_VAR | EX_OPT, kNoOptimal, &sp)) return rc;
+  Slot& s = *sp;
   s.prof_deliver = s.prof_fetched = s.prof_valid = false;
   if (!on) return WAYNE_OK;
   (void)hipSetDevice(c->device);
@@ -2772,16 +2657,15 @@ int wayne_exposure_deliver_profile(wayne_ctx* c, int slot, int on) {
   return WAYNE_OK;
 }
 
+
 int wayne_exposure_set_optimal_profile(wayne_ctx* c, int slot, const double* profile, const int* rows) {
   return wayne_exposure_set_optimal_profile_tagged(c, slot, profile, rows, 0);
 }
 
 int wayne_exposure_set_optimal_profile_tagged(wayne_ctx* c, int slot, const double* profile, const int* rows, uint64_t tag) {
-  if (!c) return WAYNE_E_INVALID;
-  if (slot < 0 || slot >= kSlots) return fail(c, WAYNE_E_INVALID, "set_optimal_profile: slot");
-  Slot& s = c->slots[slot];
-  if (!s.uploaded || !s.extract_on || !s.var_on || !s.opt_on)
-    return fail(c, WAYNE_E_STATE, "set_optimal_profile: no optimal extraction set for the slot");
+  Slot* sp;
+  if (int rc = ex_gate(c, slot, "set_optimal_profile", EX_ON | EX_VAR | EX_OPT, kNoOptimal, &sp)) return rc;
+  Slot& s = *sp;
   s.prof_fixed = false;           // from here on a refusal leaves the slot with the exposure's own profile
   if (!profile) return WAYNE_OK;
   size_t n = 0;
@@ -2811,11 +2695,9 @@ int wayne_exposure_set_optimal_profile_tagged(wayne_ctx* c, int slot, const doub
 }
 
 int wayne_exposure_fetch_profile(wayne_ctx* c, int slot) {
-  if (!c) return WAYNE_E_INVALID;
-  if (slot < 0 || slot >= kSlots) return fail(c, WAYNE_E_INVALID, "fetch_profile: slot");
-  Slot& s = c->slots[slot];
-  if (!s.uploaded || !s.extract_on || !s.var_on || !s.opt_on || !s.prof_deliver)
-    return fail(c, WAYNE_E_STATE, "fetch_profile: no profile delivery set for the slot");
+  Slot* sp;
+  if (int rc = ex_gate(c, slot, "fetch_profile", EX_ON | EX_VAR | EX_OPT | EX_PROF, "no profile delivery set for the slot", &sp)) return rc;
+  Slot& s = *sp;
   if (!s.prof_valid || s.ran) return fail(c, WAYNE_E_STATE, "fetch_profile: run, then wait_spectra or download_spectra first");
   (void)hipSetDevice(c->device);
   use_slot_stream(c, slot);
@@ -2828,11 +2710,10 @@ int wayne_exposure_fetch_profile(wayne_ctx* c, int slot) {
 }
 
 int wayne_exposure_profile(wayne_ctx* c, int slot, const double** planes, size_t* count) {
-  if (!c || !planes || !count) return WAYNE_E_INVALID;
-  if (slot < 0 || slot >= kSlots) return fail(c, WAYNE_E_INVALID, "profile: slot");
-  Slot& s = c->slots[slot];
-  if (!s.uploaded || !s.extract_on || !s.var_on || !s.opt_on || !s.prof_deliver)
-    return fail(c, WAYNE_E_STATE, "profile: no profile delivery set for the slot");
+  if (!planes || !count) return WAYNE_E_INVALID;
+  Slot* sp;
+  if (int rc = ex_gate(c, slot, "profile", EX_ON | EX_VAR | EX_OPT | EX_PROF, "no profile delivery set for the slot", &sp)) return rc;
+  Slot& s = *sp;
   if (!s.prof_fetched) return fail(c, WAYNE_E_STATE, "profile: fetch_profile first");
   (void)hipSetDevice(c->device);
   use_slot_stream(c, slot);
@@ -2843,10 +2724,10 @@ int wayne_exposure_profile(wayne_ctx* c, int slot, const double** planes, size_t
 }
 
 int wayne_exposure_download_crmask(wayne_ctx* c, int slot, uint16_t* mask) {
-  if (!c || !mask) return WAYNE_E_INVALID;
-  if (slot < 0 || slot >= kSlots) return fail(c, WAYNE_E_INVALID, "download_crmask: slot");
-  Slot& s = c->slots[slot];
-  if (!s.uploaded || !s.extract_on || !s.crrej_on) return fail(c, WAYNE_E_STATE, "download_crmask: no rejection set for the slot");
+  if (!mask) return WAYNE_E_INVALID;
+  Slot* sp;
+  if (int rc = ex_gate(c, slot, "download_crmask", EX_ON | EX_CRREJ, "no rejection set for the slot", &sp)) return rc;
+  Slot& s = *sp;
   (void)hipSetDevice(c->device);
   use_slot_stream(c, slot);
   const size_t S = (size_t)c->S;
