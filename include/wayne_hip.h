@@ -749,6 +749,57 @@ int wayne_exposure_download_fits(wayne_ctx *ctx, int slot, void *out_payload);
  * milliseconds.  wayne_profile_select's bit 9 selects it.  Synchronises. */
 int wayne_fits_profile(wayne_ctx *ctx, uint64_t *launches, double *ms);
 
+/* ---- the noise-free expected image (no reference counterpart) ------------- */
+
+/*
+ * The exposure without its noise: what the Monte-Carlo throwers converge to, rendered by a kernel of its own (k_expect)
+ * beside the exposure.  Turning every noise flag off does not give it: the thrower still throws every electron at
+ * random.  The law, in float64: a thrower keeps an electron of a bin at c iff 0 < floor(c + sigma z) < N on both axes,
+ * so with Phi the standard normal CDF
+ *
+ *   a(p; c, sigma) = Phi((p + 1 - c) / sigma) - Phi((p - c) / sigma)   for 1 <= p <= N - 1, else 0
+ *   E_r[y + 5, x + 5] = sum_s sum_{k: read(k) = r} f_{s,k}(y, x) sum_w ( n_h a(x; xs, sigma_h) a(y; ys, sigma_h)
+ *                                                                    + n_l a(x; xs, sigma_l) a(y; ys, sigma_l) )
+ *
+ * over the sources s (the target, then the contaminants), the sub-samples k of read interval r and the bins w; (xs, ys)
+ * the bin's frame position, sigma_h / sigma_l its float32 PSF widths (what the production throwers use), f the
+ * wavelength-dependent flat of sub-sample k (1 with WAYNE_F_ADD_FLAT off or without a flat cube).  (n_h, n_l) by mode:
+ *
+ *   WAYNE_EXPECT_COUNTS  count, nwide = those of this run (the same Philox draws): n_h = min(max(nwide, 0), count),
+ *                        n_l = count - n_h.  E is the exact conditional expectation of the slot's accumulators (acc_e
+ *                        of wayne_exposure_debug_fetch) given the bin counts the run drew, for WAYNE_RNG_SPLIT and
+ *                        WAYNE_RNG_PHILOX.
+ *   WAYNE_EXPECT_MEAN    lambda = the counts chain before the draw / the rounding, lambda+ = lambda finite and > 0 ?
+ *                        min(lambda, 2147483647) : 0; n_h = min(max(ratio, 0), 1) lambda+, n_l = lambda+ - n_h.  The
+ *                        unconditional expectation, up to the truncation in nwide = (int)(count ratio) (< 1 electron per
+ *                        bin and sub-sample, moved from the wide to the narrow component) and, with stellar noise off,
+ *                        rint(lambda).
+ *
+ * A component contributes nothing if its position is not finite or beyond +-1e6, or if its sigma is not finite or <= 0.
+ * The kernel drops a component from pixels more than 8 sigma of that component away from the bin: no pixel of interval
+ * r loses more than 2 Phi(-8) = 1.3e-15 of the electrons thrown in r.  NOT in E: sky, cosmic rays, dark current, the
+ * gaussian-noise stage, gain, non-linearity, charge traps -- E is the truth of the thrower stage in electrons, not a
+ * noise-free read.  The plane is R * S * S doubles, its 5-pixel border zero, all of it written on every run; the same
+ * bytes in any slot, on either stream and on every run (no floating-point atomics).  Opt-in: without
+ * wayne_exposure_set_expected every launch and every byte stay as they are.  Added within WAYNE_ABI_VERSION 7: new
+ * symbols only.
+ */
+#define WAYNE_EXPECT_COUNTS 1
+#define WAYNE_EXPECT_MEAN 2
+
+/* After wayne_exposure_upload, before run: every run of the slot also renders the plane, at the very end of its back
+ * half (behind the extraction's launches and k_fits_words) on the slot's stream (mode 0 clears).  The plane's buffer is
+ * reserved by this call, for slots that ask only.  wayne_exposure_upload clears it.  WAYNE_E_STATE on a slot that is not
+ * uploaded; WAYNE_E_INVALID in replay mode (which reproduces the reference: it has no such product), for a mode that is
+ * none of the above or with more than 16 reads -- the slot stays usable, without the option. */
+int wayne_exposure_set_expected(wayne_ctx *ctx, int slot, int mode);
+/* The plane into the caller's (pageable) memory, R * S * S doubles.  Synchronises and settles the run as
+ * wayne_exposure_download does (an exposure run a second time renders again).  WAYNE_E_STATE without the option. */
+int wayne_exposure_download_expected(wayne_ctx *ctx, int slot, double *out);
+/* HIP-event time of k_expect (every source's launch and the clearing of the plane) while wayne_profile_enable is on,
+ * since wayne_profile_reset: renderings and total milliseconds.  wayne_profile_select's bit 10 selects it.  Synchronises. */
+int wayne_expected_profile(wayne_ctx *ctx, uint64_t *launches, double *ms);
+
 /* ---- measurement ------------------------------------------------------- */
 
 #define WAYNE_PROF_KERNELS 8

@@ -31,6 +31,9 @@ OUT_FLAGS = {np.dtype(np.float32): 0, np.dtype(np.float64): F_OUT_F64, np.dtype(
 F_EXACT_SAMPLERS = 1 << 17
 PROF_KERNELS = 8
 ABI_VERSION = 7
+EXPECT_COUNTS, EXPECT_MEAN = 1, 2   # modes of the expected image (WAYNE_EXPECT_*)
+EXPECT_MODES = {"counts": EXPECT_COUNTS, "mean": EXPECT_MEAN}
+EXPECT_NAMES = {0: None, EXPECT_COUNTS: "counts", EXPECT_MEAN: "mean"}
 MAX_SOURCES = 8   # contaminants per exposure (WAYNE_MAX_SOURCES)
 MAX_TRAP_RATES = 4096   # points of a charge-trap start table (WAYNE_MAX_TRAP_RATES)
 # wayne_extract_desc.steps (WAYNE_X_*)
@@ -198,6 +201,9 @@ SYMBOLS = {
     "wayne_exposure_wait_fits": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_void_p)]),
     "wayne_exposure_download_fits": (C.c_int, [_vp, C.c_int, _vp]),
     "wayne_fits_profile": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_double)]),
+    "wayne_exposure_set_expected": (C.c_int, [_vp, C.c_int, C.c_int]),
+    "wayne_exposure_download_expected": (C.c_int, [_vp, C.c_int, _dp]),
+    "wayne_expected_profile": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_double)]),
     "wayne_profile_enable": (C.c_int, [_vp, C.c_int]),
     "wayne_profile_select": (C.c_int, [_vp, C.c_uint]),
     "wayne_profile_reset": (C.c_int, [_vp]),
@@ -326,6 +332,7 @@ class Context(object):
         self._slot_optch = set() # slots whose extraction delivers the optimal channels (set_optimal_channels succeeded)
         self._slot_prof = set()  # slots whose runs write the profile planes too (deliver_profile succeeded)
         self._slot_fits = {}     # slot -> (plane_bytes, stride, bitpix) of its FITS payload (set_fits succeeded)
+        self._slot_expected = {} # slot -> mode name of its expected image (set_expected succeeded)
         _live_contexts.add(self)
         for name, value in _knob_defaults.items():
             self.set_knob(name, value)
@@ -453,6 +460,7 @@ class Context(object):
         self._slot_prof.discard(slot)
         self._slot_optch.discard(slot)
         self._slot_fits.pop(slot, None)
+        self._slot_expected.pop(slot, None)
         sources = getattr(desc, "_sources", None)
         if sources:
             self.set_sources(slot, sources)
@@ -466,6 +474,40 @@ class Context(object):
             self.set_extraction(slot, extraction)
         if getattr(desc, "_device_fits", False):
             self.set_fits(slot)
+        expected = getattr(desc, "_expected", None)
+        if expected is not None:
+            self.set_expected(slot, expected)
+
+    # -- the noise-free expected image ---------------------------------------------
+    def set_expected(self, slot, mode):
+        """Every run of the slot also renders its noise-free expected image: mode "counts" (the conditional expectation
+        of the accumulators given the bin counts the run drew) or "mean" (the unconditional one); None clears; after
+        upload, which clears it too.  See wayne_exposure_set_expected."""
+        self._slot_expected.pop(slot, None)
+        code = expected_mode(mode)
+        self.check(self._L.wayne_exposure_set_expected(self._h, int(slot), code))
+        if code:
+            self._slot_expected[slot] = EXPECT_NAMES[code]
+
+    def has_expected(self, slot):
+        """Whether the slot's runs render the expected image (set_expected succeeded since its last upload)."""
+        return slot in self._slot_expected
+
+    def expected(self, slot):
+        """The slot's expected image [R, S, S] float64, in electrons per read interval (not cumulative), blocking:
+        waits for the slot's run and settles it as download() does."""
+        K, W, R, _ = self._slot_meta[slot]
+        if slot not in self._slot_expected:
+            raise WayneError(E_STATE, "expected: no expected image set for the slot")
+        out = np.empty((R, self.S, self.S), dtype=np.float64)
+        self.check(self._L.wayne_exposure_download_expected(self._h, int(slot), ptr(out, C.c_double)))
+        return out
+
+    def expected_profile(self):
+        """{"launches", "ms"} of k_expect by HIP events (profile_enable; since profile_reset)."""
+        n, ms = C.c_uint64(0), C.c_double(0.0)
+        self.check(self._L.wayne_expected_profile(self._h, C.byref(n), C.byref(ms)))
+        return {"launches": int(n.value), "ms": float(ms.value)}
 
     # -- device-side FITS words ----------------------------------------------------
     def set_fits(self, slot, on=True):
@@ -943,7 +985,7 @@ class Context(object):
         if names is None:
             mask = 0xFFFFFFFF
         else:
-            order = list(self.profile_get().keys())[:PROF_KERNELS] + ["k_extract", "k_fits_words"]
+            order = list(self.profile_get().keys())[:PROF_KERNELS] + ["k_extract", "k_fits_words", "k_expect"]
             mask = 0
             for n in names:
                 mask |= 1 << order.index(n)
@@ -966,13 +1008,14 @@ def make_desc(seed, exposure_index, flags, sub_scale, wl_um, flux, depth, x_ref,
               sample_read, read_dt_s, replay_seed=None, rng_mode=RNG_PHILOX, threads_compat=1,
               sky_ct_s=0.0, cosmic_rate=-1.0, scale_factor=1.0, noise_mean=0.0, noise_std=0.0,
               thrower_margin=0, thrower_splits=0, lc_z=None, lc_hidden=None, lc_rp=None, lc_ld=None, sources=None,
-              traps=None, extraction=None, device_fits=False):
+              traps=None, extraction=None, device_fits=False, expected=None):
     """The exposure descriptor.  `sources`: contaminating field stars (sources.Contaminant), carried beside the C struct
     and set by Context.upload (wayne_exposure_set_sources); None or [] = the target alone.  `traps`: charge traps
     (traps.ExposureTraps, or a traps.ChargeTraps whose table is flat at `initial`), set by Context.upload
     (wayne_exposure_set_traps); None = no trapping.  `extraction`: the spectral extraction of the exposure
     (extraction.Extraction), set by Context.upload (wayne_exposure_set_extraction); None = reads only.  `device_fits`: the reads' FITS words are formed on the device too,
-    set by Context.upload (wayne_exposure_set_fits)."""
+    set by Context.upload (wayne_exposure_set_fits).  `expected`: "counts" or "mean" -- the noise-free expected image is
+    rendered with every run, set by Context.upload (wayne_exposure_set_expected); None = none."""
     d = ExposureDesc()
     keep = []
 
@@ -1025,7 +1068,20 @@ def make_desc(seed, exposure_index, flags, sub_scale, wl_um, flux, depth, x_ref,
     d._traps = traps
     d._extraction = extraction
     d._device_fits = bool(device_fits)
+    d._expected = EXPECT_NAMES[expected_mode(expected)] if expected is not None else None
     return d
+
+
+def expected_mode(mode):
+    """The library's code of an expected-image mode: None / 0 -> 0, "counts" -> EXPECT_COUNTS, "mean" -> EXPECT_MEAN
+    (the codes themselves pass); anything else: ValueError."""
+    if mode is None or (mode == 0 and not isinstance(mode, str)):
+        return 0
+    if isinstance(mode, str) and mode in EXPECT_MODES:
+        return EXPECT_MODES[mode]
+    if not isinstance(mode, (str, bool)) and mode in EXPECT_NAMES:
+        return int(mode)
+    raise ValueError('expected: None, "counts" or "mean", not %r' % (mode,))
 
 
 def device_count():

@@ -292,6 +292,55 @@ inline bool accumulator_boxes(SpectrumEstimate& e, int W, const double* wl_um, c
   return true;
 }
 
+// Where can the expected image of read interval r (k_expect) differ from zero?  k_expect drops a component from a pixel
+// more than 8 sigma of that component from its bin, so: within 8 sigma_max of a bin.  accumulator_boxes above is NOT
+// that bound (6.9 sigma: where electrons land in practice).  The bins of sub-sample k lie on its straight trace
+// (bin_position: x and y are linear in the wavelength), between the smallest and the largest wavelength, and here every
+// sub-sample's own end points are taken, from its own trace coefficients (`tr`: trace_table of the same x_ref / y_ref).
+// + 2 px: the bound's own rounding and the float32 rounding of the sigmas.  box[r] = {x0, x1, y0, y1} in FRAME pixels,
+// clipped to [1, N) -- row and column 0 are never hit --, x0 >= x1 for an interval without sub-samples.  Numbers no bound
+// can be built on (a sigma, wavelength or position that is not finite or out of any sane range): the whole frame.
+inline void expected_boxes(const GrismDev& g, int W, const double* wl_um, int K, int R, int N, int sub_scale,
+                           const double* x_ref, const double* y_ref, const double* tr, const int32_t* sample_read,
+                           int (*box)[4]) {
+  double smax = 0., wl_lo = 0., wl_hi = 0.;
+  bool ok = W > 0;
+  for (int i = 0; i < W; ++i) {
+    const double x = wl_um[i];
+    const double sl = SpectrumEstimate::poly3(g.p_sigl, x), sh = SpectrumEstimate::poly3(g.p_sigh, x);
+    if (!(sl < 1e3 && sh < 1e3) || !(std::fabs(x) < 1e6)) ok = false;     // (a sigma <= 0 is a component that contributes nothing)
+    if (sl > smax) smax = sl;
+    if (sh > smax) smax = sh;
+    if (i == 0 || x < wl_lo) wl_lo = x;
+    if (i == 0 || x > wl_hi) wl_hi = x;
+  }
+  const double reach = 8. * smax * (1. + 1e-6) + 2.;
+  for (int r = 0; r < R && r < 16; ++r) { box[r][0] = box[r][2] = 0x3FFFFFFF; box[r][1] = box[r][3] = -0x3FFFFFFF; }
+  for (int k = 0; k < K; ++k) {
+    const int r = sample_read[k];
+    if (r < 0 || r >= R || r >= 16) continue;
+    const double* t = tr + (size_t)kTrStride * k;
+    bool fine = ok;
+    for (int end = 0; end < 2 && fine; ++end) {
+      const double wl = end ? wl_hi : wl_lo;
+      const double x = (wl - t[5]) / t[4];
+      const double y = t[0] * (x - x_ref[k]) + t[1] + y_ref[k];
+      const double xs = x - (double)sub_scale, ys = y - (double)sub_scale;
+      if (!(std::fabs(xs) < 1e6 && std::fabs(ys) < 1e6)) { fine = false; break; }
+      box[r][0] = std::min(box[r][0], (int)std::floor(xs - reach));
+      box[r][1] = std::max(box[r][1], (int)std::floor(xs + reach) + 1);
+      box[r][2] = std::min(box[r][2], (int)std::floor(ys - reach));
+      box[r][3] = std::max(box[r][3], (int)std::floor(ys + reach) + 1);
+    }
+    if (!fine) { box[r][0] = box[r][2] = 1; box[r][1] = box[r][3] = N; }
+  }
+  for (int r = 0; r < R && r < 16; ++r) {
+    box[r][0] = std::max(box[r][0], 1); box[r][2] = std::max(box[r][2], 1);
+    box[r][1] = std::min(box[r][1], N); box[r][3] = std::min(box[r][3], N);
+    if (box[r][0] >= box[r][1] || box[r][2] >= box[r][3]) box[r][0] = box[r][1] = box[r][2] = box[r][3] = 0;
+  }
+}
+
 // The host half of wayne_psf_apply (the inner drop-in boundary: pyparallel.pyx:14-38 -> pyparallel_menu.c:10-113): the
 // count reduction A1 with the reference's silent int overflows turned into errors, N = (int)(counts * ratio) per bin
 // (:89, with the C cast's behaviour at NaN and beyond int spelled out), the split mode's routing of every bin -- the rule

@@ -366,13 +366,11 @@ __device__ __forceinline__ void bin_position_bound(const PrepArgs& a, double wl,
 }
 // wl .. sigl_w: the bin's per-wavelength inputs; tr: the sub-sample's trace coefficients (k_prep_wl); depth: the
 // transit depth of (k, w) or 0
-__device__ __forceinline__ BinPlan plan_bin(const PrepArgs& a, int k, int w, double wl, double flux_w, double sens_w,
-                                            double dlam_w, double ratio_w, double sigl_w, const double* tr,
-                                            double x_ref, double y_ref, double dur, double depth) {
-  BinPlan o;
-  bin_position(a, wl, tr, x_ref, y_ref, &o.xs, &o.ys);
-  // counts chain (exposure_generator.py:344-348, 602-628, 649-687):
-  //   F (1 - depth) * Sens * dlam[um] * 1e4 [A/um] * dur[ms] * 1e-3 [s/ms] * scale
+// counts chain (exposure_generator.py:344-348, 602-628, 649-687), before the draw / the rounding:
+//   F (1 - depth) * Sens * dlam[um] * 1e4 [A/um] * dur[ms] * 1e-3 [s/ms] * scale
+// (a function of its own: k_expect's MEAN mode takes the mean where plan_bin takes the draw)
+__device__ __forceinline__ double bin_mean_counts(const PrepArgs& a, double flux_w, double sens_w, double dlam_w, double dur,
+                                                  double depth) {
   double f = flux_w;
   if (a.depth) f = f * (1. - depth);
   double lam = f * sens_w;
@@ -381,6 +379,14 @@ __device__ __forceinline__ BinPlan plan_bin(const PrepArgs& a, int k, int w, dou
   lam = lam * dur;
   lam = lam * 1e-3;
   lam = lam * a.scale_factor;
+  return lam;
+}
+__device__ __forceinline__ BinPlan plan_bin(const PrepArgs& a, int k, int w, double wl, double flux_w, double sens_w,
+                                            double dlam_w, double ratio_w, double sigl_w, const double* tr,
+                                            double x_ref, double y_ref, double dur, double depth) {
+  BinPlan o;
+  bin_position(a, wl, tr, x_ref, y_ref, &o.xs, &o.ys);
+  const double lam = bin_mean_counts(a, flux_w, sens_w, dlam_w, dur, depth);
   double cnt;
   if ((a.flags & (1u << 5)) != 0) {         // WAYNE_F_ADD_STELLAR_NOISE
     PhiloxStream rng(a.seed, STAGE_COUNTS, (uint32_t)w, (uint32_t)k, a.exposure);

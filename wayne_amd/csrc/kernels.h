@@ -19,6 +19,8 @@
 //                   k_extract_crmask                    opt-in on top of it: the cosmic-ray flag plane of the difference images
 //   k_fits.h        k_fits_words   opt-in: the reads as the big-endian data sections of their FITS file, in file order,
 //                                  padding included (a streaming byte reversal), no reference counterpart
+//   k_expect.h      k_expect       opt-in: the noise-free expected image of the thrower stage per read interval (the law
+//                                  the Monte-Carlo throwers converge to, as a gather), no reference counterpart
 //
 // "A<n>" are the row ids of SURVEY.md section 8(a); reference file:line
 // citations are next to each formula.
@@ -31,3 +33,4 @@
 #include "k_ramp.h"
 #include "k_extract.h"
 #include "k_fits.h"
+#include "k_expect.h"

@@ -38,8 +38,8 @@ int fail(wayne_ctx* c, int code, const std::string& msg);   // (keeps `msg` as t
 inline size_t align64(size_t n) { return (n + 63) & ~(size_t)63; }
 
 enum ProfKernel { PK_PREP_WL = 0, PK_PREP_SUB, PK_THROW, PK_COSMIC, PK_RAMP, PK_LIGHTCURVE, PK_NARROW, PK_LANE,
-                  PK_EXTRACT, PK_FITS };   // (PK_EXTRACT and PK_FITS lie beyond wayne_profile's arrays, which the ABI fixes: wayne_extract_profile / wayne_fits_profile report them)
-constexpr int kProfKernels = WAYNE_PROF_KERNELS + 2;
+                  PK_EXTRACT, PK_FITS, PK_EXPECT };   // (PK_EXTRACT .. PK_EXPECT lie beyond wayne_profile's arrays, which the ABI fixes: wayne_extract_profile / wayne_fits_profile / wayne_expected_profile report them)
+constexpr int kProfKernels = WAYNE_PROF_KERNELS + 3;
 const char* const kProfNames[WAYNE_PROF_KERNELS] = {"k_prep_wl", "k_prep_sub",   "k_throw",  "k_cosmic",   /* (cosmic rays ride in k_prep_sub: slot kept for the ABI) */
                                                     "k_ramp",    "k_lightcurve", "k_narrow", "k_lane"};
 
@@ -283,6 +283,10 @@ struct Slot : SourceState {
   PinnedBuf fits_pinned;
   Misc* fits_pinned_misc = nullptr;
   uint32_t fits_pinned_run = 0;
+  // the noise-free expected image of this exposure (wayne_exposure_set_expected; cleared by upload): the mode
+  // (0: none) and the plane [R][S][S] float64 that k_expect renders at the very end of the back half
+  int expect_mode = 0;
+  DevBuf expect_plane;
   // staging arena of the descriptor's arrays: uploads are enqueued from here, so
   // wayne_exposure_upload returns without waiting for the slot's stream to drain
   StageArena stage;
@@ -972,6 +976,47 @@ int launch_fits(wayne_ctx* c, Slot& s) {
   return WAYNE_OK;
 }
 
+// The expected image of slot `s` (wayne_exposure_set_expected), at the very end of the back half: the plane cleared, then
+// one k_expect launch per source, each adding into it -- on the slot's stream, so in list order.  A source's launch takes
+// k_prep_sub's arguments of THIS run (SourceState::last_prep, kept by front_source whether or not k_prep_sub was launched):
+// the kernel plans its bins itself, with plan_bin, from the same inputs.  The boxes come from the host copies of the
+// source's wavelengths, star positions and trace coefficients, which its staging arena holds until the next upload.
+int launch_expected(wayne_ctx* c, Slot& s) {
+  const int R = s.R, K = s.K, N = c->N, S = c->S;
+  ProfScope ps(c, PK_EXPECT);
+  HIP_TRY(c, hipMemsetAsync(s.expect_plane.p, 0, (size_t)R * S * S * sizeof(double), c->stream));
+  const int32_t* sread = s.stage.host_of<int32_t>(s.sread);
+  for (int i = 0; i <= s.n_extra; ++i) {
+    SourceState& ss = s.source(i);
+    const StageArena& st = i == 0 ? s.stage : ss.src_stage;
+    ExpectArgs e{};
+    e.R = R; e.S = S;
+    e.plane = s.expect_plane.as<double>();
+    plan::expected_boxes(c->g, ss.W, st.host_of<double>(ss.wl), K, R, N, s.d.sub_scale, st.host_of<double>(ss.xref),
+                         st.host_of<double>(ss.yref), st.host_of<double>(ss.tr), sread, e.box);
+    int tiles = 0;
+    for (int r = 0; r < R; ++r) {
+      const int* b = e.box[r];
+      if (b[0] >= b[1] || b[2] >= b[3]) continue;
+      tiles = std::max(tiles, ((b[1] - b[0] + kExpectTW - 1) / kExpectTW) * ((b[3] - b[2] + kExpectTH - 1) / kExpectTH));
+    }
+    if (tiles == 0) continue;      // the source reaches no pixel of the frame
+    // what flat_value reads of a thrower's arguments (front_source)
+    ThrowArgs t{};
+    t.W = ss.W; t.K = K; t.N = N; t.S = S;
+    t.flags = s.d.flags;
+    t.flat_off = s.d.sub_scale;
+    t.flat_wmin = c->g.flat_wmin; t.flat_wmax = c->g.flat_wmax;
+    t.flat_inv_range = 1.0 / (c->g.flat_wmax - c->g.flat_wmin);
+    for (int j = 0; j < 4; ++j) t.flat[j] = c->has_flat ? c->flat[j].as<float>() : nullptr;
+    const dim3 grid((unsigned)tiles, (unsigned)R), block(kExpectThreads);
+    if (s.expect_mode == WAYNE_EXPECT_COUNTS) hipLaunchKernelGGL(k_expect<1>, grid, block, 0, c->stream, ss.last_prep, t, e);
+    else hipLaunchKernelGGL(k_expect<2>, grid, block, 0, c->stream, ss.last_prep, t, e);
+    HIP_TRY(c, hipGetLastError());
+  }
+  return WAYNE_OK;
+}
+
 // No extraction on slot `s` (upload, set_extraction): every switch of it off, nothing fetched.  The profile planes and
 // the optimal channels go with the optimal extraction wherever that is cleared.
 void ex_clear(Slot& s) {
@@ -1508,6 +1553,7 @@ int wayne_exposure_upload(wayne_ctx* c, int slot, const wayne_exposure_desc* d) 
   ex_clear(s);               // ... and no spectral extraction, nor any option of it, until wayne_exposure_set_extraction says so
   s.fits_on = false;         // ... and no FITS words until wayne_exposure_set_fits says so
   s.fits_pinned_misc = nullptr;
+  s.expect_mode = 0;         // ... and no expected image until wayne_exposure_set_expected says so
   int rc;
   const size_t KW = (size_t)K * W;
   {
@@ -1957,6 +2003,8 @@ int wayne_exposure_run_back(wayne_ctx* c, int slot) {
     if (int rc = launch_extract(c, s)) return rc;   // the spectra of the reads just written, behind them on the stream
   if (s.fits_on)
     if (int rc = launch_fits(c, s)) return rc;      // ... and their FITS words
+  if (s.expect_mode)
+    if (int rc = launch_expected(c, s)) return rc;  // ... and, last of all, the expected image of the thrower stage
   s.acc_dirty = false;
 #ifdef WAYNE_TIMING_KNOBS
   if (ramp_reads_cut) s.acc_dirty = true;     // the next front half starts from cleared accumulators
@@ -2843,6 +2891,52 @@ int wayne_fits_profile(wayne_ctx* c, uint64_t* launches, double* ms) {
   if (rc) return rc;
   if (launches) *launches = c->prof_launches[PK_FITS];
   if (ms) *ms = c->prof_ms[PK_FITS];
+  return WAYNE_OK;
+}
+
+// ---------------------------------------------------------------------------
+// the noise-free expected image
+// ---------------------------------------------------------------------------
+int wayne_exposure_set_expected(wayne_ctx* c, int slot, int mode) {
+  if (!c) return WAYNE_E_INVALID;
+  if (slot < 0 || slot >= kSlots) return fail(c, WAYNE_E_INVALID, "set_expected: slot");
+  Slot& s = c->slots[slot];
+  if (!s.uploaded) return fail(c, WAYNE_E_STATE, "set_expected: slot not uploaded");
+  s.expect_mode = 0;           // from here on a refusal leaves the slot usable, without the expected image
+  if (mode == 0) return WAYNE_OK;
+  if (mode != WAYNE_EXPECT_COUNTS && mode != WAYNE_EXPECT_MEAN) return fail(c, WAYNE_E_INVALID, "set_expected: mode");
+  if (s.d.rng_mode == WAYNE_RNG_REPLAY)
+    return fail(c, WAYNE_E_INVALID, "set_expected: replay mode reproduces the reference, which has no expected image");
+  if (s.R > kExpectMaxReads) return fail(c, WAYNE_E_INVALID, "set_expected: more than 16 reads");
+  (void)hipSetDevice(c->device);
+  HIP_TRY(c, s.expect_plane.reserve((size_t)s.R * c->S * c->S * sizeof(double)));
+  s.expect_mode = mode;
+  return WAYNE_OK;
+}
+
+int wayne_exposure_download_expected(wayne_ctx* c, int slot, double* out) {
+  if (!c || !out) return WAYNE_E_INVALID;
+  if (slot < 0 || slot >= kSlots) return fail(c, WAYNE_E_INVALID, "download_expected: slot");
+  Slot& s = c->slots[slot];
+  if (!s.uploaded) return fail(c, WAYNE_E_STATE, "download_expected: slot not uploaded");
+  if (!s.expect_mode) return fail(c, WAYNE_E_STATE, "download_expected: no expected image set for the slot");
+  (void)hipSetDevice(c->device);
+  use_slot_stream(c, slot);
+  const size_t bytes = (size_t)s.R * c->S * c->S * sizeof(double);
+  HIP_TRY(c, hipMemcpyAsync(out, s.expect_plane.p, bytes, hipMemcpyDeviceToHost, c->stream));
+  bool reran = false;
+  int rc = look_at_status(c, slot, nullptr, wayne_exposure_run, &reran);
+  if (rc || !reran) return rc;
+  HIP_TRY(c, hipMemcpyAsync(out, s.expect_plane.p, bytes, hipMemcpyDeviceToHost, c->stream));
+  return look_at_status(c, slot, nullptr);
+}
+
+int wayne_expected_profile(wayne_ctx* c, uint64_t* launches, double* ms) {
+  if (!c) return WAYNE_E_INVALID;
+  int rc = collect_profile(c);
+  if (rc) return rc;
+  if (launches) *launches = c->prof_launches[PK_EXPECT];
+  if (ms) *ms = c->prof_ms[PK_EXPECT];
   return WAYNE_OK;
 }
 

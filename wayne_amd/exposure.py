@@ -31,6 +31,7 @@ class Exposure(object):
         self.SAMPSEQ = self.exp_info.get("SAMPSEQ")
         self.reads = []   # [(array (S, S), header dict)], read 0 first
         self.stored = []  # [(piece, header dict, shape, type code)], read 0 first: reads held as their FITS words (add_stored_read)
+        self.expected = None   # [R, S, S] float64: the noise-free expected image per read interval, when it was asked for (expected=)
 
     def add_read(self, data, read_info=None):
         self.reads.append((data, self.generate_read_header(read_info) if read_info is not None else {}))

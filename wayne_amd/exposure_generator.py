@@ -124,7 +124,7 @@ class ExposureGenerator(object):
                        add_initial_bias=True, progress_bar=None, threads=2,
                        rng_mode=_lib.RNG_SPLIT, out_dtype=np.float32, reference_quirks=False,
                        record=None, exact_samplers=False, contaminants=None, charge_traps=None, extraction=None,
-                       crrej=None, channels=None, variance=None, optimal=None):
+                       crrej=None, channels=None, variance=None, optimal=None, expected=None):
         """Generate a spatially scanned exposure (exposure_generator.py:178-405).
 
         Extra keywords (not in the reference): `rng_mode` -- RNG_SPLIT (default:
@@ -162,15 +162,21 @@ class ExposureGenerator(object):
         extraction (True or an extraction.Variances; it replaces the `variance` the extraction carries): the Exposure
         then carries `spectra_var` [R + 1, S], `sky_var` [R + 1] and, with channels, `channels_var` [R + 1, C] too;
         `optimal` -- the optimal (profile-weighted) extraction on top of those variances (True or an extraction.Optimal; it
-        replaces the `optimal` the extraction carries): the Exposure then carries `optimal` and `optimal_var` [R + 1, S] too.
+        replaces the `optimal` the extraction carries): the Exposure then carries `optimal` and `optimal_var` [R + 1, S] too;
+        `expected` -- "counts" or "mean": the noise-free expected image of the thrower stage is rendered beside the
+        exposure (k_expect; wayne_hip.h, wayne_exposure_set_expected) and the Exposure carries it as `expected`
+        [R, S, S] float64, electrons per read interval: what the Monte-Carlo throwers converge to, given the bin counts
+        this run drew ("counts") or before the draw ("mean").  Not in it: sky, cosmic rays, dark, the gaussian-noise
+        stage, gain, non-linearity, traps.  Not in replay mode.  staring_frame passes it on too.
         """
         eng, desc, start_time = self._host_half(
             x_ref, y_ref, x_jitter, y_jitter, wl, stellar_flux, planet_signal, scan_speed, sample_rate,
             sample_mid_points, sample_durations, read_index, ssv_generator, noise_mean, noise_std, add_dark,
             add_flat, cosmic_rate, sky_background, scale_factor, add_gain_variations, add_non_linear,
             clip_values_det_limits, add_read_noise, add_stellar_noise, add_initial_bias, progress_bar, threads,
-            rng_mode, out_dtype, reference_quirks, exact_samplers, contaminants, charge_traps, extraction, crrej, channels, variance, optimal)
-        if record is None and desc._extraction is None:
+            rng_mode, out_dtype, reference_quirks, exact_samplers, contaminants, charge_traps, extraction, crrej, channels, variance, optimal,
+            expected=expected)
+        if record is None and desc._extraction is None and desc._expected is None:
             reads = eng.ctx.synthesize(desc)
         else:
             eng.ctx.upload(0, desc)
@@ -189,6 +195,8 @@ class ExposureGenerator(object):
                                eng.ctx.optimal(0) if desc._extraction.optimal is not None else None,
                                eng.ctx.profile_planes(0) if eng.ctx.delivers_profile(0) else None,
                                eng.ctx.optimal_channels(0) if eng.ctx.has_optimal_channels(0) else None)
+        if desc._expected is not None:
+            frame.expected = eng.ctx.expected(0)
         return frame
 
     def _fill_spectra(self, spectra, sky, rejected=None, channels=None, variances=None, optimal=None, profile_planes=None,
@@ -257,7 +265,7 @@ class ExposureGenerator(object):
                    add_initial_bias=True, progress_bar=None, threads=2,
                    rng_mode=_lib.RNG_SPLIT, out_dtype=np.float32, reference_quirks=False,
                    exact_samplers=False, contaminants=None, charge_traps=None, extraction=None,
-                       crrej=None, channels=None, variance=None, optimal=None, device_fits=False):
+                       crrej=None, channels=None, variance=None, optimal=None, device_fits=False, expected=None):
         """scanning_frame's arguments -> (engine, descriptor, start time): the mode's engine (cached after its first
         use) and build_descriptor.  No GPU call once the engine exists."""
         start_time = time.time()
@@ -269,7 +277,7 @@ class ExposureGenerator(object):
             add_flat, cosmic_rate, sky_background, scale_factor, add_gain_variations, add_non_linear,
             clip_values_det_limits, add_read_noise, add_stellar_noise, add_initial_bias, progress_bar, threads,
             rng_mode, out_dtype, reference_quirks, exact_samplers, contaminants, charge_traps, extraction, crrej, channels, variance, optimal,
-            device_fits=device_fits)
+            device_fits=device_fits, expected=expected)
         return eng, desc, start_time
 
     def prepare(self, *args, staring=False, **kw):
@@ -291,13 +299,17 @@ class ExposureGenerator(object):
                          add_initial_bias=True, progress_bar=None, threads=2,
                          rng_mode=_lib.RNG_SPLIT, out_dtype=np.float32, reference_quirks=False,
                          exact_samplers=False, contaminants=None, charge_traps=None, extraction=None,
-                       crrej=None, channels=None, variance=None, optimal=None, device_fits=False):
+                       crrej=None, channels=None, variance=None, optimal=None, device_fits=False, expected=None):
         """The host half of scanning_frame: sample timing, scan positions, SSV,
         jitter / seed draws, spectrum crop (exposure_generator.py:247-334) ->
         one wayne_exposure_desc for the device.  Pure host code (`eng` may be
         None when no GPU is involved, e.g. when sharding a visit on the CPU).
         `device_fits`: Context.upload also asks the device for the reads' FITS words (wayne_exposure_set_fits), the way
-        it applies `extraction`; nothing the device computes for the reads changes."""
+        it applies `extraction`; nothing the device computes for the reads changes.  `expected`: "counts" or "mean" --
+        Context.upload also asks for the noise-free expected image (wayne_exposure_set_expected); refused here, with a
+        ValueError, for any other value and in replay mode."""
+        if _lib.expected_mode(expected) and rng_mode == _lib.RNG_REPLAY:
+            raise ValueError("expected: replay mode reproduces the reference, which has no expected image")
         out_dtype = np.dtype(out_dtype)
         if out_dtype not in _lib.OUT_FLAGS:
             raise ValueError("out_dtype must be float32, float64 or uint16, not %s" % out_dtype)
@@ -423,7 +435,7 @@ class ExposureGenerator(object):
             scale_factor=1.0 if scale_factor is None else float(scale_factor),
             noise_mean=float(noise_mean) if noise_mean else 0.0,
             noise_std=float(noise_std) if noise_std else 0.0, sources=contaminants, traps=charge_traps,
-            extraction=self.extraction_plan, device_fits=device_fits, **lc)
+            extraction=self.extraction_plan, device_fits=device_fits, expected=expected, **lc)
 
     def direct_image(self, x_ref, y_ref):
         """The unscaled 2-D gaussian direct image used to calibrate x_ref / y_ref

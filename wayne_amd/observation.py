@@ -70,6 +70,8 @@ class Observation(object):
         # it: `spectra_result["spectra_var"]` / ["sky_var"] / ["channels_var"] and the .npz's keys of those names.
         # frame_options["optimal"] (True or an extraction.Optimal; CLI: --optimal [H]) adds the optimal extraction on
         # top of those variances: `spectra_result["optimal"]` / ["optimal_var"] and the .npz's keys of those names.
+        # frame_options["expected"] ("counts" or "mean"; CLI: --expected): the noise-free expected image of every exposure
+        # (wayne_amd/expected.py), on the Exposure and as NNNN_exp.fits beside the raw file.
         # frame_options["device_fits"] (True; CLI: --device-fits): the device forms the data sections of the _raw files and
         # run_observation writes every file straight from its slot's pinned mirror (fits_delivery) -- the same files,
         # without the host's pass over the samples.  The direct image stays on the host path; not with `spectra_only`.
@@ -360,6 +362,12 @@ class Observation(object):
         device_fits = bool(self.frame_options.get("device_fits", False))
         if device_fits and self.spectra_only:
             raise ValueError("device_fits forms the data sections of the raw files; spectra_only writes none")
+        # frame_options["expected"] ("counts" / "mean"; CLI: --expected): every exposure's noise-free expected image is
+        # rendered beside it (wayne_amd/expected.py) -- the Exposure carries it and NNNN_exp.fits is written beside the raw file
+        from . import expected as _expected
+        expected = self.frame_options.get("expected")
+        _expected.refuse_combinations(expected, resume=resume, device_fits=device_fits, spectra=extraction is not None,
+                                      spectra_only=self.spectra_only)
         if self.traps_carried:
             # every exposure starts from the state its predecessor left on ONE device: the visit runs whole and in order
             if world > 1:
@@ -432,6 +440,10 @@ class Observation(object):
                                           ctx.profile_planes, ctx.channels_opt)
             if reads is not None:
                 frame = gen._fill_exposure(np.array(reads), gen._prepared[2])     # (a copy: the pinned buffer is reused)
+            if expected and frame is not None:
+                frame.expected = ctx.expected
+                if pool is not None:
+                    _expected.write_fits(os.path.join(self.outdir, "{:04d}_exp.fits".format(i + 1)), frame, ctx.expected, expected)
             if payload is not None:
                 # (views of the pinned mirror, no copy: the slot is not uploaded again until the writer has released it)
                 frame = gen._fill_stored(payload, ctx.layout, gen._prepared[2])
@@ -464,6 +476,8 @@ class Observation(object):
                 ctx = FitsDelivery(eng.ctx, extraction=ctx if extraction is not None else None)
                 n_slots = slots_for(4, pool.n_threads)
                 self._fits_active = True
+            if expected:
+                ctx = _expected.ExpectedDelivery(eng.ctx, ctx)
             run_pipelined(ctx, mine, prepare, finish, depth=3, n_slots=n_slots)
         finally:
             self._fits_active = False

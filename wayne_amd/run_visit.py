@@ -3,7 +3,7 @@
     python -m wayne_amd.run_visit -p <parameter_file> [--calibration DIR] [--device N] [--max-exposures M] [--gpus G] [--resume]
                                   [--spectra OUT.npz | --spectra-only OUT.npz] [--reject-cosmics [K]]
                                   [--channels LO:HI:N] [--no-channel-flat] [--variances [RN]] [--optimal [H]] [--optimal-profile N] [--optimal-channels]
-                                  [--float64-reads | --uint16-reads] [--device-fits]
+                                  [--float64-reads | --uint16-reads] [--device-fits] [--expected {counts,mean}]
 
 Accepts the reference's parameter files (wayne/run_visit.py:1-9, example
 examples/hd209458b_12181_simulation_parameters.yml): sections `general`
@@ -49,6 +49,11 @@ examples/hd209458b_12181_simulation_parameters.yml): sections `general`
     included) and every file is written straight from the pinned memory they are copied into: the same files, byte for
     byte, without the host's pass over the samples (wayne_amd/fits_delivery.py).  With every other option but
     --spectra-only (which writes no _raw files); the direct image stays on the host path;
+  * `--expected {counts,mean}`: the device also renders every exposure's noise-free expected image (wayne_amd/expected.py:
+    what the electron thrower converges to, given the bin counts the run drew -- counts -- or before the draw -- mean;
+    electrons per read interval, without sky, cosmic rays, dark and the detector chain) and NNNN_exp.fits is written
+    beside each _raw file: the raw file's primary header plus EXPMODE, then one image HDU EXPECT per read interval
+    (EXTVER 1 .. R, BITPIX -64).  Not with --resume, --device-fits, --spectra or --spectra-only;
   * `--gpus G`: the process starts G rank processes itself (one per GPU of this node, before anything touches a
     GPU) and waits for them; under an external launcher (WORLD_SIZE / RANK set, one process per GPU) it is one
     rank.  Each rank generates its round-robin share of the exposures (observation.py:403-405 is the axis) on the
@@ -215,6 +220,10 @@ def run(argv=None):
     ap.add_argument("--device-fits", action="store_true",
                     help="form the data sections of the _raw files on the device and write every file straight from pinned "
                          "memory: the same files, without the host's pass over the samples (not with --spectra-only)")
+    ap.add_argument("--expected", choices=("counts", "mean"), default=None,
+                    help="render every exposure's noise-free expected image on the device and write it to NNNN_exp.fits "
+                         "beside the _raw file: what the electron thrower converges to, given the bin counts the run drew "
+                         "(counts) or before the draw (mean); not with --resume, --device-fits, --spectra, --spectra-only")
     spectra = ap.add_mutually_exclusive_group()
     spectra.add_argument("--spectra", metavar="OUT.npz", default=None,
                          help="extract every exposure's column spectra on the device and write them to OUT.npz beside "
@@ -295,6 +304,11 @@ def run(argv=None):
     if args.device_fits and args.spectra_only:
         # (the API's refusal, Observation.run_observation's ValueError, raised before any rank process is started)
         raise ValueError("--device-fits forms the data sections of the _raw files; --spectra-only writes none")
+    if args.expected:
+        # (the API's refusal, Observation.run_observation's ValueError, raised before any rank process is started)
+        from . import expected as _expected
+        _expected.refuse_combinations(args.expected, resume=args.resume, device_fits=args.device_fits,
+                                      spectra=bool(args.spectra), spectra_only=bool(args.spectra_only))
     if args.resume and (args.spectra or args.spectra_only):
         raise SystemExit("--spectra / --spectra-only cannot be combined with --resume (a skipped exposure has no spectra)")
     if args.gpus < 1 or args.ranks_per_gpu < 1:
@@ -355,6 +369,8 @@ def run(argv=None):
         obs.frame_options["out_dtype"] = np.uint16
     if args.device_fits:
         obs.frame_options["device_fits"] = True
+    if args.expected:
+        obs.frame_options["expected"] = args.expected
     if args.spectra or args.spectra_only:
         obs.frame_options["extraction"] = True
         if args.reject_cosmics is not None:

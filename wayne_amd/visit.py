@@ -11,8 +11,10 @@ import os
 
 import numpy as np
 
+from . import _lib
 from . import engine as _engine
 from . import extraction as _extraction
+from .expected import ExpectedDelivery
 from .exposure import FitsWriterPool
 from .exposure_generator import ExposureGenerator
 from .fits_delivery import FitsDelivery, slots_for
@@ -88,7 +90,7 @@ class VisitRunner(object):
         return self.generator(i).build_descriptor(eng, out_dtype=self.out_dtype, rng_mode=self.rng_mode,
                                                   **self.frame_kwargs(i))
 
-    def run(self, indices, keep=False, on_reads=None, extraction=None, on_spectra=None):
+    def run(self, indices, keep=False, on_reads=None, extraction=None, on_spectra=None, expected=None, on_expected=None):
         """Synthesise the given exposures as a pipeline over the context's two HIP streams and pinned
         host buffers: while the kernels of exposure n run on one stream and the device-to-host copy of
         exposure n-1 on the other, the host prepares and uploads exposure n+1 into the next slot.
@@ -100,9 +102,13 @@ class VisitRunner(object):
         {index: (reads, spectra, sky)}.  When the extraction delivers variances, `self.spectra_var`, `self.sky_var` and
         -- with channels -- `self.channels_var` are {index: array} of every exposure run (None otherwise); when it
         extracts optimally too, so are `self.optimal` and `self.optimal_var`, and `self.profile_planes` when it delivers
-        its profile planes."""
+        its profile planes.  `expected` ("counts" or "mean"): every exposure's noise-free expected image is rendered
+        beside it (wayne_amd/expected.py) and fetched behind its settled run: `on_expected(i, planes)` gets an array
+        [R, S, S] of the caller's own, and with keep=True `self.expected` is {index: planes} (None otherwise)."""
         eng = self.engine()
         results = {}
+        _lib.expected_mode(expected)          # (ValueError for anything but None, "counts", "mean")
+        self.expected = {} if expected and keep else None
         self.spectra_var = self.sky_var = self.channels_var = None
         self.optimal = self.optimal_var = None
         self.profile_planes = None
@@ -120,6 +126,8 @@ class VisitRunner(object):
                 kw["extraction"] = extraction
             if fits:
                 kw["device_fits"] = True
+            if expected:
+                kw["expected"] = expected
             return gen.build_descriptor(eng, out_dtype=self.out_dtype, rng_mode=self.rng_mode, **kw), gen
 
         def finish(i, gen, got):
@@ -152,6 +160,11 @@ class VisitRunner(object):
                     self.profile_planes[i] = ctx.profile_planes
                 if on_spectra is not None:
                     on_spectra(i, spectra, sky)
+            if expected:
+                if on_expected is not None:
+                    on_expected(i, ctx.expected)
+                if self.expected is not None:
+                    self.expected[i] = ctx.expected
             if on_reads is not None:
                 on_reads(i, reads)
             if keep:
@@ -172,6 +185,8 @@ class VisitRunner(object):
             n_slots = slots_for(self.DEPTH, pool.n_threads)
         else:
             ctx = eng.ctx if extraction is None else _extraction.Delivery(eng.ctx, reads=True)
+        if expected:
+            ctx = ExpectedDelivery(eng.ctx, ctx)
         try:
             run_pipelined(ctx, indices, prepare, finish, self.DEPTH, n_slots)
         finally:
