@@ -800,6 +800,33 @@ int wayne_exposure_download_expected(wayne_ctx *ctx, int slot, double *out);
  * since wayne_profile_reset: renderings and total milliseconds.  wayne_profile_select's bit 10 selects it.  Synchronises. */
 int wayne_expected_profile(wayne_ctx *ctx, uint64_t *launches, double *ms);
 
+/* ---- limb darkening per wavelength bin ---------------------------------- */
+
+/* A device light curve (lc_z of the descriptor) uses ONE set of Claret coefficients, lc_ld, for every wavelength bin.
+ * With a table the slot's depth matrix is computed by k_lightcurve_ld with four coefficients per bin.  The law: with
+ * I(mu) = c0 + sum_{n=1..4} a_n mu^(n/2), c0 = 1 - sum a_n, the blocked flux is linear in the coefficients,
+ *
+ *   B_n(z, p) = int_{occulted region} mu^(n/2) dA,  n = 0 .. 4                  (B_0: the lens area)
+ *             = 2 pi (1 - mu_f^(n/2+2)) / (n/2+2)        radii wholly inside the planet, mu_f = sqrt(1 - clip(p - z, 0, 1)^2)
+ *             + int_{|z-p|}^{min(1,z+p)} mu^(n/2) r theta(r) dr                 k_lightcurve's 24-node tanh-sinh rule
+ *   deficit[k][w] = (c0(w) B_0 + sum_n a_n(w) B_n)(z_k, p_w) / (pi (1 - sum_n a_n(w) n/(n+4)))
+ *   depth[k][w]   = deficit[k][w] + p_w^2 hidden_k / (1 + p_w^2)                the eclipse term, unchanged
+ *
+ * float32 integrand, float64 sums; grid, Chebyshev interpolation in p and the decisions between its paths are
+ * k_lightcurve's (five interpolants, one per B_n).  A NaN radius ratio gives deficit 0.  Not covered: limb darkening
+ * in the eclipse term, a contaminant that eclipses, coefficients looked up from stellar parameters.  Counted under the
+ * "k_lightcurve" slot of wayne_profile.  Opt-in: without a table every launch and every byte stay as they are.  Added
+ * within WAYNE_ABI_VERSION 7: new symbols only.
+ *
+ * After wayne_exposure_upload, before run: Claret coefficients per wavelength bin, ld[w*4 + n-1], n_wl == the
+ * descriptor's n_wl.  ld == NULL or n_wl == 0 clears; wayne_exposure_upload clears.  The slot then launches
+ * k_lightcurve_ld in place of k_lightcurve; desc.lc_ld is ignored while a table is set.  The table is copied (into
+ * pinned staging, four planes of n_wl on the device): the caller's array is free on return.  WAYNE_E_STATE on a slot that
+ * is not uploaded; WAYNE_E_INVALID when the slot has no device light curve (lc_z was NULL), n_wl differs from the slot's,
+ * a coefficient is not finite or 1 - sum a_n n/(n+4) <= 0 for some bin -- the slot stays usable and runs without a
+ * table.  wayne_exposure_debug_depth serves the matrix as it is. */
+int wayne_exposure_set_limb_darkening(wayne_ctx *ctx, int slot, const double *ld, int n_wl);
+
 /* ---- measurement ------------------------------------------------------- */
 
 #define WAYNE_PROF_KERNELS 8

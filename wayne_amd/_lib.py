@@ -204,6 +204,7 @@ SYMBOLS = {
     "wayne_exposure_set_expected": (C.c_int, [_vp, C.c_int, C.c_int]),
     "wayne_exposure_download_expected": (C.c_int, [_vp, C.c_int, _dp]),
     "wayne_expected_profile": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_double)]),
+    "wayne_exposure_set_limb_darkening": (C.c_int, [_vp, C.c_int, _dp, C.c_int]),
     "wayne_profile_enable": (C.c_int, [_vp, C.c_int]),
     "wayne_profile_select": (C.c_int, [_vp, C.c_uint]),
     "wayne_profile_reset": (C.c_int, [_vp]),
@@ -477,6 +478,21 @@ class Context(object):
         expected = getattr(desc, "_expected", None)
         if expected is not None:
             self.set_expected(slot, expected)
+        ld_table = getattr(desc, "_ld_table", None)
+        if ld_table is not None:
+            self.set_limb_darkening(slot, ld_table)
+
+    # -- limb darkening per wavelength bin -------------------------------------------
+    def set_limb_darkening(self, slot, ld):
+        """Claret coefficients per wavelength bin of the slot's device light curve, an array [W, 4] (k_lightcurve_ld in
+        place of k_lightcurve); None clears; after upload, which clears it too.  See wayne_exposure_set_limb_darkening."""
+        if ld is None:
+            self.check(self._L.wayne_exposure_set_limb_darkening(self._h, int(slot), None, 0))
+            return
+        ld = f64(ld)
+        if ld.ndim != 2 or ld.shape[1] != 4:
+            raise ValueError("set_limb_darkening: expected an array [W, 4], got shape %s" % (ld.shape,))
+        self.check(self._L.wayne_exposure_set_limb_darkening(self._h, int(slot), ptr(ld, C.c_double), ld.shape[0]))
 
     # -- the noise-free expected image ---------------------------------------------
     def set_expected(self, slot, mode):
@@ -1008,14 +1024,16 @@ def make_desc(seed, exposure_index, flags, sub_scale, wl_um, flux, depth, x_ref,
               sample_read, read_dt_s, replay_seed=None, rng_mode=RNG_PHILOX, threads_compat=1,
               sky_ct_s=0.0, cosmic_rate=-1.0, scale_factor=1.0, noise_mean=0.0, noise_std=0.0,
               thrower_margin=0, thrower_splits=0, lc_z=None, lc_hidden=None, lc_rp=None, lc_ld=None, sources=None,
-              traps=None, extraction=None, device_fits=False, expected=None):
+              traps=None, extraction=None, device_fits=False, expected=None, lc_ld_table=None):
     """The exposure descriptor.  `sources`: contaminating field stars (sources.Contaminant), carried beside the C struct
     and set by Context.upload (wayne_exposure_set_sources); None or [] = the target alone.  `traps`: charge traps
     (traps.ExposureTraps, or a traps.ChargeTraps whose table is flat at `initial`), set by Context.upload
     (wayne_exposure_set_traps); None = no trapping.  `extraction`: the spectral extraction of the exposure
     (extraction.Extraction), set by Context.upload (wayne_exposure_set_extraction); None = reads only.  `device_fits`: the reads' FITS words are formed on the device too,
     set by Context.upload (wayne_exposure_set_fits).  `expected`: "counts" or "mean" -- the noise-free expected image is
-    rendered with every run, set by Context.upload (wayne_exposure_set_expected); None = none."""
+    rendered with every run, set by Context.upload (wayne_exposure_set_expected); None = none.  `lc_ld_table`: Claret
+    coefficients per wavelength bin [W, 4] of the device light curve, carried beside the C struct and set by
+    Context.upload (wayne_exposure_set_limb_darkening); None = lc_ld for every bin."""
     d = ExposureDesc()
     keep = []
 
@@ -1060,6 +1078,13 @@ def make_desc(seed, exposure_index, flags, sub_scale, wl_um, flux, depth, x_ref,
             lc_hidden = arr(lc_hidden, f64)
             d.lc_hidden = ptr(lc_hidden, C.c_double)
         d.lc_ld[:] = [float(v) for v in lc_ld]
+    if lc_ld_table is not None:
+        if lc_z is None:
+            raise ValueError("lc_ld_table needs the device light curve (lc_z)")
+        lc_ld_table = f64(lc_ld_table)
+        if lc_ld_table.shape != (W, 4):
+            raise ValueError("lc_ld_table must have shape (W, 4)")
+    d._ld_table = lc_ld_table
     d._keep = keep
     d._sources = tuple(sources) if sources else ()
     if traps is not None:

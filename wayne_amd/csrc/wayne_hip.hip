@@ -207,6 +207,11 @@ struct Slot : SourceState {
   unsigned char sky_tab0[16] = {0};
   std::vector<double> read_dt_host;
   double lc_p_lo = 0., lc_p_hi = 0.;   // range of lc_rp
+  // limb darkening per wavelength bin (wayne_exposure_set_limb_darkening; cleared by upload): four planes [4][W] in an
+  // arena of their own; the slot then launches k_lightcurve_ld in place of k_lightcurve
+  bool ld_on = false;
+  StageArena ld_stage;
+  DevBuf ld_tab;
   // charge traps of this exposure (wayne_exposure_set_traps; cleared by upload): the parameters, and the start tables
   // in one arena -- [2][G] float64 (generic loop), then [2][G] float32 (production chain)
   bool traps_on = false;
@@ -1554,6 +1559,7 @@ int wayne_exposure_upload(wayne_ctx* c, int slot, const wayne_exposure_desc* d) 
   s.fits_on = false;         // ... and no FITS words until wayne_exposure_set_fits says so
   s.fits_pinned_misc = nullptr;
   s.expect_mode = 0;         // ... and no expected image until wayne_exposure_set_expected says so
+  s.ld_on = false;           // ... and one set of limb-darkening coefficients until wayne_exposure_set_limb_darkening says so
   int rc;
   const size_t KW = (size_t)K * W;
   {
@@ -1839,6 +1845,17 @@ static int front_source(wayne_ctx* c, int slot, Slot& s, SourceState& ss, int sr
   return WAYNE_OK;
 }
 
+// tanh-sinh rule on (0, 1) of the light-curve kernels: t in [-3, 3], u = pi/2 sinh t, x = (1 + tanh u)/2 (wayne_amd/lightcurve.py)
+static void lc_rule(float* x, float* w, float* d) {
+  const double h = 6.0 / (kLcNodes - 1);
+  for (int i = 0; i < kLcNodes; ++i) {
+    const double t = -3.0 + h * i, u = 0.5 * kPi * std::sinh(t);
+    x[i] = (float)(0.5 * (1.0 + std::tanh(u)));
+    w[i] = (float)(h * 0.25 * kPi * std::cosh(t) / (std::cosh(u) * std::cosh(u)));
+    d[i] = (float)(0.5 * std::exp(-std::fabs(u)) / std::cosh(u));
+  }
+}
+
 int wayne_exposure_run_front(wayne_ctx* c, int slot) {
   if (!c) return WAYNE_E_INVALID;
   if (slot < 0 || slot >= kSlots) return fail(c, WAYNE_E_INVALID, "run: slot");
@@ -1864,7 +1881,20 @@ int wayne_exposure_run_front(wayne_ctx* c, int slot) {
     HIP_TRY(c, hipMemsetAsync(s.seg.p, 0, s.seg.cap, c->stream));
     s.acc_dirty = false;
   }
-  if (s.has_lc) {
+  if (s.has_lc && s.ld_on) {
+    LcLdArgs a{};
+    a.K = K; a.W = W;
+    a.z = s.lc_z.as<double>();
+    a.hidden = s.has_lc_hidden ? s.lc_hidden.as<double>() : nullptr;
+    a.rp = s.lc_rp.as<double>();
+    a.ld = s.ld_tab.as<double>();
+    lc_rule(a.x, a.w, a.d);
+    a.p_lo = s.lc_p_lo; a.p_hi = s.lc_p_hi;
+    a.depth = s.depth.as<double>();
+    ProfScope ps(c, PK_LIGHTCURVE);
+    hipLaunchKernelGGL(k_lightcurve_ld, dim3(K), dim3(256), 0, c->stream, a);
+    HIP_TRY(c, hipGetLastError());
+  } else if (s.has_lc) {
     LcArgs a{};
     a.K = K; a.W = W;
     a.z = s.lc_z.as<double>();
@@ -1873,14 +1903,7 @@ int wayne_exposure_run_front(wayne_ctx* c, int slot) {
     double sum = 0.;
     for (int i = 0; i < 4; ++i) { a.ld[i] = d.lc_ld[i]; sum += d.lc_ld[i] * (i + 1) / (i + 5.0); }
     a.f0 = kPi * (1.0 - sum);
-    // tanh-sinh rule on (0, 1): t in [-3, 3], u = pi/2 sinh t, x = (1 + tanh u)/2 (wayne_amd/lightcurve.py)
-    const double h = 6.0 / (kLcNodes - 1);
-    for (int i = 0; i < kLcNodes; ++i) {
-      const double t = -3.0 + h * i, u = 0.5 * kPi * std::sinh(t);
-      a.x[i] = (float)(0.5 * (1.0 + std::tanh(u)));
-      a.w[i] = (float)(h * 0.25 * kPi * std::cosh(t) / (std::cosh(u) * std::cosh(u)));
-      a.d[i] = (float)(0.5 * std::exp(-std::fabs(u)) / std::cosh(u));
-    }
+    lc_rule(a.x, a.w, a.d);
     a.p_lo = s.lc_p_lo; a.p_hi = s.lc_p_hi;
     a.depth = s.depth.as<double>();
     ProfScope ps(c, PK_LIGHTCURVE);
@@ -2304,6 +2327,44 @@ int wayne_exposure_set_sources(wayne_ctx* c, int slot, const wayne_source_desc* 
   std::memcpy(s.acc_box, box, sizeof box);
   s.use_box = use_box && !no_box;
   s.n_extra = n;
+  return WAYNE_OK;
+}
+
+// ---------------------------------------------------------------------------
+// limb darkening per wavelength bin
+// ---------------------------------------------------------------------------
+
+int wayne_exposure_set_limb_darkening(wayne_ctx* c, int slot, const double* ld, int n_wl) {
+  if (!c) return WAYNE_E_INVALID;
+  if (slot < 0 || slot >= kSlots) return fail(c, WAYNE_E_INVALID, "set_limb_darkening: slot");
+  Slot& s = c->slots[slot];
+  if (!s.uploaded) return fail(c, WAYNE_E_STATE, "set_limb_darkening: slot not uploaded");
+  s.ld_on = false;                // from here on a refusal leaves the slot usable, without a table
+  s.front_done = false;           // (the depth matrix of the last front half is not this setting's)
+  if (!ld || n_wl == 0) return WAYNE_OK;
+  if (!s.has_lc) return fail(c, WAYNE_E_INVALID, "set_limb_darkening: the slot has no device light curve (lc_z was NULL)");
+  const int W = s.W;
+  if (n_wl != W) return fail(c, WAYNE_E_INVALID, "set_limb_darkening: n_wl differs from the exposure's");
+  for (int w = 0; w < W; ++w) {
+    double sum = 0.;
+    for (int i = 0; i < 4; ++i) {
+      const double v = ld[(size_t)w * 4 + i];
+      if (!std::isfinite(v)) return fail(c, WAYNE_E_INVALID, "set_limb_darkening: coefficient not finite");
+      sum += v * (i + 1) / (i + 5.0);
+    }
+    if (!(1.0 - sum > 0.)) return fail(c, WAYNE_E_INVALID, "set_limb_darkening: the disk flux 1 - sum a_n n/(n+4) must be > 0 in every bin");
+  }
+  (void)hipSetDevice(c->device);
+  use_slot_stream(c, slot);
+  const size_t bytes = (size_t)4 * W * sizeof(double);
+  int rc = s.ld_stage.begin(c, bytes, "set_limb_darkening: pinned staging allocation failed");
+  if (rc) return rc;
+  double* h = (double*)s.ld_stage.place(s.ld_tab, bytes);
+  if (!h) return fail(c, WAYNE_E_NOMEM, "set_limb_darkening: staging arena too small");
+  for (int i = 0; i < 4; ++i)     // [W][4] -> four planes of W
+    for (int w = 0; w < W; ++w) h[(size_t)i * W + w] = ld[(size_t)w * 4 + i];
+  if ((rc = s.ld_stage.commit(c, c->stream))) return rc;
+  s.ld_on = true;
   return WAYNE_OK;
 }
 

@@ -393,6 +393,8 @@ class ExposureGenerator(object):
             # the K x W matrix is computed on the device from K + W + 4 numbers
             lc = dict(lc_z=planet_signal.z_tr, lc_hidden=planet_signal.hidden,
                       lc_rp=np.sqrt(planet_signal.planet_spectrum[i0:i1]), lc_ld=planet_signal.ld)
+            if getattr(planet_signal, "ld_table", None) is not None:     # coefficients per bin: cropped with the spectrum
+                lc["lc_ld_table"] = planet_signal.ld_table[i0:i1]
         elif planet_signal is not None:
             depth = np.ascontiguousarray(np.asarray(planet_signal, dtype=float)[:, i0:i1])
 

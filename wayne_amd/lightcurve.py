@@ -20,7 +20,13 @@ On the exposure path the K x W depth matrix is produced by the k_lightcurve
 HIP kernel from z[K], p[W] and the four coefficients (the same rule and
 nodes, float32 integrand / float64 sum); the numpy version here serves
 `Observation.show_lightcurve` and the tests.
+
+Limb darkening may vary with wavelength: `LimbDarkening` tabulates the coefficients over wavelength, `ld` is then an
+array [W, 4] and the law is evaluated through the five coefficient-free integrals of `transit_basis` (on the device:
+k_lightcurve_ld).
 """
+import hashlib
+
 import numpy as np
 
 N_NODES = 24      # 7e-11 absolute on the flux (tests/test_lightcurve.py); the device kernel uses the same rule
@@ -55,8 +61,68 @@ def stellar_flux_total(ld):
     return np.pi * (1.0 - np.sum(a * n / (n + 4.0)))
 
 
+def transit_basis(z, p):
+    """The five blocked-flux integrals B_n(z, p) = int over the occulted region of mu^(n/2) dA, n = 0 .. 4 (B_0: the
+    lens area), as a tuple of arrays of the broadcast shape of z and p (zero without a transit).  The Claret profile
+    I(mu) = c0 + sum a_n mu^(n/2), c0 = 1 - sum a_n, is linear in its coefficients, so the blocked flux of ANY set is
+    c0 B_0 + sum a_n B_n: one evaluation serves every wavelength's coefficients (`deficit_from_basis`).  Geometry, nodes
+    and the cancellation-free forms are those of `transit_flux`."""
+    z, p = np.broadcast_arrays(np.asarray(z, dtype=float), np.asarray(p, dtype=float))
+    out = [np.zeros(z.shape) for _ in range(5)]
+    touching = z < 1.0 + p
+    if not np.any(touching):
+        return tuple(out)
+    zz, pp = z[touching], p[touching]
+    r_full = np.clip(pp - zz, 0.0, 1.0)
+    mu_f = np.sqrt(1.0 - r_full ** 2)
+    ra = np.abs(zz - pp)
+    rb = np.minimum(1.0, zz + pp)
+    ok = rb > ra
+    L = np.where(ok, rb - ra, 0.0)[:, None]
+    x = _X[None, :]
+    r = ra[:, None] + L * x
+    hi = L * np.where(x < 0.5, 1 - _D[None, :], _D[None, :])         # rb - r
+    zc, pc = zz[:, None], pp[:, None]
+    num = np.maximum(pc ** 2 - (r - zc) ** 2, 0.0)
+    den = np.maximum((r + zc) ** 2 - pc ** 2, 0.0)
+    theta = 4.0 * np.arctan2(np.sqrt(num), np.sqrt(den))
+    one_minus_r = (1.0 - rb)[:, None] + hi
+    mu = np.sqrt(np.maximum(one_minus_r * (1.0 + r), 0.0))
+    g = r * theta * _W[None, :]
+    for n in range(5):
+        e = 0.5 * n + 2.0
+        full = 2 * np.pi * (1.0 - mu_f ** e) / e                      # int_{mu_f}^1 m^(n/2) 2 pi m dm
+        part = (g * mu ** (0.5 * n)).sum(axis=1) * L[:, 0] if n else g.sum(axis=1) * L[:, 0]
+        out[n][touching] = full + part
+    return tuple(out)
+
+
+def _ld_columns(ld, shape):
+    """a_1 .. a_4 of a coefficient array [4] or [W, 4], each broadcastable against `shape` (W on its last axis)."""
+    a = np.asarray(ld, dtype=float)
+    if a.ndim == 2 and a.shape[1] == 4:
+        if len(shape) == 0 or (shape[-1] != a.shape[0] and a.shape[0] != 1):
+            raise ValueError("limb darkening [W, 4]: W = %d does not match the last axis of shape %s" % (a.shape[0], shape))
+        return [a[:, n] for n in range(4)]
+    if a.shape == (4,):
+        return [a[n] for n in range(4)]
+    raise ValueError("limb darkening: expected 4 coefficients or an array [W, 4], got shape %s" % (a.shape,))
+
+
+def deficit_from_basis(basis, ld):
+    """1 - transit from the five arrays of `transit_basis` and coefficients `ld`, [4] or [W, 4] (W: the last axis of the
+    basis arrays): (c0 B_0 + sum a_n B_n) / (pi (1 - sum a_n n/(n+4)))."""
+    a1, a2, a3, a4 = _ld_columns(ld, np.shape(basis[0]))
+    c0 = 1.0 - a1 - a2 - a3 - a4
+    f0 = np.pi * (1.0 - (a1 * (1.0 / 5.0) + a2 * (2.0 / 6.0) + a3 * (3.0 / 7.0) + a4 * (4.0 / 8.0)))
+    return (c0 * basis[0] + a1 * basis[1] + a2 * basis[2] + a3 * basis[3] + a4 * basis[4]) / f0
+
+
 def transit_flux(z, p, ld):
-    """Normalised flux of the star during transit; z, p broadcastable arrays."""
+    """Normalised flux of the star during transit; z, p broadcastable arrays.  `ld`: four Claret coefficients, or an
+    array [W, 4] -- one set per element of the last axis of the broadcast shape, evaluated through `transit_basis`."""
+    if np.ndim(ld) == 2:
+        return 1.0 - deficit_from_basis(transit_basis(z, p), ld)
     z, p = np.broadcast_arrays(np.asarray(z, dtype=float), np.asarray(p, dtype=float))
     out = np.ones(z.shape)
     f0 = stellar_flux_total(ld)
@@ -254,12 +320,113 @@ class DeviceDepths(object):
     K x W transit-depth matrix computed on the GPU (k_lightcurve) instead of passing it."""
 
     def __init__(self, z_tr, hidden, planet_spectrum, ld):
+        """`ld`: four Claret coefficients for every wavelength, or an array [W, 4] with one set per element of
+        `planet_spectrum` (k_lightcurve_ld; `ld_table` is then that array and `ld` its first row, the descriptor's
+        unused lc_ld)."""
         self.z_tr = np.asarray(z_tr, dtype=float)
         self.hidden = None if hidden is None else np.asarray(hidden, dtype=float)
         self.planet_spectrum = np.asarray(planet_spectrum, dtype=float)
+        self.ld_table = None
+        if np.ndim(ld) == 2:
+            table = np.ascontiguousarray(ld, dtype=float)
+            if table.shape != (self.planet_spectrum.size, 4):
+                raise ValueError("DeviceDepths: a limb-darkening table has shape [W, 4] with W = %d, got %s"
+                                 % (self.planet_spectrum.size, table.shape))
+            self.ld_table = table
+            ld = table[0]
         self.ld = [float(v) for v in ld]
 
     def host_matrix(self):
         """The same matrix evaluated with numpy (for tests and plots)."""
         hidden = np.zeros_like(self.z_tr) if self.hidden is None else self.hidden
-        return planet_depths(self.ld, self.planet_spectrum, self.z_tr, hidden)
+        return planet_depths(self.ld if self.ld_table is None else self.ld_table, self.planet_spectrum, self.z_tr, hidden)
+
+
+class LimbDarkening(object):
+    """Limb-darkening coefficients tabulated over wavelength: nodes `wl_um` [N] (finite, increasing) and `coeffs`
+    [N, columns] in one of three laws, held as Claret coefficients (`claret` [N, 4]):
+
+      claret4    a1 a2 a3 a4         I = 1 - sum a_n (1 - mu^(n/2))
+      quadratic  u1 u2               I = 1 - u1 (1 - mu) - u2 (1 - mu)^2   ->  a2 = u1 + 2 u2, a4 = -u2
+      linear     u                   I = 1 - u (1 - mu)                     ->  a2 = u
+
+    `on_grid(wl)` interpolates every Claret coefficient linearly in wavelength, constant beyond the end nodes: I is linear
+    in the coefficients, so this is the linear interpolation of the intensity profile itself.  ValueError for nodes that
+    are not finite and increasing, a wrong column count, a coefficient that is not finite, or a disk flux
+    pi (1 - sum a_n n/(n+4)) <= 0 on a node."""
+
+    LAWS = {"claret4": 4, "quadratic": 2, "linear": 1}
+
+    def __init__(self, wl_um, coeffs, law="claret4"):
+        if law not in self.LAWS:
+            raise ValueError("limb darkening: unknown law %r (expected claret4, quadratic or linear)" % (law,))
+        try:
+            wl = np.array(wl_um, dtype=float).reshape(-1)
+            c = np.array(coeffs, dtype=float)
+        except (TypeError, ValueError):
+            raise ValueError("limb darkening: nodes and coefficients must be numbers")
+        if law == "linear" and c.ndim == 1:
+            c = c[:, None]
+        if wl.size < 1 or not np.all(np.isfinite(wl)) or not np.all(np.diff(wl) > 0):
+            raise ValueError("limb darkening: the wavelength nodes must be finite and increasing")
+        if c.ndim != 2 or c.shape != (wl.size, self.LAWS[law]):
+            raise ValueError("limb darkening: law %s takes %d column(s) per node, %d node(s): got shape %s"
+                             % (law, self.LAWS[law], wl.size, c.shape))
+        if not np.all(np.isfinite(c)):
+            raise ValueError("limb darkening: coefficients must be finite")
+        a = np.zeros((wl.size, 4))
+        if law == "claret4":
+            a[:] = c
+        elif law == "quadratic":
+            a[:, 1] = c[:, 0] + 2.0 * c[:, 1]
+            a[:, 3] = -c[:, 1]
+        else:
+            a[:, 1] = c[:, 0]
+        n = np.arange(1, 5)
+        if not np.all(1.0 - (a * (n / (n + 4.0))).sum(axis=1) > 0.0):
+            raise ValueError("limb darkening: the disk flux 1 - sum a_n n/(n+4) must be > 0 on every node")
+        self.law, self.wl_um, self.coeffs, self.claret = law, wl, c, a
+        for arr in (self.wl_um, self.coeffs, self.claret):
+            arr.setflags(write=False)
+        h = hashlib.blake2b(self.wl_um.tobytes(), digest_size=8)
+        h.update(self.claret.tobytes())
+        self.hash = h.hexdigest().upper()
+
+    @classmethod
+    def from_file(cls, path, law=None):
+        """A text file with columns wl_um and the law's coefficients (`law` None: claret4, five columns)."""
+        data = np.loadtxt(path, dtype=float, ndmin=2)
+        law = law or "claret4"
+        if law not in cls.LAWS:
+            raise ValueError("limb darkening: unknown law %r (expected claret4, quadratic or linear)" % (law,))
+        if data.shape[1] != 1 + cls.LAWS[law]:
+            raise ValueError("limb darkening: %s: law %s takes %d columns (wl_um and %d coefficient(s)), the file has %d"
+                             % (path, law, 1 + cls.LAWS[law], cls.LAWS[law], data.shape[1]))
+        return cls(data[:, 0], data[:, 1:], law)
+
+    def on_grid(self, wl):
+        """Claret coefficients [len(wl), 4] at the wavelengths `wl` (um)."""
+        wl = np.asarray(wl, dtype=float).reshape(-1)
+        return np.stack([np.interp(wl, self.wl_um, self.claret[:, n]) for n in range(4)], axis=1)
+
+    def cards(self):
+        """Primary-header cards of an exposure whose transit used the table: LDTABLE = T, the law the table was given in,
+        the number of nodes, their range, and 64 bits of a blake2b over nodes and Claret coefficients."""
+        return [("LDTABLE", True, "limb darkening per wavelength bin (table) on"),
+                ("LDLAW", self.law.upper(), "law the table was given in"),
+                ("LDNODES", int(self.wl_um.size), "wavelength nodes of the table"),
+                ("LDWLLO", float(self.wl_um[0]), "first node (um)"),
+                ("LDWLHI", float(self.wl_um[-1]), "last node (um)"),
+                ("LDHASH", self.hash, "blake2b-64 over nodes and Claret coefficients")]
+
+    def digest_bytes(self):
+        return b"ld_table" + self.wl_um.tobytes() + self.claret.tobytes()
+
+    def __eq__(self, other):
+        return isinstance(other, LimbDarkening) and self.digest_bytes() == other.digest_bytes() and self.law == other.law
+
+    def __ne__(self, other):
+        return not self == other
+
+    def __hash__(self):
+        return hash(self.digest_bytes())

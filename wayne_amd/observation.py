@@ -164,7 +164,9 @@ class Observation(object):
 
     def setup_target(self, planet, wavelengths, planet_spectrum, stellar_flux, transittime=None, ldcoeffs=None,
                      period=None, rp=None, sma=None, inclination=None, eccentricity=None, periastron=None,
-                     stellar_radius=None):
+                     stellar_radius=None, ld_table=None):
+        """`ld_table` (lightcurve.LimbDarkening): limb darkening per wavelength bin -- the light curves then use
+        `ld_table.on_grid(wavelengths)`; `ldcoeffs` stays required: the fallback and the header's LD1 .. LD4."""
         self.wl = np.asarray(wavelengths, dtype=float)
         self.stellar_flux = np.asarray(stellar_flux, dtype=float)
         self.planet_spectrum = None if planet_spectrum is None else np.asarray(planet_spectrum, dtype=float)
@@ -190,7 +192,15 @@ class Observation(object):
                                  "tools.py:220-230, which is not available)")
             self.ldcoeffs = list(ldcoeffs)
             planet.ldcoeffs = self.ldcoeffs          # written into the FITS header (exposure.py:396-402)
+            if ld_table is not None and not isinstance(ld_table, lightcurve.LimbDarkening):
+                raise TypeError("setup_target: ld_table must be a lightcurve.LimbDarkening or None")
+            self.ld_table = ld_table
+            self._ld_on_grid = None if ld_table is None else ld_table.on_grid(self.wl)
+            planet.ld_table = ld_table               # its cards too, only when there is one
         else:
+            if ld_table is not None:
+                raise ValueError("setup_target: ld_table needs a planet spectrum (there is no transit without one)")
+            self.ld_table = self._ld_on_grid = None
             self.transmission_spectroscopy = False
 
     def setup_detector(self, detector, NSAMP, SAMPSEQ, SUBARRAY):
@@ -252,13 +262,22 @@ class Observation(object):
         spectrum = np.array([depth]) if depth else self.planet_spectrum
         rp_white = self.planet.rp_over_rs or float(np.sqrt(np.mean(self.planet_spectrum)))
         z_tr, hidden = lightcurve.depth_inputs(*(self._orbit_args() + (time_array, rp_white)))
-        return 1.0 - lightcurve.planet_depths(self.ldcoeffs, spectrum, z_tr, hidden)
+        return 1.0 - lightcurve.planet_depths(self._limb_darkening(white=bool(depth)), spectrum, z_tr, hidden)
+
+    def _limb_darkening(self, white=False):
+        """What the light curves take as `ld`: the four coefficients, or with a table its coefficients on the visit's
+        wavelength grid [W, 4] (`white`: one depth for the whole band -- the table's mean profile over the grid, which is
+        the mean of its coefficients, I being linear in them)."""
+        table = getattr(self, "_ld_on_grid", None)
+        if table is None:
+            return self.ldcoeffs
+        return table.mean(axis=0, keepdims=True) if white else table
 
     def device_depths(self, time_array):
         """The same per-sub-sample depths, as the recipe the GPU evaluates."""
         rp_white = self.planet.rp_over_rs or float(np.sqrt(np.mean(self.planet_spectrum)))
         z_tr, hidden = lightcurve.depth_inputs(*(self._orbit_args() + (self._to_hjd(time_array), rp_white)))
-        return lightcurve.DeviceDepths(z_tr, hidden, self.planet_spectrum, self.ldcoeffs)
+        return lightcurve.DeviceDepths(z_tr, hidden, self.planet_spectrum, self._limb_darkening())
 
     def _to_hjd(self, time_array):
         p = self.planet
@@ -308,7 +327,7 @@ class Observation(object):
                     abs(float(p0["EXPSTART"]) - (float(self.exp_start_times[number - 1]) - 2400000.5)) < 1e-7)
         except (KeyError, TypeError, ValueError):
             return False
-        if not (same and self._contaminant_cards_match(p0) and self._trap_cards_match(p0)):
+        if not (same and self._contaminant_cards_match(p0) and self._trap_cards_match(p0) and self._ld_cards_match(p0)):
             return False
         # the visit's sample type too: uint16 reads make BITPIX 16 images, float reads float64 ones -- a file of the
         # other kind is regenerated, whichever way the visit was switched
@@ -326,6 +345,21 @@ class Observation(object):
             if not want or int(p0["NCONTAM"]) != want["NCONTAM"]:
                 return False
             return all(abs(float(p0[k]) - float(v)) <= 1e-9 * max(1.0, abs(float(v))) for k, v in want.items())
+        except (KeyError, TypeError, ValueError):
+            return False
+
+    def _ld_cards_match(self, p0):
+        """The file's LDTABLE / LDLAW / LDNODES / LDWLLO / LDWLHI / LDHASH cards are this visit's limb-darkening table
+        (absent: none), so that --resume after a table was added, removed or changed regenerates the files."""
+        table = getattr(self, "ld_table", None)
+        want = {k: v for (k, v, _) in table.cards()} if table is not None else {}
+        try:
+            if "LDTABLE" not in p0:
+                return not want
+            if not want or p0["LDTABLE"] is not True:
+                return False
+            return (str(p0["LDHASH"]).strip() == want["LDHASH"] and str(p0["LDLAW"]).strip() == want["LDLAW"] and
+                    int(p0["LDNODES"]) == want["LDNODES"])
         except (KeyError, TypeError, ValueError):
             return False
 

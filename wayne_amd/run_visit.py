@@ -22,6 +22,10 @@ examples/hd209458b_12181_simulation_parameters.yml): sections `general`
   * an optional top-level `contaminants:` list puts field stars on every exposure (wayne_amd/sources.py): per entry
     `dx`, `dy` (px from the target), `flux_ratio` (detected electrons relative to the target's) and a black-body
     `temperature` or a PHOENIX `spectrum_file`; at most 8.  First order only, not in the direct image, constant;
+  * an optional `target: ld_table: {law: claret4, wl_um: [...], coeffs: [[...], ...]}` or `target: ld_table_file: FILE`
+    (text, columns wl_um a1 a2 a3 a4; `ld_law: quadratic | linear` for a file with wl_um u1 u2 or wl_um u) gives every
+    wavelength bin its own limb darkening, interpolated linearly between the nodes (lightcurve.LimbDarkening);
+    `ldcoeffs` stays required (the header's LD1 .. LD4); the files then carry LDTABLE, LDLAW, LDNODES, LDWLLO, LDWLHI, LDHASH;
   * an optional top-level `charge_traps:` section turns on per-pixel charge trapping, the ramp effect
     (wayne_amd/traps.py): `slow` / `fast` mappings of n_traps, efficiency, lifetime_s, initial, orbit_fill; `{}` = the
     defaults, an omitted key its default; `history: carried` carries each pixel's trap state from exposure to exposure
@@ -83,6 +87,35 @@ def _get(d, key, default=None):
     except (KeyError, TypeError):
         return default
     return v
+
+
+def ld_table_from_config(target, path=lambda p: p):
+    """The optional limb-darkening table of the YAML's `target:` section -> lightcurve.LimbDarkening, or None:
+    `ld_table: {law: claret4, wl_um: [...], coeffs: [[...], ...]}` (law optional) or `ld_table_file: FILE`, text with
+    columns wl_um and the law's coefficients (`ld_law:` names the law of a file with fewer than five columns); `path`
+    resolves FILE like the section's other files.  Every defect is a WFC3SimConfigError."""
+    from . import lightcurve
+    inline, fname = _get(target, "ld_table"), _get(target, "ld_table_file")
+    if inline is None and fname is None:
+        if _get(target, "ld_law") is not None:
+            raise WFC3SimConfigError("target: ld_law is given without ld_table_file")
+        return None
+    if inline is not None and fname is not None:
+        raise WFC3SimConfigError("target: give ld_table or ld_table_file, not both")
+    try:
+        if inline is not None:
+            if not isinstance(inline, dict):
+                raise WFC3SimConfigError("target: ld_table must be a mapping with wl_um, coeffs and an optional law")
+            unknown = sorted(set(inline) - {"law", "wl_um", "coeffs"})
+            if unknown or "wl_um" not in inline or "coeffs" not in inline:
+                raise WFC3SimConfigError("target: ld_table takes wl_um, coeffs and an optional law%s"
+                                         % (" (unknown: %s)" % ", ".join(map(str, unknown)) if unknown else ""))
+            return lightcurve.LimbDarkening(inline["wl_um"], inline["coeffs"], inline.get("law") or "claret4")
+        if not isinstance(fname, str):
+            raise WFC3SimConfigError("target: ld_table_file must be a file name")
+        return lightcurve.LimbDarkening.from_file(path(fname), _get(target, "ld_law"))
+    except (OSError, ValueError) as e:
+        raise WFC3SimConfigError("target: limb-darkening table: %s" % e)
 
 
 def build_observation(cfg, base_dir=".", calibration=None, device=0):
@@ -153,10 +186,13 @@ def build_observation(cfg, base_dir=".", calibration=None, device=0):
                                   calibration=cal, device=device, seed=seed)
     obs.setup_detector(det, obs_cfg["NSAMP"], obs_cfg["SAMPSEQ"], obs_cfg["SUBARRAY"])
     obs.setup_grism(chosen_grism)
+    ld_table = ld_table_from_config(target, path)
+    if ld_table is not None and not transmission:
+        raise WFC3SimConfigError("target: ld_table needs planet_spectrum_file (there is no transit without one)")
     obs.setup_target(planet, wl, depth_planet, stellar_flux_scaled, _get(target, "transit_time"),
                      _get(target, "ldcoeffs"), _get(target, "period"), _get(target, "rp"), _get(target, "sma"),
                      _get(target, "inclination"), _get(target, "eccentricity"), _get(target, "periastron"),
-                     _get(target, "stellar_radius"))
+                     _get(target, "stellar_radius"), **({"ld_table": ld_table} if ld_table is not None else {}))
     obs.setup_visit(obs_cfg["start_JD"] or 0.0, obs_cfg["num_orbits"], exp_start_times)
     obs.setup_reductions(obs_cfg["add_dark"], obs_cfg["add_flat"], obs_cfg["add_gain_variations"],
                          obs_cfg["add_non_linear"], obs_cfg["add_initial_bias"])

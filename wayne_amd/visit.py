@@ -43,6 +43,9 @@ def descriptor_digest(desc):
     traps = getattr(desc, "_traps", None)          # charge traps (none: likewise)
     if traps is not None:
         h.update(traps.digest_bytes())
+    ld_table = getattr(desc, "_ld_table", None)    # limb darkening per wavelength bin (none: likewise)
+    if ld_table is not None:
+        h.update(b"ld_table" + np.ascontiguousarray(ld_table).tobytes())
     return h.hexdigest()
 
 
