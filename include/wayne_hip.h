@@ -227,7 +227,11 @@ typedef struct wayne_exposure_desc {
    * Observation.generate_lightcurves, observation.py:293-357).  When lc_z is
    * not NULL, `depth` must be NULL and the K x W transit-depth matrix is
    * computed on the device by k_lightcurve:
-   *   depth[k][w] = (1 - transit(z_k, rp_w, ld)) + (1 - eclipse(rp_w^2, hidden_k))      */
+   *   depth[k][w] = (1 - transit(z_k, rp_w, ld)) + (1 - eclipse(rp_w^2, hidden_k))
+   * A NaN rp_w (a negative element of the planet spectrum) is a planet of no size: depth[.][w] = 0,
+   * and the bin takes no part in the range of radius ratios the kernel interpolates over.
+   * Against the float64 law: 2e-8 for rp <= 0.2, growing in proportion to rp beyond (float32
+   * integrand; DESIGN.md, k_lightcurve).                                                  */
   const double *lc_z;      /* [K] projected separation in stellar radii (>= 10: planet behind the star) */
   const double *lc_hidden; /* [K] fraction of the planet's disk hidden by the star (eclipse), or NULL   */
   const double *lc_rp;     /* [W] Rp/R* per bin = sqrt(planet_spectrum)                                  */
@@ -813,7 +817,7 @@ int wayne_expected_profile(wayne_ctx *ctx, uint64_t *launches, double *ms);
  *   depth[k][w]   = deficit[k][w] + p_w^2 hidden_k / (1 + p_w^2)                the eclipse term, unchanged
  *
  * float32 integrand, float64 sums; grid, Chebyshev interpolation in p and the decisions between its paths are
- * k_lightcurve's (five interpolants, one per B_n).  A NaN radius ratio gives deficit 0.  Not covered: limb darkening
+ * k_lightcurve's (five interpolants, one per B_n).  A NaN radius ratio gives depth 0.  Not covered: limb darkening
  * in the eclipse term, a contaminant that eclipses, coefficients looked up from stellar parameters.  Counted under the
  * "k_lightcurve" slot of wayne_profile.  Opt-in: without a table every launch and every byte stay as they are.  Added
  * within WAYNE_ABI_VERSION 7: new symbols only.

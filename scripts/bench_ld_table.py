@@ -36,7 +36,7 @@ def table_at(wl):
 def direct_sub_samples(z, rp):
     """Sub-samples the kernels integrate wavelength by wavelength (k_lightcurve.h: `direct`)."""
     p_lo, p_hi = float(rp.min()), float(rp.max())
-    guard = 1e-9 + 1e-6 * (p_hi - p_lo)
+    guard = 1e-9 + 0.08 * (p_hi - p_lo)        # lc_guard
 
     def inside(v):
         return (v > p_lo - guard) & (v < p_hi + guard)

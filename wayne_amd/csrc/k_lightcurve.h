@@ -70,12 +70,36 @@ __device__ __forceinline__ double lc_deficit(const LcArgs& a, double z, double p
   return dF / a.f0;
 }
 
-// One workgroup per sub-sample.  The radius ratios of a spectrum span a narrow
-// interval [p_lo, p_hi] and, at fixed z, the deficit is an analytic function of p except where the
-// geometry changes regime (p = |1 - z|: a contact; p = z: the planet reaches the centre).  So the
-// quadrature is evaluated at the kLcCheb Chebyshev-Lobatto points of the interval only and every
-// wavelength evaluates the Chebyshev interpolant (its error is far below the quadrature's 2e-8) -- unless a regime change falls inside the interval for this z, in which case
-// every wavelength is integrated on its own as before.
+// One workgroup per sub-sample.  The radius ratios of a spectrum span an interval [p_lo, p_hi] and, at fixed z, the
+// deficit is an analytic function of p except where the geometry changes regime (p = |1 - z|: a contact; p = z: the
+// planet reaches the centre; p = z - 1).  So the quadrature is evaluated at the kLcCheb Chebyshev-Lobatto points of the
+// interval only and every wavelength evaluates the Chebyshev interpolant -- unless a regime change falls within
+// lc_guard(width) of the interval for this z, in which case every wavelength is integrated on its own as before.
+// At a contact the deficit behaves like (p - p*)^1.5, and a fit whose interval ends next to that branch point converges
+// only algebraically: the band therefore widens with the interval.  kLcGuardRel = 0.08 is the smallest hundredth of the
+// width with which the interpolant of the float64 law stays within 2e-9 of it -- a tenth of the 2e-8 the float32
+// integrand is allowed -- for radius ratios 0.03 .. 0.3 spread by up to +-30 % and a regime change anywhere outside the
+// band: worst 1.2e-9 (rp 0.3 +- 30 %, uniform disk, first contact just outside; 1.8e-10 at 0.1208 +- 30 %, 4.0e-12 at
+// +- 2 %; tests/test_lightcurve_plane.py).  With 0.07 it is 2.0e-9, with a band that ignores the width (1e-6) 9.4e-7.
+constexpr double kLcGuardAbs = 1e-9, kLcGuardRel = 0.08;
+__device__ __forceinline__ double lc_guard(double width) { return kLcGuardAbs + kLcGuardRel * width; }
+
+// What a sub-sample at separation z does (k_lightcurve and k_lightcurve_ld alike): nothing (no wavelength in transit; also
+// when no radius ratio is finite, p_lo = p_hi = NaN), every wavelength on its own, or the interpolant -- of which `flat`
+// (all radius ratios equal) is the single sample.
+struct LcRoute {
+  bool no_transit, direct, flat;
+};
+__device__ __forceinline__ LcRoute lc_route(double z, double p_lo, double p_hi) {
+  const double width = p_hi - p_lo, guard = lc_guard(width);
+  auto inside = [&](double v) { return v > p_lo - guard && v < p_hi + guard; };
+  LcRoute r;
+  r.no_transit = !(z < 1. + p_lo) && !(z < 1. + p_hi);
+  r.direct = !r.no_transit && (inside(fabs(1. - z)) || inside(z) || inside(z - 1.));
+  r.flat = width <= 1e-14 * p_hi;
+  return r;
+}
+
 constexpr int kLcCheb = 16;   // points: t_j = cos(j pi / (kLcCheb - 1))
 
 __global__ __launch_bounds__(256) void k_lightcurve(LcArgs a) {
@@ -87,11 +111,9 @@ __global__ __launch_bounds__(256) void k_lightcurve(LcArgs a) {
   __shared__ double s_cos[kLcCheb][kLcCheb];
   const double z = a.z[k];
   const double p_lo = a.p_lo, p_hi = a.p_hi;
-  const double width = p_hi - p_lo, guard = 1e-9 + 1e-6 * width;
-  auto inside = [&](double v) { return v > p_lo - guard && v < p_hi + guard; };
-  const bool no_transit = !(z < 1. + p_lo) && !(z < 1. + p_hi);
-  const bool direct = !no_transit && (inside(fabs(1. - z)) || inside(z) || inside(z - 1.));
-  const bool flat = width <= 1e-14 * p_hi;
+  const double width = p_hi - p_lo;
+  const LcRoute route = lc_route(z, p_lo, p_hi);
+  const bool no_transit = route.no_transit, direct = route.direct, flat = route.flat;
   if (!direct && !no_transit) {
     // samples -> Chebyshev coefficients by the discrete cosine sum (end terms halved); every wavelength
     // then evaluates the series with Clenshaw's recurrence: 16 multiply-adds, no divisions
@@ -114,11 +136,12 @@ __global__ __launch_bounds__(256) void k_lightcurve(LcArgs a) {
   const double hid = a.hidden ? a.hidden[k] : 0.;
   for (int w = threadIdx.x; w < a.W; w += blockDim.x) {
     const double p = a.rp[w];
+    const bool sized = p == p;   // a NaN radius ratio (negative depth in the input spectrum): a planet of no size, it blocks and emits nothing
     double deficit = 0.;   // 1 - transit
-    if (direct) {
-      deficit = lc_deficit(a, z, p);
-    } else if (!no_transit) {
-      if (flat) {
+    if (!no_transit && sized) {
+      if (direct) {
+        deficit = lc_deficit(a, z, p);
+      } else if (flat) {
         deficit = s_f[0];
       } else {
         const double t = (2. * p - (p_lo + p_hi)) / width;
@@ -130,12 +153,11 @@ __global__ __launch_bounds__(256) void k_lightcurve(LcArgs a) {
           b1 = b0;
         }
         deficit = s_c[0] + t * b1 - b2;
-        if (!(p == p)) deficit = 0.;   // a NaN radius ratio (negative depth in the input spectrum): no transit, as before
       }
     }
     // eclipse term: (1 - eclipse) = f hidden / (1 + f), f = planet_spectrum = p^2 (observation.py:352-355)
     double ecl = 0.;
-    if (a.hidden) {
+    if (a.hidden && sized) {
       const double f = p * p;
       ecl = f * hid / (1. + f);
     }

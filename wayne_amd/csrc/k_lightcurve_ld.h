@@ -89,11 +89,9 @@ __global__ __launch_bounds__(256) void k_lightcurve_ld(LcLdArgs a) {
   __shared__ double s_cos[kLcCheb][kLcCheb];
   const double z = a.z[k];
   const double p_lo = a.p_lo, p_hi = a.p_hi;
-  const double width = p_hi - p_lo, guard = 1e-9 + 1e-6 * width;
-  auto inside = [&](double v) { return v > p_lo - guard && v < p_hi + guard; };
-  const bool no_transit = !(z < 1. + p_lo) && !(z < 1. + p_hi);
-  const bool direct = !no_transit && (inside(fabs(1. - z)) || inside(z) || inside(z - 1.));
-  const bool flat = width <= 1e-14 * p_hi;
+  const double width = p_hi - p_lo;
+  const LcRoute route = lc_route(z, p_lo, p_hi);   // (k_lightcurve.h)
+  const bool no_transit = route.no_transit, direct = route.direct, flat = route.flat;
   if (!direct && !no_transit) {
     const int tm = threadIdx.x / kLcCheb, tj = threadIdx.x % kLcCheb;
     s_cos[tm][tj] = cos((double)(tm * tj) * kPi / (double)n);
@@ -116,8 +114,9 @@ __global__ __launch_bounds__(256) void k_lightcurve_ld(LcLdArgs a) {
   const double hid = a.hidden ? a.hidden[k] : 0.;
   for (int w = threadIdx.x; w < a.W; w += blockDim.x) {
     const double p = a.rp[w];
+    const bool sized = p == p;   // (a NaN radius ratio: no transit and no eclipse term, as in k_lightcurve)
     double deficit = 0.;   // 1 - transit
-    if (!no_transit && p == p) {   // (a NaN radius ratio: no transit, as in k_lightcurve)
+    if (!no_transit && sized) {
       LcBasis B;
       if (direct) {
         B = lc_basis(a, z, p);
@@ -148,7 +147,7 @@ __global__ __launch_bounds__(256) void k_lightcurve_ld(LcLdArgs a) {
     }
     // eclipse term, unchanged (k_lightcurve)
     double ecl = 0.;
-    if (a.hidden) {
+    if (a.hidden && sized) {
       const double f = p * p;
       ecl = f * hid / (1. + f);
     }

@@ -11,6 +11,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <limits>
 #include <map>
 #include <new>
 #include <string>
@@ -1579,8 +1580,15 @@ int wayne_exposure_upload(wayne_ctx* c, int slot, const wayne_exposure_desc* d) 
     if (!d->lc_rp) return fail(c, WAYNE_E_INVALID, "upload: lc_z needs lc_rp");
     if ((rc = upload_staged(c, s, s.lc_z, d->lc_z, (size_t)K))) return rc;
     if ((rc = upload_staged(c, s, s.lc_rp, d->lc_rp, (size_t)W))) return rc;
-    s.lc_p_lo = s.lc_p_hi = d->lc_rp[0];
-    for (int i = 1; i < W; ++i) { s.lc_p_lo = std::min(s.lc_p_lo, d->lc_rp[i]); s.lc_p_hi = std::max(s.lc_p_hi, d->lc_rp[i]); }
+    // the range of the finite radius ratios (a NaN one -- a negative element of the spectrum -- takes no part, wherever it
+    // stands); with none at all both ends stay NaN and no column is in transit (lc_route)
+    s.lc_p_lo = s.lc_p_hi = std::numeric_limits<double>::quiet_NaN();
+    for (int i = 0; i < W; ++i) {
+      const double v = d->lc_rp[i];
+      if (!std::isfinite(v)) continue;
+      if (!(s.lc_p_lo <= v)) s.lc_p_lo = v;
+      if (!(s.lc_p_hi >= v)) s.lc_p_hi = v;
+    }
     s.has_lc_hidden = d->lc_hidden != nullptr;
     if (s.has_lc_hidden && (rc = upload_staged(c, s, s.lc_hidden, d->lc_hidden, (size_t)K))) return rc;
     HIP_TRY(c, s.depth.reserve(KW * sizeof(double)));

@@ -391,8 +391,9 @@ class ExposureGenerator(object):
         lc = {}
         if isinstance(planet_signal, lightcurve.DeviceDepths):
             # the K x W matrix is computed on the device from K + W + 4 numbers
-            lc = dict(lc_z=planet_signal.z_tr, lc_hidden=planet_signal.hidden,
-                      lc_rp=np.sqrt(planet_signal.planet_spectrum[i0:i1]), lc_ld=planet_signal.ld)
+            with np.errstate(invalid="ignore"):      # (a negative element: NaN, a column without a planet -- k_lightcurve)
+                rp = np.sqrt(planet_signal.planet_spectrum[i0:i1])
+            lc = dict(lc_z=planet_signal.z_tr, lc_hidden=planet_signal.hidden, lc_rp=rp, lc_ld=planet_signal.ld)
             if getattr(planet_signal, "ld_table", None) is not None:     # coefficients per bin: cropped with the spectrum
                 lc["lc_ld_table"] = planet_signal.ld_table[i0:i1]
         elif planet_signal is not None:

@@ -307,12 +307,19 @@ def depth_inputs(period, sma_over_rs, eccentricity, inclination, periastron, mid
 
 def planet_depths(ld, planet_spectrum, z_tr, hidden):
     """1 - (transit - (1 - eclipse)) per sub-sample and wavelength bin: what
-    Observation._generate_exposure hands to scanning_frame (observation.py:349-355, 442-443)."""
-    p = np.sqrt(np.asarray(planet_spectrum, dtype=float))
+    Observation._generate_exposure hands to scanning_frame (observation.py:349-355, 442-443).  A negative (or NaN) element
+    of the spectrum has no radius ratio: a planet of no size blocks and emits nothing, its column is 0 (as on the device,
+    k_lightcurve), and every other column is what it is without that element."""
+    spec = np.asarray(planet_spectrum, dtype=float)
+    sized = spec >= 0.0
+    spec = np.where(sized, spec, 0.0)
+    p = np.sqrt(spec)
     tr = transit_flux(np.asarray(z_tr)[:, None], p[None, :], ld)
-    f = np.asarray(planet_spectrum, dtype=float)[None, :]
+    f = spec[None, :]
     ecl = (1.0 + f * (1.0 - np.asarray(hidden)[:, None])) / (1.0 + f)
-    return 1.0 - (tr - (1.0 - ecl))
+    out = 1.0 - (tr - (1.0 - ecl))
+    out[:, ~sized] = 0.0
+    return out
 
 
 class DeviceDepths(object):
