@@ -91,8 +91,8 @@ MUTANTS = [
          edits=[("k_prep.h", "  lam = lam * 1e4;", "  lam = lam * 1.01e4;")]),
     dict(name="flat_cubic_terms", stage="A11 flat (grism.py:362-385)",
          what="quadratic and cubic flat planes exchanged",
-         edits=[("k_throw.h", "((double)a.flat[2][i] * t2) +\n                   ((double)a.flat[3][i] * t3);",
-                 "((double)a.flat[2][i] * t3) +\n                   ((double)a.flat[3][i] * t2);")]),
+         edits=[("k_throw.h", "((double)f2 * t2) +\n                   ((double)f3 * t3);",
+                 "((double)f2 * t3) +\n                   ((double)f3 * t2);")]),
     # --- thrower (A1-A4)
     dict(name="wide_sigma_2pc", stage="A4 wide PSF component (pyparallel_menu.c:87-108)",
          what="sigma_h of the lane-thrown wide electrons 2.3 % large (k_lane)",

@@ -312,9 +312,13 @@ __device__ __forceinline__ void narrow_body(const ThrowArgs& a, int* const lds, 
           const float Rs = __builtin_amdgcn_sqrtf(cs * __builtin_amdgcn_logf(u01f(wb)));
           const int col = ic0 + min(max(floor_to_int(fmaf(__builtin_amdgcn_cosf(rev12(wa)), Rs, fx)), -kNarrowR), kNarrowR);
           const float u = u01f(va) * Rb;
-          int row = 0;
-#pragma unroll
-          for (int t = 0; t < kPoolRows - 1; ++t) row += (u >= s_q[t][tid]) ? 1 : 0;
+          // row = how many of the 13 thresholds s_q[0 .. 12] u has reached.  They are running sums of masses >= 0, so
+          // the count is a position: four probes instead of thirteen (7, then +-4, +-2, +-1; a count of 13 is final)
+          static_assert(kPoolRows == 14, "the residual rows' search is laid out for 13 thresholds");
+          int row = (u >= s_q[6][tid]) ? 7 : 0;
+          row += (u >= s_q[row + 3][tid]) ? 4 : 0;
+          row += (u >= s_q[row + 1][tid]) ? 2 : 0;
+          row += (row < kPoolRows - 1 && u >= s_q[min(row, kPoolRows - 2)][tid]) ? 1 : 0;
           deposit(col, J0 + row, 1);
         }
       }
@@ -392,13 +396,7 @@ __device__ __forceinline__ void narrow_body(const ThrowArgs& a, int* const lds, 
     }
   }
   __syncthreads();
-  for (int i = tid; i < tarea; i += kNarrowThreads) {
-    const int n = tile[i];
-    if (n > 0) {
-      const int ly = i / tw, lx = i - ly * tw;
-      deposit_global<FLUSH>(a, si, tx0 + lx, ty0 + ly, n);
-    }
-  }
+  flush_tile<FLUSH, false, kNarrowThreads>(a, si, tile, tx0, ty0, tw, tarea);
 }
 
 template <int FLUSH, bool FAST, bool COMPACT>
@@ -812,14 +810,7 @@ __device__ __forceinline__ void lane_body(const ThrowArgs& a, const PrepArgs& p,
       deposit_global<FLUSH>(a, si, tx0 + lx, ty0 + ly, m);
     }
   } else {
-    for (int i = tid; i < tarea; i += kLaneThreads) {
-      const int m = tile[i];
-      if (m > 0) {
-        tile[i] = 0;
-        const int ly = i / tw, lx = i - ly * tw;
-        deposit_global<FLUSH>(a, si, tx0 + lx, ty0 + ly, m);
-      }
-    }
+    flush_tile<FLUSH, BATCH, kLaneThreads>(a, si, tile, tx0, ty0, tw, tarea);     // (one sub-sample: nobody reads the tile again)
   }
   // The counter of the NEXT round is cleared here, not this round's: every thread reads this round's count after the
   // barrier above and nothing orders a late reader before a reset by thread 0 -- a wave that read 0 would skip its

@@ -1,6 +1,7 @@
 // k_throw: the electron thrower (A1-A4, A11, A12)
 #pragma once
 #include "common.h"
+#include "flush_math.h"
 #include "k_prep.h"
 
 namespace wayne {
@@ -51,6 +52,7 @@ struct ThrowArgs {
   uint32_t flags;
   int margin, lds_ints;    // per-workgroup tile: margin around its slice of the trace, LDS capacity
   int flat_off;            // (1014 - N) / 2  (grism.py:363)
+  int off32;               // the host's offsets_fit_32(N, S) (flush_math.h): flush_tile may address a cell by a 32-bit byte offset
   float lane_reach_sigmas; // k_lane: a test-free tile is the bins' box +- (this x sigma_max + 1) px (kLaneR16; knob lane_tight_tile)
   double flat_wmin, flat_wmax, flat_inv_range;   // inv_range = 1 / (wmax - wmin)
   const SubInfo* sub;      // [K]
@@ -93,7 +95,8 @@ __device__ __forceinline__ int rand_r_step(uint32_t& s) {
   return (int)r;
 }
 
-__device__ __forceinline__ double flat_value(const ThrowArgs& a, const SubInfo& si, int x, int y) {
+// (f0 .. f3: the pixel's four flat planes)
+__device__ __forceinline__ double flat_poly(const ThrowArgs& a, const SubInfo& si, int x, int y, float f0, float f1, float f2, float f3) {
   // grism.py:362-385, evaluated for frame pixel (y, x)
   const int xf = x + a.flat_off, yf = y + a.flat_off;
   const double arr = si.y_ref - (double)yf + si.a_t_i * si.x_ref - si.a_t_i * (double)xf;
@@ -103,12 +106,15 @@ __device__ __forceinline__ double flat_value(const ThrowArgs& a, const SubInfo& 
   const double wl = si.a_w * d + si.b_w;
   const double t = (wl - a.flat_wmin) * a.flat_inv_range;
   const double t2 = t * t, t3 = t2 * t;
-  const size_t i = (size_t)y * a.N + x;
-  const double f = (double)a.flat[0][i] + ((double)a.flat[1][i] * t) + ((double)a.flat[2][i] * t2) +
-                   ((double)a.flat[3][i] * t3);
+  const double f = (double)f0 + ((double)f1 * t) + ((double)f2 * t2) +
+                   ((double)f3 * t3);
   // flatfield = np.ones_like(self.flat_f0) is float32, so the assignment
   // rounds the polynomial to float32 (grism.py:380-385)
   return (double)(float)f;
+}
+__device__ __forceinline__ double flat_value(const ThrowArgs& a, const SubInfo& si, int x, int y) {
+  const size_t i = (size_t)y * a.N + x;
+  return flat_poly(a, si, x, y, a.flat[0][i], a.flat[1][i], a.flat[2][i], a.flat[3][i]);
 }
 
 // What the per-electron loop needs of a bin, as one 32-byte record (two LDS reads)
@@ -146,6 +152,64 @@ __device__ __forceinline__ void deposit_global(const ThrowArgs& a, const SubInfo
     atomicAdd((unsigned long long*)&a.acc[((size_t)si.read * a.S + (y + kBorder)) * a.S + (x + kBorder)],
               (unsigned long long)q);
   }
+}
+
+// ---------------------------------------------------------------------------
+// flush_tile : every cell of a workgroup's LDS tile that holds electrons goes to the frame
+// ---------------------------------------------------------------------------
+// The one tile scan of k_throw, k_narrow and k_lane: thread t of T takes the cells t, t + T, ... (flush_math.h: the
+// cell's frame coordinates and its byte offsets by additions, no division after the first), and a cell with m > 0
+// electrons deposits them as deposit_global does -- the same sums, bit for bit.  CLEAR: the cell is left at 0 (k_lane's
+// batches use the tile again).  Called by every thread of the workgroup, after the barrier that ends the throwing.
+// a.off32 (the host's check): the planes a cell goes to are addressed as a workgroup-uniform base -- the frame, a flat
+// plane, the read plane of THIS sub-sample -- plus the cell's 32-bit byte offset, and the charge n x flat takes the
+// one-rounding conversion of flush_math.h wherever every depositing lane of the wave passes its guard (a cell of
+// 2^23 electrons or more, a flat that is not finite: the wave converts as deposit_global does).  Without off32 the
+// walk is the same and each cell calls deposit_global.
+template <int FLUSH, bool CLEAR, int T>
+__device__ __forceinline__ void flush_tile(const ThrowArgs& a, const SubInfo& si, int* const tile, int tx0, int ty0, int tw, int tarea) {
+  const int tid = threadIdx.x;
+  if (tarea <= 0) return;
+  const FlushWalk w = flush_walk(T, tw, tx0, a.N, a.S);
+  FlushCell c = flush_first(tid, tw, tx0, ty0, a.N, a.S, kBorder, kBorder);
+  if (!a.off32) {
+    for (int i = tid; i < tarea; i += T, flush_next(c, w)) {
+      const int m = tile[i];
+      if (m > 0) {
+        if (CLEAR) tile[i] = 0;
+        deposit_global<FLUSH>(a, si, c.x, c.y, m);
+      }
+    }
+    return;
+  }
+  char* const plane = FLUSH == 0 ? reinterpret_cast<char*>(a.frame)
+                                 : reinterpret_cast<char*>(a.acc + (size_t)si.read * a.S * a.S);
+  // (one loop with the flat and one without: the choice is the launch's, not the cell's)
+  auto scan = [&](auto with_flat) {
+    constexpr bool FLAT = decltype(with_flat)::value;
+    for (int i = tid; i < tarea; i += T, flush_next(c, w)) {
+      const int m = tile[i];
+      if (m > 0) {
+        if (CLEAR) tile[i] = 0;
+        if (FLUSH == 0) {
+          atomicAdd(reinterpret_cast<int*>(plane + c.fo), m);
+        } else {
+          long long q;
+          if (FLAT) {
+            auto plane_at = [&](int j) { return *reinterpret_cast<const float*>(reinterpret_cast<const char*>(a.flat[j]) + c.fo); };
+            const double v = (double)m * flat_poly(a, si, c.x, c.y, plane_at(0), plane_at(1), plane_at(2), plane_at(3));
+            if (__builtin_expect(__all(fixed_fast_ok(v)), 1)) q = fixed_fast(v);
+            else q = __double2ll_rn(v * kQ);
+          } else {
+            q = (long long)m * (1ll << kQBits);        // (n 2^28 is an integer: nothing to round)
+          }
+          atomicAdd(reinterpret_cast<unsigned long long*>(plane + c.ao), (unsigned long long)q);
+        }
+      }
+    }
+  };
+  if (FLUSH == 1 && (a.flags & 1u) && a.flat[0]) scan(std::true_type{});     // WAYNE_F_ADD_FLAT
+  else scan(std::false_type{});
 }
 
 template <int RNG_MODE, int FLUSH>
@@ -447,13 +511,7 @@ __global__ __launch_bounds__(kThrowThreads) void k_throw(ThrowArgs a) {
   }
   __syncthreads();
   // flush the tile
-  for (int i = tid; i < tarea; i += kThrowThreads) {
-    const int n = tile[i];
-    if (n > 0) {
-      const int ly = i / tw, lx = i - ly * tw;
-      deposit_global<FLUSH>(a, si, tx0 + lx, ty0 + ly, n);
-    }
-  }
+  flush_tile<FLUSH, false, kThrowThreads>(a, si, tile, tx0, ty0, tw, tarea);
 }
 
 }  // namespace wayne

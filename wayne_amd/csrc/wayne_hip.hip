@@ -1367,6 +1367,7 @@ int wayne_psf_apply_ex(wayne_ctx* c, const int32_t* counts, int size, const doub
 
     ThrowArgs a{};
     a.W = size; a.K = 1; a.N = N; a.S = N + 2 * kBorder; a.kb = 1;
+    a.off32 = offsets_fit_32(a.N, a.S) ? 1 : 0;
     a.lane_reach_sigmas = lane_reach_sigmas(c);
     // enough workgroups to fill the chip when the call is big, one when small
     a.splits = (int)std::min<long long>(512, std::max<long long>(1, total / (64LL * kThrowThreads)));
@@ -1760,6 +1761,7 @@ static int front_source(wayne_ctx* c, int slot, Slot& s, SourceState& ss, int sr
   {
     ThrowArgs a{};
     a.W = W; a.K = K; a.N = N; a.S = S;
+    a.off32 = offsets_fit_32(N, S) ? 1 : 0;
     a.kb = ss.kb;
     a.lane_reach_sigmas = lane_reach_sigmas(c);
     // grid: one unit (128 electrons; 1 in replay mode) per lane of the workgroups of a sub-sample, from
