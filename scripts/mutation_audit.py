@@ -202,6 +202,34 @@ MUTANTS = [
          what="the inversion search gives up after 8 steps and returns the mean",
          edits=[("samplers.h", "    for (int it = 0; it < 64; ++it) {\n      if (u <= r) break;", "    for (int it = 0; it < 8; ++it) {\n      if (u <= r) break;"),
                 ("samplers.h", "    if (x >= (T)64 && x < n) x = M::floor_(n * p + (T)0.5);", "    if (x >= (T)8 && x < n) x = M::floor_(n * p + (T)0.5);")]),
+    # --- charge traps: the paths of ramp_body's TRAP / HIST that tests/test_trap_paths_gpu.py covers (arithmetic only)
+    dict(name="trap_noise_is_charge", stage="charge traps: what counts as collected charge (k_ramp.h, the generic loop)",
+         what="the interval's charge taken after the gaussian-noise stage: the noise is trapped too",
+         tests=["tests/test_trap_paths_gpu.py"],
+         edits=[("k_ramp.h", "      if constexpr (TRAP) chg = px;\n", ""),
+                ("k_ramp.h", "      if (skyv > 0.f) {                                  // += np.random.poisson(master_sky) (:495)\n",
+                 "      if constexpr (TRAP) chg = px;\n      if (skyv > 0.f) {\n")]),
+    dict(name="trap_direct_sky_uncharged", stage="charge traps: the direct sky sampler's counts (SKY = 0)",
+         what="the sky electrons of the direct sampler reach the read but not the traps",
+         tests=["tests/test_trap_paths_gpu.py"],
+         edits=[("k_ramp.h", "          const double k = (double)s_tab[r][tid];\n          px = px + k;\n          if constexpr (TRAP) chg = chg + k;\n",
+                 "          const double k = (double)s_tab[r][tid];\n          px = px + k;\n")]),
+    dict(name="trap_alias_sky_uncharged", stage="charge traps: the alias sky sampler in pieces or exact math (SKY = 2, FAST off)",
+         what="the sky electrons of the generic alias sampler reach the read but not the traps",
+         tests=["tests/test_trap_paths_gpu.py"],
+         edits=[("k_ramp.h", "            px = px + k;\n            if constexpr (TRAP) chg = chg + k;\n", "            px = px + k;\n")]),
+    dict(name="trap_start_clamp", stage="charge traps: the start table at and above rate_hi (trap_start)",
+         what="a rate at or above rate_hi takes the table's last point but one",
+         tests=["tests/test_trap_paths_gpu.py"],
+         edits=[("k_ramp.h", "return e[t.G - 1];", "return e[t.G - 2];")]),
+    dict(name="trap_start_below_lo", stage="charge traps: the start table below rate_lo (trap_start)",
+         what="a rate below rate_lo takes the table's point at rate_lo instead of the linear interpolation from f = 0",
+         tests=["tests/test_trap_paths_gpu.py"],
+         edits=[("k_ramp.h", "(e[1] - e[0]) * (f / lo)", "(e[1] - e[0]) * (T)1")]),
+    dict(name="trap_start_zero", stage="charge traps: the start table at a mean rate of zero (trap_start)",
+         what="a pixel that collected nothing takes the table's point at rate_lo instead of the one at f = 0",
+         tests=["tests/test_trap_paths_gpu.py"],
+         edits=[("k_ramp.h", "if (!(f > (T)0)) return e[0];", "if (!(f > (T)0)) return e[1];")]),
 ]
 
 
