@@ -230,7 +230,46 @@ MUTANTS = [
          what="a pixel that collected nothing takes the table's point at rate_lo instead of the one at f = 0",
          tests=["tests/test_trap_paths_gpu.py"],
          edits=[("k_ramp.h", "if (!(f > (T)0)) return e[0];", "if (!(f > (T)0)) return e[1];")]),
+    # --- the extraction at its caps: what only runs at S > 512, R > 4, C > 64 or a hull > 256, and that
+    # tests/test_extract_caps_gpu.py covers.  Every edit drops or replaces a TERM; no index, bound, barrier or launch moves.
+    dict(name="caps_bins_var_strips", stage="extraction: k_extract_bins VAR, var / F^2 of the hull's strips 4 and 5 (hull > 256)",
+         what="a lane's var / F^2 taken as 0 for the hull's columns 256 and beyond",
+         tests=["tests/test_extract_caps_gpu.py"],
+         edits=[("k_extract.h", "          vr[s] = extract_var(v, g, a.vrn2) / (F * F);",
+                 "          vr[s] = s >= 4 ? 0. : extract_var(v, g, a.vrn2) / (F * F);")]),
+    dict(name="caps_bins_var_passes", stage="extraction: k_extract_bins VAR, the w^2 gather of channels 64 and beyond",
+         what="channels_var's gather skipped for the passes k >= 1 of a lane",
+         tests=["tests/test_extract_caps_gpu.py"],
+         edits=[("k_extract.h", "      if (row && k * 64 + lane < C) {", "      if (row && k < 1 && k * 64 + lane < C) {")]),
+    dict(name="caps_binsopt_ok_256", stage="extraction: k_extract_bins_opt, W_p and ok(x) of the hull's columns 256 and beyond",
+         what="ok(x) forced false for the hull's columns 256 and beyond: they bin the box terms",
+         tests=["tests/test_extract_caps_gpu.py"],
+         edits=[("k_extract.h", "    shW[tid] = ok ? Ws : 0.;", "    shW[tid] = (ok && tid < 256) ? Ws : 0.;")]),
+    dict(name="caps_binsopt_halo", stage="extraction: k_extract_bins_opt with the exposure's own profile, the row of d with its halo",
+         what="d taken as 0 in the staged row's columns 384 and beyond (the right halo and the 16 hull columns before it)",
+         tests=["tests/test_extract_caps_gpu.py"],
+         edits=[("k_extract.h", "        bd[wave][c] = d;", "        bd[wave][c] = c >= kChanMaxHull ? 0. : d;")]),
+    dict(name="caps_finish_skyvar_512", stage="extraction: k_extract_finish VAR, the second trip of the column loop (S > 512)",
+         what="the sky level's share B^2 sky_var left out of spectra_var for columns 512 and beyond",
+         tests=["tests/test_extract_caps_gpu.py"],
+         edits=[("k_extract.h", "a.spectra_var[(size_t)p * S + x] = shV[x] + (shB[x] * shB[x]) * sv;",
+                 "a.spectra_var[(size_t)p * S + x] = shV[x] + (x >= kExtractThreads ? 0. : (shB[x] * shB[x]) * sv);")]),
+    dict(name="caps_optimal_ok_512", stage="extraction: k_extract_optimal_finish, the second trip of the column loop (S > 512)",
+         what="ok(x) forced false for columns 512 and beyond: they keep the box values",
+         tests=["tests/test_extract_caps_gpu.py"],
+         edits=[("k_extract.h", "    const bool ok = S0 > 0. && S0 * S0 > 9. * SV0 && W > 0.;",
+                 "    const bool ok = x < kExtractThreads && S0 > 0. && S0 * S0 > 9. * SV0 && W > 0.;")]),
+    dict(name="caps_term_flag_bit", stage="extraction: extract_term under rejection, the flag of read interval p (R > 8)",
+         what="channels, profile and optimal sums read interval p's flag from bit min(p, 7) of the mask",
+         tests=["tests/test_extract_caps_gpu.py"],
+         edits=[("k_extract.h", "      if ((m >> p) & 1u) v = extract_repl<T>(a, reads, SS, pix, p, lin, gain);",
+                 "      if ((m >> min(p, 7)) & 1u) v = extract_repl<T>(a, reads, SS, pix, p, lin, gain);")]),
 ]
+# all seven of the caps_* mutants in one library: run once against the REST of the extraction's tests, it shows in one visit
+# that none of the seven edited terms is reached there (each edit is confined to its own sizes; two cannot cancel)
+MUTANTS.append(dict(name="caps_all", stage="extraction: the seven caps_* edits together",
+                    what="every caps_* edit at once", tests=["tests/test_extract_caps_gpu.py"],
+                    edits=[e for m in MUTANTS if m["name"].startswith("caps_") for e in m["edits"]]))
 
 
 # Mutants of the HOST half (Python: sample loop, read trigger, frame offset, scan positions -- SURVEY 8 row A12): edits are
