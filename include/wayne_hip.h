@@ -804,6 +804,67 @@ int wayne_exposure_download_expected(wayne_ctx *ctx, int slot, double *out);
  * since wayne_profile_reset: renderings and total milliseconds.  wayne_profile_select's bit 10 selects it.  Synchronises. */
 int wayne_expected_profile(wayne_ctx *ctx, uint64_t *launches, double *ms);
 
+/* ---- the ramp fit: rate, error and flags per pixel (no reference counterpart) ---- */
+
+/*
+ * What an observer keeps of a STARING exposure: every pixel's up-the-ramp samples fitted with a line, samples behind
+ * saturation dropped, a cosmic ray -- a jump in the ramp -- cut out of it (k_ramp_fit, behind the reads on the slot's
+ * stream).  Three planes of S * S: rate (float64, e-/s), var (float64, (e-/s)^2) and word (uint32), 20 bytes a pixel.
+ * The law, float64 throughout, bordered coordinates of side S.  For a light-sensitive pixel P_k (k = 0 .. R) are the
+ * slot's reads, and L_k, g and dt_j exactly the extraction's (wayne_extract_desc above; the step bits WAYNE_X_LINEARISE,
+ * WAYNE_X_DARK and WAYNE_X_GAIN with the same meaning; the gain step is required, as for the variances); rn =
+ * read_noise_e is the read noise of a difference of two reads in electrons (wayne_variance_desc.read_noise):
+ *
+ *   e_0 = 0, e_k = L_k g                                  cumulative electrons
+ *   K   = the largest K <= R with P_k < saturation_dn for every 1 <= k <= K, and K = 0 if not P_0 < saturation_dn
+ *         (a NaN read is not < saturation_dn; a sample behind a saturated one is never used)
+ *   d_j = e_{j+1} - e_j,  r_j = d_j / dt_j,  j = 0 .. K-1;   G = {0 .. K-1}
+ *   med(G) = the element of rank floor((|G| - 1) / 2) of {r_j : j in G} in ascending order (the lower median; equal
+ *            values in order of j); 0 for an empty G
+ *   jump test (k_jump > 0), repeated while |G| >= 3:
+ *     m = med(G), f0 = max(m, 0)
+ *     z_j = (d_j - m dt_j) / sqrt(f0 dt_j + rn^2) for j in G;   j* = the lowest j with the largest z_j
+ *     z_j* > k_jump ? G <- G \ {j*}, bit j* of `jump` set : stop          (upward jumps only: a ray adds charge)
+ *   fit: f0 = max(med(G), 0);  a_j = f0 dt_j + rn^2;  o = -rn^2 / 2
+ *     the generalised least squares of d = f dt over j in G with cov(d_j, d_j) = a_j and cov(d_j, d_j+1) = o when both
+ *     are in G (two differences that share a read share its noise; a removed interval cuts the chain), solved as written:
+ *     ascending j:  j not in G: c_j = y_j = 0.  j in G: link = (j-1 in G); den = a_j - (link ? o c_{j-1} : 0);
+ *                   c_j = (j+1 in G) ? o / den : 0;   y_j = (dt_j - (link ? o y_{j-1} : 0)) / den
+ *     descending j: w_j = y_j - c_j w_{j+1}   (w_K = 0)
+ *     num = sum_{j in G, ascending} w_j d_j      den = sum_{j in G, ascending} w_j dt_j
+ *   rate = den > 0 ? num / den : 0     var = den > 0 ? 1 / den : 0     word = K << 16 | jump
+ *
+ * Reference pixels (the 5-pixel border) get rate = var = word = 0.  The host derives nsamp = K - popcount(jump), the
+ * time sum_{j in G} dt_j and a data-quality value from the word.  Limits: f0 is the median rate, not iterated on the
+ * fitted one; max(med, 0) of pure noise is biased upward, so at rate 0 an ensemble's variance is ~0.83 of the predicted
+ * one; downward jumps are not looked for.  A SCANNING exposure is not what this is for: the star crossing a pixel is a
+ * jump, and with the jump test on a scan's trace is flagged as cosmic rays.  The planes are a function of the reads
+ * alone: the same bytes in any slot, on either stream and on every run.  Works in every mode that produces reads
+ * (replay mode, carried traps, any read type).  Opt-in: without wayne_exposure_set_rampfit every launch and every byte
+ * stay as they are.  Added within WAYNE_ABI_VERSION 7: new symbols and a new struct only.
+ */
+typedef struct wayne_rampfit_desc {
+  uint32_t steps;       /* WAYNE_X_LINEARISE | WAYNE_X_DARK | WAYNE_X_GAIN; WAYNE_X_GAIN is required */
+  double read_noise_e;  /* rn: finite and > 0 (20 is the variances' default) */
+  double k_jump;        /* finite and >= 0; 0 switches the jump test off (5 is a sensible value) */
+  double saturation_dn; /* finite and > 0 (65000 lies below the 78000 DN clip and the uint16 ceiling) */
+} wayne_rampfit_desc;
+
+/* After wayne_exposure_upload, before run: every run of the slot also fits its ramps, at the end of its back half
+ * (behind the extraction's launches and k_fits_words, in front of k_expect) on the slot's stream.  desc == NULL clears;
+ * wayne_exposure_upload clears it too.  The planes' buffer (20 S^2 bytes) is reserved by this call, for slots that ask
+ * only.  WAYNE_E_STATE on a slot that is not uploaded; WAYNE_E_INVALID for a bad slot, the gain step off, a steps bit
+ * outside the three, a read_noise_e that is not finite and > 0, a k_jump or saturation_dn that is negative or not finite,
+ * or saturation_dn = 0 -- the slot stays usable and runs without the fit. */
+int wayne_exposure_set_rampfit(wayne_ctx *ctx, int slot, const wayne_rampfit_desc *desc);
+/* The planes into the caller's (pageable) memory, S * S each.  Synchronises and settles the run as
+ * wayne_exposure_download does (an exposure run a second time is fitted again).  WAYNE_E_STATE without the option or
+ * before a run. */
+int wayne_exposure_download_rampfit(wayne_ctx *ctx, int slot, double *rate, double *var, uint32_t *word);
+/* HIP-event time of k_ramp_fit while wayne_profile_enable is on, since wayne_profile_reset: launches and total
+ * milliseconds.  wayne_profile_select's bit 11 selects it.  Synchronises. */
+int wayne_rampfit_profile(wayne_ctx *ctx, uint64_t *launches, double *ms);
+
 /* ---- limb darkening per wavelength bin ---------------------------------- */
 
 /* A device light curve (lc_z of the descriptor) uses ONE set of Claret coefficients, lc_ld, for every wavelength bin.

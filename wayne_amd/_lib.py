@@ -118,6 +118,10 @@ class VarianceDesc(C.Structure):
     _fields_ = [("read_noise", C.c_double)]
 
 
+class RampFitDesc(C.Structure):
+    _fields_ = [("steps", C.c_uint32), ("read_noise_e", C.c_double), ("k_jump", C.c_double), ("saturation_dn", C.c_double)]
+
+
 class OptimalDesc(C.Structure):
     _fields_ = [("half_width", C.c_int)]
 
@@ -204,6 +208,9 @@ SYMBOLS = {
     "wayne_exposure_set_expected": (C.c_int, [_vp, C.c_int, C.c_int]),
     "wayne_exposure_download_expected": (C.c_int, [_vp, C.c_int, _dp]),
     "wayne_expected_profile": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_double)]),
+    "wayne_exposure_set_rampfit": (C.c_int, [_vp, C.c_int, C.POINTER(RampFitDesc)]),
+    "wayne_exposure_download_rampfit": (C.c_int, [_vp, C.c_int, _dp, _dp, C.POINTER(C.c_uint32)]),
+    "wayne_rampfit_profile": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_double)]),
     "wayne_exposure_set_limb_darkening": (C.c_int, [_vp, C.c_int, _dp, C.c_int]),
     "wayne_profile_enable": (C.c_int, [_vp, C.c_int]),
     "wayne_profile_select": (C.c_int, [_vp, C.c_uint]),
@@ -334,6 +341,7 @@ class Context(object):
         self._slot_prof = set()  # slots whose runs write the profile planes too (deliver_profile succeeded)
         self._slot_fits = {}     # slot -> (plane_bytes, stride, bitpix) of its FITS payload (set_fits succeeded)
         self._slot_expected = {} # slot -> mode name of its expected image (set_expected succeeded)
+        self._slot_rampfit = {}  # slot -> rampfit.RampFit of its ramp fit (set_rampfit succeeded)
         _live_contexts.add(self)
         for name, value in _knob_defaults.items():
             self.set_knob(name, value)
@@ -462,6 +470,7 @@ class Context(object):
         self._slot_optch.discard(slot)
         self._slot_fits.pop(slot, None)
         self._slot_expected.pop(slot, None)
+        self._slot_rampfit.pop(slot, None)
         sources = getattr(desc, "_sources", None)
         if sources:
             self.set_sources(slot, sources)
@@ -478,6 +487,9 @@ class Context(object):
         expected = getattr(desc, "_expected", None)
         if expected is not None:
             self.set_expected(slot, expected)
+        ramp_fit = getattr(desc, "_ramp_fit", None)
+        if ramp_fit is not None:
+            self.set_rampfit(slot, ramp_fit)
         ld_table = getattr(desc, "_ld_table", None)
         if ld_table is not None:
             self.set_limb_darkening(slot, ld_table)
@@ -523,6 +535,43 @@ class Context(object):
         """{"launches", "ms"} of k_expect by HIP events (profile_enable; since profile_reset)."""
         n, ms = C.c_uint64(0), C.c_double(0.0)
         self.check(self._L.wayne_expected_profile(self._h, C.byref(n), C.byref(ms)))
+        return {"launches": int(n.value), "ms": float(ms.value)}
+
+    # -- the ramp fit --------------------------------------------------------------
+    def set_rampfit(self, slot, ramp_fit):
+        """Every run of the slot also fits its ramps (k_ramp_fit): a rampfit.RampFit, True for its defaults; None or
+        False clears; after upload, which clears it too.  A refusal leaves the slot running without the fit.  See
+        wayne_exposure_set_rampfit."""
+        from . import rampfit as _rampfit
+        self._slot_rampfit.pop(slot, None)
+        fit = _rampfit.as_ramp_fit(ramp_fit)
+        if fit is None:
+            self.check(self._L.wayne_exposure_set_rampfit(self._h, int(slot), None))
+            return
+        d = fit.desc()
+        self.check(self._L.wayne_exposure_set_rampfit(self._h, int(slot), C.byref(d)))
+        self._slot_rampfit[slot] = fit
+
+    def has_rampfit(self, slot):
+        """Whether the slot's runs fit its ramps (set_rampfit succeeded since its last upload)."""
+        return slot in self._slot_rampfit
+
+    def rampfit(self, slot):
+        """The slot's (rate [S, S] float64 in e-/s, var [S, S] float64, word [S, S] uint32 = K << 16 | jump), blocking:
+        waits for the slot's run and settles it as download() does."""
+        if slot not in self._slot_rampfit:
+            raise WayneError(E_STATE, "rampfit: no ramp fit set for the slot")
+        rate = np.empty((self.S, self.S), dtype=np.float64)
+        var = np.empty((self.S, self.S), dtype=np.float64)
+        word = np.empty((self.S, self.S), dtype=np.uint32)
+        self.check(self._L.wayne_exposure_download_rampfit(self._h, int(slot), ptr(rate, C.c_double), ptr(var, C.c_double),
+                                                           ptr(word, C.c_uint32)))
+        return rate, var, word
+
+    def rampfit_profile(self):
+        """{"launches", "ms"} of k_ramp_fit by HIP events (profile_enable; since profile_reset)."""
+        n, ms = C.c_uint64(0), C.c_double(0.0)
+        self.check(self._L.wayne_rampfit_profile(self._h, C.byref(n), C.byref(ms)))
         return {"launches": int(n.value), "ms": float(ms.value)}
 
     # -- device-side FITS words ----------------------------------------------------
@@ -1001,7 +1050,7 @@ class Context(object):
         if names is None:
             mask = 0xFFFFFFFF
         else:
-            order = list(self.profile_get().keys())[:PROF_KERNELS] + ["k_extract", "k_fits_words", "k_expect"]
+            order = list(self.profile_get().keys())[:PROF_KERNELS] + ["k_extract", "k_fits_words", "k_expect", "k_ramp_fit"]
             mask = 0
             for n in names:
                 mask |= 1 << order.index(n)
@@ -1024,7 +1073,7 @@ def make_desc(seed, exposure_index, flags, sub_scale, wl_um, flux, depth, x_ref,
               sample_read, read_dt_s, replay_seed=None, rng_mode=RNG_PHILOX, threads_compat=1,
               sky_ct_s=0.0, cosmic_rate=-1.0, scale_factor=1.0, noise_mean=0.0, noise_std=0.0,
               thrower_margin=0, thrower_splits=0, lc_z=None, lc_hidden=None, lc_rp=None, lc_ld=None, sources=None,
-              traps=None, extraction=None, device_fits=False, expected=None, lc_ld_table=None):
+              traps=None, extraction=None, device_fits=False, expected=None, lc_ld_table=None, ramp_fit=None):
     """The exposure descriptor.  `sources`: contaminating field stars (sources.Contaminant), carried beside the C struct
     and set by Context.upload (wayne_exposure_set_sources); None or [] = the target alone.  `traps`: charge traps
     (traps.ExposureTraps, or a traps.ChargeTraps whose table is flat at `initial`), set by Context.upload
@@ -1033,7 +1082,9 @@ def make_desc(seed, exposure_index, flags, sub_scale, wl_um, flux, depth, x_ref,
     set by Context.upload (wayne_exposure_set_fits).  `expected`: "counts" or "mean" -- the noise-free expected image is
     rendered with every run, set by Context.upload (wayne_exposure_set_expected); None = none.  `lc_ld_table`: Claret
     coefficients per wavelength bin [W, 4] of the device light curve, carried beside the C struct and set by
-    Context.upload (wayne_exposure_set_limb_darkening); None = lc_ld for every bin."""
+    Context.upload (wayne_exposure_set_limb_darkening); None = lc_ld for every bin.  `ramp_fit`: a rampfit.RampFit, or
+    True for its defaults -- every run also fits the reads' ramps (rate, variance and flag word per pixel), set by
+    Context.upload (wayne_exposure_set_rampfit); None = none."""
     d = ExposureDesc()
     keep = []
 
@@ -1094,6 +1145,8 @@ def make_desc(seed, exposure_index, flags, sub_scale, wl_um, flux, depth, x_ref,
     d._extraction = extraction
     d._device_fits = bool(device_fits)
     d._expected = EXPECT_NAMES[expected_mode(expected)] if expected is not None else None
+    from . import rampfit as _rampfit
+    d._ramp_fit = _rampfit.as_ramp_fit(ramp_fit)
     return d
 
 

@@ -554,6 +554,17 @@ inline const char* variance_desc_error(unsigned steps, double read_noise) {
   return nullptr;
 }
 
+// wayne_exposure_set_rampfit's argument check (include/wayne_hip.h: wayne_rampfit_desc): null when valid.  The fit is in
+// electrons, so the gain step must be on; the only other steps are the two that form L_k.
+inline const char* rampfit_desc_error(unsigned steps, double read_noise_e, double k_jump, double saturation_dn) {
+  if (steps & ~(X_LINEARISE | X_DARK | X_GAIN)) return "steps holds bits other than WAYNE_X_LINEARISE, WAYNE_X_DARK and WAYNE_X_GAIN";
+  if (!(steps & X_GAIN)) return "the ramp fit needs WAYNE_X_GAIN: its noise model is in electrons";
+  if (!(std::isfinite(read_noise_e) && read_noise_e > 0.)) return "read_noise_e must be finite and > 0";
+  if (!(std::isfinite(k_jump) && k_jump >= 0.)) return "k_jump must be finite and >= 0";
+  if (!(std::isfinite(saturation_dn) && saturation_dn > 0.)) return "saturation_dn must be finite and > 0";
+  return nullptr;
+}
+
 // wayne_exposure_set_optimal's argument check (include/wayne_hip.h: wayne_optimal_desc): null when valid.  The half width
 // is bounded by the halo k_extract_optimal keeps beside a tile.
 inline const char* optimal_desc_error(int half_width) {

@@ -22,6 +22,8 @@
 //                                  padding included (a streaming byte reversal), no reference counterpart
 //   k_expect.h      k_expect       opt-in: the noise-free expected image of the thrower stage per read interval (the law
 //                                  the Monte-Carlo throwers converge to, as a gather), no reference counterpart
+//   k_rampfit.h     k_ramp_fit     opt-in: every pixel's up-the-ramp samples fitted with a line (saturated samples
+//                                  dropped, jumps cut out): rate, variance and flag word planes, no reference counterpart
 //
 // "A<n>" are the row ids of SURVEY.md section 8(a); reference file:line
 // citations are next to each formula.
@@ -36,3 +38,4 @@
 #include "k_extract.h"
 #include "k_fits.h"
 #include "k_expect.h"
+#include "k_rampfit.h"

@@ -39,8 +39,8 @@ int fail(wayne_ctx* c, int code, const std::string& msg);   // (keeps `msg` as t
 inline size_t align64(size_t n) { return (n + 63) & ~(size_t)63; }
 
 enum ProfKernel { PK_PREP_WL = 0, PK_PREP_SUB, PK_THROW, PK_COSMIC, PK_RAMP, PK_LIGHTCURVE, PK_NARROW, PK_LANE,
-                  PK_EXTRACT, PK_FITS, PK_EXPECT };   // (PK_EXTRACT .. PK_EXPECT lie beyond wayne_profile's arrays, which the ABI fixes: wayne_extract_profile / wayne_fits_profile / wayne_expected_profile report them)
-constexpr int kProfKernels = WAYNE_PROF_KERNELS + 3;
+                  PK_EXTRACT, PK_FITS, PK_EXPECT, PK_RAMPFIT };   // (PK_EXTRACT .. PK_RAMPFIT lie beyond wayne_profile's arrays, which the ABI fixes: wayne_extract_profile / wayne_fits_profile / wayne_expected_profile / wayne_rampfit_profile report them)
+constexpr int kProfKernels = WAYNE_PROF_KERNELS + 4;
 const char* const kProfNames[WAYNE_PROF_KERNELS] = {"k_prep_wl", "k_prep_sub",   "k_throw",  "k_cosmic",   /* (cosmic rays ride in k_prep_sub: slot kept for the ABI) */
                                                     "k_ramp",    "k_lightcurve", "k_narrow", "k_lane"};
 
@@ -293,6 +293,11 @@ struct Slot : SourceState {
   // (0: none) and the plane [R][S][S] float64 that k_expect renders at the very end of the back half
   int expect_mode = 0;
   DevBuf expect_plane;
+  // the ramp fit of this exposure (wayne_exposure_set_rampfit; cleared by upload): its parameters and the planes
+  // [rate S*S float64 | var S*S float64 | word S*S uint32] that k_ramp_fit writes near the end of the back half
+  bool rampfit_on = false, rampfit_ran = false;
+  wayne_rampfit_desc rampfit{};
+  DevBuf rampfit_planes;
   // staging arena of the descriptor's arrays: uploads are enqueued from here, so
   // wayne_exposure_upload returns without waiting for the slot's stream to drain
   StageArena stage;
@@ -1023,6 +1028,35 @@ int launch_expected(wayne_ctx* c, Slot& s) {
   return WAYNE_OK;
 }
 
+static_assert(WAYNE_X_LINEARISE == X_LINEARISE && WAYNE_X_DARK == X_DARK && WAYNE_X_GAIN == X_GAIN,
+              "include/wayne_hip.h and plan_consts.h must agree on the step bits");
+
+// The ramp fit of slot `s` (wayne_exposure_set_rampfit) behind its ramp kernel, the extraction's launches and
+// k_fits_words: one launch, a thread a pixel of the bordered frame.
+int launch_rampfit(wayne_ctx* c, Slot& s) {
+  const size_t SS = (size_t)c->S * c->S;
+  RampFitArgs a{};
+  a.R = s.R; a.S = c->S;
+  a.steps = s.rampfit.steps;
+  for (int j = 0; j < kMaxReads; ++j) a.dt[j] = j < s.R ? s.read_dt_host[j] : 0.;
+  a.rn2 = s.rampfit.read_noise_e * s.rampfit.read_noise_e;
+  a.k_jump = s.rampfit.k_jump;
+  a.sat_dn = s.rampfit.saturation_dn;
+  a.reads = s.out.p;
+  a.pfl = c->has_pfl ? c->pfl.as<float>() : nullptr;
+  for (int i = 0; i < 4; ++i) a.lin[i] = c->has_lin ? c->lin[i].as<float>() : nullptr;
+  a.dark = c->has_dark ? c->dark_sci.as<float>() : nullptr;
+  a.rate = s.rampfit_planes.as<double>();
+  a.var = a.rate + SS;
+  a.word = (uint32_t*)(a.var + SS);
+  const dim3 grid((unsigned)((SS + kRampFitThreads - 1) / kRampFitThreads)), block(kRampFitThreads);
+  ProfScope ps(c, PK_RAMPFIT);
+  with_reads(out_kind(s.d.flags), [&](auto t) { hipLaunchKernelGGL((k_ramp_fit<typename decltype(t)::type>), grid, block, 0, c->stream, a); });
+  HIP_TRY(c, hipGetLastError());
+  s.rampfit_ran = true;
+  return WAYNE_OK;
+}
+
 // No extraction on slot `s` (upload, set_extraction): every switch of it off, nothing fetched.  The profile planes and
 // the optimal channels go with the optimal extraction wherever that is cleared.
 void ex_clear(Slot& s) {
@@ -1561,6 +1595,7 @@ int wayne_exposure_upload(wayne_ctx* c, int slot, const wayne_exposure_desc* d) 
   s.fits_on = false;         // ... and no FITS words until wayne_exposure_set_fits says so
   s.fits_pinned_misc = nullptr;
   s.expect_mode = 0;         // ... and no expected image until wayne_exposure_set_expected says so
+  s.rampfit_on = s.rampfit_ran = false;   // ... and no ramp fit until wayne_exposure_set_rampfit says so
   s.ld_on = false;           // ... and one set of limb-darkening coefficients until wayne_exposure_set_limb_darkening says so
   int rc;
   const size_t KW = (size_t)K * W;
@@ -2036,6 +2071,8 @@ int wayne_exposure_run_back(wayne_ctx* c, int slot) {
     if (int rc = launch_extract(c, s)) return rc;   // the spectra of the reads just written, behind them on the stream
   if (s.fits_on)
     if (int rc = launch_fits(c, s)) return rc;      // ... and their FITS words
+  if (s.rampfit_on)
+    if (int rc = launch_rampfit(c, s)) return rc;   // ... and the fit of their ramps
   if (s.expect_mode)
     if (int rc = launch_expected(c, s)) return rc;  // ... and, last of all, the expected image of the thrower stage
   s.acc_dirty = false;
@@ -3008,6 +3045,60 @@ int wayne_expected_profile(wayne_ctx* c, uint64_t* launches, double* ms) {
   if (rc) return rc;
   if (launches) *launches = c->prof_launches[PK_EXPECT];
   if (ms) *ms = c->prof_ms[PK_EXPECT];
+  return WAYNE_OK;
+}
+
+// ---------------------------------------------------------------------------
+// the ramp fit
+// ---------------------------------------------------------------------------
+int wayne_exposure_set_rampfit(wayne_ctx* c, int slot, const wayne_rampfit_desc* desc) {
+  if (!c) return WAYNE_E_INVALID;
+  if (slot < 0 || slot >= kSlots) return fail(c, WAYNE_E_INVALID, "set_rampfit: slot");
+  Slot& s = c->slots[slot];
+  if (!s.uploaded) return fail(c, WAYNE_E_STATE, "set_rampfit: slot not uploaded");
+  s.rampfit_on = s.rampfit_ran = false;   // from here on a refusal leaves the slot usable, without the fit
+  if (!desc) return WAYNE_OK;
+  if (const char* why = plan::rampfit_desc_error(desc->steps, desc->read_noise_e, desc->k_jump, desc->saturation_dn))
+    return fail(c, WAYNE_E_INVALID, std::string("set_rampfit: ") + why);
+  if (s.R < 1 || s.R > kMaxReads) return fail(c, WAYNE_E_INVALID, "set_rampfit: n_reads outside 1 .. 15");
+  (void)hipSetDevice(c->device);
+  HIP_TRY(c, s.rampfit_planes.reserve((size_t)c->S * c->S * (2 * sizeof(double) + sizeof(uint32_t))));
+  s.rampfit = *desc;
+  s.rampfit_on = true;
+  return WAYNE_OK;
+}
+
+int wayne_exposure_download_rampfit(wayne_ctx* c, int slot, double* rate, double* var, uint32_t* word) {
+  if (!c || !rate || !var || !word) return WAYNE_E_INVALID;
+  if (slot < 0 || slot >= kSlots) return fail(c, WAYNE_E_INVALID, "download_rampfit: slot");
+  Slot& s = c->slots[slot];
+  if (!s.uploaded) return fail(c, WAYNE_E_STATE, "download_rampfit: slot not uploaded");
+  if (!s.rampfit_on) return fail(c, WAYNE_E_STATE, "download_rampfit: no ramp fit set for the slot");
+  if (!s.rampfit_ran) return fail(c, WAYNE_E_STATE, "download_rampfit: run first");
+  (void)hipSetDevice(c->device);
+  use_slot_stream(c, slot);
+  const size_t SS = (size_t)c->S * c->S;
+  const double* dev = s.rampfit_planes.as<double>();
+  auto copy = [&]() -> int {
+    HIP_TRY(c, hipMemcpyAsync(rate, dev, SS * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(var, dev + SS, SS * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(word, dev + 2 * SS, SS * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    return WAYNE_OK;
+  };
+  if (int rc = copy()) return rc;
+  bool reran = false;
+  int rc = look_at_status(c, slot, nullptr, wayne_exposure_run, &reran);
+  if (rc || !reran) return rc;
+  if ((rc = copy())) return rc;       // an exposure run a second time is fitted again
+  return look_at_status(c, slot, nullptr);
+}
+
+int wayne_rampfit_profile(wayne_ctx* c, uint64_t* launches, double* ms) {
+  if (!c) return WAYNE_E_INVALID;
+  int rc = collect_profile(c);
+  if (rc) return rc;
+  if (launches) *launches = c->prof_launches[PK_RAMPFIT];
+  if (ms) *ms = c->prof_ms[PK_RAMPFIT];
   return WAYNE_OK;
 }
 

@@ -32,6 +32,10 @@ class Exposure(object):
         self.reads = []   # [(array (S, S), header dict)], read 0 first
         self.stored = []  # [(piece, header dict, shape, type code)], read 0 first: reads held as their FITS words (add_stored_read)
         self.expected = None   # [R, S, S] float64: the noise-free expected image per read interval, when it was asked for (expected=)
+        # the ramp fit, when it was asked for (ramp_fit=; wayne_amd/rampfit.py): rate [S, S] float64 in e-/s, its variance,
+        # the device's word K << 16 | jump, and what the host derives from it: data quality, samples and time fitted
+        self.rate = self.rate_var = self.rate_word = None
+        self.rate_dq = self.rate_nsamp = self.rate_time = None
 
     def add_read(self, data, read_info=None):
         self.reads.append((data, self.generate_read_header(read_info) if read_info is not None else {}))

@@ -29,6 +29,7 @@ import numpy as np
 from . import _lib, engine as _engine, exposure, lightcurve, tools
 from . import traps as _traps
 from . import extraction as _extraction
+from . import rampfit as _rampfit
 from .trend_generators import scan_speed_varations
 
 MS_PER_YEAR = 365.25 * 86400. * 1000.
@@ -124,7 +125,7 @@ class ExposureGenerator(object):
                        add_initial_bias=True, progress_bar=None, threads=2,
                        rng_mode=_lib.RNG_SPLIT, out_dtype=np.float32, reference_quirks=False,
                        record=None, exact_samplers=False, contaminants=None, charge_traps=None, extraction=None,
-                       crrej=None, channels=None, variance=None, optimal=None, expected=None):
+                       crrej=None, channels=None, variance=None, optimal=None, expected=None, ramp_fit=None):
         """Generate a spatially scanned exposure (exposure_generator.py:178-405).
 
         Extra keywords (not in the reference): `rng_mode` -- RNG_SPLIT (default:
@@ -167,7 +168,11 @@ class ExposureGenerator(object):
         exposure (k_expect; wayne_hip.h, wayne_exposure_set_expected) and the Exposure carries it as `expected`
         [R, S, S] float64, electrons per read interval: what the Monte-Carlo throwers converge to, given the bin counts
         this run drew ("counts") or before the draw ("mean").  Not in it: sky, cosmic rays, dark, the gaussian-noise
-        stage, gain, non-linearity, traps.  Not in replay mode.  staring_frame passes it on too.
+        stage, gain, non-linearity, traps.  Not in replay mode.  staring_frame passes it on too;
+        `ramp_fit` -- True or a rampfit.RampFit: every pixel's up-the-ramp samples are fitted with a line on the device
+        (k_ramp_fit; wayne_hip.h, wayne_exposure_set_rampfit) and the Exposure carries `rate`, `rate_var` [S, S] float64
+        (e-/s), `rate_word` and the derived `rate_dq`, `rate_nsamp` and `rate_time`.  The product of a STARING exposure:
+        with the jump test on, a scan's trace is flagged as cosmic rays.  staring_frame passes it on too.
         """
         eng, desc, start_time = self._host_half(
             x_ref, y_ref, x_jitter, y_jitter, wl, stellar_flux, planet_signal, scan_speed, sample_rate,
@@ -175,8 +180,8 @@ class ExposureGenerator(object):
             add_flat, cosmic_rate, sky_background, scale_factor, add_gain_variations, add_non_linear,
             clip_values_det_limits, add_read_noise, add_stellar_noise, add_initial_bias, progress_bar, threads,
             rng_mode, out_dtype, reference_quirks, exact_samplers, contaminants, charge_traps, extraction, crrej, channels, variance, optimal,
-            expected=expected)
-        if record is None and desc._extraction is None and desc._expected is None:
+            expected=expected, ramp_fit=ramp_fit)
+        if record is None and desc._extraction is None and desc._expected is None and desc._ramp_fit is None:
             reads = eng.ctx.synthesize(desc)
         else:
             eng.ctx.upload(0, desc)
@@ -197,6 +202,8 @@ class ExposureGenerator(object):
                                eng.ctx.optimal_channels(0) if eng.ctx.has_optimal_channels(0) else None)
         if desc._expected is not None:
             frame.expected = eng.ctx.expected(0)
+        if desc._ramp_fit is not None:
+            _rampfit.fill_exposure(frame, eng.ctx.rampfit(0), self._read_dt)
         return frame
 
     def _fill_spectra(self, spectra, sky, rejected=None, channels=None, variances=None, optimal=None, profile_planes=None,
@@ -265,7 +272,7 @@ class ExposureGenerator(object):
                    add_initial_bias=True, progress_bar=None, threads=2,
                    rng_mode=_lib.RNG_SPLIT, out_dtype=np.float32, reference_quirks=False,
                    exact_samplers=False, contaminants=None, charge_traps=None, extraction=None,
-                       crrej=None, channels=None, variance=None, optimal=None, device_fits=False, expected=None):
+                       crrej=None, channels=None, variance=None, optimal=None, device_fits=False, expected=None, ramp_fit=None):
         """scanning_frame's arguments -> (engine, descriptor, start time): the mode's engine (cached after its first
         use) and build_descriptor.  No GPU call once the engine exists."""
         start_time = time.time()
@@ -277,7 +284,7 @@ class ExposureGenerator(object):
             add_flat, cosmic_rate, sky_background, scale_factor, add_gain_variations, add_non_linear,
             clip_values_det_limits, add_read_noise, add_stellar_noise, add_initial_bias, progress_bar, threads,
             rng_mode, out_dtype, reference_quirks, exact_samplers, contaminants, charge_traps, extraction, crrej, channels, variance, optimal,
-            device_fits=device_fits, expected=expected)
+            device_fits=device_fits, expected=expected, ramp_fit=ramp_fit)
         return eng, desc, start_time
 
     def prepare(self, *args, staring=False, **kw):
@@ -299,7 +306,7 @@ class ExposureGenerator(object):
                          add_initial_bias=True, progress_bar=None, threads=2,
                          rng_mode=_lib.RNG_SPLIT, out_dtype=np.float32, reference_quirks=False,
                          exact_samplers=False, contaminants=None, charge_traps=None, extraction=None,
-                       crrej=None, channels=None, variance=None, optimal=None, device_fits=False, expected=None):
+                       crrej=None, channels=None, variance=None, optimal=None, device_fits=False, expected=None, ramp_fit=None):
         """The host half of scanning_frame: sample timing, scan positions, SSV,
         jitter / seed draws, spectrum crop (exposure_generator.py:247-334) ->
         one wayne_exposure_desc for the device.  Pure host code (`eng` may be
@@ -307,7 +314,8 @@ class ExposureGenerator(object):
         `device_fits`: Context.upload also asks the device for the reads' FITS words (wayne_exposure_set_fits), the way
         it applies `extraction`; nothing the device computes for the reads changes.  `expected`: "counts" or "mean" --
         Context.upload also asks for the noise-free expected image (wayne_exposure_set_expected); refused here, with a
-        ValueError, for any other value and in replay mode."""
+        ValueError, for any other value and in replay mode.  `ramp_fit`: True or a rampfit.RampFit -- Context.upload also
+        asks for the ramp fit (wayne_exposure_set_rampfit)."""
         if _lib.expected_mode(expected) and rng_mode == _lib.RNG_REPLAY:
             raise ValueError("expected: replay mode reproduces the reference, which has no expected image")
         out_dtype = np.dtype(out_dtype)
@@ -438,7 +446,7 @@ class ExposureGenerator(object):
             scale_factor=1.0 if scale_factor is None else float(scale_factor),
             noise_mean=float(noise_mean) if noise_mean else 0.0,
             noise_std=float(noise_std) if noise_std else 0.0, sources=contaminants, traps=charge_traps,
-            extraction=self.extraction_plan, device_fits=device_fits, expected=expected, **lc)
+            extraction=self.extraction_plan, device_fits=device_fits, expected=expected, ramp_fit=ramp_fit, **lc)
 
     def direct_image(self, x_ref, y_ref):
         """The unscaled 2-D gaussian direct image used to calibrate x_ref / y_ref

@@ -72,6 +72,8 @@ class Observation(object):
         # top of those variances: `spectra_result["optimal"]` / ["optimal_var"] and the .npz's keys of those names.
         # frame_options["expected"] ("counts" or "mean"; CLI: --expected): the noise-free expected image of every exposure
         # (wayne_amd/expected.py), on the Exposure and as NNNN_exp.fits beside the raw file.
+        # frame_options["ramp_fit"] (True or a rampfit.RampFit; CLI: --rate-images): the ramp fit of every exposure
+        # (wayne_amd/rampfit.py), on the Exposure and as NNNN_rate.fits beside the raw file.
         # frame_options["device_fits"] (True; CLI: --device-fits): the device forms the data sections of the _raw files and
         # run_observation writes every file straight from its slot's pinned mirror (fits_delivery) -- the same files,
         # without the host's pass over the samples.  The direct image stays on the host path; not with `spectra_only`.
@@ -402,6 +404,11 @@ class Observation(object):
         expected = self.frame_options.get("expected")
         _expected.refuse_combinations(expected, resume=resume, device_fits=device_fits, spectra=extraction is not None,
                                       spectra_only=self.spectra_only)
+        # frame_options["ramp_fit"] (True or a rampfit.RampFit; CLI: --rate-images): every exposure's ramps are fitted on the
+        # device (wayne_amd/rampfit.py) -- the Exposure carries the planes and NNNN_rate.fits is written beside the raw file
+        from . import rampfit as _rampfit
+        ramp_fit = _rampfit.as_ramp_fit(self.frame_options.get("ramp_fit"))
+        _rampfit.refuse_combinations(ramp_fit, resume=resume, device_fits=device_fits, spectra_only=self.spectra_only)
         if self.traps_carried:
             # every exposure starts from the state its predecessor left on ONE device: the visit runs whole and in order
             if world > 1:
@@ -478,6 +485,10 @@ class Observation(object):
                 frame.expected = ctx.expected
                 if pool is not None:
                     _expected.write_fits(os.path.join(self.outdir, "{:04d}_exp.fits".format(i + 1)), frame, ctx.expected, expected)
+            if ramp_fit is not None and frame is not None:
+                _rampfit.fill_exposure(frame, ctx.ramp_fit, gen._read_dt)
+                if pool is not None:
+                    _rampfit.write_fits(os.path.join(self.outdir, "{:04d}_rate.fits".format(i + 1)), frame, ramp_fit)
             if payload is not None:
                 # (views of the pinned mirror, no copy: the slot is not uploaded again until the writer has released it)
                 frame = gen._fill_stored(payload, ctx.layout, gen._prepared[2])
@@ -512,6 +523,8 @@ class Observation(object):
                 self._fits_active = True
             if expected:
                 ctx = _expected.ExpectedDelivery(eng.ctx, ctx)
+            if ramp_fit is not None:
+                ctx = _rampfit.RampFitDelivery(eng.ctx, ctx)
             run_pipelined(ctx, mine, prepare, finish, depth=3, n_slots=n_slots)
         finally:
             self._fits_active = False

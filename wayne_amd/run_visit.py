@@ -4,6 +4,7 @@
                                   [--spectra OUT.npz | --spectra-only OUT.npz] [--reject-cosmics [K]]
                                   [--channels LO:HI:N] [--no-channel-flat] [--variances [RN]] [--optimal [H]] [--optimal-profile N] [--optimal-channels]
                                   [--float64-reads | --uint16-reads] [--device-fits] [--expected {counts,mean}]
+                                  [--rate-images [K]]
 
 Accepts the reference's parameter files (wayne/run_visit.py:1-9, example
 examples/hd209458b_12181_simulation_parameters.yml): sections `general`
@@ -58,6 +59,11 @@ examples/hd209458b_12181_simulation_parameters.yml): sections `general`
     electrons per read interval, without sky, cosmic rays, dark and the detector chain) and NNNN_exp.fits is written
     beside each _raw file: the raw file's primary header plus EXPMODE, then one image HDU EXPECT per read interval
     (EXTVER 1 .. R, BITPIX -64).  Not with --resume, --device-fits, --spectra or --spectra-only;
+  * `--rate-images [K]`: the device also fits every pixel's up-the-ramp samples with a line (wayne_amd/rampfit.py: samples
+    behind saturation dropped, jumps above K sigma -- default 5, 0 for none -- cut out of the ramp) and NNNN_rate.fits is
+    written beside each _raw file: the raw file's primary header plus RFRN, RFK and RFSAT, then the image HDUs SCI (e-/s),
+    ERR, DQ, SAMP and TIME.  The product of a staring visit: a scan's trace is flagged as cosmic rays.  The name is not
+    _flt, which is the direct image's here.  Not with --resume, --device-fits or --spectra-only;
   * `--gpus G`: the process starts G rank processes itself (one per GPU of this node, before anything touches a
     GPU) and waits for them; under an external launcher (WORLD_SIZE / RANK set, one process per GPU) it is one
     rank.  Each rank generates its round-robin share of the exposures (observation.py:403-405 is the axis) on the
@@ -260,6 +266,11 @@ def run(argv=None):
                     help="render every exposure's noise-free expected image on the device and write it to NNNN_exp.fits "
                          "beside the _raw file: what the electron thrower converges to, given the bin counts the run drew "
                          "(counts) or before the draw (mean); not with --resume, --device-fits, --spectra, --spectra-only")
+    ap.add_argument("--rate-images", nargs="?", type=float, const=5.0, default=None, metavar="K",
+                    help="fit every pixel's up-the-ramp samples with a line on the device (saturated samples dropped, jumps "
+                         "above K sigma cut out; default 5, 0: no jump test) and write rate, error, data quality, samples and "
+                         "time to NNNN_rate.fits beside the _raw file; a staring product; not with --resume, --device-fits, "
+                         "--spectra-only")
     spectra = ap.add_mutually_exclusive_group()
     spectra.add_argument("--spectra", metavar="OUT.npz", default=None,
                          help="extract every exposure's column spectra on the device and write them to OUT.npz beside "
@@ -292,6 +303,13 @@ def run(argv=None):
                     help="with --optimal and --channels: also bin the optimal extraction's weighted pixels into the channels; "
                          "OUT.npz then also holds channels_opt and channels_opt_var (meant for --optimal-profile)")
     args = ap.parse_args(argv)
+    ramp_fit = None
+    if args.rate_images is not None:
+        from . import rampfit as _rampfit
+        try:
+            ramp_fit = _rampfit.RampFit(k=args.rate_images)
+        except ValueError as e:
+            raise SystemExit("--rate-images [K] (sigma, finite and >= 0): %s" % e)
     variance = None
     if args.variances is not None:
         if not (args.spectra or args.spectra_only):
@@ -345,6 +363,10 @@ def run(argv=None):
         from . import expected as _expected
         _expected.refuse_combinations(args.expected, resume=args.resume, device_fits=args.device_fits,
                                       spectra=bool(args.spectra), spectra_only=bool(args.spectra_only))
+    if ramp_fit is not None:
+        # (the API's refusal, Observation.run_observation's ValueError, raised before any rank process is started)
+        _rampfit.refuse_combinations(ramp_fit, resume=args.resume, device_fits=args.device_fits,
+                                     spectra_only=bool(args.spectra_only))
     if args.resume and (args.spectra or args.spectra_only):
         raise SystemExit("--spectra / --spectra-only cannot be combined with --resume (a skipped exposure has no spectra)")
     if args.gpus < 1 or args.ranks_per_gpu < 1:
@@ -407,6 +429,8 @@ def run(argv=None):
         obs.frame_options["device_fits"] = True
     if args.expected:
         obs.frame_options["expected"] = args.expected
+    if ramp_fit is not None:
+        obs.frame_options["ramp_fit"] = ramp_fit
     if args.spectra or args.spectra_only:
         obs.frame_options["extraction"] = True
         if args.reject_cosmics is not None:

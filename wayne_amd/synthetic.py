@@ -17,6 +17,7 @@ CONFIGS
   cfg4  G141 spatial scan, SUBARRAY 1024, SPARS10, NSAMP 16, K = 128, E = 1e9,  5 px/s   <- the metric's config
   cfg5  cfg4 for G141 then G102, SSVSine(1.5, 1.1, 0), cosmic rate 11, sky 4.7-6.7
   tiny  G141 scan, SUBARRAY 64, RAPID, NSAMP 4, K = 6, E = 3e4   (parity / smoke)
+  stare16_128  G141 staring, SUBARRAY 128, SPARS10, NSAMP 16, K = 15, E = 2e7   (15 uneven read intervals: the ramp fit)
   ramp16_128  G141 scan, SUBARRAY 128, RAPID, NSAMP 16, K = 30, E = 3e5, 45 px/s   (15 read intervals on a small frame)
 """
 import numpy as np
@@ -127,6 +128,10 @@ CONFIGS = {
                      x_ref=404.5, y_ref=500.0),
     "small256": dict(grism="G141", SUBARRAY=256, SAMPSEQ="SPARS10", NSAMP=4, K=9, E=3e6, scan_speed=3.0,
                      x_ref=404.5, y_ref=420.0),
+    # a staring ramp of all 15 read intervals on a small frame (the ramp fit's case: wayne_amd/rampfit.py); the intervals
+    # are uneven: 0.113 s, then 7.18 s
+    "stare16_128": dict(grism="G141", SUBARRAY=128, SAMPSEQ="SPARS10", NSAMP=16, K=15, E=2e7, scan_speed=0.0,
+                        x_ref=400.0, y_ref=470.0, n_wl=900),
 }
 
 

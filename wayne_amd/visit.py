@@ -15,6 +15,7 @@ from . import _lib
 from . import engine as _engine
 from . import extraction as _extraction
 from .expected import ExpectedDelivery
+from . import rampfit as _rampfit
 from .exposure import FitsWriterPool
 from .exposure_generator import ExposureGenerator
 from .fits_delivery import FitsDelivery, slots_for
@@ -93,7 +94,8 @@ class VisitRunner(object):
         return self.generator(i).build_descriptor(eng, out_dtype=self.out_dtype, rng_mode=self.rng_mode,
                                                   **self.frame_kwargs(i))
 
-    def run(self, indices, keep=False, on_reads=None, extraction=None, on_spectra=None, expected=None, on_expected=None):
+    def run(self, indices, keep=False, on_reads=None, extraction=None, on_spectra=None, expected=None, on_expected=None,
+            ramp_fit=None, on_ramp_fit=None):
         """Synthesise the given exposures as a pipeline over the context's two HIP streams and pinned
         host buffers: while the kernels of exposure n run on one stream and the device-to-host copy of
         exposure n-1 on the other, the host prepares and uploads exposure n+1 into the next slot.
@@ -107,11 +109,18 @@ class VisitRunner(object):
         extracts optimally too, so are `self.optimal` and `self.optimal_var`, and `self.profile_planes` when it delivers
         its profile planes.  `expected` ("counts" or "mean"): every exposure's noise-free expected image is rendered
         beside it (wayne_amd/expected.py) and fetched behind its settled run: `on_expected(i, planes)` gets an array
-        [R, S, S] of the caller's own, and with keep=True `self.expected` is {index: planes} (None otherwise)."""
+        [R, S, S] of the caller's own, and with keep=True `self.expected` is {index: planes} (None otherwise).
+        `ramp_fit` (True or a rampfit.RampFit): every exposure's ramps are fitted on the device (wayne_amd/rampfit.py) and
+        the planes fetched behind its settled run: `on_ramp_fit(i, rate, var, word)` gets arrays [S, S] of the caller's
+        own, with keep=True `self.ramp_fit` is {index: (rate, var, word)} (None otherwise), and with out_dir set
+        NNNN_rate.fits is written beside each raw file."""
         eng = self.engine()
         results = {}
         _lib.expected_mode(expected)          # (ValueError for anything but None, "counts", "mean")
         self.expected = {} if expected and keep else None
+        ramp_fit = _rampfit.as_ramp_fit(ramp_fit)
+        _rampfit.refuse_combinations(ramp_fit, device_fits=self.device_fits and self.out_dir is not None)
+        self.ramp_fit = {} if ramp_fit is not None and keep else None
         self.spectra_var = self.sky_var = self.channels_var = None
         self.optimal = self.optimal_var = None
         self.profile_planes = None
@@ -131,6 +140,8 @@ class VisitRunner(object):
                 kw["device_fits"] = True
             if expected:
                 kw["expected"] = expected
+            if ramp_fit is not None:
+                kw["ramp_fit"] = ramp_fit
             return gen.build_descriptor(eng, out_dtype=self.out_dtype, rng_mode=self.rng_mode, **kw), gen
 
         def finish(i, gen, got):
@@ -168,6 +179,11 @@ class VisitRunner(object):
                     on_expected(i, ctx.expected)
                 if self.expected is not None:
                     self.expected[i] = ctx.expected
+            if ramp_fit is not None:
+                if on_ramp_fit is not None:
+                    on_ramp_fit(i, *ctx.ramp_fit)
+                if self.ramp_fit is not None:
+                    self.ramp_fit[i] = ctx.ramp_fit
             if on_reads is not None:
                 on_reads(i, reads)
             if keep:
@@ -179,7 +195,12 @@ class VisitRunner(object):
             elif pool is not None:
                 os.makedirs(self.out_dir, exist_ok=True)
                 # (a copy: the pinned buffer is reused by the next exposure)
-                pool.submit(gen._fill_exposure(reads.copy()), self.out_dir, gen.exp_info["filename"])
+                frame = gen._fill_exposure(reads.copy())
+                if ramp_fit is not None:
+                    # (written here, beside the raw file the pool writes: the header's clock aside, a function of the planes)
+                    _rampfit.fill_exposure(frame, ctx.ramp_fit, gen._read_dt)
+                    _rampfit.write_fits(os.path.join(self.out_dir, _rampfit.rate_filename(gen.exp_info["filename"])), frame, ramp_fit)
+                pool.submit(frame, self.out_dir, gen.exp_info["filename"])
 
         n_slots = self.DEPTH
         if fits:
@@ -190,6 +211,8 @@ class VisitRunner(object):
             ctx = eng.ctx if extraction is None else _extraction.Delivery(eng.ctx, reads=True)
         if expected:
             ctx = ExpectedDelivery(eng.ctx, ctx)
+        if ramp_fit is not None:
+            ctx = _rampfit.RampFitDelivery(eng.ctx, ctx)
         try:
             run_pipelined(ctx, indices, prepare, finish, self.DEPTH, n_slots)
         finally:
