@@ -865,6 +865,74 @@ int wayne_exposure_download_rampfit(wayne_ctx *ctx, int slot, double *rate, doub
  * milliseconds.  wayne_profile_select's bit 11 selects it.  Synchronises. */
 int wayne_rampfit_profile(wayne_ctx *ctx, uint64_t *launches, double *ms);
 
+/* ---- the calibrated reads: an `_ima` file's SCI, ERR and DQ (no reference counterpart) ---- */
+
+/*
+ * What a SCAN observer with a reduction of their own starts from: the instrument pipeline's intermediate file, in which
+ * every read has the zero read subtracted, is linearised, dark-subtracted and in electrons, with an error and a
+ * data-quality plane beside it (k_ima, behind k_ramp_fit on the slot's stream, in front of k_expect).  The law, float64
+ * throughout, bordered coordinates of side S, n = S * S.  For a light-sensitive pixel P_k (k = 0 .. R) are the slot's
+ * reads, any read type, and L_k, g and dt_j exactly the extraction's (wayne_extract_desc above; the step bits
+ * WAYNE_X_LINEARISE, WAYNE_X_DARK and WAYNE_X_GAIN with the same meaning; the gain step is required, as for the
+ * variances); q = g / 2.35; rn = read_noise_e the read noise of a difference of two reads in electrons
+ * (wayne_variance_desc.read_noise); sat = saturation_dn:
+ *
+ *   t_0 = 0, t_k = sum_{j<k} dt_j   (ascending j)
+ *   e_0 = 0, e_k = L_k g
+ *   K   = the ramp fit's: the largest K <= R with P_k < sat for every 1 <= k <= K, 0 if not P_0 < sat   (a NaN is not <)
+ *   s_k = sqrt(max(e_k, 0) + rn^2 (q q))    (k >= 1; s_0 = 0)
+ *   units WAYNE_IMA_COUNTS:  SCI_k = (float32) e_k            ERR_k = (float32) s_k
+ *   units WAYNE_IMA_RATE  :  SCI_k = (float32)(e_k / t_k)     ERR_k = (float32)(s_k / t_k)     (k >= 1; read 0: both 0)
+ *   DQ_k  = (k > K or (k = 0 and K = 0 and not P_0 < sat) ? 256 : 0)
+ *         | (the slot also has a ramp fit and some bit j < k of its `jump` is set ? 8192 : 0)
+ *   reference pixels (the 5-pixel border): SCI = ERR = 0, DQ = 0
+ *
+ * The cast to float32 rounds to nearest even.  A cosmic ray in interval j contaminates every cumulative e_k with k > j,
+ * so those are the reads flagged; the jump bits are those of the word k_ramp_fit has just written for the same run (with
+ * the ramp fit's own saturation_dn and k_jump; none without a ramp fit on the slot or with its k_jump = 0).  In a SCAN with
+ * the jump test on the trace itself is flagged, as in the instrument's ima.  The bit patterns of a NaN are not specified.
+ *
+ * The payload, in file order -- the last read first, as in a raw file (wayne_exposure_set_fits's convention).  With
+ * pad(b) = b rounded up to a multiple of 2880, sci_stride = pad(4 n), dq_stride = pad(2 n) and imset_stride =
+ * 2 sci_stride + dq_stride (wayne_ima_layout), imset f = 0 .. R holds read k = R - f:
+ *
+ *   [f imset_stride                 ..)  SCI_k, n big-endian float32, then zeros to sci_stride
+ *   [f imset_stride + sci_stride    ..)  ERR_k, the same
+ *   [f imset_stride + 2 sci_stride  ..)  DQ_k,  n big-endian int16, then zeros to dq_stride
+ *
+ * so that every section is one contiguous piece of a file: an image HDU's data and its padding, which is written on every
+ * run.  The payload is a function of the reads and the ramp fit's word alone: the same bytes in any slot, on either
+ * stream and on every run.  Works in every mode that produces reads (replay mode, carried traps, any read type).  Not in
+ * it: reference-pixel values and a bias-level correction, the zero-read signal correction, flat-fielding.  Opt-in:
+ * without wayne_exposure_set_ima every launch and every byte stay as they are.  Added within WAYNE_ABI_VERSION 7: new
+ * symbols and a new struct only.
+ */
+#define WAYNE_IMA_RATE 1
+#define WAYNE_IMA_COUNTS 2
+typedef struct wayne_ima_desc {
+  uint32_t steps;       /* WAYNE_X_LINEARISE | WAYNE_X_DARK | WAYNE_X_GAIN; WAYNE_X_GAIN is required */
+  int units;            /* WAYNE_IMA_RATE (e-/s) or WAYNE_IMA_COUNTS (e-) */
+  double read_noise_e;  /* rn: finite and > 0 (20 is the variances' default) */
+  double saturation_dn; /* finite and > 0 (65000 is the ramp fit's default) */
+} wayne_ima_desc;
+
+/* The strides of the payload for a frame of side S (even) with R read intervals (1 .. 15): host arithmetic, no device.
+ * The payload is (R + 1) * imset_stride bytes.  WAYNE_E_INVALID otherwise. */
+int wayne_ima_layout(int S, int R, size_t *sci_stride, size_t *dq_stride, size_t *imset_stride);
+/* After wayne_exposure_upload, before run: every run of the slot also forms its calibrated reads.  desc == NULL clears;
+ * wayne_exposure_upload clears it too.  The payload's buffer (168 MB at 1024^2 and NSAMP 16) is reserved by this call,
+ * for slots that ask only.  WAYNE_E_STATE on a slot that is not uploaded; WAYNE_E_INVALID for a bad slot, the gain step
+ * off, a steps bit outside the three, a unit that is neither of the two, a read_noise_e or saturation_dn that is not
+ * finite and > 0, or more than 16 reads -- the slot stays usable and runs without the option. */
+int wayne_exposure_set_ima(wayne_ctx *ctx, int slot, const wayne_ima_desc *desc);
+/* The payload into the caller's (pageable) memory, (R + 1) * imset_stride bytes.  Synchronises and settles the run as
+ * wayne_exposure_download_rampfit does (an exposure run a second time is calibrated again).  WAYNE_E_STATE without the
+ * option or before a run. */
+int wayne_exposure_download_ima(wayne_ctx *ctx, int slot, void *payload);
+/* HIP-event time of k_ima while wayne_profile_enable is on, since wayne_profile_reset: launches and total milliseconds.
+ * wayne_profile_select's bit 12 selects it.  Synchronises. */
+int wayne_ima_profile(wayne_ctx *ctx, uint64_t *launches, double *ms);
+
 /* ---- limb darkening per wavelength bin ---------------------------------- */
 
 /* A device light curve (lc_z of the descriptor) uses ONE set of Claret coefficients, lc_ld, for every wavelength bin.

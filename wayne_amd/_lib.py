@@ -122,6 +122,10 @@ class RampFitDesc(C.Structure):
     _fields_ = [("steps", C.c_uint32), ("read_noise_e", C.c_double), ("k_jump", C.c_double), ("saturation_dn", C.c_double)]
 
 
+class ImaDesc(C.Structure):
+    _fields_ = [("steps", C.c_uint32), ("units", C.c_int), ("read_noise_e", C.c_double), ("saturation_dn", C.c_double)]
+
+
 class OptimalDesc(C.Structure):
     _fields_ = [("half_width", C.c_int)]
 
@@ -211,6 +215,10 @@ SYMBOLS = {
     "wayne_exposure_set_rampfit": (C.c_int, [_vp, C.c_int, C.POINTER(RampFitDesc)]),
     "wayne_exposure_download_rampfit": (C.c_int, [_vp, C.c_int, _dp, _dp, C.POINTER(C.c_uint32)]),
     "wayne_rampfit_profile": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_double)]),
+    "wayne_ima_layout": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+    "wayne_exposure_set_ima": (C.c_int, [_vp, C.c_int, C.POINTER(ImaDesc)]),
+    "wayne_exposure_download_ima": (C.c_int, [_vp, C.c_int, _vp]),
+    "wayne_ima_profile": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_double)]),
     "wayne_exposure_set_limb_darkening": (C.c_int, [_vp, C.c_int, _dp, C.c_int]),
     "wayne_profile_enable": (C.c_int, [_vp, C.c_int]),
     "wayne_profile_select": (C.c_int, [_vp, C.c_uint]),
@@ -342,6 +350,7 @@ class Context(object):
         self._slot_fits = {}     # slot -> (plane_bytes, stride, bitpix) of its FITS payload (set_fits succeeded)
         self._slot_expected = {} # slot -> mode name of its expected image (set_expected succeeded)
         self._slot_rampfit = {}  # slot -> rampfit.RampFit of its ramp fit (set_rampfit succeeded)
+        self._slot_ima = {}      # slot -> (ima.Ima, ima.Layout) of its calibrated reads (set_ima succeeded)
         _live_contexts.add(self)
         for name, value in _knob_defaults.items():
             self.set_knob(name, value)
@@ -471,6 +480,7 @@ class Context(object):
         self._slot_fits.pop(slot, None)
         self._slot_expected.pop(slot, None)
         self._slot_rampfit.pop(slot, None)
+        self._slot_ima.pop(slot, None)
         sources = getattr(desc, "_sources", None)
         if sources:
             self.set_sources(slot, sources)
@@ -490,6 +500,9 @@ class Context(object):
         ramp_fit = getattr(desc, "_ramp_fit", None)
         if ramp_fit is not None:
             self.set_rampfit(slot, ramp_fit)
+        ima = getattr(desc, "_ima", None)
+        if ima is not None:
+            self.set_ima(slot, ima)
         ld_table = getattr(desc, "_ld_table", None)
         if ld_table is not None:
             self.set_limb_darkening(slot, ld_table)
@@ -572,6 +585,43 @@ class Context(object):
         """{"launches", "ms"} of k_ramp_fit by HIP events (profile_enable; since profile_reset)."""
         n, ms = C.c_uint64(0), C.c_double(0.0)
         self.check(self._L.wayne_rampfit_profile(self._h, C.byref(n), C.byref(ms)))
+        return {"launches": int(n.value), "ms": float(ms.value)}
+
+    # -- the calibrated reads ------------------------------------------------------
+    def set_ima(self, slot, ima):
+        """Every run of the slot also forms its calibrated reads (k_ima): an ima.Ima, True for its defaults, "rate" or
+        "counts"; None or False clears; after upload, which clears it too.  A refusal leaves the slot running without the
+        option.  See wayne_exposure_set_ima."""
+        from . import ima as _ima
+        self._slot_ima.pop(slot, None)
+        opt = _ima.as_ima(ima)
+        if opt is None:
+            self.check(self._L.wayne_exposure_set_ima(self._h, int(slot), None))
+            return
+        d = opt.desc()
+        self.check(self._L.wayne_exposure_set_ima(self._h, int(slot), C.byref(d)))
+        K, W, R, _ = self._slot_meta[slot]
+        self._slot_ima[slot] = (opt, _ima.layout(self.S, R))
+
+    def has_ima(self, slot):
+        """Whether the slot's runs form its calibrated reads (set_ima succeeded since its last upload)."""
+        return slot in self._slot_ima
+
+    def ima(self, slot):
+        """The slot's calibrated reads, blocking: an ima.Payload -- the payload as one uint8 array of the caller's own
+        with sci(k) / err(k) / dq(k) views of it.  Waits for the slot's run and settles it as download() does."""
+        from . import ima as _ima
+        if slot not in self._slot_ima:
+            raise WayneError(E_STATE, "ima: no calibrated reads set for the slot")
+        opt, lay = self._slot_ima[slot]
+        buf = np.empty(lay.nbytes, dtype=np.uint8)
+        self.check(self._L.wayne_exposure_download_ima(self._h, int(slot), buf.ctypes.data_as(C.c_void_p)))
+        return _ima.Payload(buf, lay, opt)
+
+    def ima_profile(self):
+        """{"launches", "ms"} of k_ima by HIP events (profile_enable; since profile_reset)."""
+        n, ms = C.c_uint64(0), C.c_double(0.0)
+        self.check(self._L.wayne_ima_profile(self._h, C.byref(n), C.byref(ms)))
         return {"launches": int(n.value), "ms": float(ms.value)}
 
     # -- device-side FITS words ----------------------------------------------------
@@ -1050,7 +1100,7 @@ class Context(object):
         if names is None:
             mask = 0xFFFFFFFF
         else:
-            order = list(self.profile_get().keys())[:PROF_KERNELS] + ["k_extract", "k_fits_words", "k_expect", "k_ramp_fit"]
+            order = list(self.profile_get().keys())[:PROF_KERNELS] + ["k_extract", "k_fits_words", "k_expect", "k_ramp_fit", "k_ima"]
             mask = 0
             for n in names:
                 mask |= 1 << order.index(n)
@@ -1073,7 +1123,7 @@ def make_desc(seed, exposure_index, flags, sub_scale, wl_um, flux, depth, x_ref,
               sample_read, read_dt_s, replay_seed=None, rng_mode=RNG_PHILOX, threads_compat=1,
               sky_ct_s=0.0, cosmic_rate=-1.0, scale_factor=1.0, noise_mean=0.0, noise_std=0.0,
               thrower_margin=0, thrower_splits=0, lc_z=None, lc_hidden=None, lc_rp=None, lc_ld=None, sources=None,
-              traps=None, extraction=None, device_fits=False, expected=None, lc_ld_table=None, ramp_fit=None):
+              traps=None, extraction=None, device_fits=False, expected=None, lc_ld_table=None, ramp_fit=None, ima=None):
     """The exposure descriptor.  `sources`: contaminating field stars (sources.Contaminant), carried beside the C struct
     and set by Context.upload (wayne_exposure_set_sources); None or [] = the target alone.  `traps`: charge traps
     (traps.ExposureTraps, or a traps.ChargeTraps whose table is flat at `initial`), set by Context.upload
@@ -1084,7 +1134,9 @@ def make_desc(seed, exposure_index, flags, sub_scale, wl_um, flux, depth, x_ref,
     coefficients per wavelength bin [W, 4] of the device light curve, carried beside the C struct and set by
     Context.upload (wayne_exposure_set_limb_darkening); None = lc_ld for every bin.  `ramp_fit`: a rampfit.RampFit, or
     True for its defaults -- every run also fits the reads' ramps (rate, variance and flag word per pixel), set by
-    Context.upload (wayne_exposure_set_rampfit); None = none."""
+    Context.upload (wayne_exposure_set_rampfit); None = none.  `ima`: an ima.Ima, True, "rate" or "counts" -- every run
+    also forms the calibrated reads (SCI, ERR and DQ of an `_ima` file), set by Context.upload (wayne_exposure_set_ima);
+    None = none."""
     d = ExposureDesc()
     keep = []
 
@@ -1147,6 +1199,8 @@ def make_desc(seed, exposure_index, flags, sub_scale, wl_um, flux, depth, x_ref,
     d._expected = EXPECT_NAMES[expected_mode(expected)] if expected is not None else None
     from . import rampfit as _rampfit
     d._ramp_fit = _rampfit.as_ramp_fit(ramp_fit)
+    from . import ima as _ima
+    d._ima = _ima.as_ima(ima)
     return d
 
 

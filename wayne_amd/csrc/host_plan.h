@@ -565,6 +565,30 @@ inline const char* rampfit_desc_error(unsigned steps, double read_noise_e, doubl
   return nullptr;
 }
 
+// wayne_ima_layout (include/wayne_hip.h, "the calibrated reads"): the strides of the `_ima` payload of a frame of side S
+// with R read intervals -- a SCI or ERR section (4 S^2 bytes) and a DQ section (2 S^2 bytes), each rounded up to the
+// 2880-byte FITS block, and the imset SCI | ERR | DQ.  False for a side that is not even and >= 12 or an R outside 1 .. 15.
+inline bool ima_layout(int S, int R, size_t* sci_stride, size_t* dq_stride, size_t* imset_stride) {
+  if (S < 12 || (S & 1) || R < 1 || R > kMaxReads) return false;
+  const size_t n = (size_t)S * S, block = 2880;
+  const size_t sci = (4 * n + block - 1) / block * block, dq = (2 * n + block - 1) / block * block;
+  if (sci_stride) *sci_stride = sci;
+  if (dq_stride) *dq_stride = dq;
+  if (imset_stride) *imset_stride = 2 * sci + dq;
+  return true;
+}
+
+// wayne_exposure_set_ima's argument check (include/wayne_hip.h: wayne_ima_desc): null when valid.  The calibrated reads
+// are in electrons, so the gain step must be on; the only other steps are the two that form L_k.  `units`: 1 rate, 2 counts.
+inline const char* ima_desc_error(unsigned steps, int units, double read_noise_e, double saturation_dn) {
+  if (steps & ~(X_LINEARISE | X_DARK | X_GAIN)) return "steps holds bits other than WAYNE_X_LINEARISE, WAYNE_X_DARK and WAYNE_X_GAIN";
+  if (!(steps & X_GAIN)) return "the calibrated reads need WAYNE_X_GAIN: they are in electrons";
+  if (units != 1 && units != 2) return "units must be WAYNE_IMA_RATE or WAYNE_IMA_COUNTS";
+  if (!(std::isfinite(read_noise_e) && read_noise_e > 0.)) return "read_noise_e must be finite and > 0";
+  if (!(std::isfinite(saturation_dn) && saturation_dn > 0.)) return "saturation_dn must be finite and > 0";
+  return nullptr;
+}
+
 // wayne_exposure_set_optimal's argument check (include/wayne_hip.h: wayne_optimal_desc): null when valid.  The half width
 // is bounded by the halo k_extract_optimal keeps beside a tile.
 inline const char* optimal_desc_error(int half_width) {

@@ -24,6 +24,8 @@
 //                                  the Monte-Carlo throwers converge to, as a gather), no reference counterpart
 //   k_rampfit.h     k_ramp_fit     opt-in: every pixel's up-the-ramp samples fitted with a line (saturated samples
 //                                  dropped, jumps cut out): rate, variance and flag word planes, no reference counterpart
+//   k_ima.h         k_ima          opt-in: the calibrated reads (electrons or e-/s, error, data quality) as the data sections
+//                                  of an `_ima` FITS file (a streaming kernel over 8-pixel units), no reference counterpart
 //
 // "A<n>" are the row ids of SURVEY.md section 8(a); reference file:line
 // citations are next to each formula.
@@ -39,3 +41,4 @@
 #include "k_fits.h"
 #include "k_expect.h"
 #include "k_rampfit.h"
+#include "k_ima.h"

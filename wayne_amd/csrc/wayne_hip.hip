@@ -39,8 +39,8 @@ int fail(wayne_ctx* c, int code, const std::string& msg);   // (keeps `msg` as t
 inline size_t align64(size_t n) { return (n + 63) & ~(size_t)63; }
 
 enum ProfKernel { PK_PREP_WL = 0, PK_PREP_SUB, PK_THROW, PK_COSMIC, PK_RAMP, PK_LIGHTCURVE, PK_NARROW, PK_LANE,
-                  PK_EXTRACT, PK_FITS, PK_EXPECT, PK_RAMPFIT };   // (PK_EXTRACT .. PK_RAMPFIT lie beyond wayne_profile's arrays, which the ABI fixes: wayne_extract_profile / wayne_fits_profile / wayne_expected_profile / wayne_rampfit_profile report them)
-constexpr int kProfKernels = WAYNE_PROF_KERNELS + 4;
+                  PK_EXTRACT, PK_FITS, PK_EXPECT, PK_RAMPFIT, PK_IMA };   // (PK_EXTRACT .. PK_IMA lie beyond wayne_profile's arrays, which the ABI fixes: wayne_extract_profile / wayne_fits_profile / wayne_expected_profile / wayne_rampfit_profile / wayne_ima_profile report them)
+constexpr int kProfKernels = WAYNE_PROF_KERNELS + 5;
 const char* const kProfNames[WAYNE_PROF_KERNELS] = {"k_prep_wl", "k_prep_sub",   "k_throw",  "k_cosmic",   /* (cosmic rays ride in k_prep_sub: slot kept for the ABI) */
                                                     "k_ramp",    "k_lightcurve", "k_narrow", "k_lane"};
 
@@ -298,6 +298,12 @@ struct Slot : SourceState {
   bool rampfit_on = false, rampfit_ran = false;
   wayne_rampfit_desc rampfit{};
   DevBuf rampfit_planes;
+  // the calibrated reads of this exposure (wayne_exposure_set_ima; cleared by upload): their parameters, the strides of
+  // the payload [(R+1)][SCI | ERR | DQ] that k_ima forms behind the ramp fit, and the payload
+  bool ima_on = false, ima_ran = false;
+  wayne_ima_desc ima{};
+  size_t ima_sci_stride = 0, ima_dq_stride = 0, ima_imset_stride = 0;
+  DevBuf ima_dev;
   // staging arena of the descriptor's arrays: uploads are enqueued from here, so
   // wayne_exposure_upload returns without waiting for the slot's stream to drain
   StageArena stage;
@@ -1057,6 +1063,35 @@ int launch_rampfit(wayne_ctx* c, Slot& s) {
   return WAYNE_OK;
 }
 
+// The calibrated reads of slot `s` (wayne_exposure_set_ima) behind its ramp fit, whose word of this run they read when
+// the slot has one: one launch, a lane a unit of 8 pixels of every imset, the grid capped and strided over.
+int launch_ima(wayne_ctx* c, Slot& s) {
+  const size_t SS = (size_t)c->S * c->S;
+  ImaArgs a{};
+  a.R = s.R; a.S = c->S;
+  a.n = (unsigned)SS;
+  a.steps = s.ima.steps;
+  a.rate = s.ima.units == WAYNE_IMA_RATE;
+  a.t[0] = 0.;
+  for (int k = 1; k <= kMaxReads; ++k) a.t[k] = k <= s.R ? a.t[k - 1] + s.read_dt_host[k - 1] : 0.;
+  a.rn2 = s.ima.read_noise_e * s.ima.read_noise_e;
+  a.sat_dn = s.ima.saturation_dn;
+  a.reads = s.out.p;
+  a.pfl = c->has_pfl ? c->pfl.as<float>() : nullptr;
+  for (int i = 0; i < 4; ++i) a.lin[i] = c->has_lin ? c->lin[i].as<float>() : nullptr;
+  a.dark = c->has_dark ? c->dark_sci.as<float>() : nullptr;
+  a.word = s.rampfit_on ? (const uint32_t*)(s.rampfit_planes.as<double>() + 2 * SS) : nullptr;
+  a.payload = s.ima_dev.as<unsigned char>();
+  a.sci_stride = s.ima_sci_stride; a.dq_stride = s.ima_dq_stride; a.imset_stride = s.ima_imset_stride;
+  const size_t units = s.ima_dq_stride / 16;
+  const dim3 grid((unsigned)std::min((size_t)kImaMaxBlocks, (units + kImaThreads - 1) / kImaThreads)), block(kImaThreads);
+  ProfScope ps(c, PK_IMA);
+  with_reads(out_kind(s.d.flags), [&](auto t) { hipLaunchKernelGGL((k_ima<typename decltype(t)::type>), grid, block, 0, c->stream, a); });
+  HIP_TRY(c, hipGetLastError());
+  s.ima_ran = true;
+  return WAYNE_OK;
+}
+
 // No extraction on slot `s` (upload, set_extraction): every switch of it off, nothing fetched.  The profile planes and
 // the optimal channels go with the optimal extraction wherever that is cleared.
 void ex_clear(Slot& s) {
@@ -1596,6 +1631,7 @@ int wayne_exposure_upload(wayne_ctx* c, int slot, const wayne_exposure_desc* d) 
   s.fits_pinned_misc = nullptr;
   s.expect_mode = 0;         // ... and no expected image until wayne_exposure_set_expected says so
   s.rampfit_on = s.rampfit_ran = false;   // ... and no ramp fit until wayne_exposure_set_rampfit says so
+  s.ima_on = s.ima_ran = false;           // ... and no calibrated reads until wayne_exposure_set_ima says so
   s.ld_on = false;           // ... and one set of limb-darkening coefficients until wayne_exposure_set_limb_darkening says so
   int rc;
   const size_t KW = (size_t)K * W;
@@ -2073,6 +2109,8 @@ int wayne_exposure_run_back(wayne_ctx* c, int slot) {
     if (int rc = launch_fits(c, s)) return rc;      // ... and their FITS words
   if (s.rampfit_on)
     if (int rc = launch_rampfit(c, s)) return rc;   // ... and the fit of their ramps
+  if (s.ima_on)
+    if (int rc = launch_ima(c, s)) return rc;       // ... and the calibrated reads, which take the fit's jump bits
   if (s.expect_mode)
     if (int rc = launch_expected(c, s)) return rc;  // ... and, last of all, the expected image of the thrower stage
   s.acc_dirty = false;
@@ -3099,6 +3137,61 @@ int wayne_rampfit_profile(wayne_ctx* c, uint64_t* launches, double* ms) {
   if (rc) return rc;
   if (launches) *launches = c->prof_launches[PK_RAMPFIT];
   if (ms) *ms = c->prof_ms[PK_RAMPFIT];
+  return WAYNE_OK;
+}
+
+// ---------------------------------------------------------------------------
+// the calibrated reads
+// ---------------------------------------------------------------------------
+static_assert(WAYNE_IMA_RATE == 1 && WAYNE_IMA_COUNTS == 2, "plan::ima_desc_error takes the units as 1 and 2");
+
+int wayne_ima_layout(int S, int R, size_t* sci_stride, size_t* dq_stride, size_t* imset_stride) {
+  return plan::ima_layout(S, R, sci_stride, dq_stride, imset_stride) ? WAYNE_OK : WAYNE_E_INVALID;
+}
+
+int wayne_exposure_set_ima(wayne_ctx* c, int slot, const wayne_ima_desc* desc) {
+  if (!c) return WAYNE_E_INVALID;
+  if (slot < 0 || slot >= kSlots) return fail(c, WAYNE_E_INVALID, "set_ima: slot");
+  Slot& s = c->slots[slot];
+  if (!s.uploaded) return fail(c, WAYNE_E_STATE, "set_ima: slot not uploaded");
+  s.ima_on = s.ima_ran = false;   // from here on a refusal leaves the slot usable, without the calibrated reads
+  if (!desc) return WAYNE_OK;
+  if (const char* why = plan::ima_desc_error(desc->steps, desc->units, desc->read_noise_e, desc->saturation_dn))
+    return fail(c, WAYNE_E_INVALID, std::string("set_ima: ") + why);
+  size_t sci = 0, dq = 0, imset = 0;
+  if (!plan::ima_layout(c->S, s.R, &sci, &dq, &imset)) return fail(c, WAYNE_E_INVALID, "set_ima: more than 16 reads, or no layout for this side");
+  (void)hipSetDevice(c->device);
+  HIP_TRY(c, s.ima_dev.reserve((size_t)(s.R + 1) * imset));
+  s.ima_sci_stride = sci; s.ima_dq_stride = dq; s.ima_imset_stride = imset;
+  s.ima = *desc;
+  s.ima_on = true;
+  return WAYNE_OK;
+}
+
+int wayne_exposure_download_ima(wayne_ctx* c, int slot, void* payload) {
+  if (!c || !payload) return WAYNE_E_INVALID;
+  if (slot < 0 || slot >= kSlots) return fail(c, WAYNE_E_INVALID, "download_ima: slot");
+  Slot& s = c->slots[slot];
+  if (!s.uploaded) return fail(c, WAYNE_E_STATE, "download_ima: slot not uploaded");
+  if (!s.ima_on) return fail(c, WAYNE_E_STATE, "download_ima: no calibrated reads set for the slot");
+  if (!s.ima_ran) return fail(c, WAYNE_E_STATE, "download_ima: run first");
+  (void)hipSetDevice(c->device);
+  use_slot_stream(c, slot);
+  const size_t bytes = (size_t)(s.R + 1) * s.ima_imset_stride;
+  HIP_TRY(c, hipMemcpyAsync(payload, s.ima_dev.p, bytes, hipMemcpyDeviceToHost, c->stream));
+  bool reran = false;
+  int rc = look_at_status(c, slot, nullptr, wayne_exposure_run, &reran);
+  if (rc || !reran) return rc;
+  HIP_TRY(c, hipMemcpyAsync(payload, s.ima_dev.p, bytes, hipMemcpyDeviceToHost, c->stream));   // an exposure run a second time is calibrated again
+  return look_at_status(c, slot, nullptr);
+}
+
+int wayne_ima_profile(wayne_ctx* c, uint64_t* launches, double* ms) {
+  if (!c) return WAYNE_E_INVALID;
+  int rc = collect_profile(c);
+  if (rc) return rc;
+  if (launches) *launches = c->prof_launches[PK_IMA];
+  if (ms) *ms = c->prof_ms[PK_IMA];
   return WAYNE_OK;
 }
 

@@ -36,6 +36,9 @@ class Exposure(object):
         # the device's word K << 16 | jump, and what the host derives from it: data quality, samples and time fitted
         self.rate = self.rate_var = self.rate_word = None
         self.rate_dq = self.rate_nsamp = self.rate_time = None
+        # the calibrated reads, when they were asked for (ima=; wayne_amd/ima.py): an ima.Payload -- the bytes of an _ima
+        # file's SCI, ERR and DQ sections as one uint8 array, with sci(k) / err(k) / dq(k) as views of it
+        self.ima = None
 
     def add_read(self, data, read_info=None):
         self.reads.append((data, self.generate_read_header(read_info) if read_info is not None else {}))

@@ -30,6 +30,7 @@ from . import _lib, engine as _engine, exposure, lightcurve, tools
 from . import traps as _traps
 from . import extraction as _extraction
 from . import rampfit as _rampfit
+from . import ima as _ima
 from .trend_generators import scan_speed_varations
 
 MS_PER_YEAR = 365.25 * 86400. * 1000.
@@ -125,7 +126,7 @@ class ExposureGenerator(object):
                        add_initial_bias=True, progress_bar=None, threads=2,
                        rng_mode=_lib.RNG_SPLIT, out_dtype=np.float32, reference_quirks=False,
                        record=None, exact_samplers=False, contaminants=None, charge_traps=None, extraction=None,
-                       crrej=None, channels=None, variance=None, optimal=None, expected=None, ramp_fit=None):
+                       crrej=None, channels=None, variance=None, optimal=None, expected=None, ramp_fit=None, ima=None):
         """Generate a spatially scanned exposure (exposure_generator.py:178-405).
 
         Extra keywords (not in the reference): `rng_mode` -- RNG_SPLIT (default:
@@ -172,7 +173,11 @@ class ExposureGenerator(object):
         `ramp_fit` -- True or a rampfit.RampFit: every pixel's up-the-ramp samples are fitted with a line on the device
         (k_ramp_fit; wayne_hip.h, wayne_exposure_set_rampfit) and the Exposure carries `rate`, `rate_var` [S, S] float64
         (e-/s), `rate_word` and the derived `rate_dq`, `rate_nsamp` and `rate_time`.  The product of a STARING exposure:
-        with the jump test on, a scan's trace is flagged as cosmic rays.  staring_frame passes it on too.
+        with the jump test on, a scan's trace is flagged as cosmic rays.  staring_frame passes it on too;
+        `ima` -- True, "rate", "counts" or an ima.Ima: the device also forms the calibrated reads, the SCI, ERR and DQ
+        arrays of an `_ima` file (k_ima; wayne_hip.h, wayne_exposure_set_ima), and the Exposure carries them as `ima`, an
+        ima.Payload: the file's bytes with sci(k) / err(k) / dq(k) views.  With `ramp_fit` too, the reads behind a jump
+        carry 8192 -- in a scan with the jump test on that is the trace itself.  staring_frame passes it on too.
         """
         eng, desc, start_time = self._host_half(
             x_ref, y_ref, x_jitter, y_jitter, wl, stellar_flux, planet_signal, scan_speed, sample_rate,
@@ -180,8 +185,8 @@ class ExposureGenerator(object):
             add_flat, cosmic_rate, sky_background, scale_factor, add_gain_variations, add_non_linear,
             clip_values_det_limits, add_read_noise, add_stellar_noise, add_initial_bias, progress_bar, threads,
             rng_mode, out_dtype, reference_quirks, exact_samplers, contaminants, charge_traps, extraction, crrej, channels, variance, optimal,
-            expected=expected, ramp_fit=ramp_fit)
-        if record is None and desc._extraction is None and desc._expected is None and desc._ramp_fit is None:
+            expected=expected, ramp_fit=ramp_fit, ima=ima)
+        if record is None and desc._extraction is None and desc._expected is None and desc._ramp_fit is None and desc._ima is None:
             reads = eng.ctx.synthesize(desc)
         else:
             eng.ctx.upload(0, desc)
@@ -204,6 +209,8 @@ class ExposureGenerator(object):
             frame.expected = eng.ctx.expected(0)
         if desc._ramp_fit is not None:
             _rampfit.fill_exposure(frame, eng.ctx.rampfit(0), self._read_dt)
+        if desc._ima is not None:
+            frame.ima = eng.ctx.ima(0)
         return frame
 
     def _fill_spectra(self, spectra, sky, rejected=None, channels=None, variances=None, optimal=None, profile_planes=None,
@@ -272,7 +279,7 @@ class ExposureGenerator(object):
                    add_initial_bias=True, progress_bar=None, threads=2,
                    rng_mode=_lib.RNG_SPLIT, out_dtype=np.float32, reference_quirks=False,
                    exact_samplers=False, contaminants=None, charge_traps=None, extraction=None,
-                       crrej=None, channels=None, variance=None, optimal=None, device_fits=False, expected=None, ramp_fit=None):
+                       crrej=None, channels=None, variance=None, optimal=None, device_fits=False, expected=None, ramp_fit=None, ima=None):
         """scanning_frame's arguments -> (engine, descriptor, start time): the mode's engine (cached after its first
         use) and build_descriptor.  No GPU call once the engine exists."""
         start_time = time.time()
@@ -284,7 +291,7 @@ class ExposureGenerator(object):
             add_flat, cosmic_rate, sky_background, scale_factor, add_gain_variations, add_non_linear,
             clip_values_det_limits, add_read_noise, add_stellar_noise, add_initial_bias, progress_bar, threads,
             rng_mode, out_dtype, reference_quirks, exact_samplers, contaminants, charge_traps, extraction, crrej, channels, variance, optimal,
-            device_fits=device_fits, expected=expected, ramp_fit=ramp_fit)
+            device_fits=device_fits, expected=expected, ramp_fit=ramp_fit, ima=ima)
         return eng, desc, start_time
 
     def prepare(self, *args, staring=False, **kw):
@@ -306,7 +313,7 @@ class ExposureGenerator(object):
                          add_initial_bias=True, progress_bar=None, threads=2,
                          rng_mode=_lib.RNG_SPLIT, out_dtype=np.float32, reference_quirks=False,
                          exact_samplers=False, contaminants=None, charge_traps=None, extraction=None,
-                       crrej=None, channels=None, variance=None, optimal=None, device_fits=False, expected=None, ramp_fit=None):
+                       crrej=None, channels=None, variance=None, optimal=None, device_fits=False, expected=None, ramp_fit=None, ima=None):
         """The host half of scanning_frame: sample timing, scan positions, SSV,
         jitter / seed draws, spectrum crop (exposure_generator.py:247-334) ->
         one wayne_exposure_desc for the device.  Pure host code (`eng` may be
@@ -315,7 +322,8 @@ class ExposureGenerator(object):
         it applies `extraction`; nothing the device computes for the reads changes.  `expected`: "counts" or "mean" --
         Context.upload also asks for the noise-free expected image (wayne_exposure_set_expected); refused here, with a
         ValueError, for any other value and in replay mode.  `ramp_fit`: True or a rampfit.RampFit -- Context.upload also
-        asks for the ramp fit (wayne_exposure_set_rampfit)."""
+        asks for the ramp fit (wayne_exposure_set_rampfit).  `ima`: True, "rate", "counts" or an ima.Ima -- Context.upload
+        also asks for the calibrated reads (wayne_exposure_set_ima)."""
         if _lib.expected_mode(expected) and rng_mode == _lib.RNG_REPLAY:
             raise ValueError("expected: replay mode reproduces the reference, which has no expected image")
         out_dtype = np.dtype(out_dtype)
@@ -446,7 +454,7 @@ class ExposureGenerator(object):
             scale_factor=1.0 if scale_factor is None else float(scale_factor),
             noise_mean=float(noise_mean) if noise_mean else 0.0,
             noise_std=float(noise_std) if noise_std else 0.0, sources=contaminants, traps=charge_traps,
-            extraction=self.extraction_plan, device_fits=device_fits, expected=expected, ramp_fit=ramp_fit, **lc)
+            extraction=self.extraction_plan, device_fits=device_fits, expected=expected, ramp_fit=ramp_fit, ima=ima, **lc)
 
     def direct_image(self, x_ref, y_ref):
         """The unscaled 2-D gaussian direct image used to calibrate x_ref / y_ref

@@ -74,6 +74,8 @@ class Observation(object):
         # (wayne_amd/expected.py), on the Exposure and as NNNN_exp.fits beside the raw file.
         # frame_options["ramp_fit"] (True or a rampfit.RampFit; CLI: --rate-images): the ramp fit of every exposure
         # (wayne_amd/rampfit.py), on the Exposure and as NNNN_rate.fits beside the raw file.
+        # frame_options["ima"] (True, "rate", "counts" or an ima.Ima; CLI: --ima): the calibrated reads of every exposure
+        # (wayne_amd/ima.py), on the Exposure and as NNNN_ima.fits beside the raw file.
         # frame_options["device_fits"] (True; CLI: --device-fits): the device forms the data sections of the _raw files and
         # run_observation writes every file straight from its slot's pinned mirror (fits_delivery) -- the same files,
         # without the host's pass over the samples.  The direct image stays on the host path; not with `spectra_only`.
@@ -409,6 +411,11 @@ class Observation(object):
         from . import rampfit as _rampfit
         ramp_fit = _rampfit.as_ramp_fit(self.frame_options.get("ramp_fit"))
         _rampfit.refuse_combinations(ramp_fit, resume=resume, device_fits=device_fits, spectra_only=self.spectra_only)
+        # frame_options["ima"] (True, "rate", "counts" or an ima.Ima; CLI: --ima): every exposure's calibrated reads are formed
+        # on the device (wayne_amd/ima.py) -- the Exposure carries the payload and NNNN_ima.fits is written beside the raw file
+        from . import ima as _ima
+        ima = _ima.as_ima(self.frame_options.get("ima"))
+        _ima.refuse_combinations(ima, resume=resume, device_fits=device_fits, spectra_only=self.spectra_only)
         if self.traps_carried:
             # every exposure starts from the state its predecessor left on ONE device: the visit runs whole and in order
             if world > 1:
@@ -489,6 +496,10 @@ class Observation(object):
                 _rampfit.fill_exposure(frame, ctx.ramp_fit, gen._read_dt)
                 if pool is not None:
                     _rampfit.write_fits(os.path.join(self.outdir, "{:04d}_rate.fits".format(i + 1)), frame, ramp_fit)
+            if ima is not None and frame is not None:
+                frame.ima = ctx.ima
+                if pool is not None:
+                    _ima.write_fits(os.path.join(self.outdir, "{:04d}_ima.fits".format(i + 1)), frame)
             if payload is not None:
                 # (views of the pinned mirror, no copy: the slot is not uploaded again until the writer has released it)
                 frame = gen._fill_stored(payload, ctx.layout, gen._prepared[2])
@@ -525,6 +536,8 @@ class Observation(object):
                 ctx = _expected.ExpectedDelivery(eng.ctx, ctx)
             if ramp_fit is not None:
                 ctx = _rampfit.RampFitDelivery(eng.ctx, ctx)
+            if ima is not None:
+                ctx = _ima.ImaDelivery(eng.ctx, ctx)
             run_pipelined(ctx, mine, prepare, finish, depth=3, n_slots=n_slots)
         finally:
             self._fits_active = False

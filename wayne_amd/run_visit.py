@@ -4,7 +4,7 @@
                                   [--spectra OUT.npz | --spectra-only OUT.npz] [--reject-cosmics [K]]
                                   [--channels LO:HI:N] [--no-channel-flat] [--variances [RN]] [--optimal [H]] [--optimal-profile N] [--optimal-channels]
                                   [--float64-reads | --uint16-reads] [--device-fits] [--expected {counts,mean}]
-                                  [--rate-images [K]]
+                                  [--rate-images [K]] [--ima [{rate,counts}]]
 
 Accepts the reference's parameter files (wayne/run_visit.py:1-9, example
 examples/hd209458b_12181_simulation_parameters.yml): sections `general`
@@ -64,6 +64,11 @@ examples/hd209458b_12181_simulation_parameters.yml): sections `general`
     written beside each _raw file: the raw file's primary header plus RFRN, RFK and RFSAT, then the image HDUs SCI (e-/s),
     ERR, DQ, SAMP and TIME.  The product of a staring visit: a scan's trace is flagged as cosmic rays.  The name is not
     _flt, which is the direct image's here.  Not with --resume, --device-fits or --spectra-only;
+  * `--ima [{rate,counts}]`: the device also forms every exposure's calibrated reads (wayne_amd/ima.py: every read with the
+    zero read subtracted, linearised, dark-subtracted and in electrons -- per second by default, `counts` for electrons --
+    with an error and a data-quality plane) and NNNN_ima.fits is written beside each _raw file, laid out like it: five
+    extensions a read, SCI, ERR and DQ with data.  What a scan observer with a reduction of their own differences.  Not
+    with --resume, --device-fits or --spectra-only;
   * `--gpus G`: the process starts G rank processes itself (one per GPU of this node, before anything touches a
     GPU) and waits for them; under an external launcher (WORLD_SIZE / RANK set, one process per GPU) it is one
     rank.  Each rank generates its round-robin share of the exposures (observation.py:403-405 is the axis) on the
@@ -271,6 +276,10 @@ def run(argv=None):
                          "above K sigma cut out; default 5, 0: no jump test) and write rate, error, data quality, samples and "
                          "time to NNNN_rate.fits beside the _raw file; a staring product; not with --resume, --device-fits, "
                          "--spectra-only")
+    ap.add_argument("--ima", nargs="?", choices=("rate", "counts"), const="rate", default=None,
+                    help="form every exposure's calibrated reads on the device (zero read subtracted, linearised, dark-subtracted, "
+                         "in electrons per second, or electrons with `counts`; error and data quality beside them) and write them "
+                         "to NNNN_ima.fits beside the _raw file, laid out like it; not with --resume, --device-fits, --spectra-only")
     spectra = ap.add_mutually_exclusive_group()
     spectra.add_argument("--spectra", metavar="OUT.npz", default=None,
                          help="extract every exposure's column spectra on the device and write them to OUT.npz beside "
@@ -367,6 +376,10 @@ def run(argv=None):
         # (the API's refusal, Observation.run_observation's ValueError, raised before any rank process is started)
         _rampfit.refuse_combinations(ramp_fit, resume=args.resume, device_fits=args.device_fits,
                                      spectra_only=bool(args.spectra_only))
+    if args.ima is not None:
+        from . import ima as _ima
+        _ima.refuse_combinations(args.ima, resume=args.resume, device_fits=args.device_fits,
+                                 spectra_only=bool(args.spectra_only))
     if args.resume and (args.spectra or args.spectra_only):
         raise SystemExit("--spectra / --spectra-only cannot be combined with --resume (a skipped exposure has no spectra)")
     if args.gpus < 1 or args.ranks_per_gpu < 1:
@@ -431,6 +444,8 @@ def run(argv=None):
         obs.frame_options["expected"] = args.expected
     if ramp_fit is not None:
         obs.frame_options["ramp_fit"] = ramp_fit
+    if args.ima is not None:
+        obs.frame_options["ima"] = args.ima
     if args.spectra or args.spectra_only:
         obs.frame_options["extraction"] = True
         if args.reject_cosmics is not None:

@@ -18,6 +18,7 @@ CONFIGS
   cfg5  cfg4 for G141 then G102, SSVSine(1.5, 1.1, 0), cosmic rate 11, sky 4.7-6.7
   tiny  G141 scan, SUBARRAY 64, RAPID, NSAMP 4, K = 6, E = 3e4   (parity / smoke)
   stare16_128  G141 staring, SUBARRAY 128, SPARS10, NSAMP 16, K = 15, E = 2e7   (15 uneven read intervals: the ramp fit)
+  full3  G141 scan, SUBARRAY 1024, RAPID, NSAMP 3, K = 6, E = 3e5, 20 px/s   (the full array, small enough for a test)
   ramp16_128  G141 scan, SUBARRAY 128, RAPID, NSAMP 16, K = 30, E = 3e5, 45 px/s   (15 read intervals on a small frame)
 """
 import numpy as np
@@ -132,6 +133,10 @@ CONFIGS = {
     # are uneven: 0.113 s, then 7.18 s
     "stare16_128": dict(grism="G141", SUBARRAY=128, SAMPSEQ="SPARS10", NSAMP=16, K=15, E=2e7, scan_speed=0.0,
                         x_ref=400.0, y_ref=470.0, n_wl=900),
+    # the full array, small enough for a test (the calibrated reads' case: wayne_amd/ima.py -- S * S = 1024^2 is the only
+    # frame size that is a multiple of 8, so the only one whose int16 plane ends on a whole 16-byte vector)
+    "full3": dict(grism="G141", SUBARRAY=1024, SAMPSEQ="RAPID", NSAMP=3, K=6, E=3e5, scan_speed=20.0,
+                  x_ref=404.5 + 379, y_ref=300.0, n_wl=900),
 }
 
 

@@ -16,6 +16,7 @@ from . import engine as _engine
 from . import extraction as _extraction
 from .expected import ExpectedDelivery
 from . import rampfit as _rampfit
+from . import ima as _ima
 from .exposure import FitsWriterPool
 from .exposure_generator import ExposureGenerator
 from .fits_delivery import FitsDelivery, slots_for
@@ -95,7 +96,7 @@ class VisitRunner(object):
                                                   **self.frame_kwargs(i))
 
     def run(self, indices, keep=False, on_reads=None, extraction=None, on_spectra=None, expected=None, on_expected=None,
-            ramp_fit=None, on_ramp_fit=None):
+            ramp_fit=None, on_ramp_fit=None, ima=None, on_ima=None):
         """Synthesise the given exposures as a pipeline over the context's two HIP streams and pinned
         host buffers: while the kernels of exposure n run on one stream and the device-to-host copy of
         exposure n-1 on the other, the host prepares and uploads exposure n+1 into the next slot.
@@ -113,7 +114,10 @@ class VisitRunner(object):
         `ramp_fit` (True or a rampfit.RampFit): every exposure's ramps are fitted on the device (wayne_amd/rampfit.py) and
         the planes fetched behind its settled run: `on_ramp_fit(i, rate, var, word)` gets arrays [S, S] of the caller's
         own, with keep=True `self.ramp_fit` is {index: (rate, var, word)} (None otherwise), and with out_dir set
-        NNNN_rate.fits is written beside each raw file."""
+        NNNN_rate.fits is written beside each raw file.  `ima` (True, "rate", "counts" or an ima.Ima): every exposure's
+        calibrated reads are formed on the device (wayne_amd/ima.py) and fetched behind its settled run: `on_ima(i, payload)`
+        gets an ima.Payload of the caller's own, with keep=True `self.ima` is {index: payload} (None otherwise), and with
+        out_dir set NNNN_ima.fits is written beside each raw file."""
         eng = self.engine()
         results = {}
         _lib.expected_mode(expected)          # (ValueError for anything but None, "counts", "mean")
@@ -121,6 +125,9 @@ class VisitRunner(object):
         ramp_fit = _rampfit.as_ramp_fit(ramp_fit)
         _rampfit.refuse_combinations(ramp_fit, device_fits=self.device_fits and self.out_dir is not None)
         self.ramp_fit = {} if ramp_fit is not None and keep else None
+        ima = _ima.as_ima(ima)
+        _ima.refuse_combinations(ima, device_fits=self.device_fits and self.out_dir is not None)
+        self.ima = {} if ima is not None and keep else None
         self.spectra_var = self.sky_var = self.channels_var = None
         self.optimal = self.optimal_var = None
         self.profile_planes = None
@@ -142,6 +149,8 @@ class VisitRunner(object):
                 kw["expected"] = expected
             if ramp_fit is not None:
                 kw["ramp_fit"] = ramp_fit
+            if ima is not None:
+                kw["ima"] = ima
             return gen.build_descriptor(eng, out_dtype=self.out_dtype, rng_mode=self.rng_mode, **kw), gen
 
         def finish(i, gen, got):
@@ -184,6 +193,11 @@ class VisitRunner(object):
                     on_ramp_fit(i, *ctx.ramp_fit)
                 if self.ramp_fit is not None:
                     self.ramp_fit[i] = ctx.ramp_fit
+            if ima is not None:
+                if on_ima is not None:
+                    on_ima(i, ctx.ima)
+                if self.ima is not None:
+                    self.ima[i] = ctx.ima
             if on_reads is not None:
                 on_reads(i, reads)
             if keep:
@@ -200,6 +214,9 @@ class VisitRunner(object):
                     # (written here, beside the raw file the pool writes: the header's clock aside, a function of the planes)
                     _rampfit.fill_exposure(frame, ctx.ramp_fit, gen._read_dt)
                     _rampfit.write_fits(os.path.join(self.out_dir, _rampfit.rate_filename(gen.exp_info["filename"])), frame, ramp_fit)
+                if ima is not None:
+                    frame.ima = ctx.ima
+                    _ima.write_fits(os.path.join(self.out_dir, _ima.ima_filename(gen.exp_info["filename"])), frame)
                 pool.submit(frame, self.out_dir, gen.exp_info["filename"])
 
         n_slots = self.DEPTH
@@ -213,6 +230,8 @@ class VisitRunner(object):
             ctx = ExpectedDelivery(eng.ctx, ctx)
         if ramp_fit is not None:
             ctx = _rampfit.RampFitDelivery(eng.ctx, ctx)
+        if ima is not None:
+            ctx = _ima.ImaDelivery(eng.ctx, ctx)
         try:
             run_pipelined(ctx, indices, prepare, finish, self.DEPTH, n_slots)
         finally:
