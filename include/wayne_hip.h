@@ -294,7 +294,9 @@ int wayne_exposure_debug_depth(wayne_ctx *ctx, int slot, double *depth);
 /* Which accumulators the ramp kernel of `slot` loads (for the byte accounting of bench.py): boxes[r*4 .. r*4+3] =
  * {x0, x1, y0, y1} of read interval r in bordered coordinates, the host's bound on where the thrower's electrons of
  * that interval can land (all zero: everything is loaded), and segments[r] = the number of 64-accumulator segments
- * (one per wave) that intersect it.  Segments with a cosmic-ray hit are loaded too and not counted here.
+ * (one per wave) that intersect it.  Segments with a cosmic-ray hit are loaded too and not counted here.  With
+ * wayne_exposure_set_ipc the ramp kernel gets each non-empty box a pixel wider on every side, clamped to the frame
+ * (coupled charge lies one pixel outside the thrower's bound): those are then the boxes reported and counted.
  * boxes: 16*4 ints, segments: 16 ints.  Returns WAYNE_OK, *use_box = 0 when the slot loads every accumulator. */
 int wayne_exposure_debug_boxes(wayne_ctx *ctx, int slot, int32_t *boxes, int32_t *segments, int *use_box);
 /* The two halves of wayne_exposure_run: front = prep + thrower + cosmic rays,
@@ -932,6 +934,38 @@ int wayne_exposure_download_ima(wayne_ctx *ctx, int slot, void *payload);
 /* HIP-event time of k_ima while wayne_profile_enable is on, since wayne_profile_reset: launches and total milliseconds.
  * wayne_profile_select's bit 12 selects it.  Synchronises. */
 int wayne_ima_profile(wayne_ctx *ctx, uint64_t *launches, double *ms);
+
+/* ---- inter-pixel capacitance ------------------------------------------- */
+
+/* In a hybrid CMOS array a pixel's reading holds a few per cent of each neighbour's charge.  With the option, the
+ * electrons each read interval collected (target, contaminants, cosmic rays: the thrower's int64 accumulators q_r,
+ * 2^-28 e-, bordered S x S) are coupled before k_ramp reads them.  The law, in integers:
+ *
+ *   W[i][j] = (int64) rint(k[i][j] * 65536)   for the eight neighbours;   W[1][1] = 65536 - sum of them
+ *   q'_r[y, x] = floor((sum_{dy, dx in -1..1} W[dy+1][dx+1] q_r[y+dy, x+dx] + 32768) / 65536)
+ *
+ * W[1][2] is the share a pixel receives from its right-hand neighbour; q is 0 beyond the frame; q' is 0 on the 5-pixel
+ * reference border (charge coupled onto reference pixels is lost).  The sum is exact for every int64 input (k_ipc.h).
+ * k_ramp, in whichever variant the slot selects, then reads q' instead of q: every cumulative read is coupled.  Not
+ * coupled: the sky (drawn inside k_ramp), the expected image, reference pixels.  Stateless; works beside every other
+ * option but replay mode.  Opt-in: without wayne_exposure_set_ipc every launch and every byte stay as they are.  Added
+ * within WAYNE_ABI_VERSION 7: new symbols and a new struct only. */
+typedef struct wayne_ipc_desc {
+  double k[3][3]; /* the eight neighbour weights; k[1][1] is not looked at (the centre is what the neighbours leave) */
+} wayne_ipc_desc;
+
+/* The nine integer weights of a kernel, w[3 i + j] = W[i][j]: host arithmetic, no device.  WAYNE_E_INVALID for a
+ * neighbour weight that is not finite or is negative, or when the rounded neighbours sum to more than 65536. */
+int wayne_ipc_weights(const wayne_ipc_desc *desc, int32_t w[9]);
+/* After wayne_exposure_upload, before run: every run of the slot couples its accumulators (k_ipc at the end of the front
+ * half, so wayne_exposure_debug_fetch's acc_e between the halves returns what k_ramp will read).  desc == NULL clears;
+ * wayne_exposure_upload clears it too.  The second accumulator array is reserved by this call, for slots that ask only.
+ * WAYNE_E_STATE on a slot that is not uploaded; WAYNE_E_INVALID for a bad slot, in replay mode (the reference has no
+ * coupling) and for what wayne_ipc_weights refuses -- the slot stays usable and runs without the option. */
+int wayne_exposure_set_ipc(wayne_ctx *ctx, int slot, const wayne_ipc_desc *desc);
+/* HIP-event time of k_ipc and k_ipc_clear (one interval spans both) while wayne_profile_enable is on, since
+ * wayne_profile_reset: coupled exposures and total milliseconds.  wayne_profile_select's bit 13 selects it.  Synchronises. */
+int wayne_ipc_profile(wayne_ctx *ctx, uint64_t *launches, double *ms);
 
 /* ---- limb darkening per wavelength bin ---------------------------------- */
 

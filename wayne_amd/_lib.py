@@ -126,6 +126,10 @@ class ImaDesc(C.Structure):
     _fields_ = [("steps", C.c_uint32), ("units", C.c_int), ("read_noise_e", C.c_double), ("saturation_dn", C.c_double)]
 
 
+class IpcDesc(C.Structure):
+    _fields_ = [("k", (C.c_double * 3) * 3)]
+
+
 class OptimalDesc(C.Structure):
     _fields_ = [("half_width", C.c_int)]
 
@@ -219,6 +223,9 @@ SYMBOLS = {
     "wayne_exposure_set_ima": (C.c_int, [_vp, C.c_int, C.POINTER(ImaDesc)]),
     "wayne_exposure_download_ima": (C.c_int, [_vp, C.c_int, _vp]),
     "wayne_ima_profile": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_double)]),
+    "wayne_ipc_weights": (C.c_int, [C.POINTER(IpcDesc), C.POINTER(C.c_int32)]),
+    "wayne_exposure_set_ipc": (C.c_int, [_vp, C.c_int, C.POINTER(IpcDesc)]),
+    "wayne_ipc_profile": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_double)]),
     "wayne_exposure_set_limb_darkening": (C.c_int, [_vp, C.c_int, _dp, C.c_int]),
     "wayne_profile_enable": (C.c_int, [_vp, C.c_int]),
     "wayne_profile_select": (C.c_int, [_vp, C.c_uint]),
@@ -506,6 +513,9 @@ class Context(object):
         ld_table = getattr(desc, "_ld_table", None)
         if ld_table is not None:
             self.set_limb_darkening(slot, ld_table)
+        ipc = getattr(desc, "_ipc", None)
+        if ipc is not None:
+            self.set_ipc(slot, ipc)
 
     # -- limb darkening per wavelength bin -------------------------------------------
     def set_limb_darkening(self, slot, ld):
@@ -932,6 +942,20 @@ class Context(object):
         self.check(self._L.wayne_extract_profile(self._h, C.byref(n), C.byref(ms)))
         return {"launches": int(n.value), "ms": float(ms.value)}
 
+    def set_ipc(self, slot, ipc):
+        """Inter-pixel capacitance of the slot's uploaded exposure: an ipc.InterpixelCapacitance (or a 3 x 3 array of
+        weights) -- None clears.  See wayne_exposure_set_ipc."""
+        if ipc is None:
+            self.check(self._L.wayne_exposure_set_ipc(self._h, int(slot), None))
+            return
+        self.check(self._L.wayne_exposure_set_ipc(self._h, int(slot), C.byref(ipc_desc(ipc))))
+
+    def ipc_profile(self):
+        """(coupled exposures, total milliseconds) of k_ipc and k_ipc_clear since profile_reset.  See wayne_ipc_profile."""
+        n, ms = C.c_uint64(0), C.c_double(0.0)
+        self.check(self._L.wayne_ipc_profile(self._h, C.byref(n), C.byref(ms)))
+        return int(n.value), float(ms.value)
+
     def set_traps(self, slot, traps):
         """Charge traps of the slot's uploaded exposure: a traps.ExposureTraps (the model and this exposure's start tables
         [2, G]) -- None clears.  See wayne_exposure_set_traps."""
@@ -1100,7 +1124,7 @@ class Context(object):
         if names is None:
             mask = 0xFFFFFFFF
         else:
-            order = list(self.profile_get().keys())[:PROF_KERNELS] + ["k_extract", "k_fits_words", "k_expect", "k_ramp_fit", "k_ima"]
+            order = list(self.profile_get().keys())[:PROF_KERNELS] + ["k_extract", "k_fits_words", "k_expect", "k_ramp_fit", "k_ima", "k_ipc"]
             mask = 0
             for n in names:
                 mask |= 1 << order.index(n)
@@ -1119,11 +1143,34 @@ class Context(object):
         return out
 
 
+def ipc_desc(ipc):
+    """ipc.InterpixelCapacitance, or a 3 x 3 array of weights -> IpcDesc."""
+    k = np.asarray(getattr(ipc, "kernel", ipc), dtype=np.float64)
+    if k.shape != (3, 3):
+        raise ValueError("inter-pixel capacitance: the kernel has shape (3, 3), got %s" % (k.shape,))
+    d = IpcDesc()
+    for i in range(3):
+        for j in range(3):
+            d.k[i][j] = float(k[i, j])
+    return d
+
+
+def ipc_weights(kernel):
+    """The nine integer weights [3, 3] int32 of a kernel (wayne_ipc_weights: host arithmetic, no device); ValueError for
+    a kernel the library refuses."""
+    w = (C.c_int32 * 9)()
+    d = ipc_desc(kernel)
+    if load().wayne_ipc_weights(C.byref(d), w) != 0:
+        raise ValueError("inter-pixel capacitance: neighbour weights must be finite, >= 0 and sum to at most 1")
+    return np.array(list(w), dtype=np.int32).reshape(3, 3)
+
+
 def make_desc(seed, exposure_index, flags, sub_scale, wl_um, flux, depth, x_ref, y_ref, dur_ms,
               sample_read, read_dt_s, replay_seed=None, rng_mode=RNG_PHILOX, threads_compat=1,
               sky_ct_s=0.0, cosmic_rate=-1.0, scale_factor=1.0, noise_mean=0.0, noise_std=0.0,
               thrower_margin=0, thrower_splits=0, lc_z=None, lc_hidden=None, lc_rp=None, lc_ld=None, sources=None,
-              traps=None, extraction=None, device_fits=False, expected=None, lc_ld_table=None, ramp_fit=None, ima=None):
+              traps=None, extraction=None, device_fits=False, expected=None, lc_ld_table=None, ramp_fit=None, ima=None,
+              ipc=None):
     """The exposure descriptor.  `sources`: contaminating field stars (sources.Contaminant), carried beside the C struct
     and set by Context.upload (wayne_exposure_set_sources); None or [] = the target alone.  `traps`: charge traps
     (traps.ExposureTraps, or a traps.ChargeTraps whose table is flat at `initial`), set by Context.upload
@@ -1201,6 +1248,8 @@ def make_desc(seed, exposure_index, flags, sub_scale, wl_um, flux, depth, x_ref,
     d._ramp_fit = _rampfit.as_ramp_fit(ramp_fit)
     from . import ima as _ima
     d._ima = _ima.as_ima(ima)
+    from . import ipc as _ipc
+    d._ipc = _ipc.as_ipc(ipc)      # (inter-pixel capacitance, set by Context.upload: wayne_exposure_set_ipc; None = none)
     return d
 
 

@@ -589,6 +589,23 @@ inline const char* ima_desc_error(unsigned steps, int units, double read_noise_e
   return nullptr;
 }
 
+// wayne_ipc_weights (include/wayne_hip.h, "inter-pixel capacitance"): the nine integer weights of a kernel k[3][3],
+// w[3 i + j] = rint(k[i][j] 65536) for the eight neighbours and the centre what they leave of 65536.  False for a neighbour
+// that is not finite or is negative, or when the rounded neighbours sum to more than 65536.  k[1][1] is not looked at.
+inline bool ipc_weights(const double* k, int32_t* w) {
+  long long sum = 0;
+  for (int i = 0; i < 9; ++i) {
+    if (i == 4) continue;
+    if (!std::isfinite(k[i]) || k[i] < 0. || k[i] > 1.) return false;
+    const long long v = (long long)std::rint(k[i] * 65536.);
+    w[i] = (int32_t)v;
+    sum += v;
+  }
+  if (sum > 65536) return false;
+  w[4] = (int32_t)(65536 - sum);
+  return true;
+}
+
 // wayne_exposure_set_optimal's argument check (include/wayne_hip.h: wayne_optimal_desc): null when valid.  The half width
 // is bounded by the halo k_extract_optimal keeps beside a tile.
 inline const char* optimal_desc_error(int half_width) {

@@ -26,6 +26,8 @@
 //                                  dropped, jumps cut out): rate, variance and flag word planes, no reference counterpart
 //   k_ima.h         k_ima          opt-in: the calibrated reads (electrons or e-/s, error, data quality) as the data sections
 //                                  of an `_ima` FITS file (a streaming kernel over 8-pixel units), no reference counterpart
+//   k_ipc.h         k_ipc / k_ipc_clear   opt-in: inter-pixel capacitance -- each read interval's accumulators coupled into
+//                                  their eight neighbours in exact integer arithmetic, in front of k_ramp, no reference counterpart
 //
 // "A<n>" are the row ids of SURVEY.md section 8(a); reference file:line
 // citations are next to each formula.
@@ -42,3 +44,4 @@
 #include "k_expect.h"
 #include "k_rampfit.h"
 #include "k_ima.h"
+#include "k_ipc.h"

@@ -39,8 +39,8 @@ int fail(wayne_ctx* c, int code, const std::string& msg);   // (keeps `msg` as t
 inline size_t align64(size_t n) { return (n + 63) & ~(size_t)63; }
 
 enum ProfKernel { PK_PREP_WL = 0, PK_PREP_SUB, PK_THROW, PK_COSMIC, PK_RAMP, PK_LIGHTCURVE, PK_NARROW, PK_LANE,
-                  PK_EXTRACT, PK_FITS, PK_EXPECT, PK_RAMPFIT, PK_IMA };   // (PK_EXTRACT .. PK_IMA lie beyond wayne_profile's arrays, which the ABI fixes: wayne_extract_profile / wayne_fits_profile / wayne_expected_profile / wayne_rampfit_profile / wayne_ima_profile report them)
-constexpr int kProfKernels = WAYNE_PROF_KERNELS + 5;
+                  PK_EXTRACT, PK_FITS, PK_EXPECT, PK_RAMPFIT, PK_IMA, PK_IPC };   // (PK_EXTRACT .. PK_IPC lie beyond wayne_profile's arrays, which the ABI fixes: wayne_extract_profile / wayne_fits_profile / wayne_expected_profile / wayne_rampfit_profile / wayne_ima_profile / wayne_ipc_profile report them)
+constexpr int kProfKernels = WAYNE_PROF_KERNELS + 6;
 const char* const kProfNames[WAYNE_PROF_KERNELS] = {"k_prep_wl", "k_prep_sub",   "k_throw",  "k_cosmic",   /* (cosmic rays ride in k_prep_sub: slot kept for the ABI) */
                                                     "k_ramp",    "k_lightcurve", "k_narrow", "k_lane"};
 
@@ -304,6 +304,12 @@ struct Slot : SourceState {
   wayne_ima_desc ima{};
   size_t ima_sci_stride = 0, ima_dq_stride = 0, ima_imset_stride = 0;
   DevBuf ima_dev;
+  // inter-pixel capacitance of this exposure (wayne_exposure_set_ipc; cleared by upload): the nine integer weights, the
+  // coupled accumulators `acc_b` [R*S*S] that k_ipc writes and k_ramp then reads and clears, and their segment bits.
+  // ipc_front: the front half that is waiting for its back half coupled; b_dirty: ... and no back half has cleared acc_b yet
+  bool ipc_on = false, ipc_front = false, b_dirty = false;
+  int ipc_w[9] = {0};
+  DevBuf acc_b, seg_b;
   // staging arena of the descriptor's arrays: uploads are enqueued from here, so
   // wayne_exposure_upload returns without waiting for the slot's stream to drain
   StageArena stage;
@@ -1633,6 +1639,7 @@ int wayne_exposure_upload(wayne_ctx* c, int slot, const wayne_exposure_desc* d) 
   s.rampfit_on = s.rampfit_ran = false;   // ... and no ramp fit until wayne_exposure_set_rampfit says so
   s.ima_on = s.ima_ran = false;           // ... and no calibrated reads until wayne_exposure_set_ima says so
   s.ld_on = false;           // ... and one set of limb-darkening coefficients until wayne_exposure_set_limb_darkening says so
+  s.ipc_on = false;          // ... and no inter-pixel capacitance until wayne_exposure_set_ipc says so
   int rc;
   const size_t KW = (size_t)K * W;
   {
@@ -1926,6 +1933,36 @@ static int front_source(wayne_ctx* c, int slot, Slot& s, SourceState& ss, int sr
   return WAYNE_OK;
 }
 
+// The boxes of a coupled exposure: each non-empty one a pixel wider on every side, clamped to the frame.
+static void ipc_dilate(const int (*box)[4], int S, int (*out)[4]) {
+  for (int r = 0; r < 16; ++r) {
+    const int* b = box[r];
+    if (box_empty(b)) { std::memcpy(out[r], b, sizeof(int) * 4); continue; }
+    out[r][0] = std::max(b[0] - 1, 0); out[r][1] = std::min(b[1] + 1, S);
+    out[r][2] = std::max(b[2] - 1, 0); out[r][3] = std::min(b[3] + 1, S);
+  }
+}
+
+// k_ipc and k_ipc_clear of a slot (k_ipc.h), at the very end of its front half
+static int launch_ipc(wayne_ctx* c, Slot& s) {
+  const int S = c->S;
+  IpcArgs a{};
+  a.R = s.R; a.S = S;
+  a.use_box = s.use_box ? 1 : 0;
+  std::memcpy(a.w, s.ipc_w, sizeof a.w);
+  a.a = s.acc.as<long long>(); a.b = s.acc_b.as<long long>();
+  a.seg_a = s.seg.as<uint32_t>(); a.seg_b = s.seg_b.as<uint32_t>();
+  const unsigned blocks = (unsigned)(((size_t)S * S + kIpcThreads - 1) / kIpcThreads);
+  ProfScope ps(c, PK_IPC);
+  ipc_dilate(s.acc_box, S, a.box);
+  hipLaunchKernelGGL(k_ipc, dim3(blocks), dim3(kIpcThreads), 0, c->stream, a);
+  HIP_TRY(c, hipGetLastError());
+  std::memcpy(a.box, s.acc_box, sizeof a.box);
+  hipLaunchKernelGGL(k_ipc_clear, dim3(blocks), dim3(kIpcThreads), 0, c->stream, a);
+  HIP_TRY(c, hipGetLastError());
+  return WAYNE_OK;
+}
+
 // tanh-sinh rule on (0, 1) of the light-curve kernels: t in [-3, 3], u = pi/2 sinh t, x = (1 + tanh u)/2 (wayne_amd/lightcurve.py)
 static void lc_rule(float* x, float* w, float* d) {
   const double h = 6.0 / (kLcNodes - 1);
@@ -1961,6 +1998,11 @@ int wayne_exposure_run_front(wayne_ctx* c, int slot) {
     HIP_TRY(c, hipMemsetAsync(s.acc.p, 0, (size_t)R * SS * sizeof(long long), c->stream));
     HIP_TRY(c, hipMemsetAsync(s.seg.p, 0, s.seg.cap, c->stream));
     s.acc_dirty = false;
+  }
+  if (s.b_dirty) {       // ... and one that was coupled: its coupled accumulators and their bits likewise
+    HIP_TRY(c, hipMemsetAsync(s.acc_b.p, 0, s.acc_b.cap, c->stream));
+    HIP_TRY(c, hipMemsetAsync(s.seg_b.p, 0, s.seg_b.cap, c->stream));
+    s.b_dirty = false;
   }
   if (s.has_lc && s.ld_on) {
     LcLdArgs a{};
@@ -2003,6 +2045,13 @@ int wayne_exposure_run_front(wayne_ctx* c, int slot) {
     if (rc) return rc;
   }
   s.acc_dirty = true;
+  // inter-pixel capacitance: behind every source's thrower and the cosmic rays, so that what lies between the halves is
+  // what k_ramp will read
+  s.ipc_front = s.ipc_on;
+  if (s.ipc_on) {
+    s.b_dirty = true;
+    if (int rc = launch_ipc(c, s)) return rc;
+  }
   s.front_done = true;
   return WAYNE_OK;
 }
@@ -2048,6 +2097,11 @@ int wayne_exposure_run_back(wayne_ctx* c, int slot) {
   a.use_box = s.use_box ? 1 : 0;
   std::memcpy(a.box, s.acc_box, sizeof a.box);
   a.seg = s.seg.as<uint32_t>();
+  if (s.ipc_front) {     // the coupled accumulators, one pixel beyond the thrower's boxes, and their own segment bits
+    a.acc = s.acc_b.as<long long>();
+    ipc_dilate(s.acc_box, S, a.box);
+    a.seg = s.seg_b.as<uint32_t>();
+  }
   const int threads = kRampThreads;
   const unsigned blocks = (unsigned)(((size_t)S * S + threads - 1) / threads);
   if (s.traps_on && s.hist_on && (!c->trap_state_valid || !c->ev_trap_chain))
@@ -2114,8 +2168,9 @@ int wayne_exposure_run_back(wayne_ctx* c, int slot) {
   if (s.expect_mode)
     if (int rc = launch_expected(c, s)) return rc;  // ... and, last of all, the expected image of the thrower stage
   s.acc_dirty = false;
+  s.b_dirty = false;
 #ifdef WAYNE_TIMING_KNOBS
-  if (ramp_reads_cut) s.acc_dirty = true;     // the next front half starts from cleared accumulators
+  if (ramp_reads_cut) { s.acc_dirty = true; s.b_dirty = s.ipc_front; }     // the next front half starts from cleared accumulators
 #endif
   s.front_done = false;
   s.ran = true;
@@ -2274,7 +2329,9 @@ static int fetch_source(wayne_ctx* c, int slot, int src, int32_t* counts, double
   if (acc_e) {
     const size_t n = (size_t)s.R * c->S * c->S;
     std::vector<long long> tmp(n);
-    HIP_TRY(c, hipMemcpyAsync(tmp.data(), s.acc.p, n * sizeof(long long), hipMemcpyDeviceToHost, c->stream));
+    // (a coupled front half: what k_ramp will read)
+    const void* from = (s.front_done && s.ipc_front) ? s.acc_b.p : s.acc.p;
+    HIP_TRY(c, hipMemcpyAsync(tmp.data(), from, n * sizeof(long long), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     for (size_t i = 0; i < n; ++i) acc_e[i] = (double)tmp[i] * kInvQ;
   }
@@ -2297,14 +2354,18 @@ int wayne_exposure_debug_boxes(wayne_ctx* c, int slot, int32_t* boxes, int32_t* 
   if (!s.uploaded) return fail(c, WAYNE_E_STATE, "debug_boxes: slot not uploaded");
   *use_box = s.use_box ? 1 : 0;
   const int S = c->S;
+  // (a coupled slot: the boxes k_ramp gets, a pixel wider on every side)
+  int box[16][4];
+  std::memcpy(box, s.acc_box, sizeof box);
+  if (s.ipc_on) ipc_dilate(s.acc_box, S, box);
   for (int r = 0; r < 16; ++r) {
-    for (int i = 0; i < 4; ++i) boxes[4 * r + i] = s.use_box ? s.acc_box[r][i] : 0;
+    for (int i = 0; i < 4; ++i) boxes[4 * r + i] = s.use_box ? box[r][i] : 0;
     int n = 0;
     if (r < s.R) {
       // the wave test of k_ramp (acc_live) over the frame's 64-pixel segments
       for (int p0 = 0; p0 < S * S; p0 += 64) {
         const int wy0 = p0 / S, wy1 = std::min(p0 + 63, S * S - 1) / S, wx0 = p0 - wy0 * S;
-        const int* b = s.acc_box[r];
+        const int* b = box[r];
         const bool rows = wy0 < b[3] && wy1 >= b[2];
         const bool cols = (wy0 != wy1) || (wx0 < b[1] && wx0 + 64 > b[0]);
         n += (!s.use_box || (rows && cols)) ? 1 : 0;
@@ -3192,6 +3253,53 @@ int wayne_ima_profile(wayne_ctx* c, uint64_t* launches, double* ms) {
   if (rc) return rc;
   if (launches) *launches = c->prof_launches[PK_IMA];
   if (ms) *ms = c->prof_ms[PK_IMA];
+  return WAYNE_OK;
+}
+
+// ---------------------------------------------------------------------------
+// inter-pixel capacitance
+// ---------------------------------------------------------------------------
+int wayne_ipc_weights(const wayne_ipc_desc* d, int32_t w[9]) {
+  if (!d || !w) return WAYNE_E_INVALID;
+  return plan::ipc_weights(&d->k[0][0], w) ? WAYNE_OK : WAYNE_E_INVALID;
+}
+
+int wayne_exposure_set_ipc(wayne_ctx* c, int slot, const wayne_ipc_desc* desc) {
+  if (!c) return WAYNE_E_INVALID;
+  if (slot < 0 || slot >= kSlots) return fail(c, WAYNE_E_INVALID, "set_ipc: slot");
+  Slot& s = c->slots[slot];
+  if (!s.uploaded) return fail(c, WAYNE_E_STATE, "set_ipc: slot not uploaded");
+  s.ipc_on = false;               // from here on a refusal leaves the slot usable, without the coupling
+  if (!desc) return WAYNE_OK;
+  if (s.d.rng_mode == WAYNE_RNG_REPLAY)
+    return fail(c, WAYNE_E_INVALID, "set_ipc: replay mode reproduces the reference, which has no inter-pixel capacitance");
+  int32_t w[9];
+  if (!plan::ipc_weights(&desc->k[0][0], w))
+    return fail(c, WAYNE_E_INVALID, "set_ipc: neighbour weights must be finite, >= 0 and sum to at most 1");
+  (void)hipSetDevice(c->device);
+  use_slot_stream(c, slot);
+  const size_t SS = (size_t)c->S * c->S;
+  const size_t acc_bytes = (size_t)s.R * SS * sizeof(long long), seg_bytes = ((SS + 63) / 64) * sizeof(uint32_t);
+  // (zeroed when allocated, on the slot's stream; from then on k_ramp leaves both clean)
+  if (s.acc_b.cap < acc_bytes) {
+    HIP_TRY(c, s.acc_b.reserve(acc_bytes));
+    HIP_TRY(c, hipMemsetAsync(s.acc_b.p, 0, s.acc_b.cap, c->stream));
+  }
+  if (s.seg_b.cap < seg_bytes) {
+    HIP_TRY(c, s.seg_b.reserve(seg_bytes));
+    HIP_TRY(c, hipMemsetAsync(s.seg_b.p, 0, s.seg_b.cap, c->stream));
+  }
+  for (int i = 0; i < 9; ++i) s.ipc_w[i] = w[i];
+  s.ipc_on = true;
+  return WAYNE_OK;
+}
+
+int wayne_ipc_profile(wayne_ctx* c, uint64_t* launches, double* ms) {
+  if (!c) return WAYNE_E_INVALID;
+  int rc = collect_profile(c);
+  if (rc) return rc;
+  if (launches) *launches = c->prof_launches[PK_IPC];
+  if (ms) *ms = c->prof_ms[PK_IPC];
   return WAYNE_OK;
 }
 

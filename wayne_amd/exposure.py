@@ -170,6 +170,11 @@ class Exposure(object):
         if traps is not None:
             # charge trapping (traps.ChargeTraps): only then, likewise; exposure_file_is_whole compares these cards too
             cards += traps.cards()
+        ipc = e.get("interpixel_capacitance")
+        if ipc is not None:
+            # inter-pixel capacitance (ipc.InterpixelCapacitance): only then, likewise; exposure_file_is_whole compares
+            # these cards too
+            cards += ipc.cards()
         ld_table = getattr(planet, "ld_table", None) if planet is not None else None
         if ld_table is not None:
             # limb darkening per wavelength bin (lightcurve.LimbDarkening): only then, likewise; exposure_file_is_whole

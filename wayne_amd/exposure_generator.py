@@ -31,6 +31,7 @@ from . import traps as _traps
 from . import extraction as _extraction
 from . import rampfit as _rampfit
 from . import ima as _ima
+from . import ipc as _ipc
 from .trend_generators import scan_speed_varations
 
 MS_PER_YEAR = 365.25 * 86400. * 1000.
@@ -126,7 +127,7 @@ class ExposureGenerator(object):
                        add_initial_bias=True, progress_bar=None, threads=2,
                        rng_mode=_lib.RNG_SPLIT, out_dtype=np.float32, reference_quirks=False,
                        record=None, exact_samplers=False, contaminants=None, charge_traps=None, extraction=None,
-                       crrej=None, channels=None, variance=None, optimal=None, expected=None, ramp_fit=None, ima=None):
+                       crrej=None, channels=None, variance=None, optimal=None, expected=None, ramp_fit=None, ima=None, ipc=None):
         """Generate a spatially scanned exposure (exposure_generator.py:178-405).
 
         Extra keywords (not in the reference): `rng_mode` -- RNG_SPLIT (default:
@@ -177,7 +178,11 @@ class ExposureGenerator(object):
         `ima` -- True, "rate", "counts" or an ima.Ima: the device also forms the calibrated reads, the SCI, ERR and DQ
         arrays of an `_ima` file (k_ima; wayne_hip.h, wayne_exposure_set_ima), and the Exposure carries them as `ima`, an
         ima.Payload: the file's bytes with sci(k) / err(k) / dq(k) views.  With `ramp_fit` too, the reads behind a jump
-        carry 8192 -- in a scan with the jump test on that is the trace itself.  staring_frame passes it on too.
+        carry 8192 -- in a scan with the jump test on that is the trace itself.  staring_frame passes it on too;
+        `ipc` -- an ipc.InterpixelCapacitance, or True for its default kernel: the electrons each read interval collected
+        are coupled into the neighbouring pixels on the device, in front of the ramp kernel (k_ipc; wayne_hip.h,
+        wayne_exposure_set_ipc; the law and its limits: wayne_amd/ipc.py).  Not in replay mode.  staring_frame passes it
+        on too.
         """
         eng, desc, start_time = self._host_half(
             x_ref, y_ref, x_jitter, y_jitter, wl, stellar_flux, planet_signal, scan_speed, sample_rate,
@@ -185,7 +190,7 @@ class ExposureGenerator(object):
             add_flat, cosmic_rate, sky_background, scale_factor, add_gain_variations, add_non_linear,
             clip_values_det_limits, add_read_noise, add_stellar_noise, add_initial_bias, progress_bar, threads,
             rng_mode, out_dtype, reference_quirks, exact_samplers, contaminants, charge_traps, extraction, crrej, channels, variance, optimal,
-            expected=expected, ramp_fit=ramp_fit, ima=ima)
+            expected=expected, ramp_fit=ramp_fit, ima=ima, ipc=ipc)
         if record is None and desc._extraction is None and desc._expected is None and desc._ramp_fit is None and desc._ima is None:
             reads = eng.ctx.synthesize(desc)
         else:
@@ -279,7 +284,7 @@ class ExposureGenerator(object):
                    add_initial_bias=True, progress_bar=None, threads=2,
                    rng_mode=_lib.RNG_SPLIT, out_dtype=np.float32, reference_quirks=False,
                    exact_samplers=False, contaminants=None, charge_traps=None, extraction=None,
-                       crrej=None, channels=None, variance=None, optimal=None, device_fits=False, expected=None, ramp_fit=None, ima=None):
+                       crrej=None, channels=None, variance=None, optimal=None, device_fits=False, expected=None, ramp_fit=None, ima=None, ipc=None):
         """scanning_frame's arguments -> (engine, descriptor, start time): the mode's engine (cached after its first
         use) and build_descriptor.  No GPU call once the engine exists."""
         start_time = time.time()
@@ -291,7 +296,7 @@ class ExposureGenerator(object):
             add_flat, cosmic_rate, sky_background, scale_factor, add_gain_variations, add_non_linear,
             clip_values_det_limits, add_read_noise, add_stellar_noise, add_initial_bias, progress_bar, threads,
             rng_mode, out_dtype, reference_quirks, exact_samplers, contaminants, charge_traps, extraction, crrej, channels, variance, optimal,
-            device_fits=device_fits, expected=expected, ramp_fit=ramp_fit, ima=ima)
+            device_fits=device_fits, expected=expected, ramp_fit=ramp_fit, ima=ima, ipc=ipc)
         return eng, desc, start_time
 
     def prepare(self, *args, staring=False, **kw):
@@ -313,7 +318,7 @@ class ExposureGenerator(object):
                          add_initial_bias=True, progress_bar=None, threads=2,
                          rng_mode=_lib.RNG_SPLIT, out_dtype=np.float32, reference_quirks=False,
                          exact_samplers=False, contaminants=None, charge_traps=None, extraction=None,
-                       crrej=None, channels=None, variance=None, optimal=None, device_fits=False, expected=None, ramp_fit=None, ima=None):
+                       crrej=None, channels=None, variance=None, optimal=None, device_fits=False, expected=None, ramp_fit=None, ima=None, ipc=None):
         """The host half of scanning_frame: sample timing, scan positions, SSV,
         jitter / seed draws, spectrum crop (exposure_generator.py:247-334) ->
         one wayne_exposure_desc for the device.  Pure host code (`eng` may be
@@ -323,7 +328,11 @@ class ExposureGenerator(object):
         Context.upload also asks for the noise-free expected image (wayne_exposure_set_expected); refused here, with a
         ValueError, for any other value and in replay mode.  `ramp_fit`: True or a rampfit.RampFit -- Context.upload also
         asks for the ramp fit (wayne_exposure_set_rampfit).  `ima`: True, "rate", "counts" or an ima.Ima -- Context.upload
-        also asks for the calibrated reads (wayne_exposure_set_ima)."""
+        also asks for the calibrated reads (wayne_exposure_set_ima).  `ipc`: an ipc.InterpixelCapacitance or True --
+        Context.upload also asks for the inter-pixel capacitance (wayne_exposure_set_ipc); refused here in replay mode."""
+        ipc = _ipc.as_ipc(ipc)
+        if ipc is not None and rng_mode == _lib.RNG_REPLAY:
+            raise ValueError("ipc: replay mode reproduces the reference, which has no inter-pixel capacitance")
         if _lib.expected_mode(expected) and rng_mode == _lib.RNG_REPLAY:
             raise ValueError("expected: replay mode reproduces the reference, which has no expected image")
         out_dtype = np.dtype(out_dtype)
@@ -370,6 +379,10 @@ class ExposureGenerator(object):
             self.exp_info["charge_traps"] = charge_traps.traps     # (the FITS header records the model: exposure.py)
         else:
             self.exp_info.pop("charge_traps", None)
+        if ipc is not None:
+            self.exp_info["interpixel_capacitance"] = ipc          # (the FITS header records the weights: exposure.py)
+        else:
+            self.exp_info.pop("interpixel_capacitance", None)
         self.exposure = exposure.Exposure(self.detector, self.grism, self.planet, self.exp_info)
 
         if add_dark and eng is not None and not eng.has_dark:
@@ -454,7 +467,7 @@ class ExposureGenerator(object):
             scale_factor=1.0 if scale_factor is None else float(scale_factor),
             noise_mean=float(noise_mean) if noise_mean else 0.0,
             noise_std=float(noise_std) if noise_std else 0.0, sources=contaminants, traps=charge_traps,
-            extraction=self.extraction_plan, device_fits=device_fits, expected=expected, ramp_fit=ramp_fit, ima=ima, **lc)
+            extraction=self.extraction_plan, device_fits=device_fits, expected=expected, ramp_fit=ramp_fit, ima=ima, ipc=ipc, **lc)
 
     def direct_image(self, x_ref, y_ref):
         """The unscaled 2-D gaussian direct image used to calibrate x_ref / y_ref

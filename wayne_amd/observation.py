@@ -92,6 +92,7 @@ class Observation(object):
         self.spectra_result = None
         self.contaminants = []       # field stars on every exposure (setup_contaminants)
         self.charge_traps = None     # per-pixel charge trapping (setup_charge_traps)
+        self.ipc = None              # inter-pixel capacitance (setup_ipc)
         self._trap_tables = None
         self.trap_history = "planned"     # "carried": the device carries each pixel's trap state through the visit
         self.trap_initial_state = None    # [S, S, 2] float32 the carried state starts from (None: the model's `initial`)
@@ -111,6 +112,15 @@ class Observation(object):
         if len(contaminants) > MAX_CONTAMINANTS:
             raise ValueError("at most %d contaminants" % MAX_CONTAMINANTS)
         self.contaminants = contaminants
+
+    def setup_ipc(self, ipc):
+        """Inter-pixel capacitance (ipc.InterpixelCapacitance; ipc.InterpixelCapacitance.from_config builds it from the
+        YAML's `interpixel_capacitance:` section; True: the default kernel); None: none.  Every exposure's collected
+        charge is then coupled into the neighbouring pixels on the device, in front of the ramp kernel, and the files
+        carry IPC = T, IPCUNIT and the nine IPCWij cards.  The direct image is not coupled.  Stateless: it goes with
+        sharding, --resume and every other option."""
+        from .ipc import as_ipc
+        self.ipc = as_ipc(ipc)
 
     def setup_charge_traps(self, traps, history=None, initial_state=None):
         """Per-pixel charge trapping, the ramp effect (traps.ChargeTraps; traps.ChargeTraps.from_config builds it from the
@@ -331,7 +341,8 @@ class Observation(object):
                     abs(float(p0["EXPSTART"]) - (float(self.exp_start_times[number - 1]) - 2400000.5)) < 1e-7)
         except (KeyError, TypeError, ValueError):
             return False
-        if not (same and self._contaminant_cards_match(p0) and self._trap_cards_match(p0) and self._ld_cards_match(p0)):
+        if not (same and self._contaminant_cards_match(p0) and self._trap_cards_match(p0) and self._ld_cards_match(p0) and
+                self._ipc_cards_match(p0)):
             return False
         # the visit's sample type too: uint16 reads make BITPIX 16 images, float reads float64 ones -- a file of the
         # other kind is regenerated, whichever way the visit was switched
@@ -364,6 +375,19 @@ class Observation(object):
                 return False
             return (str(p0["LDHASH"]).strip() == want["LDHASH"] and str(p0["LDLAW"]).strip() == want["LDLAW"] and
                     int(p0["LDNODES"]) == want["LDNODES"])
+        except (KeyError, TypeError, ValueError):
+            return False
+
+    def _ipc_cards_match(self, p0):
+        """The file's IPC / IPCUNIT / IPCWij cards are this visit's inter-pixel capacitance (absent: none), so that
+        --resume after the kernel was added, removed or changed regenerates the files."""
+        want = {k: v for (k, v, _) in self.ipc.cards()} if self.ipc is not None else {}
+        try:
+            if "IPC" not in p0:
+                return not want
+            if not want or p0["IPC"] is not True:
+                return False
+            return all(int(p0[k]) == int(v) for k, v in want.items() if k != "IPC")
         except (KeyError, TypeError, ValueError):
             return False
 
@@ -670,6 +694,8 @@ class Observation(object):
             common["contaminants"] = self.contaminants
         if self.charge_traps is not None:
             common["charge_traps"] = self.exposure_traps(index_number)
+        if self.ipc is not None:
+            common["ipc"] = self.ipc
         if self.spatial_scan:
             args = (x_ref, y_ref, self.x_jitter, self.y_jitter, self.wl, self.stellar_flux, planet_depths,
                     self.scan_speed, sample_rate, sample_mid_points, sample_durations, read_index)

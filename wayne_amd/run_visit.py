@@ -31,6 +31,9 @@ examples/hd209458b_12181_simulation_parameters.yml): sections `general`
     (wayne_amd/traps.py): `slow` / `fast` mappings of n_traps, efficiency, lifetime_s, initial, orbit_fill; `{}` = the
     defaults, an omitted key its default; `history: carried` carries each pixel's trap state from exposure to exposure
     on the device (default `planned`) -- one rank only, no --resume;
+  * an optional top-level `interpixel_capacitance:` section couples the charge each read interval collected into the
+    neighbouring pixels (wayne_amd/ipc.py): `alpha: a` or `kernel: [[..],[..],[..]]`, `{}` = the default kernel; the files
+    then carry IPC, IPCUNIT and IPCW00 .. IPCW22; goes with --gpus, --ranks-per-gpu, --resume and every other option;
   * `--spectra OUT.npz`: the device extracts every exposure's column spectra behind its reads (wayne_amd/extraction.py)
     and they are written to OUT.npz beside the _raw files: spectra [n, NSAMP, S], sky [n, NSAMP], exposure_index, row_lo,
     row_hi, bg_cols, x_ref, y_ref, read_times, exp_start.  `--spectra-only OUT.npz`: the same file, no _raw files, and
@@ -84,7 +87,7 @@ import numpy as np
 import yaml
 
 from . import calibration as _cal
-from . import detector, grism, launch, observation, sources, tools, traps
+from . import detector, grism, ipc, launch, observation, sources, tools, traps
 from .trend_generators import scan_speed_varations
 
 
@@ -230,6 +233,13 @@ def build_observation(cfg, base_dir=".", calibration=None, device=0):
         try:
             obs.setup_charge_traps(traps.ChargeTraps.from_config(cfg["charge_traps"]))
         except traps.ChargeTrapConfigError as e:
+            raise WFC3SimConfigError(str(e))
+    # optional `interpixel_capacitance:` section (no reference counterpart): the collected charge coupled into the
+    # neighbouring pixels; absent = none, `{}` = the default kernel
+    if isinstance(cfg, dict) and "interpixel_capacitance" in cfg:
+        try:
+            obs.setup_ipc(ipc.InterpixelCapacitance.from_config(cfg["interpixel_capacitance"]))
+        except ipc.IpcConfigError as e:
             raise WFC3SimConfigError(str(e))
     return obs
 

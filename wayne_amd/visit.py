@@ -17,6 +17,7 @@ from . import extraction as _extraction
 from .expected import ExpectedDelivery
 from . import rampfit as _rampfit
 from . import ima as _ima
+from . import ipc as _ipc
 from .exposure import FitsWriterPool
 from .exposure_generator import ExposureGenerator
 from .fits_delivery import FitsDelivery, slots_for
@@ -48,6 +49,9 @@ def descriptor_digest(desc):
     ld_table = getattr(desc, "_ld_table", None)    # limb darkening per wavelength bin (none: likewise)
     if ld_table is not None:
         h.update(b"ld_table" + np.ascontiguousarray(ld_table).tobytes())
+    ipc = getattr(desc, "_ipc", None)              # inter-pixel capacitance (none: likewise)
+    if ipc is not None:
+        h.update(ipc.digest_bytes())
     return h.hexdigest()
 
 
@@ -59,11 +63,14 @@ class VisitRunner(object):
     DEPTH = 4
 
     def __init__(self, visit, device=0, out_dir=None, out_dtype=np.float32, frame_overrides=None, device_lc=False,
-                 device_fits=False):
+                 device_fits=False, ipc=None):
         """`device_lc`: hand the device the K + W + 4 numbers of the light-curve model (visit.device_depths)
         instead of a K x W transit-depth matrix computed on the host.  `device_fits`: the device forms the files' data
-        sections and `run` writes each file straight from the slot's pinned mirror (fits_delivery): the same files."""
+        sections and `run` writes each file straight from the slot's pinned mirror (fits_delivery): the same files.
+        `ipc`: an ipc.InterpixelCapacitance, or True for its default kernel -- every exposure's collected charge is
+        coupled into the neighbouring pixels on the device (wayne_amd/ipc.py); None: none."""
         self.visit, self.device, self.out_dir = visit, device, out_dir
+        self.ipc = _ipc.as_ipc(ipc)
         self.out_dtype = out_dtype
         self.frame_overrides = frame_overrides or {}
         self.device_lc = device_lc
@@ -89,6 +96,8 @@ class VisitRunner(object):
         over = dict(self.frame_overrides)
         if self.device_lc:
             over["planet_signal"] = self.visit.device_depths(i)
+        if self.ipc is not None:
+            over["ipc"] = self.ipc
         return self.visit.frame_kwargs(i, **over)
 
     def descriptor(self, i, eng=None):
