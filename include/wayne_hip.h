@@ -994,6 +994,59 @@ int wayne_ipc_profile(wayne_ctx *ctx, uint64_t *launches, double *ms);
  * table.  wayne_exposure_debug_depth serves the matrix as it is. */
 int wayne_exposure_set_limb_darkening(wayne_ctx *ctx, int slot, const double *ld, int n_wl);
 
+/* ---- star spots ---------------------------------------------------------- */
+
+/* The star of a device light curve is a clean limb-darkened disc.  With spots, k_lightcurve_spots is enqueued directly
+ * behind the slot's light-curve launch (k_lightcurve or k_lightcurve_ld) on the same stream and rewrites the depth
+ * matrix in place, so k_prep_sub and wayne_exposure_debug_depth see the spotted matrix.  All quantities are float64,
+ * lengths in stellar radii in the sky frame of the planet's track (px, py).  Spot i is a circle IN PROJECTION: centre
+ * (cx, cy), radius, contrast c[i*W + w] >= 0 (spot over photosphere intensity in bin w; > 1: a facula); the
+ * limb-darkening law inside a spot is the photosphere's.  With I(mu) = c0 + sum_n a_n mu^(n/2), a'_0 = c0 = 1 - sum a_n,
+ * a'_n = a_n (the table's coefficients of bin w, or lc_ld) and F0_w = pi (1 - sum a_n n/(n+4)):
+ *
+ *   Q_n(P, C, p, r) = int over (disc of radius p at P) n (disc of radius r at C) of mu^(n/2) dA     wayne_spot_lens_basis
+ *   S_{i,n} = Q_n(C_i, C_i, r_i, r_i)                                          the whole spot
+ *   D_w     = sum_i (1 - c_{i,w}) sum_n a'_n(w) S_{i,n}
+ *   X_{k,w} = sum_i (1 - c_{i,w}) sum_n a'_n(w) Q_n(P_k, C_i, p_w, r_i)        spots in list order, n ascending
+ *   depth'[k][w] = (depth[k][w] F0_w - X_{k,w}) / (F0_w - D_w)                 rows with z_k < 10 and hidden_k = 0,
+ *                                                                              columns with a radius ratio
+ *   depth'[k][w] = depth[k][w]                                                 everywhere else
+ *
+ * An out-of-transit row stays exactly 0; without an overlap the depth is multiplied by F0 / (F0 - D), the bias of
+ * unocculted spots; during a crossing it drops by the light the planet no longer blocks.  Q_n is a FIXED rule: with
+ * d = |C - P|, u = (C - P) / d (or (1, 0)), v = (-u_y, u_x): zero for d >= p + r (decided before any node is touched);
+ * for d <= |p - r| the smaller circle in two panels, phi in [0, pi/2] and [pi/2, pi]; otherwise the part bounded by
+ * the spot's circle and the part bounded by the planet's, either side of the chord t* = (d^2 + p^2 - r^2) / (2 d).  A
+ * panel (cc, rad, sg, phi range) takes the 10 Gauss-Legendre nodes g, omega of [-1, 1] in both directions:
+ * phi_a = mid + half g_a, t = cc - sg rad cos phi_a, h = rad sin phi_a, s_b = h g_b, (x, y) = P + t u + s_b v,
+ * Q_n += omega_a half rad sin phi_a h omega_b mu(x, y)^(n/2); panels in that order, a outer, b inner, ascending.  It is
+ * within 1e-6 of the lens area of the converged integral for spots that stay inside radius 0.98.  float64 throughout,
+ * no atomics, no LDS, no scratch.  Not covered: rotation or evolution within a visit, foreshortening, spots at or
+ * across the limb, overlapping spots, spots in the eclipse term, a changed stellar spectrum, spotted contaminants,
+ * interpolation in p.  Opt-in: without spots every launch and every byte stay as they are.  Added within
+ * WAYNE_ABI_VERSION 7: new symbols and a new struct only. */
+#define WAYNE_MAX_SPOTS 8
+typedef struct wayne_spots_desc {
+  int32_t n;                        /* spots, at most WAYNE_MAX_SPOTS; 0 clears */
+  double cx[WAYNE_MAX_SPOTS], cy[WAYNE_MAX_SPOTS], radius[WAYNE_MAX_SPOTS];
+  const double *contrast;           /* [n * n_wl], spot-major */
+  const double *px, *py;            /* [n_sub]: the planet's centre at every sub-sample */
+} wayne_spots_desc;
+/* After wayne_exposure_upload (and after wayne_exposure_set_limb_darkening, which clears the spots: they are checked
+ * against the coefficients in force), before run.  desc == NULL or n == 0 clears; wayne_exposure_upload clears.  The
+ * arrays are copied: free on return.  WAYNE_E_STATE on a slot that is not uploaded; WAYNE_E_INVALID -- the slot stays
+ * usable and runs unspotted -- for more than 8 spots, a radius that is not finite or <= 0, |C_i| + r_i > 0.98, two spots
+ * with |C_i - C_j| < r_i + r_j, a contrast that is not finite or < 0, F0_w - D_w <= 0 in some bin, a slot without a
+ * device light curve, n_wl or n_sub other than the slot's, a track value that is not finite on a transit row. */
+int wayne_exposure_set_spots(wayne_ctx *ctx, int slot, const wayne_spots_desc *desc, int n_wl, int n_sub);
+/* Q_0 .. Q_4 of the rule above: pure host arithmetic, the inline function the kernel compiles. */
+void wayne_spot_lens_basis(double px, double py, double cx, double cy, double p, double r, double out[5]);
+/* The rule's Gauss-Legendre nodes and weights (numpy.polynomial.legendre.leggauss(10), to the bit). */
+void wayne_spot_rule(double nodes[10], double weights[10]);
+/* HIP-event time of k_lightcurve_spots while wayne_profile_enable is on, since wayne_profile_reset: launches and total
+ * milliseconds.  wayne_profile_select's bit 14 selects it.  Synchronises. */
+int wayne_spots_profile(wayne_ctx *ctx, uint64_t *launches, double *ms);
+
 /* ---- measurement ------------------------------------------------------- */
 
 #define WAYNE_PROF_KERNELS 8

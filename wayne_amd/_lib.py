@@ -126,6 +126,11 @@ class ImaDesc(C.Structure):
     _fields_ = [("steps", C.c_uint32), ("units", C.c_int), ("read_noise_e", C.c_double), ("saturation_dn", C.c_double)]
 
 
+class SpotsDesc(C.Structure):
+    _fields_ = [("n", C.c_int32), ("cx", C.c_double * 8), ("cy", C.c_double * 8), ("radius", C.c_double * 8),
+                ("contrast", C.POINTER(C.c_double)), ("px", C.POINTER(C.c_double)), ("py", C.POINTER(C.c_double))]
+
+
 class IpcDesc(C.Structure):
     _fields_ = [("k", (C.c_double * 3) * 3)]
 
@@ -227,6 +232,10 @@ SYMBOLS = {
     "wayne_exposure_set_ipc": (C.c_int, [_vp, C.c_int, C.POINTER(IpcDesc)]),
     "wayne_ipc_profile": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_double)]),
     "wayne_exposure_set_limb_darkening": (C.c_int, [_vp, C.c_int, _dp, C.c_int]),
+    "wayne_exposure_set_spots": (C.c_int, [_vp, C.c_int, C.POINTER(SpotsDesc), C.c_int, C.c_int]),
+    "wayne_spot_lens_basis": (None, [C.c_double] * 6 + [_dp]),
+    "wayne_spot_rule": (None, [_dp, _dp]),
+    "wayne_spots_profile": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_double)]),
     "wayne_profile_enable": (C.c_int, [_vp, C.c_int]),
     "wayne_profile_select": (C.c_int, [_vp, C.c_uint]),
     "wayne_profile_reset": (C.c_int, [_vp]),
@@ -516,6 +525,36 @@ class Context(object):
         ipc = getattr(desc, "_ipc", None)
         if ipc is not None:
             self.set_ipc(slot, ipc)
+        lc_spots = getattr(desc, "_spots", None)       # (behind the table: the spots are checked against its coefficients)
+        if lc_spots is not None:
+            self.set_spots(slot, lc_spots)
+
+    # -- star spots ------------------------------------------------------------------
+    def set_spots(self, slot, geometry):
+        """Star spots in the slot's device light curve (spots.SpotGeometry: the planet's track [K], centres, radii and
+        the contrast [n, W]); k_lightcurve_spots then rewrites the depth matrix behind the light-curve launch.  None
+        clears; after upload, which clears it too, and after set_limb_darkening.  See wayne_exposure_set_spots."""
+        if geometry is None:
+            self.check(self._L.wayne_exposure_set_spots(self._h, int(slot), None, 0, 0))
+            return
+        n = int(geometry.n)
+        if n > 8:
+            raise ValueError("set_spots: at most 8 spots, got %d" % n)
+        contrast, px, py = f64(geometry.contrast), f64(geometry.X), f64(geometry.Y)
+        if contrast.ndim != 2 or contrast.shape[0] != n or px.shape != py.shape or px.ndim != 1:
+            raise ValueError("set_spots: contrast [n, W] and a track X, Y [K] are expected")
+        d = SpotsDesc()
+        d.n = n
+        for i in range(n):
+            d.cx[i], d.cy[i], d.radius[i] = float(geometry.cx[i]), float(geometry.cy[i]), float(geometry.radius[i])
+        d.contrast, d.px, d.py = ptr(contrast, C.c_double), ptr(px, C.c_double), ptr(py, C.c_double)
+        self.check(self._L.wayne_exposure_set_spots(self._h, int(slot), C.byref(d), contrast.shape[1], px.size))
+
+    def spots_profile(self):
+        """(launches, total milliseconds) of k_lightcurve_spots since profile_reset.  See wayne_spots_profile."""
+        n, ms = C.c_uint64(0), C.c_double(0.0)
+        self.check(self._L.wayne_spots_profile(self._h, C.byref(n), C.byref(ms)))
+        return int(n.value), float(ms.value)
 
     # -- limb darkening per wavelength bin -------------------------------------------
     def set_limb_darkening(self, slot, ld):
@@ -1124,7 +1163,8 @@ class Context(object):
         if names is None:
             mask = 0xFFFFFFFF
         else:
-            order = list(self.profile_get().keys())[:PROF_KERNELS] + ["k_extract", "k_fits_words", "k_expect", "k_ramp_fit", "k_ima", "k_ipc"]
+            order = list(self.profile_get().keys())[:PROF_KERNELS] + ["k_extract", "k_fits_words", "k_expect", "k_ramp_fit", "k_ima", "k_ipc",
+                                                                     "k_lightcurve_spots"]
             mask = 0
             for n in names:
                 mask |= 1 << order.index(n)
@@ -1170,7 +1210,7 @@ def make_desc(seed, exposure_index, flags, sub_scale, wl_um, flux, depth, x_ref,
               sky_ct_s=0.0, cosmic_rate=-1.0, scale_factor=1.0, noise_mean=0.0, noise_std=0.0,
               thrower_margin=0, thrower_splits=0, lc_z=None, lc_hidden=None, lc_rp=None, lc_ld=None, sources=None,
               traps=None, extraction=None, device_fits=False, expected=None, lc_ld_table=None, ramp_fit=None, ima=None,
-              ipc=None):
+              ipc=None, lc_spots=None):
     """The exposure descriptor.  `sources`: contaminating field stars (sources.Contaminant), carried beside the C struct
     and set by Context.upload (wayne_exposure_set_sources); None or [] = the target alone.  `traps`: charge traps
     (traps.ExposureTraps, or a traps.ChargeTraps whose table is flat at `initial`), set by Context.upload
@@ -1179,7 +1219,9 @@ def make_desc(seed, exposure_index, flags, sub_scale, wl_um, flux, depth, x_ref,
     set by Context.upload (wayne_exposure_set_fits).  `expected`: "counts" or "mean" -- the noise-free expected image is
     rendered with every run, set by Context.upload (wayne_exposure_set_expected); None = none.  `lc_ld_table`: Claret
     coefficients per wavelength bin [W, 4] of the device light curve, carried beside the C struct and set by
-    Context.upload (wayne_exposure_set_limb_darkening); None = lc_ld for every bin.  `ramp_fit`: a rampfit.RampFit, or
+    Context.upload (wayne_exposure_set_limb_darkening); None = lc_ld for every bin.  `lc_spots`: star spots of the device
+    light curve (spots.SpotGeometry on the descriptor's W bins), set by Context.upload (wayne_exposure_set_spots); None =
+    a clean star.  `ramp_fit`: a rampfit.RampFit, or
     True for its defaults -- every run also fits the reads' ramps (rate, variance and flag word per pixel), set by
     Context.upload (wayne_exposure_set_rampfit); None = none.  `ima`: an ima.Ima, True, "rate" or "counts" -- every run
     also forms the calibrated reads (SCI, ERR and DQ of an `_ima` file), set by Context.upload (wayne_exposure_set_ima);
@@ -1235,6 +1277,12 @@ def make_desc(seed, exposure_index, flags, sub_scale, wl_um, flux, depth, x_ref,
         if lc_ld_table.shape != (W, 4):
             raise ValueError("lc_ld_table must have shape (W, 4)")
     d._ld_table = lc_ld_table
+    if lc_spots is not None:
+        if lc_z is None:
+            raise ValueError("lc_spots needs the device light curve (lc_z)")
+        if lc_spots.contrast.shape[1] != W or lc_spots.X.size != len(lc_z):
+            raise ValueError("lc_spots must have contrast [n, W] and a track of K points")
+    d._spots = lc_spots
     d._keep = keep
     d._sources = tuple(sources) if sources else ()
     if traps is not None:
@@ -1315,3 +1363,18 @@ def default_context(device=0):
             ctx.call_lock = threading.Lock()   # for callers that share it between threads (pyparallel.apply_psf)
             _default_ctx[device] = ctx
         return _default_ctx[device]
+
+
+def spot_lens_basis(P, C_, p, r):
+    """Q_0 .. Q_4 of the spots' lens rule from the library's own host arithmetic (wayne_spot_lens_basis): no GPU."""
+    out = np.zeros(5)
+    load().wayne_spot_lens_basis(float(P[0]), float(P[1]), float(C_[0]), float(C_[1]), float(p), float(r),
+                                 ptr(out, C.c_double))
+    return out
+
+
+def spot_rule():
+    """The library's Gauss-Legendre nodes and weights of that rule (wayne_spot_rule)."""
+    g, w = np.zeros(10), np.zeros(10)
+    load().wayne_spot_rule(ptr(g, C.c_double), ptr(w, C.c_double))
+    return g, w

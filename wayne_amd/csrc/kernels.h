@@ -2,6 +2,7 @@
 //
 //   k_lightcurve.h  k_lightcurve   transit depths depth[K][W] from z[K], rp[W], limb darkening
 //   k_lightcurve_ld.h  k_lightcurve_ld   opt-in: the same matrix with four Claret coefficients per wavelength bin
+//   k_lightcurve_spots.h  k_lightcurve_spots   opt-in: star spots -- rewrites that matrix in place (occulted and unocculted)
 //   k_prep.h        k_prep_wl      per-wavelength arrays: PSF polynomials, sensitivity LUT, bin widths   (A8, A9) -- when a
 //                                  source's grid is uploaded, not per run (k_prep_wl_run: the per-run form, knob prep_wl_per_run)
 //                   k_prep_sub     per sub-sample: trace, bin positions, expected counts, Poisson/round,
@@ -35,6 +36,7 @@
 #include "common.h"
 #include "k_lightcurve.h"
 #include "k_lightcurve_ld.h"
+#include "k_lightcurve_spots.h"
 #include "k_prep.h"
 #include "k_throw.h"
 #include "k_narrow.h"

@@ -39,8 +39,8 @@ int fail(wayne_ctx* c, int code, const std::string& msg);   // (keeps `msg` as t
 inline size_t align64(size_t n) { return (n + 63) & ~(size_t)63; }
 
 enum ProfKernel { PK_PREP_WL = 0, PK_PREP_SUB, PK_THROW, PK_COSMIC, PK_RAMP, PK_LIGHTCURVE, PK_NARROW, PK_LANE,
-                  PK_EXTRACT, PK_FITS, PK_EXPECT, PK_RAMPFIT, PK_IMA, PK_IPC };   // (PK_EXTRACT .. PK_IPC lie beyond wayne_profile's arrays, which the ABI fixes: wayne_extract_profile / wayne_fits_profile / wayne_expected_profile / wayne_rampfit_profile / wayne_ima_profile / wayne_ipc_profile report them)
-constexpr int kProfKernels = WAYNE_PROF_KERNELS + 6;
+                  PK_EXTRACT, PK_FITS, PK_EXPECT, PK_RAMPFIT, PK_IMA, PK_IPC, PK_SPOTS };   // (PK_EXTRACT .. PK_SPOTS lie beyond wayne_profile's arrays, which the ABI fixes: wayne_extract_profile / wayne_fits_profile / wayne_expected_profile / wayne_rampfit_profile / wayne_ima_profile / wayne_ipc_profile / wayne_spots_profile report them)
+constexpr int kProfKernels = WAYNE_PROF_KERNELS + 7;
 const char* const kProfNames[WAYNE_PROF_KERNELS] = {"k_prep_wl", "k_prep_sub",   "k_throw",  "k_cosmic",   /* (cosmic rays ride in k_prep_sub: slot kept for the ABI) */
                                                     "k_ramp",    "k_lightcurve", "k_narrow", "k_lane"};
 
@@ -213,6 +213,12 @@ struct Slot : SourceState {
   bool ld_on = false;
   StageArena ld_stage;
   DevBuf ld_tab;
+  // star spots (wayne_exposure_set_spots; cleared by upload and by wayne_exposure_set_limb_darkening): k_lightcurve_spots
+  // rewrites the depth matrix behind the light-curve launch.  One arena: contrast [n][W], the track px, py [K], lc_ld [4]
+  bool spots_on = false;
+  StageArena spot_stage;
+  DevBuf spot_contrast, spot_px, spot_py, spot_ld;
+  SpotArgs spot_args{};      // the geometry, the whole spots' integrals and the rule, filled when the spots are set
   // charge traps of this exposure (wayne_exposure_set_traps; cleared by upload): the parameters, and the start tables
   // in one arena -- [2][G] float64 (generic loop), then [2][G] float32 (production chain)
   bool traps_on = false;
@@ -1640,6 +1646,7 @@ int wayne_exposure_upload(wayne_ctx* c, int slot, const wayne_exposure_desc* d) 
   s.ima_on = s.ima_ran = false;           // ... and no calibrated reads until wayne_exposure_set_ima says so
   s.ld_on = false;           // ... and one set of limb-darkening coefficients until wayne_exposure_set_limb_darkening says so
   s.ipc_on = false;          // ... and no inter-pixel capacitance until wayne_exposure_set_ipc says so
+  s.spots_on = false;        // ... and a clean star until wayne_exposure_set_spots says so
   int rc;
   const size_t KW = (size_t)K * W;
   {
@@ -2031,6 +2038,22 @@ int wayne_exposure_run_front(wayne_ctx* c, int slot) {
     a.depth = s.depth.as<double>();
     ProfScope ps(c, PK_LIGHTCURVE);
     hipLaunchKernelGGL(k_lightcurve, dim3(K), dim3(256), 0, c->stream, a);
+    HIP_TRY(c, hipGetLastError());
+  }
+  if (s.has_lc && s.spots_on) {
+    // star spots: the matrix just written, rewritten in place (k_prep_sub and wayne_exposure_debug_depth see the spotted one)
+    SpotArgs a = s.spot_args;
+    a.K = K; a.W = W;
+    a.z = s.lc_z.as<double>();
+    a.hidden = s.has_lc_hidden ? s.lc_hidden.as<double>() : nullptr;
+    a.rp = s.lc_rp.as<double>();
+    a.px = s.spot_px.as<double>(); a.py = s.spot_py.as<double>();
+    a.contrast = s.spot_contrast.as<double>();
+    if (s.ld_on) { a.ld = s.ld_tab.as<double>(); a.ld_plane = (size_t)W; a.ld_step = 1; }
+    else         { a.ld = s.spot_ld.as<double>(); a.ld_plane = 1; a.ld_step = 0; }
+    a.depth = s.depth.as<double>();
+    ProfScope ps(c, PK_SPOTS);
+    hipLaunchKernelGGL(k_lightcurve_spots, dim3(K, (W + 255) / 256), dim3(256), 0, c->stream, a);
     HIP_TRY(c, hipGetLastError());
   }
 
@@ -2486,6 +2509,7 @@ int wayne_exposure_set_limb_darkening(wayne_ctx* c, int slot, const double* ld, 
   Slot& s = c->slots[slot];
   if (!s.uploaded) return fail(c, WAYNE_E_STATE, "set_limb_darkening: slot not uploaded");
   s.ld_on = false;                // from here on a refusal leaves the slot usable, without a table
+  s.spots_on = false;             // (spots were checked against the coefficients they were set with: set them again)
   s.front_done = false;           // (the depth matrix of the last front half is not this setting's)
   if (!ld || n_wl == 0) return WAYNE_OK;
   if (!s.has_lc) return fail(c, WAYNE_E_INVALID, "set_limb_darkening: the slot has no device light curve (lc_z was NULL)");
@@ -2511,6 +2535,101 @@ int wayne_exposure_set_limb_darkening(wayne_ctx* c, int slot, const double* ld, 
     for (int w = 0; w < W; ++w) h[(size_t)i * W + w] = ld[(size_t)w * 4 + i];
   if ((rc = s.ld_stage.commit(c, c->stream))) return rc;
   s.ld_on = true;
+  return WAYNE_OK;
+}
+
+// ---------------------------------------------------------------------------
+// star spots
+// ---------------------------------------------------------------------------
+
+// numpy.polynomial.legendre.leggauss(10), to the last bit (wayne_amd/spots.py hands the numpy law the same doubles)
+static const SpotRule kSpotRule = {
+    {-0.9739065285171717, -0.8650633666889845, -0.6794095682990244, -0.4333953941292472, -0.14887433898163122,
+     0.14887433898163122, 0.4333953941292472, 0.6794095682990244, 0.8650633666889845, 0.9739065285171717},
+    {0.06667134430868807, 0.14945134915058036, 0.219086362515982, 0.2692667193099965, 0.295524224714753,
+     0.295524224714753, 0.2692667193099965, 0.219086362515982, 0.14945134915058036, 0.06667134430868807}};
+
+void wayne_spot_lens_basis(double px, double py, double cx, double cy, double p, double r, double out[5]) {
+  lens_basis(kSpotRule, px, py, cx, cy, p, r, out[0], out[1], out[2], out[3], out[4]);
+}
+
+void wayne_spot_rule(double nodes[10], double weights[10]) {
+  for (int i = 0; i < kSpotNodes; ++i) { nodes[i] = kSpotRule.g[i]; weights[i] = kSpotRule.w[i]; }
+}
+
+int wayne_exposure_set_spots(wayne_ctx* c, int slot, const wayne_spots_desc* sp, int n_wl, int n_sub) {
+  if (!c) return WAYNE_E_INVALID;
+  if (slot < 0 || slot >= kSlots) return fail(c, WAYNE_E_INVALID, "set_spots: slot");
+  Slot& s = c->slots[slot];
+  if (!s.uploaded) return fail(c, WAYNE_E_STATE, "set_spots: slot not uploaded");
+  s.spots_on = false;             // from here on a refusal leaves the slot usable, with a clean star
+  s.front_done = false;           // (the depth matrix of the last front half is not this setting's)
+  if (!sp || sp->n == 0) return WAYNE_OK;
+  if (!s.has_lc) return fail(c, WAYNE_E_INVALID, "set_spots: the slot has no device light curve (lc_z was NULL)");
+  const int W = s.W, K = s.K, n = sp->n;
+  if (n < 0 || n > kSpotMax) return fail(c, WAYNE_E_INVALID, "set_spots: at most 8 spots");
+  if (n_wl != W) return fail(c, WAYNE_E_INVALID, "set_spots: n_wl differs from the exposure's");
+  if (n_sub != K) return fail(c, WAYNE_E_INVALID, "set_spots: n_sub differs from the exposure's");
+  if (!sp->contrast || !sp->px || !sp->py) return fail(c, WAYNE_E_INVALID, "set_spots: null array");
+  SpotArgs a{};
+  a.n = n;
+  a.gl = kSpotRule;
+  for (int i = 0; i < n; ++i) {
+    const double x = sp->cx[i], y = sp->cy[i], r = sp->radius[i];
+    if (!std::isfinite(r) || !(r > 0.)) return fail(c, WAYNE_E_INVALID, "set_spots: a radius must be finite and > 0");
+    if (!std::isfinite(x) || !std::isfinite(y)) return fail(c, WAYNE_E_INVALID, "set_spots: a centre must be finite");
+    if (!(std::sqrt(x * x + y * y) + r <= 0.98))
+      return fail(c, WAYNE_E_INVALID, "set_spots: |centre| + radius must be <= 0.98 (a spot may not reach the limb)");
+    for (int j = 0; j < i; ++j)
+      if (std::hypot(x - sp->cx[j], y - sp->cy[j]) < r + sp->radius[j])
+        return fail(c, WAYNE_E_INVALID, "set_spots: two spots overlap");
+    a.cx[i] = x; a.cy[i] = y; a.r[i] = r;
+    lens_basis(kSpotRule, x, y, x, y, r, r, a.S[i][0], a.S[i][1], a.S[i][2], a.S[i][3], a.S[i][4]);
+  }
+  for (size_t i = 0; i < (size_t)n * W; ++i)
+    if (!std::isfinite(sp->contrast[i]) || sp->contrast[i] < 0.)
+      return fail(c, WAYNE_E_INVALID, "set_spots: a contrast must be finite and >= 0");
+  // the planet's track on the transit rows (the pinned copies of lc_z / lc_hidden hold until the next upload)
+  const double* z = s.stage.host_of<double>(s.lc_z);
+  const double* hid = s.has_lc_hidden ? s.stage.host_of<double>(s.lc_hidden) : nullptr;
+  for (int k = 0; k < K; ++k) {
+    if (!(z[k] < 10.) || (hid && hid[k] != 0.)) continue;
+    if (!std::isfinite(sp->px[k]) || !std::isfinite(sp->py[k]))
+      return fail(c, WAYNE_E_INVALID, "set_spots: the planet's track must be finite on every transit row");
+  }
+  // the spotted disc flux F0 - D, in the kernel's own arithmetic
+  const double* tab = s.ld_on ? s.ld_stage.host_of<double>(s.ld_tab) : nullptr;
+  for (int w = 0; w < W; ++w) {
+    double l[4];
+    for (int i = 0; i < 4; ++i) l[i] = tab ? tab[(size_t)i * W + w] : s.d.lc_ld[i];
+    const double c0 = 1. - l[0] - l[1] - l[2] - l[3];
+    const double f0 = kPi * (1. - (l[0] * (1. / 5.) + l[1] * (2. / 6.) + l[2] * (3. / 7.) + l[3] * (4. / 8.)));
+    double D = 0.;
+    for (int i = 0; i < n; ++i)
+      D = D + (1. - sp->contrast[(size_t)i * W + w]) *
+                  ((((c0 * a.S[i][0] + l[0] * a.S[i][1]) + l[1] * a.S[i][2]) + l[2] * a.S[i][3]) + l[3] * a.S[i][4]);
+    if (!(f0 - D > 0.)) return fail(c, WAYNE_E_INVALID, "set_spots: the spotted disc flux F0 - D must be > 0 in every bin");
+  }
+  (void)hipSetDevice(c->device);
+  use_slot_stream(c, slot);
+  const size_t cb = (size_t)n * W * sizeof(double), kb = (size_t)K * sizeof(double);
+  int rc = s.spot_stage.begin(c, align64(cb) + 2 * align64(kb) + 64, "set_spots: pinned staging allocation failed");
+  if (rc) return rc;
+  if (!s.spot_stage.put(s.spot_contrast, sp->contrast, cb) || !s.spot_stage.put(s.spot_px, sp->px, kb) ||
+      !s.spot_stage.put(s.spot_py, sp->py, kb) || !s.spot_stage.put(s.spot_ld, s.d.lc_ld, 4 * sizeof(double)))
+    return fail(c, WAYNE_E_NOMEM, "set_spots: staging arena too small");
+  if ((rc = s.spot_stage.commit(c, c->stream))) return rc;
+  s.spot_args = a;
+  s.spots_on = true;
+  return WAYNE_OK;
+}
+
+int wayne_spots_profile(wayne_ctx* c, uint64_t* launches, double* ms) {
+  if (!c) return WAYNE_E_INVALID;
+  int rc = collect_profile(c);
+  if (rc) return rc;
+  if (launches) *launches = c->prof_launches[PK_SPOTS];
+  if (ms) *ms = c->prof_ms[PK_SPOTS];
   return WAYNE_OK;
 }
 

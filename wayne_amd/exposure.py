@@ -180,6 +180,11 @@ class Exposure(object):
             # limb darkening per wavelength bin (lightcurve.LimbDarkening): only then, likewise; exposure_file_is_whole
             # compares these cards too
             cards += ld_table.cards()
+        spot_cards = getattr(planet, "spot_cards", None) if planet is not None else None
+        if spot_cards:
+            # star spots (spots.StarSpots.cards on the visit's wavelength grid): only then, likewise;
+            # exposure_file_is_whole compares these cards too
+            cards += list(spot_cards)
         return fitsio.Header(cards)
 
     @staticmethod

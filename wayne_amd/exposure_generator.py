@@ -425,6 +425,8 @@ class ExposureGenerator(object):
             lc = dict(lc_z=planet_signal.z_tr, lc_hidden=planet_signal.hidden, lc_rp=rp, lc_ld=planet_signal.ld)
             if getattr(planet_signal, "ld_table", None) is not None:     # coefficients per bin: cropped with the spectrum
                 lc["lc_ld_table"] = planet_signal.ld_table[i0:i1]
+            if getattr(planet_signal, "spots", None) is not None:        # star spots: their contrast likewise
+                lc["lc_spots"] = planet_signal.spots.crop(i0, i1)
         elif planet_signal is not None:
             depth = np.ascontiguousarray(np.asarray(planet_signal, dtype=float)[:, i0:i1])
 

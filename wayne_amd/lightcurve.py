@@ -21,6 +21,9 @@ HIP kernel from z[K], p[W] and the four coefficients (the same rule and
 nodes, float32 integrand / float64 sum); the numpy version here serves
 `Observation.show_lightcurve` and the tests.
 
+The star may carry spots (wayne_amd/spots.py): `depth_inputs_track` also returns the planet's track on the sky, and
+`planet_depths` / `DeviceDepths` take a `spots.SpotGeometry` (on the device: k_lightcurve_spots).
+
 Limb darkening may vary with wavelength: `LimbDarkening` tabulates the coefficients over wavelength, `ld` is then an
 array [W, 4] and the law is evaluated through the five coefficient-free integrals of `transit_basis` (on the device:
 k_lightcurve_ld).
@@ -238,21 +241,21 @@ def _cheb_matrix(x):
     return nodes, B
 
 
-def planet_orbit_short_span(period, sma_over_rs, eccentricity, inclination_deg, periastron_deg, mid_time, time_array):
-    """planet_orbit for the K sub-sample times of ONE exposure (thousands of them on a finely sampled scan: 2233 in
+def planet_track_short_span(period, sma_over_rs, eccentricity, inclination_deg, periastron_deg, mid_time, time_array):
+    """planet_position (X, Y, Zlos) for the K sub-sample times of ONE exposure (thousands of them on a finely sampled scan: 2233 in
     the reference's example visit, the host's largest per-exposure cost at 0.15 ms).  Over an exposure the planet moves
     along ~1e-4 of its orbit and its position is an analytic function of time, so X, Y and Z are evaluated at ten
     Chebyshev points of the span and interpolated (barycentric form; the n-th term of their Taylor series falls like
     (2 pi span / period)^n / n!: the interpolant is exact to rounding, tests/test_lightcurve.py) -- the position, not
     the separation sqrt(X^2 + Y^2), which has a corner at mid-transit for an edge-on orbit.  Longer spans (more than
-    0.4 % of the period: half an hour of a five-day orbit) or few samples take planet_orbit."""
+    0.4 % of the period: half an hour of a five-day orbit) or few samples take planet_position."""
     t = np.asarray(time_array, dtype=float)
     if t.size < 4 * _CHEB_NODES:
-        return planet_orbit(period, sma_over_rs, eccentricity, inclination_deg, periastron_deg, mid_time, t)
+        return planet_position(period, sma_over_rs, eccentricity, inclination_deg, periastron_deg, mid_time, t)
     t_lo, t_hi = float(t.min()), float(t.max())
     half = 0.5 * (t_hi - t_lo)
     if not (0.0 < half <= 0.002 * period):
-        return planet_orbit(period, sma_over_rs, eccentricity, inclination_deg, periastron_deg, mid_time, t)
+        return planet_position(period, sma_over_rs, eccentricity, inclination_deg, periastron_deg, mid_time, t)
     # the sub-sample times of every exposure of a visit are the same offsets from its start: one matrix serves them all.
     # Abscissae AND node times are built from the offsets and ONE centre, t[0] + off_mid: at JD-scale times (ulp 4.7e-10
     # d) a centre taken as (t_hi + t_lo) / 2 rounds differently from exposure to exposure, and a cached matrix built
@@ -262,7 +265,7 @@ def planet_orbit_short_span(period, sma_over_rs, eccentricity, inclination_deg, 
     half = 0.5 * (off_hi - off_lo)
     off_mid = 0.5 * (off_hi + off_lo)
     if not half > 0.0:
-        return planet_orbit(period, sma_over_rs, eccentricity, inclination_deg, periastron_deg, mid_time, t)
+        return planet_position(period, sma_over_rs, eccentricity, inclination_deg, periastron_deg, mid_time, t)
     key = (t.size, off[1], off[-1], half)
     hit = _cheb_cache.get(key)
     if hit is None or not np.array_equal(hit[0], off):
@@ -275,7 +278,14 @@ def planet_orbit_short_span(period, sma_over_rs, eccentricity, inclination_deg, 
     X, Y, Zlos = planet_position(period, sma_over_rs, eccentricity, inclination_deg, periastron_deg, mid_time,
                                  off_mid + half * nodes, time_origin=float(t[0]))
     P = B @ np.stack([X, Y, Zlos], axis=1)
-    return np.sqrt(P[:, 0] * P[:, 0] + P[:, 1] * P[:, 1]), P[:, 2]
+    return P[:, 0], P[:, 1], P[:, 2]
+
+
+def planet_orbit_short_span(period, sma_over_rs, eccentricity, inclination_deg, periastron_deg, mid_time, time_array):
+    """planet_orbit (separation z and line-of-sight coordinate) by the route of planet_track_short_span."""
+    X, Y, Zlos = planet_track_short_span(period, sma_over_rs, eccentricity, inclination_deg, periastron_deg, mid_time,
+                                         time_array)
+    return np.sqrt(X * X + Y * Y), Zlos
 
 
 def transit(ld, rp_over_rs, period, sma_over_rs, eccentricity, inclination, periastron, mid_time, time_array):
@@ -296,20 +306,28 @@ def eclipse(fp_over_fs, rp_over_rs, period, sma_over_rs, eccentricity, inclinati
 def depth_inputs(period, sma_over_rs, eccentricity, inclination, periastron, mid_time, time_array, rp_white):
     """The K-vectors the device kernel needs: z for the transit (>= 10 when the planet is
     behind the star) and the hidden fraction of the planet for the eclipse term."""
-    z, los = planet_orbit_short_span(period, sma_over_rs, eccentricity, inclination, periastron, mid_time, time_array)
+    return depth_inputs_track(period, sma_over_rs, eccentricity, inclination, periastron, mid_time, time_array, rp_white)[:2]
+
+
+def depth_inputs_track(period, sma_over_rs, eccentricity, inclination, periastron, mid_time, time_array, rp_white):
+    """depth_inputs and the planet's track on the sky, X and Y [K] in stellar radii (what spots.SpotGeometry takes):
+    z_tr, hidden, X, Y."""
+    X, Y, los = planet_track_short_span(period, sma_over_rs, eccentricity, inclination, periastron, mid_time, time_array)
+    z = np.sqrt(X * X + Y * Y)
     z_tr = np.where(los > 0, z, 10.0 + z)
     behind = los < 0
     hidden = np.zeros(z.shape)
     if behind.any():                     # (the eclipse side of the orbit only: in transit there is nothing to evaluate)
         hidden[behind] = uniform_overlap_fraction(z[behind], rp_white)
-    return z_tr, hidden
+    return z_tr, hidden, X, Y
 
 
-def planet_depths(ld, planet_spectrum, z_tr, hidden):
+def planet_depths(ld, planet_spectrum, z_tr, hidden, spots=None):
     """1 - (transit - (1 - eclipse)) per sub-sample and wavelength bin: what
     Observation._generate_exposure hands to scanning_frame (observation.py:349-355, 442-443).  A negative (or NaN) element
     of the spectrum has no radius ratio: a planet of no size blocks and emits nothing, its column is 0 (as on the device,
-    k_lightcurve), and every other column is what it is without that element."""
+    k_lightcurve), and every other column is what it is without that element.  `spots` (spots.SpotGeometry): the depths
+    of a spotted star (wayne_amd/spots.py)."""
     spec = np.asarray(planet_spectrum, dtype=float)
     sized = spec >= 0.0
     spec = np.where(sized, spec, 0.0)
@@ -319,6 +337,8 @@ def planet_depths(ld, planet_spectrum, z_tr, hidden):
     ecl = (1.0 + f * (1.0 - np.asarray(hidden)[:, None])) / (1.0 + f)
     out = 1.0 - (tr - (1.0 - ecl))
     out[:, ~sized] = 0.0
+    if spots is not None:
+        out = spots.apply(out, z_tr, hidden, planet_spectrum, ld)
     return out
 
 
@@ -326,10 +346,11 @@ class DeviceDepths(object):
     """Hand this to ExposureGenerator.scanning_frame as `planet_signal` to have the
     K x W transit-depth matrix computed on the GPU (k_lightcurve) instead of passing it."""
 
-    def __init__(self, z_tr, hidden, planet_spectrum, ld):
+    def __init__(self, z_tr, hidden, planet_spectrum, ld, spots=None):
         """`ld`: four Claret coefficients for every wavelength, or an array [W, 4] with one set per element of
         `planet_spectrum` (k_lightcurve_ld; `ld_table` is then that array and `ld` its first row, the descriptor's
-        unused lc_ld)."""
+        unused lc_ld).  `spots` (spots.SpotGeometry: the planet's track, the spots and their contrast per element of
+        `planet_spectrum`): the star is spotted, k_lightcurve_spots rewrites the matrix behind the light-curve kernel."""
         self.z_tr = np.asarray(z_tr, dtype=float)
         self.hidden = None if hidden is None else np.asarray(hidden, dtype=float)
         self.planet_spectrum = np.asarray(planet_spectrum, dtype=float)
@@ -342,11 +363,18 @@ class DeviceDepths(object):
             self.ld_table = table
             ld = table[0]
         self.ld = [float(v) for v in ld]
+        if spots is not None:
+            if spots.X.size != self.z_tr.size or spots.contrast.shape[1] != self.planet_spectrum.size:
+                raise ValueError("DeviceDepths: spots with a track of %d points and %d wavelengths, the light curve has "
+                                 "%d and %d" % (spots.X.size, spots.contrast.shape[1], self.z_tr.size,
+                                                self.planet_spectrum.size))
+        self.spots = spots
 
     def host_matrix(self):
         """The same matrix evaluated with numpy (for tests and plots)."""
         hidden = np.zeros_like(self.z_tr) if self.hidden is None else self.hidden
-        return planet_depths(self.ld if self.ld_table is None else self.ld_table, self.planet_spectrum, self.z_tr, hidden)
+        return planet_depths(self.ld if self.ld_table is None else self.ld_table, self.planet_spectrum, self.z_tr, hidden,
+                             spots=self.spots)
 
 
 class LimbDarkening(object):

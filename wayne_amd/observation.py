@@ -178,9 +178,10 @@ class Observation(object):
 
     def setup_target(self, planet, wavelengths, planet_spectrum, stellar_flux, transittime=None, ldcoeffs=None,
                      period=None, rp=None, sma=None, inclination=None, eccentricity=None, periastron=None,
-                     stellar_radius=None, ld_table=None):
+                     stellar_radius=None, ld_table=None, spots=None):
         """`ld_table` (lightcurve.LimbDarkening): limb darkening per wavelength bin -- the light curves then use
-        `ld_table.on_grid(wavelengths)`; `ldcoeffs` stays required: the fallback and the header's LD1 .. LD4."""
+        `ld_table.on_grid(wavelengths)`; `ldcoeffs` stays required: the fallback and the header's LD1 .. LD4.
+        `spots` (spots.StarSpots): a spotted star (set_spots)."""
         self.wl = np.asarray(wavelengths, dtype=float)
         self.stellar_flux = np.asarray(stellar_flux, dtype=float)
         self.planet_spectrum = None if planet_spectrum is None else np.asarray(planet_spectrum, dtype=float)
@@ -216,6 +217,41 @@ class Observation(object):
                 raise ValueError("setup_target: ld_table needs a planet spectrum (there is no transit without one)")
             self.ld_table = self._ld_on_grid = None
             self.transmission_spectroscopy = False
+        self.set_spots(spots)
+
+    def set_spots(self, spots):
+        """The star's spots (spots.StarSpots; None: a clean star), after setup_target: the light curves of every path
+        (device_depths, generate_lightcurves) are those of the spotted star, and the files carry the SPOTS cards.
+        ValueError without a planet spectrum, or when the spotted disc flux is not positive in some bin."""
+        from . import spots as _spots
+        if spots is None:
+            self.spots = self._spot_contrast = None
+            if getattr(self, "planet", None) is not None:
+                self.planet.spot_cards = None
+            return
+        if not isinstance(spots, _spots.StarSpots):
+            raise TypeError("set_spots: spots must be a spots.StarSpots or None")
+        if not self.transmission_spectroscopy:
+            raise ValueError("set_spots: spots need a planet spectrum (there is no transit without one)")
+        spots.check_flux(self._limb_darkening(), self.wl)
+        self.spots = spots
+        self._spot_contrast = spots.on_grid(self.wl)
+        self.planet.spot_cards = spots.cards(self.wl)       # only when there are spots
+
+    def planet_position_at_phase(self, phase):
+        """(X, Y) of the planet's centre on the sky, in stellar radii, `phase` periods from mid-transit."""
+        period, sma, e, inc, peri, _ = self._orbit_args()
+        X, Y, _ = lightcurve.planet_position(period, sma, e, inc, peri, 0.0, np.array([float(phase) * period]))
+        return float(X[0]), float(Y[0])
+
+    def _spot_geometry(self, X, Y, white=False):
+        """spots.SpotGeometry of the track X, Y (None: a clean star); `white`: one depth for the whole band, the band
+        mean of every spot's contrast."""
+        if getattr(self, "spots", None) is None:
+            return None
+        from . import spots as _spots
+        contrast = self._spot_contrast.mean(axis=1, keepdims=True) if white else self._spot_contrast
+        return _spots.SpotGeometry(X, Y, self.spots.cx, self.spots.cy, self.spots.radius, contrast)
 
     def setup_detector(self, detector, NSAMP, SAMPSEQ, SUBARRAY):
         self.detector, self.NSAMP, self.SAMPSEQ, self.SUBARRAY = detector, NSAMP, SAMPSEQ, SUBARRAY
@@ -275,8 +311,9 @@ class Observation(object):
         time_array = self._to_hjd(time_array)
         spectrum = np.array([depth]) if depth else self.planet_spectrum
         rp_white = self.planet.rp_over_rs or float(np.sqrt(np.mean(self.planet_spectrum)))
-        z_tr, hidden = lightcurve.depth_inputs(*(self._orbit_args() + (time_array, rp_white)))
-        return 1.0 - lightcurve.planet_depths(self._limb_darkening(white=bool(depth)), spectrum, z_tr, hidden)
+        z_tr, hidden, X, Y = lightcurve.depth_inputs_track(*(self._orbit_args() + (time_array, rp_white)))
+        return 1.0 - lightcurve.planet_depths(self._limb_darkening(white=bool(depth)), spectrum, z_tr, hidden,
+                                              spots=self._spot_geometry(X, Y, white=bool(depth)))
 
     def _limb_darkening(self, white=False):
         """What the light curves take as `ld`: the four coefficients, or with a table its coefficients on the visit's
@@ -290,8 +327,9 @@ class Observation(object):
     def device_depths(self, time_array):
         """The same per-sub-sample depths, as the recipe the GPU evaluates."""
         rp_white = self.planet.rp_over_rs or float(np.sqrt(np.mean(self.planet_spectrum)))
-        z_tr, hidden = lightcurve.depth_inputs(*(self._orbit_args() + (self._to_hjd(time_array), rp_white)))
-        return lightcurve.DeviceDepths(z_tr, hidden, self.planet_spectrum, self._limb_darkening())
+        z_tr, hidden, X, Y = lightcurve.depth_inputs_track(*(self._orbit_args() + (self._to_hjd(time_array), rp_white)))
+        return lightcurve.DeviceDepths(z_tr, hidden, self.planet_spectrum, self._limb_darkening(),
+                                       spots=self._spot_geometry(X, Y))
 
     def _to_hjd(self, time_array):
         p = self.planet
@@ -342,7 +380,7 @@ class Observation(object):
         except (KeyError, TypeError, ValueError):
             return False
         if not (same and self._contaminant_cards_match(p0) and self._trap_cards_match(p0) and self._ld_cards_match(p0) and
-                self._ipc_cards_match(p0)):
+                self._ipc_cards_match(p0) and self._spot_cards_match(p0)):
             return False
         # the visit's sample type too: uint16 reads make BITPIX 16 images, float reads float64 ones -- a file of the
         # other kind is regenerated, whichever way the visit was switched
@@ -375,6 +413,20 @@ class Observation(object):
                 return False
             return (str(p0["LDHASH"]).strip() == want["LDHASH"] and str(p0["LDLAW"]).strip() == want["LDLAW"] and
                     int(p0["LDNODES"]) == want["LDNODES"])
+        except (KeyError, TypeError, ValueError):
+            return False
+
+    def _spot_cards_match(self, p0):
+        """The file's SPOTS / NSPOTS / SPTHASH cards are this visit's star spots (absent: none), so that --resume after a
+        spot was added, removed or changed regenerates the files."""
+        cards = getattr(getattr(self, "planet", None), "spot_cards", None)
+        want = {k: v for (k, v, _) in cards} if cards else {}
+        try:
+            if "SPOTS" not in p0:
+                return not want
+            if not want or p0["SPOTS"] is not True:
+                return False
+            return str(p0["SPTHASH"]).strip() == want["SPTHASH"] and int(p0["NSPOTS"]) == want["NSPOTS"]
         except (KeyError, TypeError, ValueError):
             return False
 

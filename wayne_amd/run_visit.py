@@ -27,6 +27,12 @@ examples/hd209458b_12181_simulation_parameters.yml): sections `general`
     (text, columns wl_um a1 a2 a3 a4; `ld_law: quadratic | linear` for a file with wl_um u1 u2 or wl_um u) gives every
     wavelength bin its own limb darkening, interpolated linearly between the nodes (lightcurve.LimbDarkening);
     `ldcoeffs` stays required (the header's LD1 .. LD4); the files then carry LDTABLE, LDLAW, LDNODES, LDWLLO, LDWLHI, LDHASH;
+  * an optional `target: spots: {photosphere_temperature: 5000, list: [{x: -0.21, y: 0.33, radius: 0.10, temperature:
+    4200}, {at_phase: 0.0021, radius: 0.06, contrast: 0.75}]}` puts star spots into the light curves, occulted and
+    unocculted (wayne_amd/spots.py): at most 8 circles in projection, centre and radius in stellar radii (`at_phase`:
+    centred where the planet's centre is at that orbital phase from mid-transit, in periods), each with a `contrast` or
+    a `temperature` (K; `photosphere_temperature` is then required); the files then carry SPOTS, NSPOTS, SPTXn, SPTYn,
+    SPTRn, SPTCn and SPTHASH;
   * an optional top-level `charge_traps:` section turns on per-pixel charge trapping, the ramp effect
     (wayne_amd/traps.py): `slow` / `fast` mappings of n_traps, efficiency, lifetime_s, initial, orbit_fill; `{}` = the
     defaults, an omitted key its default; `history: carried` carries each pixel's trap state from exposure to exposure
@@ -207,6 +213,15 @@ def build_observation(cfg, base_dir=".", calibration=None, device=0):
                      _get(target, "ldcoeffs"), _get(target, "period"), _get(target, "rp"), _get(target, "sma"),
                      _get(target, "inclination"), _get(target, "eccentricity"), _get(target, "periastron"),
                      _get(target, "stellar_radius"), **({"ld_table": ld_table} if ld_table is not None else {}))
+    spot_cfg = _get(target, "spots")
+    if spot_cfg is not None:
+        if not transmission:
+            raise WFC3SimConfigError("target: spots need planet_spectrum_file (there is no transit without one)")
+        from . import spots as _spots
+        try:
+            obs.set_spots(_spots.StarSpots.from_config(spot_cfg, obs.planet_position_at_phase))
+        except (TypeError, ValueError) as e:
+            raise WFC3SimConfigError("target: spots: %s" % e)
     obs.setup_visit(obs_cfg["start_JD"] or 0.0, obs_cfg["num_orbits"], exp_start_times)
     obs.setup_reductions(obs_cfg["add_dark"], obs_cfg["add_flat"], obs_cfg["add_gain_variations"],
                          obs_cfg["add_non_linear"], obs_cfg["add_initial_bias"])

@@ -201,11 +201,18 @@ class Visit(object):
         transit of the same depth spectrum (observation.py:293-357)."""
         from . import lightcurve
         t = self.exp_start_days[i] + self.sample_mid_points / 86400e3
-        z_tr, hidden = lightcurve.depth_inputs(mid_time=0.0, time_array=t, rp_white=np.sqrt(self.depth0.mean()),
-                                               **self.ORBIT)
         # an optional `ld_table` attribute (lightcurve.LimbDarkening): coefficients per wavelength bin instead of LD
         table = getattr(self, "ld_table", None)
-        return lightcurve.DeviceDepths(z_tr, hidden, self.depth0, self.LD if table is None else table.on_grid(self.wl))
+        ld = self.LD if table is None else table.on_grid(self.wl)
+        # an optional `spots` attribute (spots.StarSpots): a spotted star, which needs the planet's track too
+        star_spots = getattr(self, "spots", None)
+        if star_spots is None:
+            z_tr, hidden = lightcurve.depth_inputs(mid_time=0.0, time_array=t, rp_white=np.sqrt(self.depth0.mean()),
+                                                   **self.ORBIT)
+            return lightcurve.DeviceDepths(z_tr, hidden, self.depth0, ld)
+        z_tr, hidden, X, Y = lightcurve.depth_inputs_track(mid_time=0.0, time_array=t,
+                                                           rp_white=np.sqrt(self.depth0.mean()), **self.ORBIT)
+        return lightcurve.DeviceDepths(z_tr, hidden, self.depth0, ld, spots=star_spots.geometry(X, Y, self.wl))
 
     def scale_factor(self, i):
         return 1.0 - 0.002 * np.exp(-i / 6.0)     # a hook-like visit trend

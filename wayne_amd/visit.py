@@ -49,6 +49,9 @@ def descriptor_digest(desc):
     ld_table = getattr(desc, "_ld_table", None)    # limb darkening per wavelength bin (none: likewise)
     if ld_table is not None:
         h.update(b"ld_table" + np.ascontiguousarray(ld_table).tobytes())
+    lc_spots = getattr(desc, "_spots", None)       # star spots of the device light curve (none: likewise)
+    if lc_spots is not None:
+        h.update(lc_spots.digest_bytes())
     ipc = getattr(desc, "_ipc", None)              # inter-pixel capacitance (none: likewise)
     if ipc is not None:
         h.update(ipc.digest_bytes())
