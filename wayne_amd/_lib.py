@@ -550,11 +550,15 @@ class Context(object):
         d.contrast, d.px, d.py = ptr(contrast, C.c_double), ptr(px, C.c_double), ptr(py, C.c_double)
         self.check(self._L.wayne_exposure_set_spots(self._h, int(slot), C.byref(d), contrast.shape[1], px.size))
 
+    def _kernel_profile(self, which, as_dict=True):
+        """wayne_<which>_profile: launches and milliseconds by HIP events since profile_reset."""
+        n, ms = C.c_uint64(0), C.c_double(0.0)
+        self.check(getattr(self._L, "wayne_%s_profile" % which)(self._h, C.byref(n), C.byref(ms)))
+        return {"launches": int(n.value), "ms": float(ms.value)} if as_dict else (int(n.value), float(ms.value))
+
     def spots_profile(self):
         """(launches, total milliseconds) of k_lightcurve_spots since profile_reset.  See wayne_spots_profile."""
-        n, ms = C.c_uint64(0), C.c_double(0.0)
-        self.check(self._L.wayne_spots_profile(self._h, C.byref(n), C.byref(ms)))
-        return int(n.value), float(ms.value)
+        return self._kernel_profile("spots", as_dict=False)
 
     # -- limb darkening per wavelength bin -------------------------------------------
     def set_limb_darkening(self, slot, ld):
@@ -595,9 +599,7 @@ class Context(object):
 
     def expected_profile(self):
         """{"launches", "ms"} of k_expect by HIP events (profile_enable; since profile_reset)."""
-        n, ms = C.c_uint64(0), C.c_double(0.0)
-        self.check(self._L.wayne_expected_profile(self._h, C.byref(n), C.byref(ms)))
-        return {"launches": int(n.value), "ms": float(ms.value)}
+        return self._kernel_profile("expected")
 
     # -- the ramp fit --------------------------------------------------------------
     def set_rampfit(self, slot, ramp_fit):
@@ -632,9 +634,7 @@ class Context(object):
 
     def rampfit_profile(self):
         """{"launches", "ms"} of k_ramp_fit by HIP events (profile_enable; since profile_reset)."""
-        n, ms = C.c_uint64(0), C.c_double(0.0)
-        self.check(self._L.wayne_rampfit_profile(self._h, C.byref(n), C.byref(ms)))
-        return {"launches": int(n.value), "ms": float(ms.value)}
+        return self._kernel_profile("rampfit")
 
     # -- the calibrated reads ------------------------------------------------------
     def set_ima(self, slot, ima):
@@ -669,9 +669,7 @@ class Context(object):
 
     def ima_profile(self):
         """{"launches", "ms"} of k_ima by HIP events (profile_enable; since profile_reset)."""
-        n, ms = C.c_uint64(0), C.c_double(0.0)
-        self.check(self._L.wayne_ima_profile(self._h, C.byref(n), C.byref(ms)))
-        return {"launches": int(n.value), "ms": float(ms.value)}
+        return self._kernel_profile("ima")
 
     # -- device-side FITS words ----------------------------------------------------
     def set_fits(self, slot, on=True):
@@ -715,9 +713,7 @@ class Context(object):
 
     def fits_profile(self):
         """{"launches", "ms"} of k_fits_words by HIP events (profile_enable; since profile_reset)."""
-        n, ms = C.c_uint64(0), C.c_double(0.0)
-        self.check(self._L.wayne_fits_profile(self._h, C.byref(n), C.byref(ms)))
-        return {"launches": int(n.value), "ms": float(ms.value)}
+        return self._kernel_profile("fits")
 
     def set_crrej(self, slot, crrej):
         """Cosmic-ray rejection of the slot's extraction: an extraction.CosmicRejection (k, read_noise) -- None clears;
@@ -977,9 +973,7 @@ class Context(object):
 
     def extract_profile(self):
         """{"launches", "ms"} of the extraction's kernels by HIP events (profile_enable; since profile_reset)."""
-        n, ms = C.c_uint64(0), C.c_double(0.0)
-        self.check(self._L.wayne_extract_profile(self._h, C.byref(n), C.byref(ms)))
-        return {"launches": int(n.value), "ms": float(ms.value)}
+        return self._kernel_profile("extract")
 
     def set_ipc(self, slot, ipc):
         """Inter-pixel capacitance of the slot's uploaded exposure: an ipc.InterpixelCapacitance (or a 3 x 3 array of
@@ -991,9 +985,7 @@ class Context(object):
 
     def ipc_profile(self):
         """(coupled exposures, total milliseconds) of k_ipc and k_ipc_clear since profile_reset.  See wayne_ipc_profile."""
-        n, ms = C.c_uint64(0), C.c_double(0.0)
-        self.check(self._L.wayne_ipc_profile(self._h, C.byref(n), C.byref(ms)))
-        return int(n.value), float(ms.value)
+        return self._kernel_profile("ipc", as_dict=False)
 
     def set_traps(self, slot, traps):
         """Charge traps of the slot's uploaded exposure: a traps.ExposureTraps (the model and this exposure's start tables

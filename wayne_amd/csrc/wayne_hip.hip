@@ -163,6 +163,29 @@ struct SourceState {
 
 constexpr int kMaxSources = WAYNE_MAX_SOURCES;   // contaminants per exposure
 
+// the layout of a slot's status block `misc`, declared here only: [8] the last run that overflowed, [12] the last run
+// that met a bin beyond its launch sequence (PrepArgs::status points at these two; the first word is spare)
+struct SlotMisc {
+  unsigned long long spare;
+  uint32_t over_run, beyond_run;
+  int bits(uint32_t run) const { return (run && over_run == run ? 1 : 0) | (run && beyond_run == run ? 2 : 0); }   // as wayne_exposure_status reports them
+};
+
+// The pinned host mirror of one of a slot's products (its reads, its spectra block, its FITS words), followed by a copy
+// of the slot's status block -- inside the pinned block: a copy into pageable memory would block the caller -- and the
+// number of the run the copies were enqueued behind.  `misc` is null until a fetch has succeeded.
+struct PinnedMirror {
+  PinnedBuf buf;
+  SlotMisc* misc = nullptr;
+  uint32_t run = 0;
+  bool fetched() const { return buf.p && misc; }
+  // What fetch_async / fetch_spectra_async / fetch_fits_async share, on c->stream: room for `bytes` and the status block
+  // (refused as `nomem`), then the copies of `dev` and of the slot's status block, read against the slot's current run.
+  // record_kdone: the exposure on the other stream waits for this one's KERNELS, not for its copy (wayne_ctx::ev_kdone)
+  // -- the caller's choice: the reads always, FITS words unless this run's reads went in front of them, spectra never.
+  int fetch(wayne_ctx* c, int slot, const void* dev, size_t bytes, bool record_kdone, const char* nomem);
+};
+
 // An exposure slot.  Its own SourceState is the target's (source 0); extra[0 .. n_extra) are the contaminants.
 struct Slot : SourceState {
   bool uploaded = false;
@@ -174,8 +197,8 @@ struct Slot : SourceState {
   // The runs of the slot are numbered (from 1; counted on by wayne_exposure_run_front): a kernel raises a status word to
   // the number of its run and nothing clears the block on the device (k_prep.h, raise_status).  A copy of the block is
   // read against the number that was current when the copy was ENQUEUED: run_no for a read that waits for the stream,
-  // pinned_run / ex_pinned_run for the copies fetch_async / fetch_spectra_async enqueue.
-  uint32_t run_no = 0, pinned_run = 0, ex_pinned_run = 0;
+  // PinnedMirror::run for the copies fetch_async / fetch_spectra_async / fetch_fits_async enqueue.
+  uint32_t run_no = 0;
   wayne_exposure_desc d{};  // host copy (pointers are NOT valid after upload)
   int K = 0, R = 0;
   bool has_depth = false, has_replay_seed = false, has_lc = false, has_lc_hidden = false;
@@ -188,15 +211,8 @@ struct Slot : SourceState {
   DevBuf seg;             // cosmic-ray segments (CosmicArgs::seg): zeroed when allocated, k_ramp clears what it reads
   bool use_box = false;   // acc_box is valid: k_ramp loads the accumulators of a read only inside it (and where `seg` says)
   int acc_box[16][4] = {{0}};
-  PinnedBuf pinned;       // pinned host copy of `out` (fetch_async / wait), followed by a copy of `misc`
-  // the layout of `misc`, declared here only: [8] the last run that overflowed, [12] the last run that met a bin beyond
-  // its launch sequence (PrepArgs::status points at these two; the first word is spare)
-  struct Misc {
-    unsigned long long spare;
-    uint32_t over_run, beyond_run;
-    int bits(uint32_t run) const { return (run && over_run == run ? 1 : 0) | (run && beyond_run == run ? 2 : 0); }   // as wayne_exposure_status reports them
-  };
-  Misc* pinned_misc = nullptr;   // inside `pinned`: a copy into pageable memory would block the caller
+  using Misc = SlotMisc;
+  PinnedMirror pinned;    // pinned host copy of `out` (fetch_async / wait)
   // sky alias tables of this exposure (k_ramp): their arena, the view of the device copy, the lam_max they were built for
   StageArena sky_stage;
   DevBuf sky_tab;
@@ -241,8 +257,7 @@ struct Slot : SourceState {
   int ex_chunks = 0;
   DevBuf ex_part, ex_out;
   plan::SpectraLayout lay;
-  PinnedBuf ex_pinned;
-  Misc* ex_pinned_misc = nullptr;
+  PinnedMirror ex_pinned;
   const char* ex_base = nullptr;
   std::vector<double> ex_host;
   // cosmic-ray rejection of the extraction (wayne_exposure_set_crrej; cleared by upload and set_extraction): the flag
@@ -287,14 +302,11 @@ struct Slot : SourceState {
   uint64_t prof_fix_hash = 0;
   int prof_fix_R = 0;
   // FITS words of this exposure (wayne_exposure_set_fits; cleared by upload): the payload [(R+1)][fits_stride] bytes that
-  // k_fits_words writes behind the ramp kernel and the extraction, and its pinned mirror followed by a copy of `misc`
-  // (fetch_fits_async / wait_fits; fits_pinned_run: the run the copy was enqueued behind)
+  // k_fits_words writes behind the ramp kernel and the extraction, and its pinned mirror (fetch_fits_async / wait_fits)
   bool fits_on = false;
   size_t fits_plane_bytes = 0, fits_stride = 0;
   DevBuf fits_dev;
-  PinnedBuf fits_pinned;
-  Misc* fits_pinned_misc = nullptr;
-  uint32_t fits_pinned_run = 0;
+  PinnedMirror fits_pinned;
   // the noise-free expected image of this exposure (wayne_exposure_set_expected; cleared by upload): the mode
   // (0: none) and the plane [R][S][S] float64 that k_expect renders at the very end of the back half
   int expect_mode = 0;
@@ -669,24 +681,33 @@ size_t out_elem_size(uint32_t flags) {
   return k == 1 ? sizeof(double) : k == 2 ? sizeof(uint16_t) : sizeof(float);
 }
 
-template <class OutT, bool FAST, int SKY, bool NOISE>
-void (*ramp_kernel())(RampArgs) {
+// The ramp kernels are templates on <reads' type, production / exact math, sky sampler, gaussian-noise stage>, in three
+// families: k_ramp / k_ramp_wide, k_ramp_trap for a slot with charge traps, k_ramp_hist for one with a carried history on
+// top of them.  ramp_variant names one instantiation of a family; pick_ramp is the descent over the four switches,
+// written once.  (The ALLON instantiations are not on the ladder: select_ramp, pick_ramp_trap and pick_ramp_hist name them.)
+typedef void (*RampTrapKernel)(RampArgs, TrapArgs);
+typedef void (*RampHistKernel)(RampArgs, TrapArgs, TrapHistArgs);
+enum RampFamily { RAMP, RAMP_TRAP, RAMP_HIST };
+template <RampFamily F, class OutT, bool FAST, int SKY, bool NOISE>
+auto ramp_variant() {
+  if constexpr (F == RAMP_TRAP) return RampTrapKernel(k_ramp_trap<OutT, FAST, SKY, NOISE, false>);
+  else if constexpr (F == RAMP_HIST) return RampHistKernel(k_ramp_hist<OutT, FAST, SKY, NOISE, false>);
   // (pinned to 8 waves per SIMD where that does not spill: see k_ramp / k_ramp_wide)
-  if constexpr (FAST && SKY != 0 && !NOISE) return k_ramp<OutT, FAST, SKY, NOISE>;
-  else return k_ramp_wide<OutT, FAST, SKY, NOISE>;
+  else if constexpr (FAST && SKY != 0 && !NOISE) return (void (*)(RampArgs))k_ramp<OutT, FAST, SKY, NOISE>;
+  else return (void (*)(RampArgs))k_ramp_wide<OutT, FAST, SKY, NOISE>;
 }
-template <class OutT, bool FAST, int SKY>
-void (*ramp_noise(bool noise))(RampArgs) { return noise ? ramp_kernel<OutT, FAST, SKY, true>() : ramp_kernel<OutT, FAST, SKY, false>(); }
-template <class OutT, bool FAST>
-void (*ramp_sky(int sky, bool noise))(RampArgs) {
-  return sky == 1 ? ramp_noise<OutT, FAST, 1>(noise) : sky == 2 ? ramp_noise<OutT, FAST, 2>(noise) : ramp_noise<OutT, FAST, 0>(noise);
+template <RampFamily F, class OutT, bool FAST, int SKY>
+auto ramp_noise(bool noise) { return noise ? ramp_variant<F, OutT, FAST, SKY, true>() : ramp_variant<F, OutT, FAST, SKY, false>(); }
+template <RampFamily F, class OutT, bool FAST>
+auto ramp_sky(int sky, bool noise) {
+  return sky == 1 ? ramp_noise<F, OutT, FAST, 1>(noise) : sky == 2 ? ramp_noise<F, OutT, FAST, 2>(noise) : ramp_noise<F, OutT, FAST, 0>(noise);
 }
-// k_ramp<reads' type, production / exact math, sky sampler, gaussian-noise stage>
 // (reads' type: 0 float, 1 double, 2 uint16_t -- out_kind())
-void (*pick_ramp(int out, bool exact, int sky, bool noise))(RampArgs) {
-  return out == 1 ? (exact ? ramp_sky<double, false>(sky, noise) : ramp_sky<double, true>(sky, noise))
-       : out == 2 ? (exact ? ramp_sky<uint16_t, false>(sky, noise) : ramp_sky<uint16_t, true>(sky, noise))
-                  : (exact ? ramp_sky<float, false>(sky, noise) : ramp_sky<float, true>(sky, noise));
+template <RampFamily F>
+auto pick_ramp(int out, bool exact, int sky, bool noise) {
+  return out == 1 ? (exact ? ramp_sky<F, double, false>(sky, noise) : ramp_sky<F, double, true>(sky, noise))
+       : out == 2 ? (exact ? ramp_sky<F, uint16_t, false>(sky, noise) : ramp_sky<F, uint16_t, true>(sky, noise))
+                  : (exact ? ramp_sky<F, float, false>(sky, noise) : ramp_sky<F, float, true>(sky, noise));
 }
 
 // k_lane's tile reach in sigmas (knob lane_tight_tile: the same frames either way -- an electron beyond the tile takes
@@ -726,33 +747,14 @@ int launch_thrower(wayne_ctx* c, const ThrowArgs& a) {
 }
 
 // k_ramp_trap<reads' type, production / exact math, sky sampler, gaussian-noise stage, every switch on>
-typedef void (*RampTrapKernel)(RampArgs, TrapArgs);
-template <class OutT, bool FAST, int SKY>
-RampTrapKernel trap_noise(bool noise) { return noise ? k_ramp_trap<OutT, FAST, SKY, true, false> : k_ramp_trap<OutT, FAST, SKY, false, false>; }
-template <class OutT, bool FAST>
-RampTrapKernel trap_sky(int sky, bool noise) {
-  return sky == 1 ? trap_noise<OutT, FAST, 1>(noise) : sky == 2 ? trap_noise<OutT, FAST, 2>(noise) : trap_noise<OutT, FAST, 0>(noise);
-}
 RampTrapKernel pick_ramp_trap(int out, bool exact, int sky, bool noise, bool allon) {
   if (allon) return out == 2 ? k_ramp_trap<uint16_t, true, 1, false, true> : k_ramp_trap<float, true, 1, false, true>;
-  return out == 1 ? (exact ? trap_sky<double, false>(sky, noise) : trap_sky<double, true>(sky, noise))
-       : out == 2 ? (exact ? trap_sky<uint16_t, false>(sky, noise) : trap_sky<uint16_t, true>(sky, noise))
-                  : (exact ? trap_sky<float, false>(sky, noise) : trap_sky<float, true>(sky, noise));
+  return pick_ramp<RAMP_TRAP>(out, exact, sky, noise);
 }
-
 // k_ramp_hist<...>: k_ramp_trap's list again, for a slot with a carried history
-typedef void (*RampHistKernel)(RampArgs, TrapArgs, TrapHistArgs);
-template <class OutT, bool FAST, int SKY>
-RampHistKernel hist_noise(bool noise) { return noise ? k_ramp_hist<OutT, FAST, SKY, true, false> : k_ramp_hist<OutT, FAST, SKY, false, false>; }
-template <class OutT, bool FAST>
-RampHistKernel hist_sky(int sky, bool noise) {
-  return sky == 1 ? hist_noise<OutT, FAST, 1>(noise) : sky == 2 ? hist_noise<OutT, FAST, 2>(noise) : hist_noise<OutT, FAST, 0>(noise);
-}
 RampHistKernel pick_ramp_hist(int out, bool exact, int sky, bool noise, bool allon) {
   if (allon) return out == 2 ? k_ramp_hist<uint16_t, true, 1, false, true> : k_ramp_hist<float, true, 1, false, true>;
-  return out == 1 ? (exact ? hist_sky<double, false>(sky, noise) : hist_sky<double, true>(sky, noise))
-       : out == 2 ? (exact ? hist_sky<uint16_t, false>(sky, noise) : hist_sky<uint16_t, true>(sky, noise))
-                  : (exact ? hist_sky<float, false>(sky, noise) : hist_sky<float, true>(sky, noise));
+  return pick_ramp<RAMP_HIST>(out, exact, sky, noise);
 }
 
 // The k_ramp instantiation the back half of slot `s` launches, and (if asked) its name as the kernel trace prints it.
@@ -766,7 +768,7 @@ void (*select_ramp(const wayne_ctx* c, const Slot& s, std::string* name, RampTra
   const char* out_name = out == 1 ? "double" : out == 2 ? "unsigned short" : "float";
   const int sky_mode = !s.sky_alias_on ? 0 : (s.sky_pieces ? 2 : 1);
   const bool noise = d.noise_mean != 0. && d.noise_std != 0.;
-  void (*kern)(RampArgs) = pick_ramp(out, exact, sky_mode, noise);
+  void (*kern)(RampArgs) = pick_ramp<RAMP>(out, exact, sky_mode, noise);
   // the production variant with every detector switch on (the rule) has an instantiation of its own (k_ramp.h, ALLON)
   const uint32_t all_on = WAYNE_F_ADD_DARK | WAYNE_F_ADD_NON_LINEAR | WAYNE_F_CLIP_DET_LIMITS | WAYNE_F_ADD_READ_NOISE;
   const bool allon = !f64 && !exact && sky_mode == 1 && !noise && (d.flags & all_on) == all_on && c->has_dark && c->has_lin;
@@ -775,7 +777,7 @@ void (*select_ramp(const wayne_ctx* c, const Slot& s, std::string* name, RampTra
   if (trap) *trap = s.traps_on && !with_hist ? pick_ramp_trap(out, exact, sky_mode, noise, allon) : nullptr;
   if (hist) *hist = with_hist ? pick_ramp_hist(out, exact, sky_mode, noise, allon) : nullptr;
   if (name) {
-    const bool pinned = !exact && sky_mode != 0 && !noise;      // ramp_kernel(): k_ramp where it fits 64 registers, else k_ramp_wide
+    const bool pinned = !exact && sky_mode != 0 && !noise;      // ramp_variant(): k_ramp where it fits 64 registers, else k_ramp_wide
     char buf[96];
     if (s.traps_on)
       std::snprintf(buf, sizeof buf, "%s<%s, %s, %d, %s, %s>", with_hist ? "k_ramp_hist" : "k_ramp_trap", out_name,
@@ -1109,7 +1111,7 @@ int launch_ima(wayne_ctx* c, Slot& s) {
 void ex_clear(Slot& s) {
   s.extract_on = s.crrej_on = s.chan_on = s.var_on = s.opt_on = s.optch_on = false;
   s.prof_deliver = s.prof_fetched = s.prof_valid = s.prof_fixed = false;
-  s.ex_pinned_misc = nullptr;
+  s.ex_pinned.misc = nullptr;
   s.ex_base = nullptr;
 }
 
@@ -1121,7 +1123,7 @@ void ex_clear(Slot& s) {
 int ex_relayout(wayne_ctx* c, Slot& s) {
   const int C = s.chan_on ? s.ch_C : 0;
   s.lay = plan::spectra_layout(c->S, s.R, s.crrej_on, C, s.var_on, s.opt_on, s.optch_on);
-  s.ex_pinned_misc = nullptr;
+  s.ex_pinned.misc = nullptr;
   s.ex_base = nullptr;
   (void)hipSetDevice(c->device);
   const hipError_t e = s.ex_out.reserve(plan::spectra_layout(c->S, s.R, true, C, s.var_on, s.opt_on, s.optch_on).bytes);
@@ -1130,17 +1132,53 @@ int ex_relayout(wayne_ctx* c, Slot& s) {
   return WAYNE_OK;
 }
 
-// What the extraction's entry points may ask of a slot beyond an upload, and the head they share: the context, the slot
-// number and the switches `need` names, refused as `who`: `missing`.  *sp: the slot.
-enum : unsigned { EX_ON = 1, EX_CRREJ = 2, EX_CHAN = 4, EX_VAR = 8, EX_OPT = 16, EX_OPTCH = 32, EX_PROF = 64 };
-int ex_gate(wayne_ctx* c, int slot, const char* who, unsigned need, const char* missing, Slot** sp) {
+// The head of an entry point that takes a slot: the context, the slot number ("<who>: slot") and the upload ("<who>: slot
+// not uploaded").  *sp: the slot.  A head that says anything else -- run_back, wait, debug_depth, upload, which needs no
+// upload, device_reads, which returns a pointer -- is written out where it stands.
+int slot_gate(wayne_ctx* c, int slot, const char* who, Slot** sp) {
   if (!c) return WAYNE_E_INVALID;
   if (slot < 0 || slot >= kSlots) return fail(c, WAYNE_E_INVALID, std::string(who) + ": slot");
-  Slot& s = c->slots[slot];
+  *sp = &c->slots[slot];
+  if (!(*sp)->uploaded) return fail(c, WAYNE_E_STATE, std::string(who) + ": slot not uploaded");
+  return WAYNE_OK;
+}
+
+// What the extraction's entry points may ask of a slot beyond an upload, and the head they share: slot_gate, then the
+// switches `need` names, refused as `who`: `missing` -- the words for a slot that is not uploaded either.
+enum : unsigned { EX_ON = 1, EX_CRREJ = 2, EX_CHAN = 4, EX_VAR = 8, EX_OPT = 16, EX_OPTCH = 32, EX_PROF = 64 };
+int ex_gate(wayne_ctx* c, int slot, const char* who, unsigned need, const char* missing, Slot** sp) {
+  const int rc = slot_gate(c, slot, who, sp);
+  if (rc && rc != WAYNE_E_STATE) return rc;
+  const Slot& s = **sp;
   const unsigned have = (s.extract_on ? EX_ON : 0) | (s.crrej_on ? EX_CRREJ : 0) | (s.chan_on ? EX_CHAN : 0) | (s.var_on ? EX_VAR : 0) |
                         (s.opt_on ? EX_OPT : 0) | (s.optch_on ? EX_OPTCH : 0) | (s.prof_deliver ? EX_PROF : 0);
-  if (!s.uploaded || (need & ~have)) return fail(c, WAYNE_E_STATE, std::string(who) + ": " + missing);
-  *sp = &s;
+  if (rc || (need & ~have)) return fail(c, WAYNE_E_STATE, std::string(who) + ": " + missing);
+  return WAYNE_OK;
+}
+
+// launches and milliseconds of profiled kernel `pk` since wayne_profile_reset (either pointer may be null)
+int kernel_profile(wayne_ctx* c, int pk, uint64_t* launches, double* ms) {
+  if (!c) return WAYNE_E_INVALID;
+  int rc = collect_profile(c);
+  if (rc) return rc;
+  if (launches) *launches = c->prof_launches[pk];
+  if (ms) *ms = c->prof_ms[pk];
+  return WAYNE_OK;
+}
+
+int PinnedMirror::fetch(wayne_ctx* c, int slot, const void* dev, size_t bytes, bool record_kdone, const char* nomem) {
+  const Slot& s = c->slots[slot];
+  const size_t tail = align64(bytes);
+  misc = nullptr;
+  if (!buf.reserve(tail + 64)) return fail(c, WAYNE_E_NOMEM, nomem);
+  misc = (SlotMisc*)(buf.p + tail);
+  if (record_kdone && c->n_streams == 2 && c->ev_kdone[slot % 2]) {
+    HIP_TRY(c, hipEventRecord(c->ev_kdone[slot % 2], c->stream));
+    c->kdone_valid[slot % 2] = true;
+  }
+  HIP_TRY(c, hipMemcpyAsync(buf.p, dev, bytes, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(misc, s.misc.p, sizeof(SlotMisc), hipMemcpyDeviceToHost, c->stream));
+  run = s.run_no;
   return WAYNE_OK;
 }
 constexpr const char* kNoExtraction = "no extraction set for the slot";
@@ -1302,6 +1340,34 @@ static int settle(wayne_ctx* c) {
   }
   return err;
 }
+
+}  // extern "C"
+
+namespace {
+// A blocking download of slot `slot`, settled: `copy` enqueues the caller's copies on c->stream (the slot's), the status
+// word is read behind them, and an exposure that has to be run a second time is, with k_throw -- it is then extracted,
+// fitted, calibrated and rendered again -- and copied and looked at once more.  What every wayne_exposure_download* runs,
+// and wayne_exposure_run_checked with nothing to copy.  (Whether the slot has been run at all is the caller's to ask:
+// download_rampfit and download_ima refuse before a run, download, download_spectra, download_fits and
+// download_expected deliver what the buffer holds.)
+template <class Copy>
+int download_settled(wayne_ctx* c, int slot, Copy&& copy) {
+  bool reran = false;
+  int rc = copy();
+  if (rc || (rc = look_at_status(c, slot, nullptr, wayne_exposure_run, &reran)) || !reran) return rc;
+  if ((rc = copy())) return rc;
+  return look_at_status(c, slot, nullptr);
+}
+// ... of one buffer
+int download_settled(wayne_ctx* c, int slot, void* dst, const void* dev, size_t bytes) {
+  return download_settled(c, slot, [&]() -> int {
+    HIP_TRY(c, hipMemcpyAsync(dst, dev, bytes, hipMemcpyDeviceToHost, c->stream));
+    return WAYNE_OK;
+  });
+}
+}  // namespace
+
+extern "C" {
 
 int wayne_ctx_synchronize(wayne_ctx* c) {
   if (!c) return WAYNE_E_INVALID;
@@ -1640,7 +1706,7 @@ int wayne_exposure_upload(wayne_ctx* c, int slot, const wayne_exposure_desc* d) 
   s.hist_on = false;         // ... nor a carried history (wayne_exposure_set_trap_history)
   ex_clear(s);               // ... and no spectral extraction, nor any option of it, until wayne_exposure_set_extraction says so
   s.fits_on = false;         // ... and no FITS words until wayne_exposure_set_fits says so
-  s.fits_pinned_misc = nullptr;
+  s.fits_pinned.misc = nullptr;
   s.expect_mode = 0;         // ... and no expected image until wayne_exposure_set_expected says so
   s.rampfit_on = s.rampfit_ran = false;   // ... and no ramp fit until wayne_exposure_set_rampfit says so
   s.ima_on = s.ima_ran = false;           // ... and no calibrated reads until wayne_exposure_set_ima says so
@@ -1982,10 +2048,9 @@ static void lc_rule(float* x, float* w, float* d) {
 }
 
 int wayne_exposure_run_front(wayne_ctx* c, int slot) {
-  if (!c) return WAYNE_E_INVALID;
-  if (slot < 0 || slot >= kSlots) return fail(c, WAYNE_E_INVALID, "run: slot");
-  Slot& s = c->slots[slot];
-  if (!s.uploaded) return fail(c, WAYNE_E_STATE, "run: slot not uploaded");
+  Slot* sp;
+  if (int rc = slot_gate(c, slot, "run", &sp)) return rc;
+  Slot& s = *sp;
   // a supplied profile is laid out for its own window heights: refused before anything is enqueued, the slot stays usable
   if (s.extract_on && s.opt_on && s.prof_fixed && !plan::profile_rows_match(c->S, s.R, s.ex.steps, s.ex.row_lo, s.ex.row_hi, s.prof_rows))
     return fail(c, WAYNE_E_INVALID, "run: the optimal profile was made for other window heights than the extraction's");
@@ -2201,12 +2266,11 @@ int wayne_exposure_run_back(wayne_ctx* c, int slot) {
 }
 
 int wayne_exposure_ramp_variant(wayne_ctx* c, int slot, char* buf, int cap) {
-  if (!c || !buf || cap <= 0) return WAYNE_E_INVALID;
-  if (slot < 0 || slot >= kSlots) return fail(c, WAYNE_E_INVALID, "ramp_variant: slot");
-  const Slot& s = c->slots[slot];
-  if (!s.uploaded) return fail(c, WAYNE_E_STATE, "ramp_variant: slot not uploaded");
+  if (!buf || cap <= 0) return WAYNE_E_INVALID;
+  Slot* sp;
+  if (int rc = slot_gate(c, slot, "ramp_variant", &sp)) return rc;
   std::string name;
-  (void)select_ramp(c, s, &name);
+  (void)select_ramp(c, *sp, &name);
   std::snprintf(buf, (size_t)cap, "%s", name.c_str());
   return WAYNE_OK;
 }
@@ -2218,10 +2282,10 @@ int wayne_exposure_run(wayne_ctx* c, int slot) {
 }
 
 int wayne_exposure_status(wayne_ctx* c, int slot, int* status) {
-  if (!c || !status) return WAYNE_E_INVALID;
-  if (slot < 0 || slot >= kSlots) return fail(c, WAYNE_E_INVALID, "status: slot");
-  Slot& s = c->slots[slot];
-  if (!s.uploaded) return fail(c, WAYNE_E_STATE, "status: slot not uploaded");
+  if (!status) return WAYNE_E_INVALID;
+  Slot* sp;
+  if (int rc = slot_gate(c, slot, "status", &sp)) return rc;
+  Slot& s = *sp;
   (void)hipSetDevice(c->device);
   use_slot_stream(c, slot);
   Slot::Misc m{};
@@ -2238,72 +2302,50 @@ unsigned long long wayne_ctx_profile_uploads(const wayne_ctx* c) { return c ? (u
 int wayne_exposure_run_checked(wayne_ctx* c, int slot) {
   int rc = wayne_exposure_run(c, slot);
   if (rc) return rc;
-  bool reran = false;
-  if ((rc = look_at_status(c, slot, nullptr, wayne_exposure_run, &reran)) || !reran) return rc;
-  return look_at_status(c, slot, nullptr);
+  return download_settled(c, slot, [] { return WAYNE_OK; });
 }
 
 int wayne_exposure_download(wayne_ctx* c, int slot, void* out_reads) {
-  if (!c || !out_reads) return WAYNE_E_INVALID;
-  if (slot < 0 || slot >= kSlots) return fail(c, WAYNE_E_INVALID, "download: slot");
-  Slot& s = c->slots[slot];
-  if (!s.uploaded) return fail(c, WAYNE_E_STATE, "download: slot not uploaded");
+  if (!out_reads) return WAYNE_E_INVALID;
+  Slot* sp;
+  if (int rc = slot_gate(c, slot, "download", &sp)) return rc;
+  Slot& s = *sp;
   (void)hipSetDevice(c->device);
   use_slot_stream(c, slot);
-  const size_t SS = (size_t)c->S * c->S;
-  const size_t out_elem = out_elem_size(s.d.flags);
-  HIP_TRY(c, hipMemcpyAsync(out_reads, s.out.p, (size_t)(s.R + 1) * SS * out_elem, hipMemcpyDeviceToHost, c->stream));
-  bool reran = false;
-  int rc = look_at_status(c, slot, nullptr, wayne_exposure_run, &reran);
-  if (rc || !reran) return rc;
-  HIP_TRY(c, hipMemcpyAsync(out_reads, s.out.p, (size_t)(s.R + 1) * SS * out_elem, hipMemcpyDeviceToHost, c->stream));
-  return look_at_status(c, slot, nullptr);
+  return download_settled(c, slot, out_reads, s.out.p, (size_t)(s.R + 1) * c->S * c->S * out_elem_size(s.d.flags));
 }
 
 int wayne_exposure_fetch_async(wayne_ctx* c, int slot) {
-  if (!c) return WAYNE_E_INVALID;
-  if (slot < 0 || slot >= kSlots) return fail(c, WAYNE_E_INVALID, "fetch_async: slot");
-  Slot& s = c->slots[slot];
-  if (!s.uploaded) return fail(c, WAYNE_E_STATE, "fetch_async: slot not uploaded");
+  Slot* sp;
+  if (int rc = slot_gate(c, slot, "fetch_async", &sp)) return rc;
+  Slot& s = *sp;
   (void)hipSetDevice(c->device);
   use_slot_stream(c, slot);
-  const size_t SS = (size_t)c->S * c->S;
-  const size_t bytes = (size_t)(s.R + 1) * SS * out_elem_size(s.d.flags);
-  const size_t tail = align64(bytes);
-  s.pinned_misc = nullptr;
-  if (!s.pinned.reserve(tail + 64)) return fail(c, WAYNE_E_NOMEM, "fetch_async: pinned host allocation failed");
-  s.pinned_misc = (Slot::Misc*)(s.pinned.p + tail);
   // The copy follows the slot's kernels on the slot's own stream: while it runs (1.2 ms at 55 GB/s for a full
   // frame) the kernels of the exposure in the next slot run on the other stream.  (A separate copy stream fed by
   // events was measured: 660-700 exposures/s instead of 810-826 -- scripts/probe_pipeline.py.)
-  if (c->n_streams == 2 && c->ev_kdone[slot % 2]) {
-    HIP_TRY(c, hipEventRecord(c->ev_kdone[slot % 2], c->stream));
-    c->kdone_valid[slot % 2] = true;
-  }
-  HIP_TRY(c, hipMemcpyAsync(s.pinned.p, s.out.p, bytes, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(s.pinned_misc, s.misc.p, sizeof(Slot::Misc), hipMemcpyDeviceToHost, c->stream));
-  s.pinned_run = s.run_no;
-  return WAYNE_OK;
+  return s.pinned.fetch(c, slot, s.out.p, (size_t)(s.R + 1) * c->S * c->S * out_elem_size(s.d.flags), true,
+                        "fetch_async: pinned host allocation failed");
 }
 
 int wayne_exposure_wait(wayne_ctx* c, int slot, void** host_reads) {
   if (!c || !host_reads) return WAYNE_E_INVALID;
   if (slot < 0 || slot >= kSlots) return fail(c, WAYNE_E_INVALID, "wait: slot");
   Slot& s = c->slots[slot];
-  if (!s.uploaded || !s.pinned.p || !s.pinned_misc) return fail(c, WAYNE_E_STATE, "wait: fetch_async first");
+  if (!s.uploaded || !s.pinned.fetched()) return fail(c, WAYNE_E_STATE, "wait: fetch_async first");
   (void)hipSetDevice(c->device);
   use_slot_stream(c, slot);
   HIP_TRY(c, hipStreamSynchronize(c->stream));
-  *host_reads = s.pinned.p;
+  *host_reads = s.pinned.buf.p;
   bool reran = false;                        // (the status word came with the reads)
-  int rc = look_at_status(c, slot, s.pinned_misc, wayne_exposure_run, &reran, s.pinned_run);
+  int rc = look_at_status(c, slot, s.pinned.misc, wayne_exposure_run, &reran, s.pinned.run);
   if (rc || !reran) return rc;
   if ((rc = wayne_exposure_fetch_async(c, slot))) return rc;     // a bin beyond the lanes' reach: once more, with k_throw
   // (spectra fetched beside the reads are those of the first run: fetched again too, with the second run's status word)
-  if (s.extract_on && s.ex_pinned_misc && (rc = wayne_exposure_fetch_spectra_async(c, slot))) return rc;
-  if (s.fits_on && s.fits_pinned_misc && (rc = wayne_exposure_fetch_fits_async(c, slot))) return rc;   // (... and FITS words likewise)
+  if (s.extract_on && s.ex_pinned.misc && (rc = wayne_exposure_fetch_spectra_async(c, slot))) return rc;
+  if (s.fits_on && s.fits_pinned.misc && (rc = wayne_exposure_fetch_fits_async(c, slot))) return rc;   // (... and FITS words likewise)
   HIP_TRY(c, hipStreamSynchronize(c->stream));
-  return look_at_status(c, slot, s.pinned_misc, nullptr, nullptr, s.pinned_run);
+  return look_at_status(c, slot, s.pinned.misc, nullptr, nullptr, s.pinned.run);
 }
 
 void* wayne_exposure_device_reads(wayne_ctx* c, int slot) {
@@ -2320,10 +2362,9 @@ int wayne_exposure_synthesize(wayne_ctx* c, const wayne_exposure_desc* d, void* 
 
 // debug_fetch of source `src` of the slot (0 = the target; acc_e is the slot's, shared by all sources)
 static int fetch_source(wayne_ctx* c, int slot, int src, int32_t* counts, double* x_pos, double* y_pos, double* acc_e) {
-  if (!c) return WAYNE_E_INVALID;
-  if (slot < 0 || slot >= kSlots) return fail(c, WAYNE_E_INVALID, "debug_fetch: slot");
-  Slot& s = c->slots[slot];
-  if (!s.uploaded) return fail(c, WAYNE_E_STATE, "debug_fetch: slot not uploaded");
+  Slot* sp;
+  if (int rc = slot_gate(c, slot, "debug_fetch", &sp)) return rc;
+  Slot& s = *sp;
   if (src < 0 || src > s.n_extra) return fail(c, WAYNE_E_INVALID, "debug_fetch: no such source in this slot");
   SourceState& ss = s.source(src);
   (void)hipSetDevice(c->device);
@@ -2371,10 +2412,10 @@ int wayne_exposure_debug_fetch_source(wayne_ctx* c, int slot, int source, int32_
 }
 
 int wayne_exposure_debug_boxes(wayne_ctx* c, int slot, int32_t* boxes, int32_t* segments, int* use_box) {
-  if (!c || !boxes || !segments || !use_box) return WAYNE_E_INVALID;
-  if (slot < 0 || slot >= kSlots) return fail(c, WAYNE_E_INVALID, "debug_boxes: slot");
-  Slot& s = c->slots[slot];
-  if (!s.uploaded) return fail(c, WAYNE_E_STATE, "debug_boxes: slot not uploaded");
+  if (!boxes || !segments || !use_box) return WAYNE_E_INVALID;
+  Slot* sp;
+  if (int rc = slot_gate(c, slot, "debug_boxes", &sp)) return rc;
+  Slot& s = *sp;
   *use_box = s.use_box ? 1 : 0;
   const int S = c->S;
   // (a coupled slot: the boxes k_ramp gets, a pixel wider on every side)
@@ -2416,10 +2457,9 @@ int wayne_exposure_debug_depth(wayne_ctx* c, int slot, double* depth) {
 // ---------------------------------------------------------------------------
 
 int wayne_exposure_set_sources(wayne_ctx* c, int slot, const wayne_source_desc* src, int n) {
-  if (!c) return WAYNE_E_INVALID;
-  if (slot < 0 || slot >= kSlots) return fail(c, WAYNE_E_INVALID, "set_sources: slot");
-  Slot& s = c->slots[slot];
-  if (!s.uploaded) return fail(c, WAYNE_E_STATE, "set_sources: slot not uploaded");
+  Slot* sp;
+  if (int rc = slot_gate(c, slot, "set_sources", &sp)) return rc;
+  Slot& s = *sp;
   if (n < 0 || n > kMaxSources) return fail(c, WAYNE_E_INVALID, "set_sources: n must be 0 .. WAYNE_MAX_SOURCES");
   if (n > 0 && !src) return fail(c, WAYNE_E_INVALID, "set_sources: null list");
   if (n > 0 && s.d.rng_mode == WAYNE_RNG_REPLAY)
@@ -2504,10 +2544,9 @@ int wayne_exposure_set_sources(wayne_ctx* c, int slot, const wayne_source_desc* 
 // ---------------------------------------------------------------------------
 
 int wayne_exposure_set_limb_darkening(wayne_ctx* c, int slot, const double* ld, int n_wl) {
-  if (!c) return WAYNE_E_INVALID;
-  if (slot < 0 || slot >= kSlots) return fail(c, WAYNE_E_INVALID, "set_limb_darkening: slot");
-  Slot& s = c->slots[slot];
-  if (!s.uploaded) return fail(c, WAYNE_E_STATE, "set_limb_darkening: slot not uploaded");
+  Slot* sp;
+  if (int rc = slot_gate(c, slot, "set_limb_darkening", &sp)) return rc;
+  Slot& s = *sp;
   s.ld_on = false;                // from here on a refusal leaves the slot usable, without a table
   s.spots_on = false;             // (spots were checked against the coefficients they were set with: set them again)
   s.front_done = false;           // (the depth matrix of the last front half is not this setting's)
@@ -2558,10 +2597,9 @@ void wayne_spot_rule(double nodes[10], double weights[10]) {
 }
 
 int wayne_exposure_set_spots(wayne_ctx* c, int slot, const wayne_spots_desc* sp, int n_wl, int n_sub) {
-  if (!c) return WAYNE_E_INVALID;
-  if (slot < 0 || slot >= kSlots) return fail(c, WAYNE_E_INVALID, "set_spots: slot");
-  Slot& s = c->slots[slot];
-  if (!s.uploaded) return fail(c, WAYNE_E_STATE, "set_spots: slot not uploaded");
+  Slot* slotp;
+  if (int rc = slot_gate(c, slot, "set_spots", &slotp)) return rc;
+  Slot& s = *slotp;
   s.spots_on = false;             // from here on a refusal leaves the slot usable, with a clean star
   s.front_done = false;           // (the depth matrix of the last front half is not this setting's)
   if (!sp || sp->n == 0) return WAYNE_OK;
@@ -2624,24 +2662,16 @@ int wayne_exposure_set_spots(wayne_ctx* c, int slot, const wayne_spots_desc* sp,
   return WAYNE_OK;
 }
 
-int wayne_spots_profile(wayne_ctx* c, uint64_t* launches, double* ms) {
-  if (!c) return WAYNE_E_INVALID;
-  int rc = collect_profile(c);
-  if (rc) return rc;
-  if (launches) *launches = c->prof_launches[PK_SPOTS];
-  if (ms) *ms = c->prof_ms[PK_SPOTS];
-  return WAYNE_OK;
-}
+int wayne_spots_profile(wayne_ctx* c, uint64_t* launches, double* ms) { return kernel_profile(c, PK_SPOTS, launches, ms); }
 
 // ---------------------------------------------------------------------------
 // charge trapping
 // ---------------------------------------------------------------------------
 
 int wayne_exposure_set_traps(wayne_ctx* c, int slot, const wayne_trap_desc* t) {
-  if (!c) return WAYNE_E_INVALID;
-  if (slot < 0 || slot >= kSlots) return fail(c, WAYNE_E_INVALID, "set_traps: slot");
-  Slot& s = c->slots[slot];
-  if (!s.uploaded) return fail(c, WAYNE_E_STATE, "set_traps: slot not uploaded");
+  Slot* sp;
+  if (int rc = slot_gate(c, slot, "set_traps", &sp)) return rc;
+  Slot& s = *sp;
   s.traps_on = false;             // from here on a refusal leaves the slot usable, without traps
   s.hist_on = false;              // (a history belongs to the traps it was set after)
   if (!t) return WAYNE_OK;
@@ -2745,10 +2775,9 @@ int wayne_ctx_trap_state_download(wayne_ctx* c, float* state) {
 }
 
 int wayne_exposure_set_trap_history(wayne_ctx* c, int slot, const wayne_trap_history_desc* h) {
-  if (!c) return WAYNE_E_INVALID;
-  if (slot < 0 || slot >= kSlots) return fail(c, WAYNE_E_INVALID, "set_trap_history: slot");
-  Slot& s = c->slots[slot];
-  if (!s.uploaded) return fail(c, WAYNE_E_STATE, "set_trap_history: slot not uploaded");
+  Slot* sp;
+  if (int rc = slot_gate(c, slot, "set_trap_history", &sp)) return rc;
+  Slot& s = *sp;
   s.hist_on = false;              // from here on a refusal leaves the slot usable, without a history
   if (!h) return WAYNE_OK;
   if (!s.traps_on) return fail(c, WAYNE_E_STATE, "set_trap_history: wayne_exposure_set_traps first");
@@ -2773,7 +2802,7 @@ int wayne_exposure_set_trap_history(wayne_ctx* c, int slot, const wayne_trap_his
 
 int wayne_exposure_set_extraction(wayne_ctx* c, int slot, const wayne_extract_desc* x) {
   Slot* sp;
-  if (int rc = ex_gate(c, slot, "set_extraction", 0, "slot not uploaded", &sp)) return rc;
+  if (int rc = slot_gate(c, slot, "set_extraction", &sp)) return rc;
   Slot& s = *sp;
   ex_clear(s);                    // from here on a refusal leaves the slot usable, without extraction
   if (!x) return WAYNE_OK;
@@ -2877,47 +2906,40 @@ int wayne_exposure_set_optimal(wayne_ctx* c, int slot, const wayne_optimal_desc*
 
 int wayne_exposure_fetch_spectra_async(wayne_ctx* c, int slot) {
   Slot* sp;
-  if (int rc = ex_gate(c, slot, "fetch_spectra_async", 0, "slot not uploaded", &sp)) return rc;
+  if (int rc = slot_gate(c, slot, "fetch_spectra_async", &sp)) return rc;
   Slot& s = *sp;
   if (!s.extract_on) return fail(c, WAYNE_E_STATE, "fetch_spectra_async: no extraction set for the slot");
   (void)hipSetDevice(c->device);
   use_slot_stream(c, slot);
-  const size_t bytes = s.lay.bytes, tail = align64(bytes);
-  s.ex_pinned_misc = nullptr;
-  if (!s.ex_pinned.reserve(tail + 64)) return fail(c, WAYNE_E_NOMEM, "fetch_spectra_async: pinned host allocation failed");
-  s.ex_pinned_misc = (Slot::Misc*)(s.ex_pinned.p + tail);
   // (120 KB behind the slot's kernels on its own stream: nothing here for the other stream to keep out of phase with)
-  HIP_TRY(c, hipMemcpyAsync(s.ex_pinned.p, s.ex_out.p, bytes, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(s.ex_pinned_misc, s.misc.p, sizeof(Slot::Misc), hipMemcpyDeviceToHost, c->stream));
-  s.ex_pinned_run = s.run_no;
-  return WAYNE_OK;
+  return s.ex_pinned.fetch(c, slot, s.ex_out.p, s.lay.bytes, false, "fetch_spectra_async: pinned host allocation failed");
 }
 
 int wayne_exposure_wait_spectra(wayne_ctx* c, int slot, double** spectra, double** sky) {
   if (!spectra || !sky) return WAYNE_E_INVALID;
   Slot* sp;
-  if (int rc = ex_gate(c, slot, "wait_spectra", 0, "slot not uploaded", &sp)) return rc;
+  if (int rc = slot_gate(c, slot, "wait_spectra", &sp)) return rc;
   Slot& s = *sp;
   if (!s.extract_on) return fail(c, WAYNE_E_STATE, "wait_spectra: no extraction set for the slot");
-  if (!s.ex_pinned.p || !s.ex_pinned_misc) return fail(c, WAYNE_E_STATE, "wait_spectra: fetch_spectra_async first");
+  if (!s.ex_pinned.fetched()) return fail(c, WAYNE_E_STATE, "wait_spectra: fetch_spectra_async first");
   (void)hipSetDevice(c->device);
   use_slot_stream(c, slot);
   HIP_TRY(c, hipStreamSynchronize(c->stream));
-  s.ex_base = s.ex_pinned.p;
-  *spectra = (double*)(s.ex_pinned.p + s.lay.spectra);
-  *sky = (double*)(s.ex_pinned.p + s.lay.sky);
+  s.ex_base = s.ex_pinned.buf.p;
+  *spectra = (double*)(s.ex_pinned.buf.p + s.lay.spectra);
+  *sky = (double*)(s.ex_pinned.buf.p + s.lay.sky);
   bool reran = false;                        // (the status word came with the spectra)
-  int rc = look_at_status(c, slot, s.ex_pinned_misc, wayne_exposure_run, &reran, s.ex_pinned_run);
+  int rc = look_at_status(c, slot, s.ex_pinned.misc, wayne_exposure_run, &reran, s.ex_pinned.run);
   if (rc || !reran) return rc;
   if ((rc = wayne_exposure_fetch_spectra_async(c, slot))) return rc;     // a bin beyond the lanes' reach: once more, with k_throw
   HIP_TRY(c, hipStreamSynchronize(c->stream));
-  return look_at_status(c, slot, s.ex_pinned_misc, nullptr, nullptr, s.ex_pinned_run);
+  return look_at_status(c, slot, s.ex_pinned.misc, nullptr, nullptr, s.ex_pinned.run);
 }
 
 int wayne_exposure_download_spectra(wayne_ctx* c, int slot, double* spectra, double* sky) {
   if (!spectra || !sky) return WAYNE_E_INVALID;
   Slot* sp;
-  if (int rc = ex_gate(c, slot, "download_spectra", 0, "slot not uploaded", &sp)) return rc;
+  if (int rc = slot_gate(c, slot, "download_spectra", &sp)) return rc;
   Slot& s = *sp;
   if (!s.extract_on) return fail(c, WAYNE_E_STATE, "download_spectra: no extraction set for the slot");
   (void)hipSetDevice(c->device);
@@ -2929,20 +2951,13 @@ int wayne_exposure_download_spectra(wayne_ctx* c, int slot, double* spectra, dou
   s.ex_host.resize((l.bytes + 7) / 8);
   char* const host = (char*)s.ex_host.data();
   s.ex_base = host;
-  auto copy = [&]() -> int {
+  return download_settled(c, slot, [&]() -> int {
     HIP_TRY(c, hipMemcpyAsync(spectra, (const char*)s.ex_out.p + l.spectra, l.sky - l.spectra, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipMemcpyAsync(sky, (const char*)s.ex_out.p + l.sky, head - l.sky, hipMemcpyDeviceToHost, c->stream));
     if (l.bytes > head)
       HIP_TRY(c, hipMemcpyAsync(host + head, (const char*)s.ex_out.p + head, l.bytes - head, hipMemcpyDeviceToHost, c->stream));
     return WAYNE_OK;
-  };
-  int rc = copy();
-  if (rc) return rc;
-  bool reran = false;
-  rc = look_at_status(c, slot, nullptr, wayne_exposure_run, &reran);
-  if (rc || !reran) return rc;
-  if ((rc = copy())) return rc;
-  return look_at_status(c, slot, nullptr);
+  });
 }
 
 // A region of the block the slot's last wait_spectra / download_spectra brought back (null: the region is off).
@@ -3112,14 +3127,7 @@ int wayne_exposure_download_crmask(wayne_ctx* c, int slot, uint16_t* mask) {
   return WAYNE_OK;
 }
 
-int wayne_extract_profile(wayne_ctx* c, uint64_t* launches, double* ms) {
-  if (!c) return WAYNE_E_INVALID;
-  int rc = collect_profile(c);
-  if (rc) return rc;
-  if (launches) *launches = c->prof_launches[PK_EXTRACT];
-  if (ms) *ms = c->prof_ms[PK_EXTRACT];
-  return WAYNE_OK;
-}
+int wayne_extract_profile(wayne_ctx* c, uint64_t* launches, double* ms) { return kernel_profile(c, PK_EXTRACT, launches, ms); }
 
 // ---------------------------------------------------------------------------
 // device-side FITS words
@@ -3129,12 +3137,11 @@ int wayne_fits_layout(int S, int R, uint32_t out_flags, size_t* plane_bytes, siz
 }
 
 int wayne_exposure_set_fits(wayne_ctx* c, int slot, int on) {
-  if (!c) return WAYNE_E_INVALID;
-  if (slot < 0 || slot >= kSlots) return fail(c, WAYNE_E_INVALID, "set_fits: slot");
-  Slot& s = c->slots[slot];
-  if (!s.uploaded) return fail(c, WAYNE_E_STATE, "set_fits: slot not uploaded");
+  Slot* sp;
+  if (int rc = slot_gate(c, slot, "set_fits", &sp)) return rc;
+  Slot& s = *sp;
   s.fits_on = false;           // from here on a refusal leaves the slot usable, without FITS words
-  s.fits_pinned_misc = nullptr;
+  s.fits_pinned.misc = nullptr;
   if (!on) return WAYNE_OK;
   size_t pb = 0, stride = 0;
   if (!fits_layout(c->S, s.R, s.d.flags, &pb, &stride, nullptr)) return fail(c, WAYNE_E_INVALID, "set_fits: no layout for this side");
@@ -3147,87 +3154,62 @@ int wayne_exposure_set_fits(wayne_ctx* c, int slot, int on) {
 }
 
 int wayne_exposure_fetch_fits_async(wayne_ctx* c, int slot) {
-  if (!c) return WAYNE_E_INVALID;
-  if (slot < 0 || slot >= kSlots) return fail(c, WAYNE_E_INVALID, "fetch_fits_async: slot");
-  Slot& s = c->slots[slot];
-  if (!s.uploaded) return fail(c, WAYNE_E_STATE, "fetch_fits_async: slot not uploaded");
+  Slot* sp;
+  if (int rc = slot_gate(c, slot, "fetch_fits_async", &sp)) return rc;
+  Slot& s = *sp;
   if (!s.fits_on) return fail(c, WAYNE_E_STATE, "fetch_fits_async: no FITS words set for the slot");
   (void)hipSetDevice(c->device);
   use_slot_stream(c, slot);
-  const size_t bytes = (size_t)(s.R + 1) * s.fits_stride, tail = align64(bytes);
-  s.fits_pinned_misc = nullptr;
-  if (!s.fits_pinned.reserve(tail + 64)) return fail(c, WAYNE_E_NOMEM, "fetch_fits_async: pinned host allocation failed");
-  s.fits_pinned_misc = (Slot::Misc*)(s.fits_pinned.p + tail);
-  // (the exposure on the other stream waits for this one's kernels, not for its copy: as wayne_exposure_fetch_async --
-  // which has made the record already when this run's reads were fetched in front of the payload)
-  if (c->n_streams == 2 && c->ev_kdone[slot % 2] && !(s.pinned_misc && s.pinned_run == s.run_no)) {
-    HIP_TRY(c, hipEventRecord(c->ev_kdone[slot % 2], c->stream));
-    c->kdone_valid[slot % 2] = true;
-  }
-  HIP_TRY(c, hipMemcpyAsync(s.fits_pinned.p, s.fits_dev.p, bytes, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(s.fits_pinned_misc, s.misc.p, sizeof(Slot::Misc), hipMemcpyDeviceToHost, c->stream));
-  s.fits_pinned_run = s.run_no;
-  return WAYNE_OK;
+  // (the record of the kernels' end, as wayne_exposure_fetch_async -- which has made it already when this run's reads
+  // were fetched in front of the payload)
+  return s.fits_pinned.fetch(c, slot, s.fits_dev.p, (size_t)(s.R + 1) * s.fits_stride, !(s.pinned.misc && s.pinned.run == s.run_no),
+                             "fetch_fits_async: pinned host allocation failed");
 }
 
 int wayne_exposure_wait_fits(wayne_ctx* c, int slot, void** host_payload) {
-  if (!c || !host_payload) return WAYNE_E_INVALID;
-  if (slot < 0 || slot >= kSlots) return fail(c, WAYNE_E_INVALID, "wait_fits: slot");
-  Slot& s = c->slots[slot];
-  if (!s.uploaded) return fail(c, WAYNE_E_STATE, "wait_fits: slot not uploaded");
+  if (!host_payload) return WAYNE_E_INVALID;
+  Slot* sp;
+  if (int rc = slot_gate(c, slot, "wait_fits", &sp)) return rc;
+  Slot& s = *sp;
   if (!s.fits_on) return fail(c, WAYNE_E_STATE, "wait_fits: no FITS words set for the slot");
-  if (!s.fits_pinned.p || !s.fits_pinned_misc) return fail(c, WAYNE_E_STATE, "wait_fits: fetch_fits_async first");
+  if (!s.fits_pinned.fetched()) return fail(c, WAYNE_E_STATE, "wait_fits: fetch_fits_async first");
   (void)hipSetDevice(c->device);
   use_slot_stream(c, slot);
   HIP_TRY(c, hipStreamSynchronize(c->stream));
-  *host_payload = s.fits_pinned.p;
-  const uint32_t first_run = s.fits_pinned_run;
+  *host_payload = s.fits_pinned.buf.p;
+  const uint32_t first_run = s.fits_pinned.run;
   bool reran = false;                        // (the status word came with the payload)
-  int rc = look_at_status(c, slot, s.fits_pinned_misc, wayne_exposure_run, &reran, s.fits_pinned_run);
+  int rc = look_at_status(c, slot, s.fits_pinned.misc, wayne_exposure_run, &reran, s.fits_pinned.run);
   if (rc || !reran) return rc;
   if ((rc = wayne_exposure_fetch_fits_async(c, slot))) return rc;     // a bin beyond the lanes' reach: once more, with k_throw
   // (reads and spectra fetched beside the payload are those of the first run: fetched again too)
-  if (s.pinned_misc && s.pinned_run == first_run && (rc = wayne_exposure_fetch_async(c, slot))) return rc;
-  if (s.extract_on && s.ex_pinned_misc && (rc = wayne_exposure_fetch_spectra_async(c, slot))) return rc;
+  if (s.pinned.misc && s.pinned.run == first_run && (rc = wayne_exposure_fetch_async(c, slot))) return rc;
+  if (s.extract_on && s.ex_pinned.misc && (rc = wayne_exposure_fetch_spectra_async(c, slot))) return rc;
   HIP_TRY(c, hipStreamSynchronize(c->stream));
-  *host_payload = s.fits_pinned.p;
-  return look_at_status(c, slot, s.fits_pinned_misc, nullptr, nullptr, s.fits_pinned_run);
+  *host_payload = s.fits_pinned.buf.p;
+  return look_at_status(c, slot, s.fits_pinned.misc, nullptr, nullptr, s.fits_pinned.run);
 }
 
 int wayne_exposure_download_fits(wayne_ctx* c, int slot, void* out_payload) {
-  if (!c || !out_payload) return WAYNE_E_INVALID;
-  if (slot < 0 || slot >= kSlots) return fail(c, WAYNE_E_INVALID, "download_fits: slot");
-  Slot& s = c->slots[slot];
-  if (!s.uploaded) return fail(c, WAYNE_E_STATE, "download_fits: slot not uploaded");
+  if (!out_payload) return WAYNE_E_INVALID;
+  Slot* sp;
+  if (int rc = slot_gate(c, slot, "download_fits", &sp)) return rc;
+  Slot& s = *sp;
   if (!s.fits_on) return fail(c, WAYNE_E_STATE, "download_fits: no FITS words set for the slot");
   (void)hipSetDevice(c->device);
   use_slot_stream(c, slot);
-  const size_t bytes = (size_t)(s.R + 1) * s.fits_stride;
-  HIP_TRY(c, hipMemcpyAsync(out_payload, s.fits_dev.p, bytes, hipMemcpyDeviceToHost, c->stream));
-  bool reran = false;
-  int rc = look_at_status(c, slot, nullptr, wayne_exposure_run, &reran);
-  if (rc || !reran) return rc;
-  HIP_TRY(c, hipMemcpyAsync(out_payload, s.fits_dev.p, bytes, hipMemcpyDeviceToHost, c->stream));
-  return look_at_status(c, slot, nullptr);
+  return download_settled(c, slot, out_payload, s.fits_dev.p, (size_t)(s.R + 1) * s.fits_stride);
 }
 
-int wayne_fits_profile(wayne_ctx* c, uint64_t* launches, double* ms) {
-  if (!c) return WAYNE_E_INVALID;
-  int rc = collect_profile(c);
-  if (rc) return rc;
-  if (launches) *launches = c->prof_launches[PK_FITS];
-  if (ms) *ms = c->prof_ms[PK_FITS];
-  return WAYNE_OK;
-}
+int wayne_fits_profile(wayne_ctx* c, uint64_t* launches, double* ms) { return kernel_profile(c, PK_FITS, launches, ms); }
 
 // ---------------------------------------------------------------------------
 // the noise-free expected image
 // ---------------------------------------------------------------------------
 int wayne_exposure_set_expected(wayne_ctx* c, int slot, int mode) {
-  if (!c) return WAYNE_E_INVALID;
-  if (slot < 0 || slot >= kSlots) return fail(c, WAYNE_E_INVALID, "set_expected: slot");
-  Slot& s = c->slots[slot];
-  if (!s.uploaded) return fail(c, WAYNE_E_STATE, "set_expected: slot not uploaded");
+  Slot* sp;
+  if (int rc = slot_gate(c, slot, "set_expected", &sp)) return rc;
+  Slot& s = *sp;
   s.expect_mode = 0;           // from here on a refusal leaves the slot usable, without the expected image
   if (mode == 0) return WAYNE_OK;
   if (mode != WAYNE_EXPECT_COUNTS && mode != WAYNE_EXPECT_MEAN) return fail(c, WAYNE_E_INVALID, "set_expected: mode");
@@ -3241,39 +3223,25 @@ int wayne_exposure_set_expected(wayne_ctx* c, int slot, int mode) {
 }
 
 int wayne_exposure_download_expected(wayne_ctx* c, int slot, double* out) {
-  if (!c || !out) return WAYNE_E_INVALID;
-  if (slot < 0 || slot >= kSlots) return fail(c, WAYNE_E_INVALID, "download_expected: slot");
-  Slot& s = c->slots[slot];
-  if (!s.uploaded) return fail(c, WAYNE_E_STATE, "download_expected: slot not uploaded");
+  if (!out) return WAYNE_E_INVALID;
+  Slot* sp;
+  if (int rc = slot_gate(c, slot, "download_expected", &sp)) return rc;
+  Slot& s = *sp;
   if (!s.expect_mode) return fail(c, WAYNE_E_STATE, "download_expected: no expected image set for the slot");
   (void)hipSetDevice(c->device);
   use_slot_stream(c, slot);
-  const size_t bytes = (size_t)s.R * c->S * c->S * sizeof(double);
-  HIP_TRY(c, hipMemcpyAsync(out, s.expect_plane.p, bytes, hipMemcpyDeviceToHost, c->stream));
-  bool reran = false;
-  int rc = look_at_status(c, slot, nullptr, wayne_exposure_run, &reran);
-  if (rc || !reran) return rc;
-  HIP_TRY(c, hipMemcpyAsync(out, s.expect_plane.p, bytes, hipMemcpyDeviceToHost, c->stream));
-  return look_at_status(c, slot, nullptr);
+  return download_settled(c, slot, out, s.expect_plane.p, (size_t)s.R * c->S * c->S * sizeof(double));
 }
 
-int wayne_expected_profile(wayne_ctx* c, uint64_t* launches, double* ms) {
-  if (!c) return WAYNE_E_INVALID;
-  int rc = collect_profile(c);
-  if (rc) return rc;
-  if (launches) *launches = c->prof_launches[PK_EXPECT];
-  if (ms) *ms = c->prof_ms[PK_EXPECT];
-  return WAYNE_OK;
-}
+int wayne_expected_profile(wayne_ctx* c, uint64_t* launches, double* ms) { return kernel_profile(c, PK_EXPECT, launches, ms); }
 
 // ---------------------------------------------------------------------------
 // the ramp fit
 // ---------------------------------------------------------------------------
 int wayne_exposure_set_rampfit(wayne_ctx* c, int slot, const wayne_rampfit_desc* desc) {
-  if (!c) return WAYNE_E_INVALID;
-  if (slot < 0 || slot >= kSlots) return fail(c, WAYNE_E_INVALID, "set_rampfit: slot");
-  Slot& s = c->slots[slot];
-  if (!s.uploaded) return fail(c, WAYNE_E_STATE, "set_rampfit: slot not uploaded");
+  Slot* sp;
+  if (int rc = slot_gate(c, slot, "set_rampfit", &sp)) return rc;
+  Slot& s = *sp;
   s.rampfit_on = s.rampfit_ran = false;   // from here on a refusal leaves the slot usable, without the fit
   if (!desc) return WAYNE_OK;
   if (const char* why = plan::rampfit_desc_error(desc->steps, desc->read_noise_e, desc->k_jump, desc->saturation_dn))
@@ -3287,38 +3255,25 @@ int wayne_exposure_set_rampfit(wayne_ctx* c, int slot, const wayne_rampfit_desc*
 }
 
 int wayne_exposure_download_rampfit(wayne_ctx* c, int slot, double* rate, double* var, uint32_t* word) {
-  if (!c || !rate || !var || !word) return WAYNE_E_INVALID;
-  if (slot < 0 || slot >= kSlots) return fail(c, WAYNE_E_INVALID, "download_rampfit: slot");
-  Slot& s = c->slots[slot];
-  if (!s.uploaded) return fail(c, WAYNE_E_STATE, "download_rampfit: slot not uploaded");
+  if (!rate || !var || !word) return WAYNE_E_INVALID;
+  Slot* sp;
+  if (int rc = slot_gate(c, slot, "download_rampfit", &sp)) return rc;
+  Slot& s = *sp;
   if (!s.rampfit_on) return fail(c, WAYNE_E_STATE, "download_rampfit: no ramp fit set for the slot");
   if (!s.rampfit_ran) return fail(c, WAYNE_E_STATE, "download_rampfit: run first");
   (void)hipSetDevice(c->device);
   use_slot_stream(c, slot);
   const size_t SS = (size_t)c->S * c->S;
   const double* dev = s.rampfit_planes.as<double>();
-  auto copy = [&]() -> int {
+  return download_settled(c, slot, [&]() -> int {
     HIP_TRY(c, hipMemcpyAsync(rate, dev, SS * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipMemcpyAsync(var, dev + SS, SS * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipMemcpyAsync(word, dev + 2 * SS, SS * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
     return WAYNE_OK;
-  };
-  if (int rc = copy()) return rc;
-  bool reran = false;
-  int rc = look_at_status(c, slot, nullptr, wayne_exposure_run, &reran);
-  if (rc || !reran) return rc;
-  if ((rc = copy())) return rc;       // an exposure run a second time is fitted again
-  return look_at_status(c, slot, nullptr);
+  });
 }
 
-int wayne_rampfit_profile(wayne_ctx* c, uint64_t* launches, double* ms) {
-  if (!c) return WAYNE_E_INVALID;
-  int rc = collect_profile(c);
-  if (rc) return rc;
-  if (launches) *launches = c->prof_launches[PK_RAMPFIT];
-  if (ms) *ms = c->prof_ms[PK_RAMPFIT];
-  return WAYNE_OK;
-}
+int wayne_rampfit_profile(wayne_ctx* c, uint64_t* launches, double* ms) { return kernel_profile(c, PK_RAMPFIT, launches, ms); }
 
 // ---------------------------------------------------------------------------
 // the calibrated reads
@@ -3330,10 +3285,9 @@ int wayne_ima_layout(int S, int R, size_t* sci_stride, size_t* dq_stride, size_t
 }
 
 int wayne_exposure_set_ima(wayne_ctx* c, int slot, const wayne_ima_desc* desc) {
-  if (!c) return WAYNE_E_INVALID;
-  if (slot < 0 || slot >= kSlots) return fail(c, WAYNE_E_INVALID, "set_ima: slot");
-  Slot& s = c->slots[slot];
-  if (!s.uploaded) return fail(c, WAYNE_E_STATE, "set_ima: slot not uploaded");
+  Slot* sp;
+  if (int rc = slot_gate(c, slot, "set_ima", &sp)) return rc;
+  Slot& s = *sp;
   s.ima_on = s.ima_ran = false;   // from here on a refusal leaves the slot usable, without the calibrated reads
   if (!desc) return WAYNE_OK;
   if (const char* why = plan::ima_desc_error(desc->steps, desc->units, desc->read_noise_e, desc->saturation_dn))
@@ -3349,31 +3303,18 @@ int wayne_exposure_set_ima(wayne_ctx* c, int slot, const wayne_ima_desc* desc) {
 }
 
 int wayne_exposure_download_ima(wayne_ctx* c, int slot, void* payload) {
-  if (!c || !payload) return WAYNE_E_INVALID;
-  if (slot < 0 || slot >= kSlots) return fail(c, WAYNE_E_INVALID, "download_ima: slot");
-  Slot& s = c->slots[slot];
-  if (!s.uploaded) return fail(c, WAYNE_E_STATE, "download_ima: slot not uploaded");
+  if (!payload) return WAYNE_E_INVALID;
+  Slot* sp;
+  if (int rc = slot_gate(c, slot, "download_ima", &sp)) return rc;
+  Slot& s = *sp;
   if (!s.ima_on) return fail(c, WAYNE_E_STATE, "download_ima: no calibrated reads set for the slot");
   if (!s.ima_ran) return fail(c, WAYNE_E_STATE, "download_ima: run first");
   (void)hipSetDevice(c->device);
   use_slot_stream(c, slot);
-  const size_t bytes = (size_t)(s.R + 1) * s.ima_imset_stride;
-  HIP_TRY(c, hipMemcpyAsync(payload, s.ima_dev.p, bytes, hipMemcpyDeviceToHost, c->stream));
-  bool reran = false;
-  int rc = look_at_status(c, slot, nullptr, wayne_exposure_run, &reran);
-  if (rc || !reran) return rc;
-  HIP_TRY(c, hipMemcpyAsync(payload, s.ima_dev.p, bytes, hipMemcpyDeviceToHost, c->stream));   // an exposure run a second time is calibrated again
-  return look_at_status(c, slot, nullptr);
+  return download_settled(c, slot, payload, s.ima_dev.p, (size_t)(s.R + 1) * s.ima_imset_stride);
 }
 
-int wayne_ima_profile(wayne_ctx* c, uint64_t* launches, double* ms) {
-  if (!c) return WAYNE_E_INVALID;
-  int rc = collect_profile(c);
-  if (rc) return rc;
-  if (launches) *launches = c->prof_launches[PK_IMA];
-  if (ms) *ms = c->prof_ms[PK_IMA];
-  return WAYNE_OK;
-}
+int wayne_ima_profile(wayne_ctx* c, uint64_t* launches, double* ms) { return kernel_profile(c, PK_IMA, launches, ms); }
 
 // ---------------------------------------------------------------------------
 // inter-pixel capacitance
@@ -3384,10 +3325,9 @@ int wayne_ipc_weights(const wayne_ipc_desc* d, int32_t w[9]) {
 }
 
 int wayne_exposure_set_ipc(wayne_ctx* c, int slot, const wayne_ipc_desc* desc) {
-  if (!c) return WAYNE_E_INVALID;
-  if (slot < 0 || slot >= kSlots) return fail(c, WAYNE_E_INVALID, "set_ipc: slot");
-  Slot& s = c->slots[slot];
-  if (!s.uploaded) return fail(c, WAYNE_E_STATE, "set_ipc: slot not uploaded");
+  Slot* sp;
+  if (int rc = slot_gate(c, slot, "set_ipc", &sp)) return rc;
+  Slot& s = *sp;
   s.ipc_on = false;               // from here on a refusal leaves the slot usable, without the coupling
   if (!desc) return WAYNE_OK;
   if (s.d.rng_mode == WAYNE_RNG_REPLAY)
@@ -3413,14 +3353,7 @@ int wayne_exposure_set_ipc(wayne_ctx* c, int slot, const wayne_ipc_desc* desc) {
   return WAYNE_OK;
 }
 
-int wayne_ipc_profile(wayne_ctx* c, uint64_t* launches, double* ms) {
-  if (!c) return WAYNE_E_INVALID;
-  int rc = collect_profile(c);
-  if (rc) return rc;
-  if (launches) *launches = c->prof_launches[PK_IPC];
-  if (ms) *ms = c->prof_ms[PK_IPC];
-  return WAYNE_OK;
-}
+int wayne_ipc_profile(wayne_ctx* c, uint64_t* launches, double* ms) { return kernel_profile(c, PK_IPC, launches, ms); }
 
 uint32_t wayne_source_seed(uint32_t seed, uint32_t tag) {
   if (tag == 0) return seed;
